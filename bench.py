@@ -8,7 +8,7 @@ One "step"  on a batch of B synthetic traje
      [all-reduce of loss+grads over ranks], clip-by-global-norm(100) + Adam     (gmpc_critic_loss_grad, gmpc_adam_clip_step)
 All inputs are resident in HBM before the timed region.  fp32 throughout (the reference's dtype).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--backend nccl|gloo]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--backend nccl|gloo] [--dump-outputs DIR]
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (WORLD_SIZE set) this process
 is one rank; started bare, it launches `python -m torch.distributed.run --nproc-per-node N ... bench.py`
 as a child BEFORE touching the GPU, relays rank 0's JSON line and exits with the child's code.
@@ -56,6 +56,35 @@ WORKLOADS = {
 
 PEAK_FP32_TFLOPS = 157.3   # MI355X_MICROARCH.md: fp32 vector == fp32 MFMA peak
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, per_traj, whole):
+    """--dump-outputs: write device tensors as <out_dir>/<name>.npy in float32.  `whole` (name -> tensor) is
+    written in full; `per_traj` (name -> tensor, the trajectory batch on the leading axis) in full when everything
+    fits in DUMP_BYTES, else the same fixed sample of trajectories (seed 0, ascending) from every array.  The
+    caller has synchronised the device.  Returns a note for stderr."""
+    import numpy as np
+    import torch
+    B = next(iter(per_traj.values())).shape[0]
+    head = 128                                           # bytes of one .npy header at these ranks
+    fixed = sum(t.numel() * 4 + head for t in whole.values()) + head * len(per_traj)
+    row = sum(t[0].numel() * 4 for t in per_traj.values())
+    keep = min(B, (DUMP_BYTES - fixed) // row)
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one trajectory's outputs ({row} bytes) exceed the {DUMP_BYTES}-byte budget")
+    idx = None
+    if keep < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in per_traj.items():
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    for name, t in whole.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    what = "all" if idx is None else f"a fixed sample of {keep} of the"
+    return f"bench.py: wrote {len(per_traj) + len(whole)} arrays to {out_dir} ({what} {B} trajectories)"
 
 
 def linearize_flops_per_sample(n, m, dyn_dims):
@@ -323,6 +352,11 @@ def main():
     ap.add_argument("--dump-step", default="",
                     help="rank 0 saves the last step's all-reduced [mean loss | mean critic gradient] and the critic "
                          "parameters to this .npz (tests/test_gpu_multirank.py: N ranks against one)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last step of the contract's timed window computed -- states, costs, "
+                         "feedback / feedforward gains, gradient, adjoints of its trajectories (a fixed sample of them "
+                         "when the whole exceeds 64 MB), the critic's all-reduced loss and gradient sums, its "
+                         "parameters and Adam moments after the step -- as DIR/<name>.npy (float32)")
     ap.add_argument("--windows", type=int, default=5,
                     help="timed windows of --steps steps each (the first one is the contract's: value / ms_per_step)")
     ap.add_argument("--no-overlap", action="store_true",
@@ -348,6 +382,8 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="weak: the workload's batch per GPU; strong: that batch split over the ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)
@@ -521,6 +557,15 @@ def main():
         dt = float(tmax.item())
     ms_per_step = dt / args.steps * 1e3
     value = global_B * args.steps / dt
+    # before the windows below move the critic on: the outputs of step warmup + steps - 1 (synchronised above)
+    if args.dump_outputs and rank == 0:
+        Xlast = xbufs[(args.warmup + args.steps - 1) % len(xbufs)][B:]
+        sys.stderr.write(dump_outputs(
+            args.dump_outputs,
+            {"states": Xlast, "costs": costs, "feedback_gains": bw["K"], "feedforward_gains": bw["k"],
+             "grad": bw["grad"], "adjoints": bw["adjoints"]},
+            {"critic_loss_sum": loss_view, "critic_grad_sum": grad_view, "critic_params": critic,
+             "critic_adam_m": adam_m, "critic_adam_v": adam_v}) + "\n")
     # spread: four more windows of the same length (every rank runs them: they contain the collective)
     win = [ms_per_step]
     for wi in range(args.windows - 1):

@@ -2,22 +2,23 @@
 """Golden vectors from the REFERENCE's own host modules (run in the build container only).
 
 The three reference modules that need nothing but numpy / yaml -- data_normalizer.py,
-data_buffers.py, config/load_config.py -- are loaded by file path from /root/reference and driven
+data_buffers.py, config/load_config.py -- are loaded by file path from a checkout of the reference and driven
 with seeded synthetic inputs; inputs and outputs are stored in reference_host_fixtures.npz /
 reference_config_fixture.json.  The reference never travels: tests read only these data files.
 
-    python tests/golden/make_reference_fixtures.py
+    python tests/golden/make_reference_fixtures.py <reference checkout>
 """
 import contextlib
 import importlib.util
 import io
 import json
 import os
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+REF = None  # the reference checkout: the command-line argument
 
 
 def load(name, rel):
@@ -79,4 +80,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    REF = sys.argv[1]
     main()
