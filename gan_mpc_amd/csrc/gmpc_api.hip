@@ -251,6 +251,9 @@ struct gmpc_ctx {
   // dynamics regression (allocated on first use)
   float *dfpred = nullptr, *dfacts = nullptr, *dfdels = nullptr, *dfloss = nullptr, *dfsave = nullptr;
   int dfstride = 0;
+  // expert model training (gmpc_expert_loss_grad): grown to the largest B * S seen, never shrunk
+  float *efacts = nullptr, *efdels = nullptr, *efsave = nullptr, *efloss = nullptr;
+  size_t efacts_cap = 0, efdels_cap = 0, efsave_cap = 0;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;
@@ -1228,6 +1231,87 @@ extern "C" int gmpc_expert_rollout(gmpc_ctx* c, int B, int hist, const gmpc_expe
   a.history = history; a.goal = goal; a.U = init_U;
   if (gmpc_launch_expert(a, static_cast<hipStream_t>(stream)) != 0)
     return fail(GMPC_EINVAL, "expert kernel: unsupported shape");
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// expert model training --------------------------------------------------------------------------
+int gmpc_expert_fit_layout(ExpertFitArgs&);
+void gmpc_launch_expert_fit(const ExpertFitArgs&, hipStream_t);
+
+// replace a workspace buffer by a larger one (the only allocation of the expert training path)
+static int regrow(gmpc_ctx* c, float** p, size_t* cap, size_t need) {
+  if (*cap >= need) return 0;
+  if (*p) {
+    for (size_t i = 0; i < c->allocs.size(); ++i)
+      if (c->allocs[i] == *p) { c->allocs.erase(c->allocs.begin() + i); break; }
+    HIP_TRY(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+  }
+  TRY(dalloc(c, p, need));
+  *cap = need;
+  return 0;
+}
+
+extern "C" int gmpc_expert_loss_grad(gmpc_ctx* c, int B, int S, const gmpc_expert_shape* es, const float* expert,
+                                     const float* xseq, const float* useq, const float* next_xseq, double discount,
+                                     int teacher_forcing, float* loss_sum, float* grad_sum, void* stream) {
+  TRY(check_call(c, B, false));     // the expert model has its own parameters
+  const int nx = c->nx, m = c->sh.m;
+  TRY(check_expert_shape(es, nx, m));
+  if (S < 1) return fail(GMPC_EINVAL, "S=%d: at least one step is needed", S);
+  if ((long)B * S > (1L << 30)) return fail(GMPC_EINVAL, "B*S=%ld rows: too many", (long)B * S);
+  if (es->lstm_features == 0 && es->head_dims_x[0] > 512)
+    return fail(GMPC_EINVAL, "expert MLP first width %d > 512", es->head_dims_x[0]);
+  if (!expert || !xseq || !useq || !next_xseq || !loss_sum) return fail(GMPC_EINVAL, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ExpertFitArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.S = S; a.n = nx; a.m = m; a.F = es->lstm_features; a.Y = es->head_dims_x[0];
+  const long F = a.F, Y = a.Y, L = es->head_layers;
+  a.Wcat = expert;
+  a.bcat = expert + (F > 0 ? (nx + F) * 4 * F : (long)nx * Y);
+  const float* heads = a.bcat + (F > 0 ? 4 * F : Y);
+  bind_mlp(a.hx, (int)L, es->head_dims_x, heads, nullptr);
+  bind_mlp(a.hu, (int)L, es->head_dims_u, heads + mlp_count((int)L, es->head_dims_x), nullptr);
+  a.xseq = xseq; a.useq = useq; a.yseq = next_xseq;
+  a.gamma = (float)discount;
+  a.teacher_forcing = teacher_forcing != 0;
+  a.grad = grad_sum != nullptr;
+  const size_t stride = (size_t)gmpc_expert_fit_layout(a);
+  const size_t rows = (size_t)B * S;
+  if (!c->efloss) TRY(dalloc(c, &c->efloss, c->maxB));
+  a.loss = c->efloss;
+  if (a.grad) {
+    // the MFMA weight-gradient GEMM reads 8 rows past the end of both operands: keep them zero
+    TRY(regrow(c, &c->efacts, &c->efacts_cap, (rows + 8) * stride));
+    TRY(regrow(c, &c->efdels, &c->efdels_cap, (rows + 8) * stride));
+    TRY(regrow(c, &c->efsave, &c->efsave_cap, rows * a.sstride));
+    HIP_TRY(hipMemsetAsync(c->efacts + rows * stride, 0, 8 * stride * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(c->efdels + rows * stride, 0, 8 * stride * sizeof(float), s));
+    a.acts = c->efacts; a.dels = c->efdels; a.save = c->efsave;
+  }
+  gmpc_launch_expert_fit(a, s);
+  if (a.grad) {
+    const int R = (int)rows;
+    float* g = grad_sum;
+    const int M0 = F > 0 ? (int)(nx + F) : nx, N0 = F > 0 ? (int)(4 * F) : (int)Y;
+    gmpc_launch_wgrad(R, M0, N0, c->efacts, (int)stride, c->efdels, (int)stride, g, g + (long)M0 * N0, R, c->wpart,
+                      256, s, c->wpart_floats, true);
+    g += (long)M0 * N0 + N0;
+    for (int h = 0; h < 2; ++h) {
+      const MlpDesc& d = h == 0 ? a.hx : a.hu;
+      for (int l = 0; l < d.L; ++l) {
+        const int M = d.dims[l], N = d.dims[l + 1];
+        const int ao = h == 0 ? a.ax[l] : a.au[l], dof = h == 0 ? a.dx[l] : a.du[l];
+        gmpc_launch_wgrad(R, M, N, c->efacts + ao, (int)stride, c->efdels + dof, (int)stride, g, g + (long)M * N, R,
+                          c->wpart, 256, s, c->wpart_floats, true);
+        g += (long)M * N + N;
+      }
+    }
+  }
+  gmpc_launch_sum(B, c->efloss, loss_sum, 0, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -277,6 +277,22 @@ struct ExpertArgs {
   int hw;                        // set by the launcher: LDS activations per head (>= every head width)
 };
 
+// expert sequence model training (gmpc_expert_fit.hip): one minibatch of windows, loss and BPTT
+struct ExpertFitArgs {
+  int B, S, n, m, F, Y, hw;      // F == 0: the MLP variant; Y = width of y; hw = widest head layer
+  const float* Wcat;             // LSTM: [(n+F)][4F] (Wx rows, then Wh rows);  MLP: [n][Y]
+  const float* bcat;             // LSTM: [4F];  MLP: [Y]
+  MlpDesc hx, hu;                // heads, dims[0] = Y
+  int ax[GMPC_MAX_LAYERS], au[GMPC_MAX_LAYERS];    // acts offsets of the heads' layer inputs
+  int dx[GMPC_MAX_LAYERS], du[GMPC_MAX_LAYERS];    // dels offsets of the heads' layer output deltas
+  const float* xseq; const float* useq; const float* yseq;   // [B][S][n], [B][S][m], [B][S][n]
+  float gamma;
+  int teacher_forcing, grad;
+  float* acts; float* dels; int stride;
+  float* save; int sstride;
+  float* loss;                   // [B]
+};
+
 // batched "TN" GEMM of the large-state path (gmpc_large.hip)
 struct BgemmArgs {
   int batch, M, N, K;

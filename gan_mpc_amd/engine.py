@@ -226,6 +226,24 @@ class Engine:
                                                 _ptr(history), _ptr(goal), _ptr(init_U), self._stream()))
         return goal, init_U
 
+    def expert_loss_grad(self, xseq, useq, next_xseq, expert_flat, expert_shape, discount, teacher_forcing,
+                         want_grad=True, loss_sum=None, grad_sum=None):
+        """Expert-model training loss of B windows xseq, next_xseq (B, S, nx), useq (B, S, m) ->
+        (loss_sum[1], grad_sum[expert count] or None): sums over the batch (gmpc_expert_loss_grad)."""
+        B, S = xseq.shape[0], xseq.shape[1]
+        count = self.lib.gmpc_expert_param_count(self.nx, C.byref(expert_shape))
+        assert expert_flat.numel() == count, (expert_flat.numel(), count)
+        loss_sum = self.new(1) if loss_sum is None else loss_sum
+        if want_grad:
+            grad_sum = self.new(count) if grad_sum is None else grad_sum
+            assert grad_sum.numel() == count
+        else:
+            grad_sum = None
+        _lib.check(self.lib.gmpc_expert_loss_grad(
+            self.ctx, B, S, C.byref(expert_shape), _ptr(expert_flat), _ptr(xseq), _ptr(useq), _ptr(next_xseq),
+            float(discount), int(bool(teacher_forcing)), _ptr(loss_sum), _ptr(grad_sum), self._stream()))
+        return loss_sum, grad_sum
+
     def dynamics_loss_grad(self, xseq, useq, next_xseq, discount, teacher_forcing, loss_sum=None,
                            grad_sum=None):
         """-> (loss_sum[1], grad_sum[dyn_count]) of the multi-step prediction loss over the batch."""

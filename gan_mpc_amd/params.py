@@ -306,3 +306,27 @@ def pack_expert(ex):
     flat = np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in parts])
     dims = lambda layers: [layers[0][0].shape[0]] + [W.shape[1] for W, _ in layers]
     return flat, F, dims(ex["head_x"]), dims(ex["head_u"])
+
+
+def unpack_expert(flat, lstm_features, head_dims_x, head_dims_u):
+    """Inverse of pack_expert: flat vector -> plain dict (lstm | first, head_x, head_u) of fp32 arrays."""
+    flat = np.asarray(flat, np.float32).reshape(-1)
+    off = [0]
+
+    def take(*shape):
+        size = int(np.prod(shape))
+        out = flat[off[0]:off[0] + size].reshape(shape).copy()
+        off[0] += size
+        return out
+
+    n, F, Y = head_dims_x[-1], int(lstm_features), head_dims_x[0]
+    ex = {}
+    if F > 0:
+        ex["lstm"] = dict(Wx=take(n, 4 * F), Wh=take(F, 4 * F), b=take(4 * F))
+    else:
+        ex["first"] = (take(n, Y), take(Y))
+    for key, dims in (("head_x", head_dims_x), ("head_u", head_dims_u)):
+        ex[key] = [(take(a, b), take(b)) for a, b in zip(dims[:-1], dims[1:])]
+    if off[0] != flat.size:
+        raise ValueError(f"expert vector of {flat.size} floats, layout needs {off[0]}")
+    return ex

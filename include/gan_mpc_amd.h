@@ -236,6 +236,23 @@ int gmpc_expert_rollout(gmpc_ctx* ctx, int B, int hist, const gmpc_expert_shape*
                         void* stream);
 long gmpc_expert_param_count(int n, const gmpc_expert_shape* es);
 
+/* Training of the expert sequence model: expert/trainer.py:10-31 (calculate_loss under jax.value_and_grad,
+ * :34-58) with expert/nn.py:10-61 and utils.py:231-240 (discounted_sum).  For each of the B windows, from the
+ * zero carry: x_in_t = teacher_forcing ? xseq[t] : next_x_{t-1} (x_in_0 = xseq[0]), (next_x_t, u_t) = model(x_in_t),
+ * loss = sum_t discount^t (|u_t - useq[t]|^2 + |next_x_t - next_xseq[t]|^2), the discount built by repeated
+ * fp32 multiplication.  The LSTM carry is fed back in both modes.
+ *   xseq, next_xseq [B][S][x_size], useq [B][S][m], expert in the layout of gmpc_expert_rollout
+ *   -> loss_sum [1], grad_sum [gmpc_expert_param_count] in the same flat layout: SUMS over the batch,
+ *      overwritten (the caller divides by the global batch).  grad_sum == NULL: the loss only.
+ * S >= 1 is independent of the ctx's T; B <= max_batch; caps as gmpc_expert_rollout (F <= 128, x_size, m and
+ * head widths <= 1024, the MLP variant's first width <= 512); anything else fails with GMPC_EINVAL before any
+ * launch.  Workspace: the ctx keeps buffers for the BPTT rows (B * S of them) and grows them on the first call
+ * that needs more (hipMalloc / hipFree: that call allocates and synchronises); every later call of the same or
+ * a smaller size only enqueues work.  Fixed reduction order, no atomics: identical calls give identical bits. */
+int gmpc_expert_loss_grad(gmpc_ctx* ctx, int B, int S, const gmpc_expert_shape* es, const float* expert,
+                          const float* xseq, const float* useq, const float* next_xseq, double discount,
+                          int teacher_forcing, float* loss_sum, float* grad_sum, void* stream);
+
 /* N3: dynamics-model regression, norm/dynamics_trainer.py:14-47 (predict_loss) and
  * :62-86 (batch mean + value_and_grad) with utils.py:230-240 (discounted_sum).  For each of the B
  * sequences: x_in_t = teacher_forcing ? xseq[t] : pred_{t-1} (x_in_0 = xseq[0]),
