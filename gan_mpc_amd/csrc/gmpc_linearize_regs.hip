@@ -61,31 +61,14 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 // [A | B] four at a time with its weight operands through buffer loads, and the accumulator tiles -- lanes are
 // stacked rows here -- are transposed through a wave-private LDS tile so that the rows of AB are written in
 // 128-byte segments.
-// REST: the same kernel under a second name -- the launch that runs the ragged last round on its own (launch_regs), so
-// that a kernel trace lists it on a row of its own
-// LIST: the samples are those of the trajectories tlist[0 .. *tcount) (T each, NSamp = capacity x T): the launch that
-// runs the chain of a compacted subset of a batch (gmpc_ilqr_solve's early chain) with balanced tiles; rows of AB are
-// written at the trajectory's own place.  Its workgroups are EIGHT waves (two per SIMD, 256 registers each: the whole
-// register file of a CU), so that `grid` workgroups occupy exactly `grid` CUs and leave every other CU entirely to
-// the kernel they run beside (k_ls16 needs a whole CU per workgroup).
-// (LIST = 2: the same through ordinary four-wave workgroups -- the chain of "everything else", balanced because the
-// tiles are those of the listed trajectories only: with flags instead, a wave's share of the static split is
-// whatever its tiles happen to hold)
-template <int NT, int KS, int TAIL = 0, bool WIDE = false, bool REST = false, int LIST = 0>
-__global__ __launch_bounds__(LIST == 1 ? 2 * GMPC_THREADS : GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linearize_regs(
+template <int NT, int KS, int TAIL = 0, bool WIDE = false>
+__global__ __launch_bounds__(GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linearize_regs(
     int NSamp, int T, int n, int m, MlpDesc dyn, LinPad lp, const uint32_t* masks, const int* active,
-    float* AB, int ntiles, int samp_mul, int samp_add, int tile0, const int* tlist = nullptr,
-    const int* tcount = nullptr) {
+    float* AB, int ntiles, int samp_mul, int samp_add) {
   static_assert(NT <= 8 && 2 * KS <= 32 * NT + TAIL && (TAIL == 0 || TAIL == 8), "shape");
   constexpr bool AG = GMPC_REGS_OCC(NT, TAIL) == 1;      // register half of the accumulators (mfma_fence)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* wl_s = reinterpret_cast<float*>(smem);          // W_L  [(H + pad)][n]
-  int lcount = 0;
-  if constexpr (LIST != 0) {
-    lcount = *tcount;
-    if (lcount <= 0) return;                             // (nothing was handed over this time)
-    ntiles = min(ntiles, (int)(((long)lcount * T * n + 31) / 32));
-  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
   const int Lh = dyn.L - 1, nm = n + m;
@@ -118,25 +101,14 @@ __global__ __launch_bounds__(LIST == 1 ? 2 * GMPC_THREADS : GMPC_THREADS, GMPC_R
   // (static split: 27,200 tiles over 2,048 waves are 13.28 per wave, 14 rounds.  Handing the tiles out through a
   // global ticket counter -- requested before the input GEMM, read after the stores, so its round trip is off the
   // critical path -- was measured in round 3 and is not kept: 1.121 vs 1.107 ms on the same box.)
-  // (tile0: first tile of this launch -- the ragged last round of a long tile list can be a launch of its own, so
-  // that a caller's event between the two lets other streams use the wave slots the last round leaves idle)
-  constexpr int WPB = (LIST == 1 ? 2 * GMPC_THREADS : GMPC_THREADS) / 64;      // waves per workgroup
-  for (int tile = tile0 + blockIdx.x * WPB + wave; tile < ntiles; tile += gridDim.x * WPB) {
+  constexpr int WPB = GMPC_THREADS / 64;      // waves per workgroup
+  for (int tile = blockIdx.x * WPB + wave; tile < ntiles; tile += gridDim.x * WPB) {
     const int r0 = tile * 32;
     int R = r0 + l31;                          // this lane's stacked Jacobian row
     const bool rvalid = R < Rtot;
     if (!rvalid) R = Rtot - 1;                 // clamped reads, no writes
     const int s = R / n, irow = R - s * n;
     size_t sid = (size_t)s * samp_mul + samp_add;
-    int Rout = R;
-    bool lvalid = rvalid;
-    if constexpr (LIST != 0) {
-      const int tb = s / T, tq = s - tb * T;
-      lvalid = rvalid && tb < lcount;
-      if (__ballot(lvalid) == 0ull) continue;
-      sid = (size_t)tlist[min(tb, lcount - 1)] * T + tq;
-      Rout = (int)sid * n + irow;
-    }
     if (active != nullptr) {
       const bool on = active[sid / T] != 0;
       if (__ballot(on && rvalid) == 0ull) continue;
@@ -370,8 +342,8 @@ __global__ __launch_bounds__(LIST == 1 ? 2 * GMPC_THREADS : GMPC_THREADS, GMPC_R
       }
       GMPC_STAMP(3)
       mfma_fence<AG>(acc0);
-      if (LIST != 0 ? lvalid : rvalid) {
-        float* dst = AB + (size_t)(LIST != 0 ? Rout : R) * nm;
+      if (rvalid) {
+        float* dst = AB + (size_t)R * nm;
 #pragma unroll
         for (int rg = 0; rg < 16; ++rg) {
           const int c = (rg & 3) + 8 * (rg >> 2) + 4 * half;
@@ -390,15 +362,11 @@ __global__ __launch_bounds__(LIST == 1 ? 2 * GMPC_THREADS : GMPC_THREADS, GMPC_R
 static char g_last_name[64] = "";
 const char* gmpc_linearize_regs_last_name() { return g_last_name; }
 
-// mid_event (optional): when the static split leaves a ragged last round -- less than GMPC_LIN_SPLIT_MAX of the wave
-// slots busy for a whole tile time (C3: 27,200 tiles over 2,048 slots = 13 full rounds + 576 tiles, 28 %) -- the last
-// round is launched as a kernel of its own and the event is recorded between the two: a stream waiting for it (the
-// critic chain, bench.py) starts while the last tiles are still running, on the CUs and register halves they leave
-// free.  Returns 1 when the event was recorded here, 0 when it was not (one launch), -1 on an unsupported shape.
+// returns 0 on launch, -1 on an unsupported shape
 template <int NT, int KS, int TAIL = 0, bool WIDE = false>
 static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                        const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
-                       hipStream_t s, hipEvent_t mid_event = nullptr) {
+                       hipStream_t s) {
   const long Rtot = (long)NSamp * n;
   if (Rtot >= (1L << 31) - 64) return -1;
   const int ntiles = (int)((Rtot + 31) / 32);
@@ -414,80 +382,17 @@ static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const
   // (measured, round 3: one workgroup per CU -- 256 of the 512 registers of every SIMD left to other kernels --
   // costs 5.5 % alone (1.141 -> 1.204 ms), and the critic's kernels beside it are starved by its back-to-back
   // 64-cycle MFMAs: k_head2 0.05 -> 0.37 ms, k_lstm_bwd2 0.11 -> 0.87 ms.  The chain keeps the chip to itself.)
-  // (as rocprofv3's kernel trace prints the instantiation: REST = false, LIST = 0 for the single launch)
-  snprintf(g_last_name, sizeof(g_last_name), "k_linearize_regs<%d, %d, %d, %s, false, 0>", NT, KS, TAIL,
-           WIDE ? "true" : "false");
-  const int slots = grid * 4;
-  const int full = ntiles / slots, rest = ntiles - full * slots;
-  static const int split_pct = []() {
-    const char* e = getenv("GMPC_LIN_SPLIT");      // percent of a round below which the last round is split off; 0: never
-    // (default 0 -- measured in round 4 and not kept: with the critic chain gated on the event between the two
-    // launches the chain runs 0.04 ms longer (the last round's workgroups restage their LDS tables and share their
-    // SIMDs with the critic's first kernel) and the step is 0.006 ms slower, not faster)
-    return e != nullptr ? atoi(e) : 0;
-  }();
-  if (mid_event != nullptr && active == nullptr && full >= 2 && rest > 0 && rest * 100 < slots * split_pct) {
-    hipLaunchKernelGGL((k_linearize_regs<NT, KS, TAIL, WIDE>), dim3(grid), dim3(GMPC_THREADS), lds, s, NSamp, T, n, m,
-                       dyn, lp, masks, active, AB, full * slots, samp_mul, samp_add, 0);
-    if (hipEventRecord(mid_event, s) != hipSuccess) return -1;
-    hipLaunchKernelGGL((k_linearize_regs<NT, KS, TAIL, WIDE, !WIDE>), dim3((rest + 3) / 4), dim3(GMPC_THREADS), lds, s,
-                       NSamp, T, n, m, dyn, lp, masks, active, AB, ntiles, samp_mul, samp_add, full * slots);
-    return 1;
-  }
+  // (as rocprofv3's kernel trace prints the instantiation)
+  snprintf(g_last_name, sizeof(g_last_name), "k_linearize_regs<%d, %d, %d, %s>", NT, KS, TAIL, WIDE ? "true" : "false");
   hipLaunchKernelGGL((k_linearize_regs<NT, KS, TAIL, WIDE>), dim3(grid), dim3(GMPC_THREADS), lds, s, NSamp, T, n, m,
-                     dyn, lp, masks, active, AB, ntiles, samp_mul, samp_add, 0);
+                     dyn, lp, masks, active, AB, ntiles, samp_mul, samp_add);
   return 0;
 }
 
-// the chain of the trajectories tlist[0 .. *tcount), at most `cap` of them.  whole_cus > 0: on that many workgroups of
-// eight waves = that many whole CUs; 0: on the persistent four-wave workgroups of the ordinary launch
-template <int NT, int KS, int TAIL = 0>
-static int launch_regs_list(int cap, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp, const uint32_t* masks,
-                            const int* tlist, const int* tcount, float* AB, int whole_cus, hipStream_t s) {
-  const long Rtot = (long)cap * T * n;
-  if (Rtot >= (1L << 31) - 64 || cap < 1) return -1;
-  const int ntiles = (int)((Rtot + 31) / 32);
-  const int Lh = dyn.L - 1;
-  size_t lds = (size_t)(dyn.dims[Lh] + GMPC_LIN_PADROWS) * n * sizeof(float) + (size_t)2 * KS * 32 * sizeof(float);
-  if (TAIL > 0) lds += (size_t)(Lh - 1) * 2 * KS * 8 * sizeof(float);
-  if (lds > 64 * 1024) return -1;
-  static_assert(GMPC_REGS_OCC(NT, TAIL) == 2, "eight waves of 256 registers");
-  if (whole_cus > 0) {
-    const int grid = std::min(whole_cus, (ntiles + 7) / 8);
-    hipLaunchKernelGGL((k_linearize_regs<NT, KS, TAIL, false, false, 1>), dim3(grid), dim3(2 * GMPC_THREADS), lds, s,
-                       cap * T, T, n, m, dyn, lp, masks, nullptr, AB, ntiles, 1, 0, 0, tlist, tcount);
-  } else {
-    const int grid = std::min(256 * GMPC_REGS_OCC(NT, TAIL), (ntiles + 3) / 4);
-    hipLaunchKernelGGL((k_linearize_regs<NT, KS, TAIL, false, false, 2>), dim3(grid), dim3(GMPC_THREADS), lds, s,
-                       cap * T, T, n, m, dyn, lp, masks, nullptr, AB, ntiles, 1, 0, 0, tlist, tcount);
-  }
-  return 0;
-}
-int gmpc_launch_linearize_regs_list(int cap, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
-                                    const uint32_t* masks, const int* tlist, const int* tcount, float* AB, int whole_cus,
-                                    hipStream_t s) {
-  const int H = dyn.dims[1];
-  // (the 200-wide instantiation only: the one that runs two waves per SIMD, and the only width k_ls16 serves)
-  if (H == 200 && lp.NT == 7)
-    return launch_regs_list<6, 100, 8>(cap, T, n, m, dyn, lp, masks, tlist, tcount, AB, whole_cus, s);
-  return -1;
-}
-
-// true when gmpc_launch_linearize_regs serves this (narrow) shape -- the same conditions as its dispatch below
-bool gmpc_linearize_regs_covers(int n, int m, const MlpDesc& dyn, const LinPad& lp) {
-  const int Lh = dyn.L - 1;
-  if (Lh < 2 || n + m > 32 || lp.NTF != 1 || lp.NGF != 1) return false;
-  const int H = dyn.dims[1];
-  for (int l = 1; l <= Lh; ++l)
-    if (dyn.dims[l] != H) return false;
-  return (H == 200 && lp.NT == 7) || (H == 128 && lp.NT == 4) || (H == 64 && lp.NT == 2);
-}
-
-// returns 0 on launch (1: and mid_event was recorded between its two launches), -1 when the shape is not one this
-// variant is compiled for
+// returns 0 on launch, -1 when the shape is not one this variant is compiled for
 int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                const uint32_t* masks, const int* active, float* AB, int samp_mul,
-                               int samp_add, hipStream_t s, hipEvent_t mid_event) {
+                               int samp_add, hipStream_t s) {
   const int Lh = dyn.L - 1;
   if (Lh < 2) return -1;
   const int H = dyn.dims[1];
@@ -497,18 +402,18 @@ int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dy
     // wide inputs (large-state path): the 200-wide instantiation only
     static const bool off = getenv("GMPC_LIN_WIDE") != nullptr && getenv("GMPC_LIN_WIDE")[0] == '0';
     if (off || H != 200 || lp.NT != 7 || 32 * lp.NTF * lp.NGF < ((n + m + 31) / 32 + 3) / 4 * 4 * 32) return -1;
-    return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s) < 0 ? -1 : 0;
+    return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   }
   if (lp.NTF != 1 || lp.NGF != 1) return -1;
   if (H == 200 && lp.NT == 7) {
     static const bool no_tail = getenv("GMPC_LIN_NOTAIL") != nullptr;
     if (!no_tail)
-      return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s, mid_event);
-    return launch_regs<7, 100>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s, mid_event);
+      return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    return launch_regs<7, 100>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   }
   if (H == 128 && lp.NT == 4)
-    return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s, mid_event);
+    return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   if (H == 64 && lp.NT == 2)
-    return launch_regs<2, 32>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s, mid_event);
+    return launch_regs<2, 32>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   return -1;
 }

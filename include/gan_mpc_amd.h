@@ -288,17 +288,13 @@ int gmpc_linesearch_stats(gmpc_ctx* ctx, long* out, int n);
 
 /* Stream overlap hook.  `hip_event` (a hipEvent_t, or NULL to clear) is recorded on the backward pass's stream
  * behind the Jacobian chain of gmpc_lqr_backward(_after_rollout) / of every iteration of gmpc_ilqr_solve.  Order of
- * the small-state pass since round 3: terminal quadratisation, Jacobian chain, EVENT, Riccati sweep (the terminal
- * quadratisation needs X only and runs first, so that the sweep is the launch right behind the chain;
- * GMPC_TERMINAL_FIRST=0 restores chain, event, terminal, sweep).  Large-state path: the event is recorded at the top
- * of the pass, before the terminal quadratisation and the step-major pipeline.  With GMPC_LIN_SPLIT=<percent> the
- * chain's ragged last round is a launch of its own and the event sits between the two launches -- the waiter then
- * starts while the last Jacobians are still being written, so it must not read them (bench.py's critic step does not);
- * off by default (measured, no gain).  A caller that runs independent work on a second stream -- the critic step of
- * the GAN loop: reference gan/runner.py:120-168 has no data dependence between it and the policy's backward pass --
- * makes that stream wait for the event: the work then shares the chip with the Riccati sweep (two wavefronts per
- * trajectory: most wave slots and registers are free) instead of taking workgroup slots from the matrix-core-bound
- * Jacobian chain.  The event must outlive its use. */
+ * the small-state pass: terminal quadratisation, Jacobian chain, EVENT, Riccati sweep (the terminal quadratisation
+ * needs X only and runs first, so that the sweep is the launch right behind the chain).  Large-state path: the event
+ * is recorded at the top of the pass, before the terminal quadratisation and the step-major pipeline.  A caller that
+ * runs independent work on a second stream -- the critic step of the GAN loop: reference gan/runner.py:120-168 has no
+ * data dependence between it and the policy's backward pass -- makes that stream wait for the event: the work then
+ * shares the chip with the Riccati sweep (two wavefronts per trajectory: most wave slots and registers are free)
+ * instead of taking workgroup slots from the matrix-core-bound Jacobian chain.  The event must outlive its use. */
 int gmpc_set_linearize_event(gmpc_ctx* ctx, void* hip_event);
 
 /* Optional per-kernel timing with HIP events recorded on the launch stream around each kernel
