@@ -158,10 +158,19 @@ class Engine:
                                               _ptr(costs), self._stream()))
         return X, costs
 
+    @staticmethod
+    def _check_rows(call, B, **args):
+        """The single-evaluation kernels read B rows of a fixed width from each argument: a tensor with fewer or
+        narrower rows would be read past its end.  args: name -> (tensor or None, row width)."""
+        for name, (t, width) in args.items():
+            if t is not None and (t.dim() != 2 or tuple(t.shape) != (B, width)):
+                raise _lib.GmpcError(f"{call}: {name} must be ({B}, {width}), got {tuple(t.shape)}")
+
     def get_cost(self, x, u, goal_row, terminal):
         """cost_model.get_cost for B independent (x, u) pairs: the staging branch against goal_row
         (B, n), or (terminal) the terminal branch of an arbitrary state -> (B,)."""
         B = x.shape[0]
+        self._check_rows("get_cost", B, x=(x, self.n), u=(u, self.m), goal_row=(goal_row, self.nx))
         cost = self.new(B)
         _lib.check(self.lib.gmpc_get_cost(self.ctx, B, _ptr(x), _ptr(u), _ptr(goal_row),
                                           int(bool(terminal)), _ptr(cost), self._stream()))
@@ -170,6 +179,7 @@ class Engine:
     def predict(self, x, u):
         """dynamics_model.predict for B independent (x, u) pairs -> next_x (B, n)."""
         B = x.shape[0]
+        self._check_rows("predict", B, x=(x, self.n), u=(u, self.m))
         nxt = self.new(B, self.n)
         _lib.check(self.lib.gmpc_predict(self.ctx, B, _ptr(x), _ptr(u), _ptr(nxt), self._stream()))
         return nxt

@@ -128,3 +128,25 @@ def test_pack_layout_lets_a_caller_pack_a_flax_tree_without_the_python_packers()
     lib = _lib.load()
     bad = make_shape(5, 2, 4, [7, 7, 9, 5], [5, 6, 4])
     assert lib.gmpc_pack_layout(C.byref(bad), 2, None, 0) == -1 and b"no critic" in lib.gmpc_last_error()
+
+
+def test_single_evaluations_refuse_rows_they_would_read_past():
+    """Engine.get_cost / Engine.predict check every argument is (B, width) before the kernel reads B rows of that
+    width from it: a narrower goal row (an x_size-wide goal handed to a full-state engine), a wrong u width or fewer
+    rows than x are errors, not reads past the end of the tensor.  The check runs before the library is called, so
+    it is exercised here without a context."""
+    from gan_mpc_amd.engine import Engine
+    eng = Engine.__new__(Engine)
+    eng.n, eng.m, eng.nx = 20, 2, 4         # an LSTM-dynamics engine: xc = [x (4), c, h (8 + 8)]
+    x, u, g = torch.zeros(5, 20), torch.zeros(5, 2), torch.zeros(5, 4)
+    bad = [("get_cost", (torch.zeros(5, 4), u, g, False)),        # x of the goal's width
+           ("get_cost", (x, u, torch.zeros(5, 20), False)),       # goal of the state's width
+           ("get_cost", (x, torch.zeros(5, 3), g, False)),
+           ("get_cost", (x, u, torch.zeros(4, 4), False)),        # fewer goal rows than x
+           ("get_cost", (x, torch.zeros(4, 2), None, True)),
+           ("get_cost", (x.reshape(-1), u, g, False)),
+           ("predict", (x, torch.zeros(3, 2))),
+           ("predict", (torch.zeros(5, 4), u))]
+    for call, args in bad:
+        with pytest.raises(_lib.GmpcError, match=f"{call}: .* must be"):
+            getattr(eng, call)(*args)

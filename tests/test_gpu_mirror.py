@@ -127,6 +127,11 @@ def test_loss_and_grad_matches_oracle_batch_mean(cls):
             critic=p.get("critic"), kwargs={"maxiter": 2})
         res[dt] = (l, gu.pack_grads_cost(g_mpc, g_cost))
     gu.assert_parity("loss", float(loss), res[np.float32][0], res[np.float64][0], tol=1e-4, slack=10)
+    # at the GPU's own iterate, stage by stage, under the default bars (the end-to-end figure is the one below)
+    _check_policy_gradient_at_the_gpu_iterate(policy, _oracle_problem(params, data, idx, np.float32),
+                                              _oracle_problem(params, data, idx, np.float64),
+                                              0 if cls is l2_policy.L2MPC else 1, float(loss), grads, len(idx),
+                                              end_to_end=False)
     gu.assert_parity("grads", grads.cpu().numpy(), res[np.float32][1], res[np.float64][1], tol=1e-3,
                      slack=10)
 
@@ -411,9 +416,36 @@ def test_policies_with_the_lstm_dynamics_variant():
                                                 critic=p["critic"], kwargs=kw)
         res[dt] = (l, gu.pack_grads_cost(g_mpc, g_cost))
     gu.assert_parity("lstm-dynamics loss", float(loss), res[np.float32][0], res[np.float64][0], tol=1e-4, slack=10)
-    # end to end through the Hessian solve two iLQR iterations from a random start: with the dynamics' curvature in
-    # it the Hessian is far from positive definite there and the solve is badly conditioned (the NumPy fp32 oracle
-    # is ~0.2 from fp64).  The stage-wise checks of test_bilevel_grad[dynl-*] carry the parity claim; here the
-    # mirror must simply be no worse than fp32 NumPy on the same problem.
+    # the policy layer at the GPU's own iterate, stage by stage (the method of test_gpu_parity.test_bilevel_grad):
+    # the batch-mean gradient against the fp64 cost_vjp of the GPU's own (H, dX) is the check that sees the
+    # policy's packing, sign, mean and carry handling; loss, Bvec, the Hessian solve's residual, the tangent roll
+    # and the end-to-end gradient follow
+    _check_policy_gradient_at_the_gpu_iterate(policy, p32, p64, 1, float(loss), grads, len(idx))
+    # (recorded for comparison) each oracle running its own solve two iLQR iterations from a random start: with the
+    # dynamics' curvature in it the Hessian is far from positive definite there and the solve is badly conditioned
+    # (the NumPy fp32 oracle is ~0.2 from fp64), so this bar only rejects a gradient that is non-finite or off by
+    # more than its own size
     gu.assert_parity("lstm-dynamics grads", grads.cpu().numpy(), res[np.float32][1], res[np.float64][1], tol=1e-3,
                      slack=1.0, ceiling=1.0, el_slack=1e9)
+
+
+def _check_policy_gradient_at_the_gpu_iterate(policy, p32, p64, loss_kind, loss, grads, B, end_to_end=True):
+    eng = policy._engine
+    T, n, m = eng.T, eng.n, eng.m
+    X = eng.debug_buffer(0, (B, T + 1, n)).cpu().numpy()
+    U = eng.debug_buffer(1, (B, T, m)).cpu().numpy()
+    Hd = eng.debug_buffer(2, (B, T, m)).cpu().numpy()
+    dXd = eng.debug_buffer(3, (B, T + 1, n)).cpu().numpy()
+    Bvd = eng.debug_buffer(4, (B, T, m)).cpu().numpy()
+    # the solve started from [x0, zero carry]
+    np.testing.assert_array_equal(X[:, 0, :eng.nx], p32["x0"])
+    np.testing.assert_array_equal(X[:, 0, eng.nx:], 0.0)
+    X64, U64 = X.astype(np.float64), U.astype(np.float64)
+    keep = ~(gu.dyn_near_kink(p64["dyn"], X64, U64).any(1) | gu.near_kink(p64["cmlp"], X64[:, T]))
+    assert keep.sum() >= max(1, B // 2), "too many trajectories near a relu kink; change the seed"
+    # the end-to-end figure is the policy's batch mean, which cannot leave a trajectory out: the data seed of
+    # _build (3) and these batches put no pre-activation near a kink (checked here, so that a change of data fails
+    # as such and not as a parity failure)
+    assert keep.all() or not end_to_end, f"trajectories {np.flatnonzero(~keep)} sit at a relu kink; change the seed"
+    gu.check_bilevel_at_iterate(p32, p64, loss_kind, X, U, np.float32(loss), grads.cpu().numpy(), Hd, dXd, Bvd,
+                                batch_mean=True, keep=keep, end_to_end=end_to_end)

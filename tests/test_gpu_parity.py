@@ -446,77 +446,7 @@ def test_bilevel_grad(name, loss_kind):
     Hd = eng.debug_buffer(2, (B, T, m)).cpu().numpy()
     dXd = eng.debug_buffer(3, (B, T + 1, n)).cpu().numpy()
     Bvd = eng.debug_buffer(4, (B, T, m)).cpu().numpy()
-
-    def stages(p, dt):
-        Xa, Ua = X.astype(dt), U.astype(dt)
-        lqr = orc.get_lqr_params(p["dyn"], p["cmlp"], p["mpc_w"], p["goal"], Xa, Ua)
-        if loss_kind == 0:
-            lv, lx = orc.l2_loss(Xa, p["true_seq"]), orc.l2_loss_grad_x(Xa, p["true_seq"])
-        else:
-            lv, lx = orc.generator_loss(p["critic"], Xa), orc.generator_loss_grad_x(p["critic"], Xa)
-        Bv = orc.loss_grad_wrt_control(lqr[5], lqr[6], lx)
-        # the LQ model whose Hessian is the reference's dense one (curvature of smooth dynamics included)
-        lqr = orc.second_order_lqr(p["dyn"], lqr, orc.adjoint(lqr[5], lqr[6], lqr[1], lqr[3])[1], Xa, Ua)
-        Hc, dX = orc.hessian_solve(lqr, Bv)
-        g_mpc, g_cost = orc.cost_vjp(p["cmlp"], p["mpc_w"], p["goal"], Xa, Ua, Hd.astype(dt),
-                                     dXd.astype(dt))
-        g_from_hip_H = gu.pack_grads_cost(g_mpc.sum(0), [(a.sum(0), b.sum(0)) for a, b in g_cost])
-        g_mpc, g_cost = orc.cost_vjp(p["cmlp"], p["mpc_w"], p["goal"], Xa, Ua, Hc, dX)
-        g_full = gu.pack_grads_cost(g_mpc.sum(0), [(a.sum(0), b.sum(0)) for a, b in g_cost])
-        return dict(lqr=lqr, loss=lv, Bv=Bv, H=Hc, g_stage=g_from_hip_H, g_full=g_full)
-
-    s32, s64 = stages(pb, np.float32), stages(pb64, np.float64)
-    gu.assert_parity("loss", loss.cpu().numpy(), s32["loss"], s64["loss"])
-    gu.assert_parity("Bvec", Bvd, s32["Bv"], s64["Bv"])
-    # residual of the structured solve, per trajectory, in fp64
-    def resid(H):
-        r = orc.hessian_apply(s64["lqr"], H.astype(np.float64)) - s64["Bv"]
-        return np.sqrt((r ** 2).sum((1, 2)) / (s64["Bv"] ** 2).sum((1, 2)))
-    r_hip, r_o32 = resid(Hd), resid(s32["H"])
-    gu._record(dict(stage="Hessian solve residual |A H - B| / |B| (fp64 A, B; max over trajectories)",
-                    config=gu.CURRENT_CONFIG[0], e_hip=float(r_hip.max()), e_o32=float(r_o32.max()), tol=1e-4,
-                    tol_used=float(np.maximum(1e-4, 10 * r_o32).min()), branch="tol" if r_hip.max() <= 1e-4 else "slack",
-                    entries=int(Hd.size), passed=bool((r_hip <= np.maximum(1e-4, 10 * r_o32)).all())))
-    assert np.median(r_hip) < 1e-4 and (r_hip <= np.maximum(1e-4, 10 * r_o32)).all(), (r_hip, r_o32)
-    # tangent roll consistent with H
-    lq = s64["lqr"]
-    dx = np.zeros((B, T + 1, n))
-    for t in range(T):
-        dx[:, t + 1] = np.einsum("bij,bj->bi", lq[5][:, t], dx[:, t]) + np.einsum(
-            "bnm,bm->bn", lq[6][:, t], Hd[:, t].astype(np.float64))
-    assert gu.rel_err(dXd, dx) < 1e-4
-    # a11 given the same (H, dX)
-    gu.assert_parity("cost_vjp stage", gsum.cpu().numpy(), s32["g_stage"], s64["g_stage"])
-    # end to end.  The forward error of the gradient is the Hessian solve's backward error (the residual checked
-    # above, fp32-sized) seen through cond(A) -- for a given residual SIZE it varies with the residual's direction
-    # (6e-6 .. 6e-4 across these configs for the HIP path and for the fp32 oracle alike, uncorrelated), so one
-    # draw of the fp32 oracle's own forward error is a poor yardstick.  The bar: 1e-4, or 10 x the fp32 oracle's
-    # error, or 4 x what a backward error of HIP's size does to the gradient in fp64 (largest of four random
-    # right-hand-side perturbations of relative norm r_hip per trajectory); never above 1e-3.  The elementwise
-    # rule gets the same third term.
-    rng = np.random.default_rng(7)
-    Bv64 = s64["Bv"]
-    e_pert, el_pert = 0.0, 0.0
-    for _ in range(4):
-        noise = rng.standard_normal(Bv64.shape)
-        noise *= (r_hip * np.sqrt((Bv64 ** 2).sum((1, 2)) / (noise ** 2).sum((1, 2))))[:, None, None]
-        Hp, dXp = orc.hessian_solve(s64["lqr"], Bv64 + noise)
-        g_mpc, g_cost = orc.cost_vjp(pb64["cmlp"], pb64["mpc_w"], pb64["goal"], X.astype(np.float64),
-                                     U.astype(np.float64), Hp, dXp)
-        gp = gu.pack_grads_cost(g_mpc.sum(0), [(a.sum(0), b.sum(0)) for a, b in g_cost])
-        e_pert = max(e_pert, gu.rel_err(gp, s64["g_full"]))
-        el_pert = max(el_pert, gu.el_err(gp, s64["g_full"])[0])
-    gu._record(dict(stage="gradient response to a backward error of HIP's size (fp64, 4 random directions)",
-                    config=gu.CURRENT_CONFIG[0], e_hip=e_pert, e_o32=float(r_hip.max()), tol=1e-4, tol_used=1e-3,
-                    branch="info", el_hip=el_pert, entries=int(s64["g_full"].size), passed=True))
-    # (the round-2 bar, fixed 1e-4, kept as a recorded check: profiles/parity_r04.md lists which shapes pass it)
-    e_fixed, e_fixed32 = gu.rel_err(gsum.cpu().numpy(), s64["g_full"]), gu.rel_err(s32["g_full"], s64["g_full"])
-    gu._record(dict(stage="bilevel grad end-to-end against the round-2 fixed bar 1e-4 (recorded, not asserted)",
-                    config=gu.CURRENT_CONFIG[0], e_hip=e_fixed, e_o32=e_fixed32, tol=1e-4, tol_used=1e-4, branch="info",
-                    entries=int(s64["g_full"].size), passed=bool(e_fixed <= 1e-4)))
-    gu.assert_parity("bilevel grad end-to-end", gsum.cpu().numpy(), s32["g_full"], s64["g_full"],
-                     tol=min(max(1e-4, 4.0 * e_pert), gu.SLACK_CEILING), slack=10.0,
-                     el_tol=max(1e-3, 4.0 * el_pert))
+    gu.check_bilevel_at_iterate(pb, pb64, loss_kind, X, U, loss.cpu().numpy(), gsum.cpu().numpy(), Hd, dXd, Bvd)
 
 
 @pytest.mark.parametrize("name", ["ls16-ragged", "ls16-n12", "ls16-n14m8", "ls16-pendulum", "ls16-m8", "trained-like",
