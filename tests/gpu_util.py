@@ -176,6 +176,22 @@ def critic_flat(pb):
     return P.pack_critic(P.critic_dict_to_tree(pb["critic"]))
 
 
+def split_critic_flat(v, n, F, head_dims):
+    """The blocks of a flat critic vector (parameters or gradient) in pack_critic's layout
+    Wx[n][4F] | Wh[F][4F] | b[4F] | W[K][N], b[N] per head layer: a list of (name, 1-D view).
+    head_dims = (F, hidden..., 1)."""
+    v = np.asarray(v).reshape(-1)
+    sizes = [("Wx", n * 4 * F), ("Wh", F * 4 * F), ("b", 4 * F)]
+    for l, (K, N) in enumerate(zip(head_dims[:-1], head_dims[1:])):
+        sizes += [(f"head{l}.W", K * N), (f"head{l}.b", N)]
+    assert sum(s for _, s in sizes) == v.size, (v.size, sizes)
+    out, o = [], 0
+    for name, s in sizes:
+        out.append((name, v[o:o + s]))
+        o += s
+    return out
+
+
 def near_kink(layers, q, thresh=3e-6):
     """(rows,) bool: some hidden pre-activation is within `thresh` (relative to that sample's layer scale)
     of the relu kink, where the derivative is discontinuous (hard part iii)."""
