@@ -375,8 +375,7 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
       const size_t hl = s.dyn_dims[s.dyn_layers - 1];
       size_t hmax = 0;
       for (int l = 1; l < s.dyn_layers; ++l) hmax = (size_t)s.dyn_dims[l] > hmax ? s.dyn_dims[l] : hmax;
-      const bool force = getenv("GMPC_BIG_LOWRANK") != nullptr && hl < n;     // (A/B timing)
-      if (!c->dynl && (2 * hl < n || force) && getenv("GMPC_BIG_DENSE") == nullptr) {
+      if (!c->dynl && 2 * hl < n && getenv("GMPC_BIG_DENSE") == nullptr) {
         c->bw.h = (int)hl;
         B_(Vt, B * hl * nm + pad);
         B_(W1b, B * hl * n + pad);
@@ -385,42 +384,31 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
         B_(Sb, B * hmax * hl + pad);
       }
     }
-    // one-step-ahead Jacobians on a side stream (MLP dynamics; GMPC_BIG_PIPELINE=0: one stream, one buffer)
-    {
-      const char* e = getenv("GMPC_BIG_PIPELINE");
-      // (the low-rank form supports it too -- Vt2 / Sm -- and gains nothing: its factor GEMMs and k_big_step slow
-      // each other down by what the overlap saves, C5 1.980 vs 1.984 s; GMPC_BIG_PIPELINE=2 turns it on there)
-      const bool lr_too = e != nullptr && e[0] == '2';
-      if (!c->dynl && !(e != nullptr && e[0] == '0') && (c->bw.h == 0 || lr_too)) {
-        // (the second copy and the side stream are an optimisation: when any of them cannot be had -- the copy is
-        // B n (n + m) floats, 4.5 GB at n = 1024 -- the pass runs on one stream with one buffer)
-        if (!rc) {
-          const size_t cnt2 = c->bw.h > 0 ? B * (size_t)c->bw.h * nm + pad : B * n * nm + pad;
-          const size_t cnt3 = c->bw.h > 0 ? B * (size_t)c->bw.h * c->bw.h + pad : 0;
-          float *p2 = nullptr, *p3 = nullptr;
-          bool ok = hipMalloc(reinterpret_cast<void**>(&p2), cnt2 * sizeof(float)) == hipSuccess;
-          if (ok && cnt3) ok = hipMalloc(reinterpret_cast<void**>(&p3), cnt3 * sizeof(float)) == hipSuccess;
-          ok = ok && hipMemset(p2, 0, cnt2 * sizeof(float)) == hipSuccess;
-          if (ok && p3) ok = hipMemset(p3, 0, cnt3 * sizeof(float)) == hipSuccess;
-          ok = ok && hipStreamCreateWithFlags(&c->bw.side, hipStreamNonBlocking) == hipSuccess;
-          ok = ok && hipEventCreateWithFlags(&c->bw.ev_start, hipEventDisableTiming) == hipSuccess;
-          for (int i = 0; i < 2 && ok; ++i)
-            ok = hipEventCreateWithFlags(&c->bw.ev_ready[i], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&c->bw.ev_free[i], hipEventDisableTiming) == hipSuccess;
-          if (ok) {
-            c->allocs.push_back(p2);
-            if (p3) c->allocs.push_back(p3);
-            if (c->bw.h > 0) { c->bw.Vt2 = p2; c->bw.Sm = p3; } else { c->bw.ABt2 = p2; }
-          } else {
-            (void)hipGetLastError();
-            if (p2) (void)hipFree(p2);
-            if (p3) (void)hipFree(p3);
-            if (c->bw.side) { (void)hipStreamDestroy(c->bw.side); c->bw.side = nullptr; }
-            if (c->bw.ev_start) { (void)hipEventDestroy(c->bw.ev_start); c->bw.ev_start = nullptr; }
-            for (int i = 0; i < 2; ++i) {
-              if (c->bw.ev_ready[i]) { (void)hipEventDestroy(c->bw.ev_ready[i]); c->bw.ev_ready[i] = nullptr; }
-              if (c->bw.ev_free[i]) { (void)hipEventDestroy(c->bw.ev_free[i]); c->bw.ev_free[i] = nullptr; }
-            }
+    // one-step-ahead Jacobians on a side stream (MLP dynamics, dense form)
+    if (!c->dynl && c->bw.h == 0) {
+      // (the second copy and the side stream are an optimisation: when any of them cannot be had -- the copy is
+      // B n (n + m) floats, 4.5 GB at n = 1024 -- the pass runs on one stream with one buffer)
+      if (!rc) {
+        const size_t cnt2 = B * n * nm + pad;
+        float* p2 = nullptr;
+        bool ok = hipMalloc(reinterpret_cast<void**>(&p2), cnt2 * sizeof(float)) == hipSuccess;
+        ok = ok && hipMemset(p2, 0, cnt2 * sizeof(float)) == hipSuccess;
+        ok = ok && hipStreamCreateWithFlags(&c->bw.side, hipStreamNonBlocking) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&c->bw.ev_start, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < 2 && ok; ++i)
+          ok = hipEventCreateWithFlags(&c->bw.ev_ready[i], hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&c->bw.ev_free[i], hipEventDisableTiming) == hipSuccess;
+        if (ok) {
+          c->allocs.push_back(p2);
+          c->bw.ABt2 = p2;
+        } else {
+          (void)hipGetLastError();
+          if (p2) (void)hipFree(p2);
+          if (c->bw.side) { (void)hipStreamDestroy(c->bw.side); c->bw.side = nullptr; }
+          if (c->bw.ev_start) { (void)hipEventDestroy(c->bw.ev_start); c->bw.ev_start = nullptr; }
+          for (int i = 0; i < 2; ++i) {
+            if (c->bw.ev_ready[i]) { (void)hipEventDestroy(c->bw.ev_ready[i]); c->bw.ev_ready[i] = nullptr; }
+            if (c->bw.ev_free[i]) { (void)hipEventDestroy(c->bw.ev_free[i]); c->bw.ev_free[i] = nullptr; }
           }
         }
       }
@@ -673,24 +661,19 @@ static int backward_pass(gmpc_ctx* c, int B, const float* X, const float* U, con
   }
   {
     ProfScope ps(c, PROF_LINEARIZE, s);
-    // matrix-core chain; the VALU chain only serves shapes the MFMA tiling does not cover (or
-    // GMPC_LINEARIZE=valu, kept for A/B timing) -- both are HIP kernels of this library
-    static const int force = []() {
-      const char* e = getenv("GMPC_LINEARIZE");
-      return !e ? 0 : strcmp(e, "valu") == 0 ? 2 : strcmp(e, "lds") == 0 ? 1 : 0;
-    }();
+    // matrix-core chain; the VALU chain only serves shapes the MFMA tiling does not cover -- both are HIP
+    // kernels of this library
     // 1st choice: register-resident chain (compiled for the common equal-width shapes), 2nd: the
     // LDS-operand chain (any shape), 3rd: VALU
     if (c->dynl) {
       gmpc_launch_dynl_jac(B, sh.T, sh.T, 0, c->dl, X, U, active, AB, s);
       c->lin_kernel = "k_dynl_jac";
-    } else if (force == 0 && gmpc_launch_linearize_regs(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks,
-                                                         active, AB, 1, 0, s) == 0) {
+    } else if (gmpc_launch_linearize_regs(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
+                                          s) == 0) {
       snprintf(c->lin_kernel_buf, sizeof(c->lin_kernel_buf), "%s", gmpc_linearize_regs_last_name());
       c->lin_kernel = c->lin_kernel_buf;
-    } else if (force == 2 ||
-        gmpc_launch_linearize_mfma(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
-                                   s) != 0) {
+    } else if (gmpc_launch_linearize_mfma(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
+                                          s) != 0) {
       if (gmpc_launch_linearize(B, sh.T, sh.n, sh.m, c->dyn, c->masks, active, AB, s) != 0)
         return fail(GMPC_EINVAL, "linearize: unsupported row count for n=%d", sh.n);
       c->lin_kernel = "k_linearize (vector ALU)";

@@ -685,7 +685,7 @@ bool gmpc_riccati_w_shape(const RiccatiArgs& a);
 void gmpc_launch_riccati_w(const RiccatiArgs& a, hipStream_t s);
 
 void gmpc_launch_riccati(const RiccatiArgs& a, hipStream_t s) {
-  if (gmpc_riccati_w_shape(a)) {          // one wave per trajectory, products on the matrix pipe
+  if (gmpc_riccati_w_shape(a)) {          // two waves per trajectory, products on the matrix pipe
     gmpc_launch_riccati_w(a, s);
     return;
   }

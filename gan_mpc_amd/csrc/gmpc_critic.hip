@@ -11,7 +11,6 @@
 // the concatenated kernel Wcat = [Wx; Wh] ((n+F) x 4F, exactly the flat critic layout), the cell
 // update runs as thread (unit, wave).  Saved per (sequence, step): activated gates, c_t, h_{t-1}.
 #include "gmpc_device.h"
-#include <cstdlib>
 
 
 // NXR > 0: the input size n is known at compile time and thread j keeps column j of [Wx; Wh]
@@ -1052,7 +1051,7 @@ bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_float
   // one chunk length (rows per wave-tile) for all problems, so that every wave does the same amount
   // of work: the shortest one whose partial sums fit the buffer and that needs <= 4096 wave-tiles
   static const int rpcs[] = {64, 96, 128, 192, 256, 384, 512, 768, 1024, 2048, 4096, 8192, 1 << 30};
-  static const long max_items = getenv("GMPC_WG_ITEMS") ? atol(getenv("GMPC_WG_ITEMS")) : 4096;
+  constexpr long max_items = 4096;
   int rpc = 0;
   for (int cand : rpcs) {
     long need = 0, items = 0;

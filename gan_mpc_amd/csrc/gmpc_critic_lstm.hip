@@ -25,7 +25,6 @@
 // Saved by the forward sweep for the backward one (internal layouts, one float per thread and step, coalesced):
 // the activated gates AFTER the transpose (4 planes), c_t, h_t.
 #include "gmpc_device.h"
-#include <cstdlib>
 
 typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
 
@@ -381,13 +380,8 @@ bool gmpc_launch_lstm_fwd2(int Bc, const CriticDesc& cd, const float* xseq, floa
   }
 }
 
-#ifndef GMPC_LSTM2_BWD_NG
-#define GMPC_LSTM2_BWD_NG 2     // groups of 4 sequences per workgroup of the backward sweep (see k_lstm_bwd2)
-#endif
-static int bwd2_groups(int Bc) {
-  static const int env = getenv("GMPC_LSTM2_BWD_NG") ? atoi(getenv("GMPC_LSTM2_BWD_NG")) : GMPC_LSTM2_BWD_NG;
-  return (env == 2 && Bc > 4) ? 2 : 1;
-}
+// groups of 4 sequences per workgroup of the backward sweep (see k_lstm_bwd2)
+static int bwd2_groups(int Bc) { return Bc > 4 ? 2 : 1; }
 
 template <int NX>
 static void launch_bwd2(int Bc, const CriticDesc& cd, const float* xseq, const float* G, const float* Cst,
@@ -720,25 +714,15 @@ void gmpc_launch_mlp_transpose_all(const MlpDesc& d, hipStream_t s) {
   hipLaunchKernelGGL(k_mlp_transpose_all, dim3((cmax + 31) / 32, (rmax + 31) / 32, d.L), dim3(256), 0, s, d);
 }
 
-int gmpc_head2_rows() {
-  static const int g = [] {
-    const char* e = getenv("GMPC_HEAD_G");
-    // rows per workgroup = 4 G.  Measured (C3, 2048 sequences, head 3 x 256, alone): G = 2 0.049 ms, 3 0.056, 4 0.063 --
-    // the layer chain is latency-bound per workgroup, more workgroups beat more rows per weight load
-    const int v = e ? atoi(e) : 2;
-    return v >= 2 && v <= 4 ? v : 2;
-  }();
-  return 4 * g;
-}
+// rows per workgroup = 4 G with G = 2.  Measured (C3, 2048 sequences, head 3 x 256, alone): G = 2 0.049 ms, 3 0.056,
+// 4 0.063 -- the layer chain is latency-bound per workgroup, more workgroups beat more rows per weight load
+int gmpc_head2_rows() { return 8; }
 
 void gmpc_launch_head2(int Bc, const CriticDesc& cd, int loss_kind, const float* hT, const float* label, float* score,
                        float* loss, float* acts, float* dels, float* plast, float* dhT, int act_stride,
                        hipStream_t s) {
   const int R = gmpc_head2_rows();
   const dim3 grid((Bc + R - 1) / R), blk(GMPC_THREADS);
-  switch (R / 4) {
-    case 2: hipLaunchKernelGGL(k_head2<2>, grid, blk, 0, s, Bc, cd, loss_kind, hT, label, score, loss, acts, dels, plast, dhT, act_stride); break;
-    case 4: hipLaunchKernelGGL(k_head2<4>, grid, blk, 0, s, Bc, cd, loss_kind, hT, label, score, loss, acts, dels, plast, dhT, act_stride); break;
-    default: hipLaunchKernelGGL(k_head2<3>, grid, blk, 0, s, Bc, cd, loss_kind, hT, label, score, loss, acts, dels, plast, dhT, act_stride); break;
-  }
+  hipLaunchKernelGGL(k_head2<2>, grid, blk, 0, s, Bc, cd, loss_kind, hT, label, score, loss, acts, dels, plast, dhT,
+                     act_stride);
 }

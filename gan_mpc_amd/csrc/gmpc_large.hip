@@ -538,17 +538,9 @@ static void launch_lds(const BgemmArgs& a0, hipStream_t s) {
   const long total = (long)a.batch * lb;
   const long per = (total + 7) / 8;
   // 16-byte staging needs columns in groups of four (M, N multiples of 4); the ROWS need not start on 16 bytes:
-  // buffer_load_dwordx4 takes any 4-byte-aligned address (ld = n + m = 393 at C4) -- GMPC_BG_VEC_ALIGNED=1 asks for
-  // 16-byte rows as the first version did
-  static const bool want_al = [] { const char* e = getenv("GMPC_BG_VEC_ALIGNED"); return e != nullptr && e[0] == '1'; }();
-  auto al4 = [](const void* p_, long st, int ld) {
-    return p_ == nullptr || !want_al || (((uintptr_t)p_ & 15) == 0 && (st & 3) == 0 && (ld & 3) == 0);
-  };
+  // buffer_load_dwordx4 takes any 4-byte-aligned address (ld = n + m = 393 at C4)
   // (192-wide blocks stage 16 bytes per thread with 16-row stages only: 8 rows x 192 columns are 1.5 loads per thread)
-  const bool vec = (a.M & 3) == 0 && (a.N & 3) == 0 && al4(a.X, a.sx, a.ldx) &&
-                   al4(a.Y, a.sy, a.ldy) && al4(a.K2 ? a.X2 : nullptr, a.sx2, a.ldx2) &&
-                   al4(a.K2 ? a.Y2 : nullptr, a.sy2, a.ldy2) && al4(a.K3 ? a.X3 : nullptr, a.sx3, a.ldx3) &&
-                   al4(a.K3 ? a.Y3 : nullptr, a.sy3, a.ldy3);
+  const bool vec = (a.M & 3) == 0 && (a.N & 3) == 0;
   if (vec)
     hipLaunchKernelGGL((k_bgemm_tn_lds<WMT, WNT, WNT == 2 ? GMPC_BG_KC_VEC22 : GMPC_BG_KC_VEC, true>), dim3((unsigned)(per * 8)),
                        dim3(GMPC_THREADS), 0, s, a);
@@ -560,28 +552,24 @@ static void launch_lds(const BgemmArgs& a0, hipStream_t s) {
 void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s) {
   // a thin product whose wide operand is worth streaming (k_bthin)
   {
-    static const bool off = [] { const char* e = getenv("GMPC_BTHIN"); return e != nullptr && e[0] == '0'; }();
     const bool widex = a.N <= 64 && a.M >= 128, widey = a.M <= 64 && a.N >= 128;
-    if (!off && (widex || widey) && a.K >= 2 * BT_RD && a.E == nullptr && a.rowmask == nullptr && a.K2 == 0 &&
+    if ((widex || widey) && a.K >= 2 * BT_RD && a.E == nullptr && a.rowmask == nullptr && a.K2 == 0 &&
         a.K3 == 0 && !a.upper_only) {
       const int Wd = widex ? a.M : a.N, Th = widex ? a.N : a.M;
       // 128 columns per wave (16-byte loads) when that still gives every SIMD a few waves, else 64 (8-byte loads,
       // twice the waves: PB at the C4 shard is 1536 waves of 128 columns -- 1.5 per SIMD, 0.084 ms -- or 3072 of
       // 64, 0.073 ms); a thin operand of 33..64 columns goes through one wave as two strips
-      static const int ntj_env = [] { const char* e = getenv("GMPC_BTHIN_NTJ"); return e ? atoi(e) : 0; }();
-      static const int ns_env = [] { const char* e = getenv("GMPC_BTHIN_NS"); return e ? atoi(e) : 0; }();
-      const int ns = ns_env == 1 ? 1 : Th > 32 ? 2 : 1;
+      const int ns = Th > 32 ? 2 : 1;
       const long waves4 = (long)a.batch * ((Wd + 127) / 128) * ((Th + 32 * ns - 1) / (32 * ns));
       // (two strips x four tiles are 268 registers, one wave per SIMD: 0.387 ms against 0.360 with two tiles for
       // the [64 x 1088] x K = 200 products of C5)
-      const int ntj = ntj_env == 2 || ntj_env == 4 ? ntj_env : (waves4 < 4096 || ns == 2) ? 2 : 4;
+      const int ntj = (waves4 < 4096 || ns == 2) ? 2 : 4;
       const long total = (long)a.batch * ((Wd + 32 * ntj - 1) / (32 * ntj)) * ((Th + 32 * ns - 1) / (32 * ns));
       const dim3 grid((unsigned)((total + 3) / 4)), blk(GMPC_THREADS);
 #define BT_LAUNCH(WX, NJ, S) hipLaunchKernelGGL((k_bthin<WX, NJ, BT_RD, S>), grid, blk, 0, s, a)
-#define BT_LAUNCH2(WX, NJ) do { if (ns == 2) BT_LAUNCH(WX, NJ, 2); else BT_LAUNCH(WX, NJ, 1); } while (0)
-      if (widex) { if (ntj == 2) BT_LAUNCH2(true, 2); else BT_LAUNCH2(true, 4); }
-      else       { if (ntj == 2) BT_LAUNCH2(false, 2); else BT_LAUNCH2(false, 4); }
-#undef BT_LAUNCH2
+      if (ns == 2)       { if (widex) BT_LAUNCH(true, 2, 2); else BT_LAUNCH(false, 2, 2); }
+      else if (ntj == 2) { if (widex) BT_LAUNCH(true, 2, 1); else BT_LAUNCH(false, 2, 1); }
+      else               { if (widex) BT_LAUNCH(true, 4, 1); else BT_LAUNCH(false, 4, 1); }
 #undef BT_LAUNCH
       return;
     }
@@ -603,8 +591,6 @@ void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s) {
       }
       if (waste < 0 || padded <= waste) { waste = padded; best = w; }
     }
-    static const int w_env = [] { const char* e = getenv("GMPC_BG_UPPER_W"); return e ? atoi(e) : 0; }();
-    if (a.upper_only && w_env >= 2 && w_env <= 4) best = w_env;      // (A/B timing of the block width)
     switch (best) {
       case 2: launch_lds<2, 2>(a, s); break;
       case 3: launch_lds<2, 3>(a, s); break;
@@ -1487,20 +1473,18 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
   // (read per pass, not once: the tests compare the two forms of the gain solve inside one process)
   const char* sv_env = getenv("GMPC_BIG_SOLVE");
   const bool solve_valu = sv_env != nullptr && strcmp(sv_env, "valu") == 0;
-  // One step ahead on a side stream: the Jacobians of a step ([A | B], or the factor V^T of the low-rank form) do
-  // not depend on P.  Step t's are produced into copy t & 1 of their buffer while step t + 1's products run on the
-  // caller's stream -- the Jacobian chain / the factor GEMMs fill the matrix pipe under k_big_step, k_big_pupdate,
-  // the thin products and the transposes, which leave it idle.  ev_ready[i]: copy i is written; ev_free[i]: the point of
-  // the caller's stream behind which copy i may be overwritten.
-  const bool pipe = w.side != nullptr && dl == nullptr && (lowrank ? w.Vt2 != nullptr : w.ABt2 != nullptr);
-  float* const ABc[2] = {w.ABt, pipe && !lowrank ? w.ABt2 : w.ABt};
-  float* const Vtc[2] = {w.Vt, pipe && lowrank ? w.Vt2 : w.Vt};
+  // One step ahead on a side stream (dense form): the Jacobians [A | B] of a step do not depend on P.  Step t's
+  // are produced into copy t & 1 of the buffer while step t + 1's products run on the caller's stream -- the
+  // Jacobian chain fills the matrix pipe under k_big_step, k_big_pupdate, the thin products and the transposes, which
+  // leave it idle.  ev_ready[i]: copy i is written; ev_free[i]: the point of the caller's stream behind which copy i
+  // may be overwritten.  (The low-rank form gains nothing from it: its factor GEMMs and k_big_step slow each other
+  // down by what the overlap saves, C5 1.980 vs 1.984 s.)
+  const bool pipe = !lowrank && dl == nullptr && w.side != nullptr && w.ABt2 != nullptr;
+  float* const ABc[2] = {w.ABt, pipe ? w.ABt2 : w.ABt};
   int rc_side = 0;
   auto jacobians = [&](int t, hipStream_t st) {
     if (lowrank) {
-      BigWork wv = w;
-      wv.Vt = Vtc[t & 1];
-      big_lowrank_factors(wv, B, dyn, masks, t, active, st);
+      big_lowrank_factors(w, B, dyn, masks, t, active, st);
     } else if (gmpc_launch_linearize_regs(B, T, n, m, dyn, lp, masks, active, ABc[t & 1], T, t, st) != 0 &&
                gmpc_launch_linearize_mfma(B, T, n, m, dyn, lp, masks, active, ABc[t & 1], T, t, st) != 0) {
       rc_side = -1;
@@ -1523,20 +1507,8 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
   for (int t = T - 1; t >= 0; --t) {
     const float* A = ABc[t & 1];
     const float* Bm = ABc[t & 1] + n;
-    const float* Vt_t = Vtc[t & 1];
     const long shn = (long)h * n, shnm = (long)h * nm;
     const float* WLT = lowrank ? dyn.WT[dyn.L - 1] : nullptr;     // [n][h]: W_L^T, the TN left operand of W_L (.)
-    // step t - 1's Jacobians start when step t reaches its stretch of kernels that leave the matrix pipe idle (the
-    // thin products, k_big_step, ...): started at the top of the step they only shared the pipe with the step's
-    // first big GEMM, both at half speed (kernel trace: linearize 0.66 ms beside PA 1.04 ms, then 0.36 ms of thin
-    // products and k_big_step alone)
-    auto start_next = [&]() {
-      if (!pipe || t == 0) return;
-      ev(hipEventRecord(w.ev_free[(t - 1) & 1], s));        // (the copy's last reader was step t + 1; this point is later)
-      ev(hipStreamWaitEvent(w.side, w.ev_free[(t - 1) & 1], 0));
-      jacobians(t - 1, w.side);
-      ev(hipEventRecord(w.ev_ready[(t - 1) & 1], w.side));
-    };
     if (pipe) ev(hipStreamWaitEvent(s, w.ev_ready[t & 1], 0));
     else if (dl == nullptr) jacobians(t, s);
     if (rc_side != 0) return bail();
@@ -1551,23 +1523,22 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
       float* Yt = w.PAB;                                                                        // [n][h]
       hipLaunchKernelGGL(k_btranspose, dim3((n + 63) / 64, (h + 63) / 64, B), dim3(GMPC_THREADS), 0, s, h, n,
                          w.W1b, Yt, active);
-      float* S = pipe ? w.Sm : w.Sa;                          // [h][h] (Sa / Sb are the factor products' scratch)
+      float* S = w.Sa;                                        // [h][h] (Sa / Sb are the factor products' scratch)
       const long shh = (long)h * h;
       gmpc_launch_bgemm_tn(gemm(h, h, n, WLT, 0, h, Yt, shn, h, S, shh, h), s);                 // S = W_L Y^T
       // W2b = S V^T / 2 + [Y | 0] = [Z | S Vu^T / 2]   (S symmetric up to rounding: S^T V^T is the TN form)
-      BgemmArgs g2 = gemm(h, n, h, S, shh, h, Vt_t, shnm, nm, w.W2b, shnm, nm);
+      BgemmArgs g2 = gemm(h, n, h, S, shh, h, w.Vt, shnm, nm, w.W2b, shnm, nm);
       g2.alpha = 0.5f; g2.E = w.W1b; g2.se = shn; g2.lde = n; g2.En = n;
       gmpc_launch_bgemm_tn(g2, s);
-      BgemmArgs g3 = gemm(h, m, h, S, shh, h, Vt_t + n, shnm, nm, w.W2b + n, shnm, nm);
+      BgemmArgs g3 = gemm(h, m, h, S, shh, h, w.Vt + n, shnm, nm, w.W2b + n, shnm, nm);
       g3.alpha = 0.5f;
       gmpc_launch_bgemm_tn(g3, s);
-      BgemmArgs g4 = gemm(m, nm, h, Vt_t + n, shnm, nm, w.W2b, shnm, nm, w.HG, smnm, nm);       // 2 Vu W2b
+      BgemmArgs g4 = gemm(m, nm, h, w.Vt + n, shnm, nm, w.W2b, shnm, nm, w.HG, smnm, nm);       // 2 Vu W2b
       g4.alpha = 2.f;
       gmpc_launch_bgemm_tn(g4, s);
-      BgemmArgs g5 = gemm(m, n, h, Vt_t + n, shnm, nm, w.W1b, shn, n, w.HG, smnm, nm);          // - Vu [Y | 0]
+      BgemmArgs g5 = gemm(m, n, h, w.Vt + n, shnm, nm, w.W1b, shn, n, w.HG, smnm, nm);          // - Vu [Y | 0]
       g5.alpha = -1.f; g5.beta = 1.f;
       gmpc_launch_bgemm_tn(g5, s);
-      start_next();
     } else {
     if (dl) gmpc_launch_dynl_jac(B, T, 1, t, *dl, X, U, active, w.ABt, s);
     // [PA | PB] = P [A | B]   (P symmetric, so P = P^T is the "TN" left operand)
@@ -1575,16 +1546,25 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
     gmpc_launch_bgemm_tn(gemm(n, m, n, w.P, snn, n, Bm, snm, nm, w.PAB + n, snm, nm), s);
     // [H | Gr] = B^T [PA | PB]
     gmpc_launch_bgemm_tn(gemm(m, nm, n, Bm, snm, nm, w.PAB, snm, nm, w.HG, smnm, nm), s);
-    // (behind the two thin products: started behind PA the chain stretched [H | G_r] from 0.09 to 0.6 ms -- C4 98.8 /
-    // 100.3 / 98.0 ms for a start behind PA / PB / [H | G_r], 99.6 without the side stream)
-    start_next();
+    // step t - 1's Jacobians start when step t reaches its stretch of kernels that leave the matrix pipe idle (the
+    // thin products, k_big_step, ...): started at the top of the step they only shared the pipe with the step's
+    // first big GEMM, both at half speed (kernel trace: linearize 0.66 ms beside PA 1.04 ms, then 0.36 ms of thin
+    // products and k_big_step alone); behind the two thin products: started behind PA the chain stretched [H | G_r]
+    // from 0.09 to 0.6 ms -- C4 98.8 / 100.3 / 98.0 ms for a start behind PA / PB / [H | G_r], 99.6 without the side
+    // stream
+    if (pipe && t > 0) {
+      ev(hipEventRecord(w.ev_free[(t - 1) & 1], s));        // (the copy's last reader was step t + 1; this point is later)
+      ev(hipStreamWaitEvent(w.side, w.ev_free[(t - 1) & 1], 0));
+      jacobians(t - 1, w.side);
+      ev(hipEventRecord(w.ev_ready[(t - 1) & 1], w.side));
+    }
     }
     if (curv) {
       gmpc_launch_dynl_curv(B, T, 1, t, *dl, X, U, lam_sol, active, w.Phi, s);
       gmpc_launch_add_phi(B, n, m, w.Phi, w.HG, nullptr, s);
     }
     BigStepArgs a;
-    a.Vt = lowrank ? Vt_t : nullptr; a.WL = lowrank ? dyn.W[dyn.L - 1] : nullptr; a.h = h;
+    a.Vt = lowrank ? w.Vt : nullptr; a.WL = lowrank ? dyn.W[dyn.L - 1] : nullptr; a.h = h;
     a.B = B; a.n = n; a.m = m; a.T = T; a.t = t;
     a.mode = lx != nullptr ? 1 : 0; a.lx = lx; a.Bvec = Bvec;
     a.X = X; a.U = U; a.goal = goal; a.ng = w.ng; a.mpc_w = mpc_w; a.ABt = A; a.HG = w.HG; a.KV = w.KV; a.VK = w.VK;
@@ -1593,16 +1573,15 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
     a.solve_valu = solve_valu ? 1 : 0;
     hipLaunchKernelGGL(k_big_step, dim3(B), dim3(GMPC_THREADS), lds, s, a);
     // T1 = A^T (PA) + [K; V]^T [V; K], upper blocks only   (low-rank form: P + Vx Z + Z^T Vx^T)
-    BgemmArgs g = lowrank ? gemm(n, n, h, Vt_t, shnm, nm, w.W2b, shnm, nm, w.T1, snn, n)
+    BgemmArgs g = lowrank ? gemm(n, n, h, w.Vt, shnm, nm, w.W2b, shnm, nm, w.T1, snn, n)
                           : gemm(n, n, n, A, snm, nm, w.PAB, snm, nm, w.T1, snn, n);
     g.X2 = w.KV; g.sx2 = 2 * smn; g.ldx2 = n;
     g.Y2 = w.VK; g.sy2 = 2 * smn; g.ldy2 = n; g.K2 = 2 * m;
     if (lowrank) {
       g.E = w.P; g.se = snn; g.lde = n; g.En = n;
-      g.X3 = w.W2b; g.sx3 = shnm; g.ldx3 = nm; g.Y3 = Vt_t; g.sy3 = shnm; g.ldy3 = nm; g.K3 = h;
+      g.X3 = w.W2b; g.sx3 = shnm; g.ldx3 = nm; g.Y3 = w.Vt; g.sy3 = shnm; g.ldy3 = nm; g.K3 = h;
     }
-    static const bool full_t1 = getenv("GMPC_BIG_FULL_T1") != nullptr;   // A/B timing only
-    g.upper_only = full_t1 ? 0 : 1;
+    g.upper_only = 1;
     gmpc_launch_bgemm_tn(g, s);
     if (curv) gmpc_launch_add_phi(B, n, m, w.Phi, nullptr, w.T1, s);
     hipLaunchKernelGGL(k_big_pupdate, dim3(nt * (nt + 1) / 2, 1, B), dim3(GMPC_THREADS), 0, s, n, w.ng > 0 ? w.ng : n, T, t, X,

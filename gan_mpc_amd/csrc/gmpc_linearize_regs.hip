@@ -20,7 +20,6 @@
 // 2 KS - 1), all hidden layers of the same width, n + m <= 32.  Everything else runs the LDS variant.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 
 #include "gmpc_device.h"
 #ifndef GMPC_LIN_RD0
@@ -400,17 +399,12 @@ int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dy
     if (dyn.dims[l] != H) return -1;
   if (n + m > 32) {
     // wide inputs (large-state path): the 200-wide instantiation only
-    static const bool off = getenv("GMPC_LIN_WIDE") != nullptr && getenv("GMPC_LIN_WIDE")[0] == '0';
-    if (off || H != 200 || lp.NT != 7 || 32 * lp.NTF * lp.NGF < ((n + m + 31) / 32 + 3) / 4 * 4 * 32) return -1;
+    if (H != 200 || lp.NT != 7 || 32 * lp.NTF * lp.NGF < ((n + m + 31) / 32 + 3) / 4 * 4 * 32) return -1;
     return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   }
   if (lp.NTF != 1 || lp.NGF != 1) return -1;
-  if (H == 200 && lp.NT == 7) {
-    static const bool no_tail = getenv("GMPC_LIN_NOTAIL") != nullptr;
-    if (!no_tail)
-      return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
-    return launch_regs<7, 100>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
-  }
+  if (H == 200 && lp.NT == 7)
+    return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   if (H == 128 && lp.NT == 4)
     return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   if (H == 64 && lp.NT == 2)

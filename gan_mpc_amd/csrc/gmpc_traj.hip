@@ -1,7 +1,7 @@
 // Sequential-in-time trajectory kernels: rollout + cost, and the DDP line search.  This file holds the
 // general (any network shape) VALU form, the line-search bookkeeping kernels and the launchers; the
 // reference's default dynamics network (3 x 200) takes the register-weight MFMA form of
-// gmpc_traj_rw.hip (GMPC_TRAJ=valu forces the general form).
+// gmpc_traj_rw.hip.
 //
 // One 256-thread workgroup owns GMPC_TB = 4 trajectories for the whole horizon.  The state and
 // control of the current step live in LDS as float4 (one component per trajectory), every layer is
