@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "gmpc_device.h"
+#include "gmpc_fused_solve.h"
 
 // launchers defined in the kernel translation units ---------------------------------------------
 void gmpc_launch_rollout(const TrajArgs&, hipStream_t);
@@ -229,6 +230,7 @@ struct gmpc_ctx {
   float *obj, *alpha, *obj_step, *U_step;
   int *iters, *cont;
   int* hcont = nullptr;                       // pinned ring of continuation flags (gmpc_ilqr_solve)
+  float* fzcand = nullptr;                    // line-search candidates of gmpc_ilqr_solve_fused (shapes it covers)
   hipEvent_t poll_ev[GMPC_POLL_DEPTH] = {};
   int solB = 0;
   // bilevel workspace
@@ -427,6 +429,7 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
   A_(adjs, B * (T + 1) * n);
   A_(obj, B); A_(alpha, B); A_(obj_step, B); A_(U_step, B);
   A_(iters, B); A_(cont, B);
+  if (!c->dynl && !c->big && s.T <= GMPC_FZ_MAX_T) A_(fzcand, B * GMPC_FZ_NC * ((T + 1) * n + T * m));
   // bilevel
   int cin = 0, cout_ = 0;
   for (int l = 0; l < s.cost_layers; ++l) { cin += s.cost_dims[l]; cout_ += s.cost_dims[l + 1]; }
@@ -829,6 +832,42 @@ extern "C" int gmpc_ilqr_solve(gmpc_ctx* c, int B, const float* x0, const float*
 }
 
 // critic ---------------------------------------------------------------------------------------
+// The whole solve in one launch (gmpc_fused_solve.hip): same results and ctx state as gmpc_ilqr_solve on the shapes
+// it covers, nothing waited for on the host.
+extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const float* U_init,
+                                     const float* goal, const gmpc_ilqr_opts* opts, float* X, float* U,
+                                     float* obj, float* grad, float* adjoints, int* iterations,
+                                     void* stream) {
+  TRY(check_call(c, B));
+  if (!x0 || !U_init || !goal || !opts) return fail(GMPC_EINVAL, "null argument");
+  if (opts->make_psd) return fail(GMPC_EINVAL, "make_psd=1 is not on the reference path");
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl) return fail(GMPC_EINVAL, "fused solve: MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
+  if (c->big)
+    return fail(GMPC_EINVAL, "fused solve: n <= 64 and m <= 32 only (n=%d m=%d)", sh.n, sh.m);
+  if (sh.T > GMPC_FZ_MAX_T) return fail(GMPC_EINVAL, "fused solve: T <= %d only (T=%d)", GMPC_FZ_MAX_T, sh.T);
+  int k_max = 0;   // step sizes alpha_0 / 2^k above alpha_min (the line search's loop, as gmpc_launch_linesearch counts)
+  for (float al = opts->alpha_0; al > opts->alpha_min && k_max <= GMPC_FZ_MAX_HALVINGS; al *= 0.5f) ++k_max;
+  if (k_max > GMPC_FZ_MAX_HALVINGS)
+    return fail(GMPC_EINVAL, "fused solve: alpha_0 / alpha_min allow more than %d halvings", GMPC_FZ_MAX_HALVINGS);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  c->solB = 0;
+  FusedSolveArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = sh.n; a.m = sh.m; a.T = sh.T; a.k_max = k_max;
+  a.dyn = c->dyn; a.cost = c->cost; a.mpc_w = c->mpc_w; a.opts = *opts;
+  a.x0 = x0; a.U_init = U_init; a.goal_in = goal;
+  a.X = c->Xs; a.U = c->Us; a.goal = c->goals; a.AB = c->AB; a.QT = c->QT; a.qT = c->qT;
+  a.K = c->Ks; a.k = c->ks; a.grad = c->grads; a.adj = c->adjs;
+  a.obj = c->obj; a.alpha = c->alpha; a.obj_step = c->obj_step; a.U_step = c->U_step; a.iters = c->iters;
+  a.cand = c->fzcand;
+  a.oX = X; a.oU = U; a.oobj = obj; a.ograd = grad; a.oadj = adjoints; a.oiters = iterations;
+  gmpc_launch_ilqr_fused(a, B, s);
+  HIP_TRY(hipGetLastError());
+  c->solB = B;   // stream-ordered: a later call on the same stream sees the finished solve
+  return 0;
+}
+
 static int bind_critic(gmpc_ctx* c, const float* critic, CriticDesc& cd, hipStream_t s, bool head_transpose = true) {
   const gmpc_shape& sh = c->sh;
   if (sh.lstm_features <= 0) return fail(GMPC_EINVAL, "this ctx was created without a critic");

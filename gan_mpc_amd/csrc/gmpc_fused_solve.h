@@ -1,0 +1,31 @@
+// Argument block and limits of the one-launch iLQR solve (gmpc_fused_solve.hip, gmpc_ilqr_solve_fused).
+#pragma once
+#include "gmpc_device.h"
+
+#define GMPC_FZ_NC 8          // line-search candidates evaluated together (the rows of one forward pass)
+#define GMPC_FZ_JR 16         // rows of one pass of the mask / Jacobian chains
+#define GMPC_FZ_MAX_T 32      // horizon limit
+#define GMPC_FZ_MAX_HALVINGS 16
+#define GMPC_FZ_LHM (GMPC_MAX_LAYERS - 1)   // hidden layers of one MLP at most
+
+struct FusedSolveArgs {
+  int n, m, T, k_max;             // k_max: step sizes alpha_0 / 2^k, k < k_max, that stay above alpha_min
+  MlpDesc dyn, cost;              // W / WT / b of both MLPs (WT: the transposed copies gmpc_set_params builds)
+  const float* mpc_w;
+  gmpc_ilqr_opts opts;
+  const float* x0;                // [B][n]
+  const float* U_init;            // [B][T][m]
+  const float* goal_in;           // [B][T+1][n]
+  // ctx state the solve leaves behind (gmpc_bilevel_grad / gmpc_debug_buffer read it)
+  float *X, *U, *goal, *AB, *QT, *qT, *K, *k, *grad, *adj;
+  float *obj, *alpha, *obj_step, *U_step;
+  int* iters;
+  float* cand;                    // [B][GMPC_FZ_NC][(T+1) n + T m] candidate trajectories of the line search
+  // caller outputs (any may be null)
+  float *oX, *oU, *oobj, *ograd, *oadj;
+  int* oiters;
+};
+
+// LDS bytes of the kernel for a shape (the largest of its phases)
+size_t gmpc_fused_lds_bytes(int n, int m, int T);
+void gmpc_launch_ilqr_fused(const FusedSolveArgs& a, int B, hipStream_t s);

@@ -198,13 +198,21 @@ class Engine:
         return out
 
     def ilqr_solve(self, x0, U, goal, kwargs=None):
+        return self._solve(self.lib.gmpc_ilqr_solve, x0, U, goal, kwargs)
+
+    def ilqr_solve_fused(self, x0, U, goal, kwargs=None):
+        """The same solve in one kernel launch (gmpc_ilqr_solve_fused: MLP dynamics, n <= 64, m <= 32, T <= 32);
+        returns the same dict as ilqr_solve without synchronising the stream."""
+        return self._solve(self.lib.gmpc_ilqr_solve_fused, x0, U, goal, kwargs)
+
+    def _solve(self, fn, x0, U, goal, kwargs):
         B = x0.shape[0]
         n, m, T = self.n, self.m, self.T
         opts = make_opts(kwargs)
         out = dict(X=self.new(B, T + 1, n), U=self.new(B, T, m), obj=self.new(B),
                    grad=self.new(B, T, m), adjoints=self.new(B, T + 1, n),
                    iterations=self.new(B, dtype=torch.int32))
-        _lib.check(self.lib.gmpc_ilqr_solve(
+        _lib.check(fn(
             self.ctx, B, _ptr(x0), _ptr(U), _ptr(goal), C.byref(opts), _ptr(out["X"]), _ptr(out["U"]),
             _ptr(out["obj"]), _ptr(out["grad"]), _ptr(out["adjoints"]), _ptr(out["iterations"]),
             self._stream()))

@@ -44,8 +44,16 @@ class LqrBlock:
 
 
 class EvalMPC:
+    SOLVERS = ("rounds", "fused")
+
     def __init__(self, config, cost_model, dynamics_model, expert_model,
-                 trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None):
+                 trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds"):
+        """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
+        gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
+        short-horizon / batch-1 MPC action)."""
+        if solver not in self.SOLVERS:
+            raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
+        self.solver = solver
         self.config = config
         self.cost_model = cost_model
         self.dynamics_model = dynamics_model

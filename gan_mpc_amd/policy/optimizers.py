@@ -6,11 +6,17 @@ replaced by the policy object that owns the engine and the bound parameters.  Ev
 over the leading axis (the reference's jax.vmap axis)."""
 
 
+def _solver(policy, eng):
+    """The engine entry point of the policy's solver: "rounds" (gmpc_ilqr_solve, host-driven iterations) or
+    "fused" (gmpc_ilqr_solve_fused, the whole solve in one launch)."""
+    return eng.ilqr_solve_fused if getattr(policy, "solver", "rounds") == "fused" else eng.ilqr_solve
+
+
 def ilqr_solve(policy, dparams, x0, U, goal, trajax_ilqr_kwargs=None):
     """reference policy/optimizers.py:10-21 -> trajax ilqr.  Device tensors in, dict of device
     tensors out: X, U, obj, grad, adjoints, iterations (the `lqr` tuple stays in the ctx)."""
     eng = policy.bind(dparams, x0.shape[0])
-    return eng.ilqr_solve(x0, U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
+    return _solver(policy, eng)(x0, U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
 
 
 def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=None,
@@ -20,7 +26,7 @@ def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=N
     sign=+1 reproduces the reference as written."""
     B = x0.shape[0]
     eng = policy.bind(dparams, B)
-    sol = eng.ilqr_solve(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
+    sol = _solver(policy, eng)(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
     critic = dparams.view("critic_params") if loss_kind == 1 else None
     loss, grad_sum = eng.bilevel_grad(B, loss_kind, desired=desired, critic=critic, sign=sign,
                                       grad_sum=grad_sum)

@@ -159,6 +159,24 @@ int gmpc_ilqr_solve(gmpc_ctx* ctx, int B, const float* x0, const float* U_init, 
                     const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad,
                     float* adjoints, int* iterations, void* stream);
 
+/* a6 in ONE kernel launch: the complete iLQR solve of every trajectory, one workgroup per trajectory from the first
+ * rollout to the last iteration, no host round trip between iterations (the short-horizon / batch-1 MPC action regime:
+ * policy/eval.py:126-128 runs one solve per control step).  Same arguments and results as gmpc_ilqr_solve (the line
+ * search evaluates its halvings in groups and accepts the first decrease in halving order, as the sequential loop
+ * does); asynchronous on `stream`: nothing is synchronised, no host-built vectors.
+ * Coverage -- checked before any launch, anything else fails with GMPC_EINVAL ("fused ..."):
+ *   MLP dynamics only (dyn_lstm_features == 0); n <= 64 and m <= 32; T <= 32; at most 16 step sizes
+ *   alpha_0 / 2^k above alpha_min (the reference's 1 / 5e-5 needs 15); make_psd refused as by gmpc_ilqr_solve.
+ *   Every hidden width and cost fout the ctx accepts.
+ * ctx state left behind, as after gmpc_ilqr_solve: X, U, goals, obj, grad, adjoints; [A|B] of the final linearisation
+ * (gmpc_debug_buffer 5, [B][T][n][n+m]); the terminal quadratisation; K / k (6 / 7); alpha / obj_step / U_step
+ * (8 / 9 / 10); the held batch size -- gmpc_bilevel_grad / gmpc_upper_loss may follow on the same stream.  The relu masks
+ * of gmpc_rollout_cost, the line-search work lists and counters (gmpc_linesearch_candidates / _stats, debug buffers 12
+ * / 13) still describe the last round-based solve. */
+int gmpc_ilqr_solve_fused(gmpc_ctx* ctx, int B, const float* x0, const float* U_init, const float* goal,
+                          const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad,
+                          float* adjoints, int* iterations, void* stream);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
