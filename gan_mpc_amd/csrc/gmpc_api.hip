@@ -34,7 +34,7 @@ int gmpc_launch_dynfit(int, int, int, int, const MlpDesc&, const float*, const f
 int gmpc_big_backward(const BigWork&, int, const MlpDesc&, const LinPad&, const uint32_t*, const float*,
                       const float*, const float*, const float*, const float*, const float*, const int*,
                       float*, float*, float*, float*, const float*, float*, hipStream_t,
-                      const DynlDesc* dl = nullptr, const float* lam_sol = nullptr);
+                      const DynlDesc* dl = nullptr, const float* lam_sol = nullptr, const float* lu = nullptr);
 int gmpc_big_forward_tangent(const BigWork&, int, const MlpDesc&, const LinPad&, const uint32_t*,
                              const float*, const float*, float*, float*, hipStream_t,
                              const DynlDesc* dl = nullptr, const float* X = nullptr, const float* U = nullptr);
@@ -47,7 +47,7 @@ int gmpc_launch_terminal(int, int, int, const MlpDesc&, const float*, const floa
                          float*, float*, hipStream_t);
 void gmpc_launch_riccati(const RiccatiArgs&, hipStream_t);
 bool gmpc_riccati_w2h_shape(const RiccatiArgs&);
-void gmpc_launch_riccati_w2h(const RiccatiArgs&, const float* lx, float* bvec_out, hipStream_t);
+void gmpc_launch_riccati_w2h(const RiccatiArgs&, const float* lx, const float* lu, float* bvec_out, hipStream_t);
 size_t gmpc_riccati_lds_bytes(int n, int m);
 void gmpc_launch_transpose(int, int, const float*, float*, hipStream_t);
 void gmpc_launch_lstm_fwd(int, const CriticDesc&, const float*, float*, float*, float*, float*,
@@ -73,7 +73,7 @@ void gmpc_launch_adam(long, float*, const float*, float*, float*, float, int, do
                       double, double, float*, hipStream_t);
 void gmpc_launch_polyak(long, const float*, const float*, double, float*, hipStream_t);
 void gmpc_launch_l2loss(int, int, int, int, const float*, const float*, float*, float*, hipStream_t);
-void gmpc_launch_bvec(int, int, int, int, const float*, const float*, float*, hipStream_t);
+void gmpc_launch_bvec(int, int, int, int, const float*, const float*, const float*, float*, hipStream_t);
 void gmpc_launch_costvjp(int, int, int, int, const MlpDesc&, const float*, float, const float*,
                          const float*, const float*, int, const float*, const float*, float*, float*,
                          float*, int, hipStream_t);
@@ -1501,23 +1501,19 @@ extern "C" int gmpc_polyak(gmpc_ctx* c, long count, const float* prev, const flo
 }
 
 // bilevel ----------------------------------------------------------------------------------------
-extern "C" int gmpc_bilevel_grad(gmpc_ctx* c, int B, int loss_kind, const float* desired,
-                                 const float* critic, float sign, float* loss, float* grad_sum,
-                                 void* stream) {
-  TRY(check_call(c, B));
-  if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
-  if (!loss || !grad_sum) return fail(GMPC_EINVAL, "null argument");
-  hipStream_t s = static_cast<hipStream_t>(stream);
+// a8-a11 from the loss's cotangents at the solution held by the ctx: lx = dL/dX [B][T+1][n] (never null here),
+// lu = dL/dU [B][T][m] or null (a loss of X only).  Writes Bvec, H, dX and grad_sum.
+static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const float* lu, float sign,
+                                   float* grad_sum, hipStream_t s) {
   const gmpc_shape& sh = c->sh;
   const int n = sh.n, m = sh.m, T = sh.T;
-  TRY(upper_loss(c, B, loss_kind, desired, critic, loss, true, s));
   // a8: Bvec; a9+solve: structured Hessian solve; a11: cost_vjp
   if (c->big) {
     // step-major: the loss adjoint (Bvec) and the Riccati sweep of the Hessian solve share one
     // backward pass over re-linearised steps, the tangent roll is a second, forward pass
     if (gmpc_big_backward(c->bw, B, c->dyn, c->lp, c->masks, c->Xs, c->Us, c->goals, c->mpc_w, c->QT,
-                          c->qT, nullptr, c->Ks, c->ks, nullptr, nullptr, c->lx, c->Bvec, s,
-                          c->dynl ? &c->dl : nullptr, c->dynl ? c->adjs : nullptr) != 0 ||
+                          c->qT, nullptr, c->Ks, c->ks, nullptr, nullptr, lx, c->Bvec, s,
+                          c->dynl ? &c->dl : nullptr, c->dynl ? c->adjs : nullptr, lu) != 0 ||
         gmpc_big_forward_tangent(c->bw, B, c->dyn, c->lp, c->masks, c->Ks, c->ks, c->Hout, c->dX, s,
                                  c->dynl ? &c->dl : nullptr, c->Xs, c->Us) != 0)
       return fail(GMPC_EINVAL, "large-state bilevel: Jacobian kernel does not cover this shape");
@@ -1530,9 +1526,9 @@ extern "C" int gmpc_bilevel_grad(gmpc_ctx* c, int B, int loss_kind, const float*
     if (!c->dynl && gmpc_riccati_w2h_shape(r)) {
       // two waves per trajectory, products on the matrix pipe, the loss adjoint (a8) in the same sweep
       ProfScope ps(c, PROF_RICCATI, s);      // (bench.py: secondary.bilevel.kernel_ms)
-      gmpc_launch_riccati_w2h(r, c->lx, c->Bvec, s);
+      gmpc_launch_riccati_w2h(r, lx, lu, c->Bvec, s);
     } else {
-      gmpc_launch_bvec(B, T, n, m, c->AB, c->lx, c->Bvec, s);
+      gmpc_launch_bvec(B, T, n, m, c->AB, lx, lu, c->Bvec, s);
       if (c->dynl) {
         // smooth dynamics: the dense Hessian the reference solves with carries lam_{t+1} . d^2 f (oracle
         // second_order_lqr); lam = the adjoints of the solve's last backward pass
@@ -1557,6 +1553,36 @@ extern "C" int gmpc_bilevel_grad(gmpc_ctx* c, int B, int loss_kind, const float*
     aoff += M;
     doff += N;
   }
+  return 0;
+}
+
+extern "C" int gmpc_bilevel_grad(gmpc_ctx* c, int B, int loss_kind, const float* desired,
+                                 const float* critic, float sign, float* loss, float* grad_sum,
+                                 void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
+  if (!loss || !grad_sum) return fail(GMPC_EINVAL, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TRY(upper_loss(c, B, loss_kind, desired, critic, loss, true, s));
+  TRY(bilevel_from_cotangents(c, B, c->lx, nullptr, sign, grad_sum, s));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// a caller-defined upper-level loss (reference policy/optimizers.py:34-83 takes any `loss`): the caller has
+// differentiated it; the kernels read its lx / lu directly.  A null lx is a loss of U only: c->lx is zeroed.
+extern "C" int gmpc_bilevel_grad_cotangent(gmpc_ctx* c, int B, const float* lx, const float* lu, float sign,
+                                           float* grad_sum, void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
+  if (!grad_sum) return fail(GMPC_EINVAL, "null argument");
+  if (!lx && !lu) return fail(GMPC_EINVAL, "lx and lu are both null: the loss has no cotangent");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!lx) {
+    HIP_TRY(hipMemsetAsync(c->lx, 0, (size_t)B * (c->sh.T + 1) * c->sh.n * sizeof(float), s));
+    lx = c->lx;
+  }
+  TRY(bilevel_from_cotangents(c, B, lx, lu, sign, grad_sum, s));
   HIP_TRY(hipGetLastError());
   return 0;
 }

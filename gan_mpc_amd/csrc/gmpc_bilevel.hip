@@ -31,9 +31,11 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_l2loss(int B, int T, int n, in
   if (tid == 0) loss[b] = sh[0] * inv;
 }
 
-// a8: Bvec_t = B_t^T mu_{t+1}, mu_T = lx_T, mu_t = lx_t + A_t^T mu_{t+1}.  One wave per trajectory.
-__global__ __launch_bounds__(64) void k_bvec(int B, int T, int n, int m, const float* AB,
-                                             const float* lx, float* Bvec) {
+// a8: Bvec_t = B_t^T mu_{t+1} (+ lu_t), mu_T = lx_T, mu_t = lx_t + A_t^T mu_{t+1}.  One wave per trajectory.
+// lu = dL/dU [B][T][m] of a loss that depends on the controls (gmpc_bilevel_grad_cotangent), or null: then the
+// term is not added at all (adding 0 would turn a -0 of B^T mu into +0).
+__global__ __launch_bounds__(64) void k_bvec(int /*B*/, int T, int n, int m, const float* AB,
+                                             const float* lx, const float* lu, float* Bvec) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ABs = reinterpret_cast<float*>(smem);
   float* mu = ABs + n * (n + m);
@@ -48,6 +50,7 @@ __global__ __launch_bounds__(64) void k_bvec(int B, int T, int n, int m, const f
     for (int j = lane; j < m; j += 64) {
       float v = 0.f;
       for (int i = 0; i < n; ++i) v = fmaf(ABs[i * nm + n + j], mu[i], v);
+      if (lu != nullptr) v = v + lu[bt * m + j];
       Bvec[bt * m + j] = v;
     }
     for (int c = lane; c < n; c += 64) {
@@ -188,10 +191,10 @@ void gmpc_launch_l2loss(int B, int T, int n, int ng, const float* X, const float
                         float* lx, hipStream_t s) {
   hipLaunchKernelGGL(k_l2loss, dim3(B), dim3(GMPC_THREADS), 0, s, B, T, n, ng, X, desired, loss, lx);
 }
-void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* lx, float* Bvec,
+void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* lx, const float* lu, float* Bvec,
                       hipStream_t s) {
   const size_t lds = ((size_t)n * (n + m) + 2 * n) * sizeof(float);
-  hipLaunchKernelGGL(k_bvec, dim3(B), dim3(64), lds, s, B, T, n, m, AB, lx, Bvec);
+  hipLaunchKernelGGL(k_bvec, dim3(B), dim3(64), lds, s, B, T, n, m, AB, lx, lu, Bvec);
 }
 void gmpc_launch_costvjp(int B, int T, int n, int m, const MlpDesc& cm, const float* mpc_w,
                          float sign, const float* X, const float* U, const float* goal, int ng,

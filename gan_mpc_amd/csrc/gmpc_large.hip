@@ -623,6 +623,7 @@ struct BigStepArgs {
                          // 1: bilevel Hessian solve (oracle hessian_solve: no regulariser, LU with
                          //    partial pivoting, linear term -Bvec_t, loss adjoint mu in `lam`)
   const float* lx;       // mode 1: [B][T+1][n] d loss / d X
+  const float* lu;       // mode 1: [B][T][m]   d loss / d U, or null (a loss of X only: no term at all)
   float* Bvec;           // mode 1: [B][T][m]   out: B_t^T mu_{t+1}
   const float* X; const float* U; const float* goal; const float* mpc_w;
   int ng;                // columns of `goal` (0: n)
@@ -863,12 +864,13 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_big_step(BigStepArgs a) {
   const float isu = 1.f / su, isu3 = 1.f / (su * su * su);
   if (tid == 0) a.sbuf[b] = s;
   // linear terms of the two vector recursions: mode 0 the cost gradient (q_t, r_t) for both the
-  // adjoint lambda and the value vector p; mode 1 (d loss/d x_t, 0) for the loss adjoint and (0, -Bvec_t)
-  // for p
+  // adjoint lambda and the value vector p; mode 1 (d loss/d x_t, d loss/d u_t or 0) for the loss adjoint and
+  // (0, -Bvec_t) for p
   const bool m1 = a.mode == 1;
   for (int i = tid; i < n; i += blockDim.x)
     qv[i] = m1 ? a.lx[((size_t)b * (T + 1) + t) * n + i] : w1 * dv[i] / s;
-  for (int j = tid; j < m; j += blockDim.x) rv[j] = m1 ? 0.f : w0 * uv[j] / su;
+  for (int j = tid; j < m; j += blockDim.x)
+    rv[j] = m1 ? (a.lu != nullptr ? a.lu[bt * m + j] : 0.f) : w0 * uv[j] / su;
   __syncthreads();
   BS_STAMP(1)
   const bool lowrank = a.Vt != nullptr;
@@ -949,7 +951,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_big_step(BigStepArgs a) {
       for (int r = 0; r < RP; ++r) { gs += part[r * MC + tid]; hs += part[GMPC_THREADS + r * MC + tid]; }
       gs = rv[tid] + gs;
       if (m1) {
-        a.Bvec[bt * m + tid] = gs;          // B_t^T mu_{t+1}
+        a.Bvec[bt * m + tid] = gs;          // B_t^T mu_{t+1} (+ lu_t)
         hv[tid] = hs - gs;                  // h = -Bvec_t + B^T p
       } else {
         hv[tid] = rv[tid] + hs;
@@ -1440,11 +1442,12 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
                       const uint32_t* masks, const float* X, const float* U, const float* goal,
                       const float* mpc_w, const float* QT, const float* qT, const int* active, float* K,
                       float* k, float* grad, float* adj, const float* lx, float* Bvec, hipStream_t s,
-                      const DynlDesc* dl, const float* lam_sol) {
+                      const DynlDesc* dl, const float* lam_sol, const float* lu) {
   // lam_sol (bilevel solve of the LSTM dynamics only): the adjoints of the rollout objective at the solution;
   // the step's curvature Phi = lam_{t+1} . d^2 f joins R, M^T (through [H | G_r]) and Q (through T1)
   const bool curv = dl != nullptr && lx != nullptr && lam_sol != nullptr && w.Phi != nullptr;
-  // lx != null: the bilevel Hessian solve (k_big_step mode 1); grad / adj are not written then
+  // lx != null: the bilevel Hessian solve (k_big_step mode 1); grad / adj are not written then.  lu (mode 1 only,
+  // may be null): d loss / d U of a loss that depends on the controls, the linear term of Bvec
   const int n = w.n, m = w.m, T = w.T, nm = n + m;
   const dim3 ge((n * n + 255) / 256, B);
   hipLaunchKernelGGL(k_big_init, ge, dim3(256), 0, s, B, n, T, QT, qT, active, w.P, w.pvec, w.lam, adj,
@@ -1566,7 +1569,7 @@ int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad&
     BigStepArgs a;
     a.Vt = lowrank ? w.Vt : nullptr; a.WL = lowrank ? dyn.W[dyn.L - 1] : nullptr; a.h = h;
     a.B = B; a.n = n; a.m = m; a.T = T; a.t = t;
-    a.mode = lx != nullptr ? 1 : 0; a.lx = lx; a.Bvec = Bvec;
+    a.mode = lx != nullptr ? 1 : 0; a.lx = lx; a.lu = lx != nullptr ? lu : nullptr; a.Bvec = Bvec;
     a.X = X; a.U = U; a.goal = goal; a.ng = w.ng; a.mpc_w = mpc_w; a.ABt = A; a.HG = w.HG; a.KV = w.KV; a.VK = w.VK;
     a.pvec = w.pvec; a.lam = w.lam; a.sbuf = w.sbuf; a.gn2 = w.gn2; a.active = active;
     a.K = K; a.k = k; a.grad = grad; a.adj = adj;

@@ -349,14 +349,18 @@ __global__ __launch_bounds__(128) void k_riccati_w2(RiccatiArgs a) {
 //   * linear terms q~ = 0, r~_t = -Bvec_t with Bvec_t = B_t^T mu_{t+1}, mu_T = lx_T, mu_t = lx_t + A_t^T mu_{t+1}
 //     (policy/optimizers.py:78-83: the gradient of the upper loss with respect to the controls).  The helper wave
 //     runs that adjoint recursion in the same backward sweep -- it is the recursion it runs for lambda in mode 0
-//     with lx_t in the place of q_t -- and writes Bvec out: k_bvec (a launch of its own, 0.14 ms) is folded in;
+//     with lx_t in the place of q_t -- and writes Bvec out: k_bvec (a launch of its own, 0.14 ms) is folded in.
+//     LU: a loss that depends on the controls adds its cotangent, Bvec_t = lu_t + B_t^T mu_{t+1}
+//     (gmpc_bilevel_grad_cotangent); lu_t is prefetched one step ahead with lx_t.  Without LU the term is absent,
+//     not zero (adding 0 would turn a -0 of B^T mu into +0);
 //   * after the sweep, the forward tangent roll dU_t = k_t + K_t dX_t, dX_{t+1} = A_t dX_t + B_t dU_t on wave 0, the
 //     next step's operands requested one step ahead.
 // Reference: policy/optimizers.py:61-71, 86-105 (dense hessian + solve), restated as the structured solve of
 // oracle/gan_mpc_oracle.py:hessian_solve.
 // ------------------------------------------------------------------------------------------------
-template <int N_, int M_>
-__global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float* lx, float* bvec_out) {
+template <int N_, int M_, bool LU>
+__global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float* lx, const float* lu,
+                                                     float* bvec_out) {
   constexpr int n = N_, m = M_, nm = n + m, LD = 32;
   constexpr int NR = (n + 1) & ~1;
   constexpr int KP = NR / 2;
@@ -383,7 +387,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
     // ================= helper =================
     constexpr int PFN = (n * nm + 63) / 64;
     float pf_ab[PFN];
-    float pf_d = 0.f, pf_u = 0.f, pf_lx = 0.f;
+    float pf_d = 0.f, pf_u = 0.f, pf_lx = 0.f, pf_lu = 0.f;
     auto prefetch = [&](int tp) {
       const size_t btp = (size_t)b * T + tp;
 #pragma unroll
@@ -397,6 +401,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
         pf_lx = lx[((size_t)b * (T + 1) + tp) * n + lane];
       }
       if (lane < m) pf_u = a.U[btp * m + lane];
+      if (LU && lane >= n && lane < nm) pf_lu = lu[btp * m + lane - n];
     };
     // everything of step tp that needs neither P nor p: operands into buffer tp & 1, scalars, the loss adjoint
     auto prepare = [&](int tp) {
@@ -409,7 +414,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
       }
       if (lane < n) dvb[bf][lane] = pf_d;
       if (lane < m) uvb[bf][lane] = pf_u;
-      const float lxt = pf_lx;
+      const float lxt = pf_lx, lut = pf_lu;
       RW_SYNC();
       if (tp > 0) prefetch(tp - 1);
       const float* dv = dvb[bf];
@@ -432,8 +437,9 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
           ln = lxt + vl;                             // mu_t = lx_t + A^T mu
         } else {
           const int j = lane - n;
-          bvec_out[bt * m + j] = vl;                 // Bvec_t = B^T mu
-          rvb[bf][j] = -vl;                          // the Riccati sweep's linear term r~_t
+          const float bv = LU ? vl + lut : vl;
+          bvec_out[bt * m + j] = bv;                 // Bvec_t = B^T mu (+ lu_t)
+          rvb[bf][j] = -bv;                          // the Riccati sweep's linear term r~_t
         }
       }
       RW_SYNC();                                     // (every lane has read mu)
@@ -706,8 +712,12 @@ bool gmpc_riccati_w2h_shape(const RiccatiArgs& a) {
   if (e != nullptr && strcmp(e, "valu") == 0) return false;
   return a.mode == 1 && a.Phi == nullptr && a.active == nullptr && a.n == 17 && a.m == 6 && (a.ng == 0 || a.ng == a.n);
 }
-void gmpc_launch_riccati_w2h(const RiccatiArgs& a, const float* lx, float* bvec_out, hipStream_t s) {
-  hipLaunchKernelGGL((k_riccati_w2h<17, 6>), dim3(a.B), dim3(128), 0, s, a, lx, bvec_out);
+void gmpc_launch_riccati_w2h(const RiccatiArgs& a, const float* lx, const float* lu, float* bvec_out,
+                             hipStream_t s) {
+  if (lu != nullptr)
+    hipLaunchKernelGGL((k_riccati_w2h<17, 6, true>), dim3(a.B), dim3(128), 0, s, a, lx, lu, bvec_out);
+  else
+    hipLaunchKernelGGL((k_riccati_w2h<17, 6, false>), dim3(a.B), dim3(128), 0, s, a, lx, lu, bvec_out);
 }
 void gmpc_launch_riccati_w(const RiccatiArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((k_riccati_w2<17, 6>), dim3(a.B), dim3(128), 0, s, a);

@@ -227,6 +227,19 @@ class Engine:
                                               float(sign), _ptr(loss), _ptr(grad_sum), self._stream()))
         return loss, grad_sum
 
+    def bilevel_grad_cotangent(self, B, lx=None, lu=None, sign=1.0, grad_sum=None):
+        """The bilevel gradient of a caller-defined loss L(X, U) at the held solution: lx = dL/dX (B, T+1, n), lu =
+        dL/dU (B, T, m), either may be None (gmpc_bilevel_grad_cotangent).  -> grad_sum [3 + cost_count], summed
+        over the batch; grad_sum: optional caller-owned view."""
+        for name, t, shape in (("lx", lx, (B, self.T + 1, self.n)), ("lu", lu, (B, self.T, self.m))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"bilevel_grad_cotangent: {name} must be {shape}, got {tuple(t.shape)}")
+        grad_sum = self.new(3 + self.cost_count) if grad_sum is None else grad_sum
+        assert grad_sum.numel() == 3 + self.cost_count
+        _lib.check(self.lib.gmpc_bilevel_grad_cotangent(self.ctx, B, _ptr(lx), _ptr(lu), float(sign),
+                                                        _ptr(grad_sum), self._stream()))
+        return grad_sum
+
     def upper_loss(self, B, loss_kind, desired=None, critic=None):
         loss = self.new(B)
         _lib.check(self.lib.gmpc_upper_loss(self.ctx, B, int(loss_kind), _ptr(desired), _ptr(critic),

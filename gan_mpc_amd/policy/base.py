@@ -11,7 +11,9 @@ from gan_mpc_amd.policy import optimizers as opt
 
 
 class BaseMPC(eval_policy.EvalMPC):
-    LOSS_KIND = None  # 0: L2, 1: JS generator
+    # 0: L2, 1: JS generator (the kernels' own losses); None: the subclass's torch `loss`, differentiated per
+    # trajectory under torch.func (optimizers.loss_cotangents)
+    LOSS_KIND = None
 
     def __init__(self, config, cost_model, dynamics_model, expert_model, loss_vmap=(0,),
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, bilevel_sign=1.0, solver="rounds"):
@@ -34,18 +36,34 @@ class BaseMPC(eval_policy.EvalMPC):
         return super().get_optimal_values(params, history_x)
 
     def loss(self, xcseq, useq, params, *args):
+        """The upper-level loss of ONE trajectory (reference policy/base.py:84-85): xcseq (T+1, n) -- xc, carry
+        columns included --, useq (T, m), params the device parameters; a scalar torch tensor.  A subclass with
+        LOSS_KIND None overrides it with torch operations that torch.func can vmap and differentiate."""
         raise NotImplementedError
+
+    def _custom_loss(self):
+        """True for the subclass's own torch loss; NotImplementedError when there is no loss at all."""
+        if self.LOSS_KIND is not None:
+            return False
+        if type(self).loss is BaseMPC.loss:
+            raise NotImplementedError(f"{type(self).__name__} sets no LOSS_KIND and does not override loss()")
+        return True
 
     def batch_loss(self, dparams, history_X, desired):
         """mean over the (global) batch of loss(iLQR(x)) -- norm/cost_trainer.py:13-21."""
+        custom = self._custom_loss()
         B = len(history_X)
         packed = parallel.new_packed(1, self.device(), B)
         if B > 0:            # an empty shard still joins the exchange, with count 0
             dparams, sol = self._solve(dparams, history_X)
             eng = self._engine
-            crit = dparams.view("critic_params") if self.LOSS_KIND == 1 else None
-            loss = eng.upper_loss(B, self.LOSS_KIND, desired=eng.to_dev(desired) if desired is not None
-                                  else None, critic=crit)
+            if custom:       # the reference's jax.vmap(policy.loss, in_axes=(0, 0, None, 0))
+                loss, _, _ = opt.loss_cotangents(self.loss, sol["X"], sol["U"], dparams, (desired,),
+                                                 (0 if desired is not None else None,), want_grad=False)
+            else:
+                crit = dparams.view("critic_params") if self.LOSS_KIND == 1 else None
+                loss = eng.upper_loss(B, self.LOSS_KIND, desired=eng.to_dev(desired) if desired is not None
+                                      else None, critic=crit)
             torch.sum(loss, dim=0, keepdim=True, out=packed[:1])
         return parallel.allreduce_mean_from_sums(packed)[0]
 
@@ -54,8 +72,7 @@ class BaseMPC(eval_policy.EvalMPC):
         returns (avg_loss, grads) where grads is a flat device vector over [mpc_weights | cost_params]
         (every other leaf's gradient is exactly zero in the reference), both averaged
         over the global batch."""
-        if self.LOSS_KIND is None:
-            raise NotImplementedError
+        custom = self._custom_loss()
         dparams = self.to_device_params(params)
         hx = np.asarray(history_X, np.float32)
         B = hx.shape[0]
@@ -70,9 +87,14 @@ class BaseMPC(eval_policy.EvalMPC):
             x0 = d(hx[:, -1])
             if eng.n > eng.nx:       # xc = concat[x, carry], the training policy's carry is zero (:31-38, :101-102)
                 x0 = torch.cat([x0, d(self.get_dynamics_carry(hx))], dim=1).contiguous()
-            loss, _, _, _ = opt.bilevel_optimization(
-                self, dparams, x0, d(init_U), d(goal), self.LOSS_KIND, desired=desired,
-                sign=self.bilevel_sign, grad_sum=packed[1:-1])
+            if custom:       # loss(xcseq, useq, params, *batch_loss_args), vmapped over (0, 0, None) + loss_vmap
+                loss, _, _, _ = opt.bilevel_optimization(
+                    self, dparams, x0, d(init_U), d(goal), self.loss, sign=self.bilevel_sign,
+                    grad_sum=packed[1:-1], loss_args=tuple(batch_loss_args or ()), loss_vmap=self.loss_vmap)
+            else:
+                loss, _, _, _ = opt.bilevel_optimization(
+                    self, dparams, x0, d(init_U), d(goal), self.LOSS_KIND, desired=desired,
+                    sign=self.bilevel_sign, grad_sum=packed[1:-1])
             torch.sum(loss, dim=0, keepdim=True, out=packed[:1])
         means = parallel.allreduce_mean_from_sums(packed)
         return means[0], means[1:]

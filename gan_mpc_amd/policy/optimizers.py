@@ -5,6 +5,8 @@ evaluations and their derivatives are fused HIP kernels behind the C ABI, so the
 replaced by the policy object that owns the engine and the bound parameters.  Everything is batched
 over the leading axis (the reference's jax.vmap axis)."""
 
+import torch
+
 
 def _solver(policy, eng):
     """The engine entry point of the policy's solver: "rounds" (gmpc_ilqr_solve, host-driven iterations) or
@@ -20,14 +22,58 @@ def ilqr_solve(policy, dparams, x0, U, goal, trajax_ilqr_kwargs=None):
 
 
 def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=None,
-                         trajax_ilqr_kwargs=None, sign=1.0, grad_sum=None):
+                         trajax_ilqr_kwargs=None, sign=1.0, grad_sum=None, loss_args=(), loss_vmap=None):
     """reference policy/optimizers.py:34-75, batched, WITHOUT the batch mean: returns
     (loss [B], low_level_grad [B,T,m], grad_sum [3 + cost_count] summed over the batch, itr [B]).
-    sign=+1 reproduces the reference as written."""
+    sign=+1 reproduces the reference as written.
+
+    loss_kind 0 (L2, against `desired`) and 1 (JS, the policy's critic) run on the kernels' own losses.  A
+    callable is the reference's `loss(X, U, params, *loss_args)` of ONE trajectory: it is evaluated and
+    differentiated per trajectory under torch.func.vmap (loss_cotangents; loss_vmap: the in_dims of loss_args,
+    default 0 for each), its cotangents go to gmpc_bilevel_grad_cotangent."""
     B = x0.shape[0]
     eng = policy.bind(dparams, B)
     sol = _solver(policy, eng)(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
+    if callable(loss_kind):
+        loss, lx, lu = loss_cotangents(loss_kind, sol["X"], sol["U"], dparams, loss_args, loss_vmap)
+        grad_sum = eng.bilevel_grad_cotangent(B, lx, lu, sign=sign, grad_sum=grad_sum)
+        return loss, sol["grad"], grad_sum, sol["iterations"]
     critic = dparams.view("critic_params") if loss_kind == 1 else None
     loss, grad_sum = eng.bilevel_grad(B, loss_kind, desired=desired, critic=critic, sign=sign,
                                       grad_sum=grad_sum)
     return loss, sol["grad"], grad_sum, sol["iterations"]
+
+
+def loss_cotangents(loss, X, U, params, loss_args=(), loss_vmap=None, want_grad=True):
+    """Per-trajectory values and cotangents of a caller-defined upper-level loss, the reference's
+    jax.vmap(loss, in_axes=(0, 0, None) + loss_vmap) with jax.grad wrt (X, U): `loss(x, u, params, *args)` takes one
+    trajectory x (T+1, n), u (T, m) and returns a scalar.  X (B, T+1, n), U (B, T, m); `params` is passed unmapped
+    and not differentiated (the reference drops the loss's direct parameter dependence as well); loss_args mapped
+    over loss_vmap (an int or None per argument; default 0 each), arrays moved to X's device.
+    -> (loss [B], lx [B, T+1, n], lu [B, T, m]) as contiguous fp32 tensors; lx, lu None without want_grad."""
+    from torch.func import grad_and_value, vmap
+
+    loss_args = tuple(loss_args)
+    loss_vmap = (0,) * len(loss_args) if loss_vmap is None else tuple(loss_vmap)
+    if len(loss_vmap) != len(loss_args):
+        raise ValueError(f"loss_vmap has {len(loss_vmap)} entries for {len(loss_args)} loss arguments")
+    args = tuple(a if d is None else _as_tensor(a, X.device) for a, d in zip(loss_args, loss_vmap))
+    in_dims = (0, 0, None) + loss_vmap
+    B = X.shape[0]
+    if not want_grad:
+        val = vmap(loss, in_dims=in_dims)(X, U, params, *args)
+        return _per_sample(val, B), None, None
+    (lx, lu), val = vmap(grad_and_value(loss, argnums=(0, 1)), in_dims=in_dims)(X, U, params, *args)
+    f32 = lambda t: t.to(torch.float32).contiguous()  # noqa: E731
+    return _per_sample(val, B), f32(lx), f32(lu)
+
+
+def _as_tensor(a, device):
+    t = torch.as_tensor(a, device=device) if not torch.is_tensor(a) else a.to(device)
+    return t.to(torch.float32) if t.is_floating_point() else t
+
+
+def _per_sample(val, B):
+    if tuple(val.shape) != (B,):
+        raise ValueError(f"the loss must return a scalar per trajectory, got shape {tuple(val.shape[1:])}")
+    return val.to(torch.float32).contiguous()

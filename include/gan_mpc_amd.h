@@ -15,7 +15,7 @@
  *    thread-local description of the last failure.  No C++ exception crosses this ABI.
  *  - A gmpc_ctx belongs to one GPU and is thread-compatible (one caller at a time).
  *  - There is no CPU fallback: without a HIP device every compute entry point fails.
- *  - Ordering contract: gmpc_bilevel_grad / gmpc_upper_loss differentiate the solution the ctx holds
+ *  - Ordering contract: gmpc_bilevel_grad(_cotangent) / gmpc_upper_loss differentiate the solution the ctx holds
  *    after a COMPLETED gmpc_ilqr_solve of the same batch size.  gmpc_set_params, gmpc_rollout_cost,
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
@@ -186,6 +186,17 @@ int gmpc_ilqr_solve_fused(gmpc_ctx* ctx, int B, const float* x0, const float* U_
  *   -> loss [B]; grad_sum [3 + cost_count]: SUM over the batch of d/d(mpc_w, cost params). */
 int gmpc_bilevel_grad(gmpc_ctx* ctx, int B, int loss_kind, const float* desired,
                       const float* critic, float sign, float* loss, float* grad_sum, void* stream);
+
+/* a8-a11 for a caller-defined upper-level loss, at the iLQR solution held by the ctx (the reference's `loss` is any
+ * callable, policy/optimizers.py:34-83, policy/base.py:84-85): the caller passes lx = dL/dX [B][T+1][n] (xc columns;
+ * carry columns included for LSTM dynamics) and/or lu = dL/dU [B][T][m] (either may be NULL, not both); then
+ * Bvec_t = lu_t + B_t^T mu_{t+1}.  -> grad_sum [3 + cost_count], the SUM over the batch, as gmpc_bilevel_grad.
+ * Follows gmpc_ilqr_solve or gmpc_ilqr_solve_fused of the same B (else GMPC_EINVAL, "must precede"); leaves the
+ * same ctx state as gmpc_bilevel_grad (Bvec, H, dX: debug buffers 4 / 2 / 3).  lx and lu are only read; with
+ * lx NULL the ctx's own lx buffer (debug buffer 11) is zeroed and used.  With lu NULL and the lx that
+ * gmpc_bilevel_grad computes, the result is bit-identical to gmpc_bilevel_grad's. */
+int gmpc_bilevel_grad_cotangent(gmpc_ctx* ctx, int B, const float* lx, const float* lu, float sign,
+                                float* grad_sum, void* stream);
 
 /* a13/a16 only: the upper-level loss [B] at the solution held by the ctx, without the gradient
  * (test-loss evaluation, norm/cost_trainer.py:13-21). */
