@@ -77,6 +77,11 @@ void gmpc_launch_bvec(int, int, int, int, const float*, const float*, const floa
 void gmpc_launch_costvjp(int, int, int, int, const MlpDesc&, const float*, float, const float*,
                          const float*, const float*, int, const float*, const float*, float*, float*,
                          float*, int, hipStream_t);
+int gmpc_launch_input_grads(int, int, int, int, int, const float*, const float*, const float*, const float*,
+                            const float*, const float*, const float*, const float*, const float*, float*, float*,
+                            hipStream_t);
+void gmpc_launch_goal_grad(int, int, int, int, const float*, const float*, const float*, const float*, float*,
+                           hipStream_t);
 
 // LSTM dynamics variant (gmpc_dynl.hip)
 void gmpc_launch_dynl_rollout(DynlTrajArgs, hipStream_t);
@@ -233,6 +238,9 @@ struct gmpc_ctx {
   float* fzcand = nullptr;                    // line-search candidates of gmpc_ilqr_solve_fused (shapes it covers)
   hipEvent_t poll_ev[GMPC_POLL_DEPTH] = {};
   int solB = 0;
+  // batch size whose Bvec / H / dX (and Phi) a completed bilevel tail left for the held solution (0: none); every
+  // change of the held solution clears it
+  int gradB = 0;
   // bilevel workspace
   float *lx, *Bvec, *Hout, *dX, *gmpc, *cact, *cdel, *bl_loss;
   int cstride;
@@ -546,6 +554,7 @@ extern "C" int gmpc_set_params(gmpc_ctx* c, const float* mpc_w, const float* dyn
   (void)hipGetLastError();   // clean slate (see check_call)
   c->mpc_w = mpc_w;
   c->solB = 0;   // a held solution belongs to the previous parameters
+  c->gradB = 0;
   bind_mlp(c->cost, c->sh.cost_layers, c->sh.cost_dims, cost, c->costT);
   transpose_mlp(c->cost, s);
   if (c->dynl) {
@@ -604,6 +613,7 @@ extern "C" int gmpc_rollout_cost(gmpc_ctx* c, int B, const float* x0, const floa
   if (!x0 || !U || !goal || !X) return fail(GMPC_EINVAL, "null argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;   // overwrites the ctx's relu masks and objectives: any held solution is gone
+  c->gradB = 0;
   if (c->dynl) {
     DynlTrajArgs d = base_dynl(c, B, goal);
     d.x0 = x0; d.U = U; d.X = X; d.costs = costs; d.obj = c->obj;
@@ -711,6 +721,7 @@ extern "C" int gmpc_lqr_backward(gmpc_ctx* c, int B, const float* X, const float
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (c->big && AB) return fail(GMPC_EINVAL, "AB output is not materialised for n > 64 (pass NULL)");
   c->solB = 0;   // overwrites masks, QT/qT and (with NULL outputs) the ctx's K / AB
+  c->gradB = 0;
   // relu masks at (X, U): recomputed so that any trajectory may be passed (the LSTM variant's Jacobian
   // kernel recomputes its forward pass itself)
   if (!c->dynl) gmpc_launch_masks(B, c->sh.n, c->sh.m, c->sh.T, c->dyn, X, U, c->masks, s);
@@ -728,6 +739,7 @@ extern "C" int gmpc_lqr_backward_after_rollout(gmpc_ctx* c, int B, const float* 
   if (c->big && AB) return fail(GMPC_EINVAL, "AB output is not materialised for n > 64 (pass NULL)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;   // overwrites QT/qT and (with NULL outputs) the ctx's K / AB
+  c->gradB = 0;
   return backward_pass(c, B, X, U, goal, nullptr, K ? K : c->Ks, k ? k : c->ks, grad, adjoints,
                        AB ? AB : c->AB, nullptr, nullptr, s);
 }
@@ -752,6 +764,7 @@ extern "C" int gmpc_ilqr_solve(gmpc_ctx* c, int B, const float* x0, const float*
   if (opts->make_psd) return fail(GMPC_EINVAL, "make_psd=1 is not on the reference path");
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;   // restored only when the solve has completed (an early error return leaves none)
+  c->gradB = 0;
   const gmpc_shape& sh = c->sh;
   const size_t n = sh.n, m = sh.m, T = sh.T;
   HIP_TRY(hipMemcpyAsync(c->Us, U_init, B * T * m * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -852,6 +865,7 @@ extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const 
     return fail(GMPC_EINVAL, "fused solve: alpha_0 / alpha_min allow more than %d halvings", GMPC_FZ_MAX_HALVINGS);
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;
+  c->gradB = 0;
   FusedSolveArgs a;
   memset(&a, 0, sizeof(a));
   a.n = sh.n; a.m = sh.m; a.T = sh.T; a.k_max = k_max;
@@ -1115,6 +1129,7 @@ extern "C" int gmpc_upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* d
   TRY(check_call(c, B));
   if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
   if (!loss) return fail(GMPC_EINVAL, "null argument");
+  c->gradB = 0;   // the L2 loss rewrites the ctx's lx, which gmpc_bilevel_grad_inputs would read
   TRY(upper_loss(c, B, loss_kind, desired, critic, loss, false, static_cast<hipStream_t>(stream)));
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1383,6 +1398,7 @@ extern "C" int gmpc_predict(gmpc_ctx* c, int B, const float* x, const float* u, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t n = c->sh.n;
   c->solB = 0;   // the one-step rollout below overwrites the ctx's relu masks and objectives
+  c->gradB = 0;
   // a horizon-1 rollout through the trajectory kernel: X = [x, f(x, u)] in the line-search scratch
   HIP_TRY(hipMemsetAsync(c->goals, 0, (size_t)B * 2 * n * sizeof(float), s));
   if (c->dynl) {
@@ -1507,6 +1523,7 @@ static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const fl
                                    float* grad_sum, hipStream_t s) {
   const gmpc_shape& sh = c->sh;
   const int n = sh.n, m = sh.m, T = sh.T;
+  c->gradB = 0;
   // a8: Bvec; a9+solve: structured Hessian solve; a11: cost_vjp
   if (c->big) {
     // step-major: the loss adjoint (Bvec) and the Riccati sweep of the Hessian solve share one
@@ -1553,6 +1570,7 @@ static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const fl
     aoff += M;
     doff += N;
   }
+  c->gradB = B;   // H, dX (and Phi) now belong to the held solution: gmpc_bilevel_grad_inputs may follow
   return 0;
 }
 
@@ -1563,6 +1581,7 @@ extern "C" int gmpc_bilevel_grad(gmpc_ctx* c, int B, int loss_kind, const float*
   if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
   if (!loss || !grad_sum) return fail(GMPC_EINVAL, "null argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
+  c->gradB = 0;   // the loss below rewrites the ctx's lx
   TRY(upper_loss(c, B, loss_kind, desired, critic, loss, true, s));
   TRY(bilevel_from_cotangents(c, B, c->lx, nullptr, sign, grad_sum, s));
   HIP_TRY(hipGetLastError());
@@ -1583,6 +1602,33 @@ extern "C" int gmpc_bilevel_grad_cotangent(gmpc_ctx* c, int B, const float* lx, 
     lx = c->lx;
   }
   TRY(bilevel_from_cotangents(c, B, lx, lu, sign, grad_sum, s));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// dL/dx0 and dL/dgoal of the loss whose bilevel gradient the ctx has just computed (gmpc_input_grads.hip): the
+// implicit-function gradient through the held solution, from the H, dX (and Phi) the bilevel tail left.  Read-only
+// for every other ctx buffer.
+extern "C" int gmpc_bilevel_grad_inputs(gmpc_ctx* c, int B, const float* lx, float* grad_x0, float* grad_goal,
+                                        void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B || c->gradB != B)
+    return fail(GMPC_EINVAL, "gmpc_bilevel_grad or gmpc_bilevel_grad_cotangent with B=%d on the held solution must "
+                "precede this call", B);
+  if (!grad_x0 && !grad_goal) return fail(GMPC_EINVAL, "grad_x0 and grad_goal are both null");
+  if (grad_x0 && c->big)
+    return fail(GMPC_EINVAL, "grad_x0: the step-major pipeline (n=%d > 64 or m=%d > 32) keeps no [A_t | B_t] of the "
+                "solution; only grad_goal is available for this shape", c->sh.n, c->sh.m);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const gmpc_shape& sh = c->sh;
+  if (!lx) lx = c->lx;
+  if (grad_x0) {
+    if (gmpc_launch_input_grads(B, sh.T, sh.n, c->nx, sh.m, c->mpc_w, c->Xs, c->goals, c->dX, c->Hout, lx, c->AB,
+                                c->QT, c->dynl ? c->phi : nullptr, grad_x0, grad_goal, s) != 0)
+      return fail(GMPC_EINVAL, "grad_x0: shape n=%d m=%d not covered", sh.n, sh.m);
+  } else {
+    gmpc_launch_goal_grad(B, sh.T, sh.n, c->nx, c->mpc_w, c->Xs, c->goals, c->dX, grad_goal, s);
+  }
   HIP_TRY(hipGetLastError());
   return 0;
 }

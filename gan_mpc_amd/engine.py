@@ -120,6 +120,7 @@ class Engine:
                                         C.byref(ctx)))
         self.ctx = ctx
         self._bound = None
+        self.solve_count = 0      # solves issued on this ctx (policy.differentiable: a backward checks it is current)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -207,6 +208,7 @@ class Engine:
 
     def _solve(self, fn, x0, U, goal, kwargs):
         B = x0.shape[0]
+        self.solve_count += 1     # before the call: a failed solve drops the held solution as well
         n, m, T = self.n, self.m, self.T
         opts = make_opts(kwargs)
         out = dict(X=self.new(B, T + 1, n), U=self.new(B, T, m), obj=self.new(B),
@@ -239,6 +241,19 @@ class Engine:
         _lib.check(self.lib.gmpc_bilevel_grad_cotangent(self.ctx, B, _ptr(lx), _ptr(lu), float(sign),
                                                         _ptr(grad_sum), self._stream()))
         return grad_sum
+
+    def bilevel_grad_inputs(self, B, lx=None, want_x0=True, want_goal=True):
+        """dL/dx0 (B, n) and dL/dgoal (B, T+1, nx) of the loss whose bilevel gradient was just computed
+        (gmpc_bilevel_grad_inputs; must follow bilevel_grad or bilevel_grad_cotangent on the same held solution).  The
+        true derivative, whatever `sign` the bilevel call used.  lx: the dL/dX passed to bilevel_grad_cotangent, or
+        None for the ctx's own (bilevel_grad's loss; the zeroed one of a cotangent call without lx).  -> (grad_x0,
+        grad_goal), None where not wanted.  grad_x0 is refused on the step-major pipeline (self.big)."""
+        if lx is not None and tuple(lx.shape) != (B, self.T + 1, self.n):
+            raise _lib.GmpcError(f"bilevel_grad_inputs: lx must be {(B, self.T + 1, self.n)}, got {tuple(lx.shape)}")
+        gx0 = self.new(B, self.n) if want_x0 else None
+        ggoal = self.new(B, self.T + 1, self.nx) if want_goal else None
+        _lib.check(self.lib.gmpc_bilevel_grad_inputs(self.ctx, B, _ptr(lx), _ptr(gx0), _ptr(ggoal), self._stream()))
+        return gx0, ggoal
 
     def upper_loss(self, B, loss_kind, desired=None, critic=None):
         loss = self.new(B)

@@ -1,0 +1,76 @@
+"""The batched iLQR solve as a differentiable torch op: (X, U) = ilqr_layer(policy, params, x0, goal, init_U).
+
+Backward is the implicit-function gradient through the solution U* (grad_U J(U*; x0, goal, theta) = 0): the incoming
+cotangents gX = dL/dX, gU = dL/dU go to gmpc_bilevel_grad_cotangent with sign -1 (the true derivative, not the
+reference's sign), then gmpc_bilevel_grad_inputs gives dL/dx0 and dL/dgoal from the same Hessian solve (DESIGN.md
+section 12).
+
+  - params: a DeviceParams; its flat vector `params.flat` is the differentiable leaf.  Only its mpc_weights and
+    cost_params ranges receive gradient, summed over the batch; dynamics, critic and expert parameters get none, as
+    in the reference (their gradient needs the dynamics' mixed second derivatives).
+  - x0 (B, n) -- xc, carry columns included for LSTM dynamics -- and goal (B, T+1, x_size) receive per-sample
+    gradients.  dL/dx0 is not available on the step-major pipeline (n > 64 or m > 32): asking for it (x0 requiring
+    grad) fails in forward.
+  - init_U receives none: at a stationary point the solution does not depend on the initial guess (away from the
+    solver's stopping tolerance, where it does, but not differentiably).
+  - The engine holds one solution at a time.  Backward must run before another solve on the same engine; otherwise it
+    raises instead of differentiating the wrong solution."""
+
+import torch
+
+from gan_mpc_amd._lib import GmpcError
+from gan_mpc_amd.policy import optimizers as opt
+
+_THETA_KEYS = ("mpc_weights", "cost_params")
+
+
+class ILQRFunction(torch.autograd.Function):
+    """forward(policy, dparams, kwargs, flat, x0, goal, init_U) -> (X, U); flat is dparams.flat."""
+
+    @staticmethod
+    def forward(ctx, policy, dparams, kwargs, flat, x0, goal, init_U):
+        B = x0.shape[0]
+        eng = policy.bind(dparams, B)
+        if ctx.needs_input_grad[4] and eng.big:
+            raise GmpcError(f"ilqr_layer: dL/dx0 is not available on the step-major pipeline (n={eng.n} > 64 or "
+                            f"m={eng.m} > 32); pass x0 without requires_grad (goal gradients work)")
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+        sol = opt._solver(policy, eng)(f32(x0), f32(init_U), f32(goal), kwargs or policy.trajax_ilqr_kwargs)
+        ctx.eng, ctx.solve_count, ctx.B = eng, eng.solve_count, B
+        ctx.theta = dparams.range_of(_THETA_KEYS)
+        ctx.flat_shape = flat.shape
+        return sol["X"], sol["U"]
+
+    @staticmethod
+    def backward(ctx, gX, gU):
+        eng, B = ctx.eng, ctx.B
+        if eng.ctx is None or eng.solve_count != ctx.solve_count:
+            raise RuntimeError("ilqr_layer backward: another iLQR solve ran on this engine after the forward, so the "
+                               "solution it differentiates is gone; run backward before the next solve")
+        want_theta, want_x0, want_goal = ctx.needs_input_grad[3:6]
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        lx, lu = f32(gX), f32(gU)
+        if lx is None and lu is None:
+            return (None,) * 7
+        try:
+            grad_sum = eng.bilevel_grad_cotangent(B, lx, lu, sign=-1.0)
+            gx0 = ggoal = None
+            if want_x0 or want_goal:
+                gx0, ggoal = eng.bilevel_grad_inputs(B, lx, want_x0=want_x0, want_goal=want_goal)
+        except GmpcError as e:
+            raise RuntimeError(f"ilqr_layer backward: the engine no longer holds the forward's solution ({e})") from e
+        gflat = None
+        if want_theta:
+            lo, cnt = ctx.theta
+            gflat = torch.zeros(ctx.flat_shape, dtype=grad_sum.dtype, device=grad_sum.device)
+            gflat[lo:lo + cnt] = grad_sum
+        return None, None, None, gflat, gx0, ggoal, None
+
+
+def ilqr_layer(policy, params, x0, goal, init_U, trajax_ilqr_kwargs=None):
+    """(X (B, T+1, n), U (B, T, m)) of the policy's iLQR solve (its `solver`, "rounds" or "fused"), differentiable
+    w.r.t. x0, goal and the mpc_weights / cost_params ranges of params.flat (see the module docstring).  params: the
+    policy's DeviceParams (a parameter tree is converted, and then is not differentiable); x0, goal, init_U: device
+    tensors."""
+    dparams = policy.to_device_params(params)
+    return ILQRFunction.apply(policy, dparams, trajax_ilqr_kwargs, dparams.flat, x0, goal, init_U)

@@ -198,6 +198,19 @@ int gmpc_bilevel_grad(gmpc_ctx* ctx, int B, int loss_kind, const float* desired,
 int gmpc_bilevel_grad_cotangent(gmpc_ctx* ctx, int B, const float* lx, const float* lu, float sign,
                                 float* grad_sum, void* stream);
 
+/* The gradients of the same upper-level loss with respect to the solver's inputs, through the held solution:
+ * grad_x0 [B][n] = dL/dx0 (xc: carry columns included for LSTM dynamics) and grad_goal [B][T+1][x_size] = dL/dgoal
+ * (row T is 0: the terminal cost does not read it).  The TRUE derivative: no reference-compatibility sign.
+ * Must follow gmpc_bilevel_grad or gmpc_bilevel_grad_cotangent of the same B on the same held solution (else
+ * GMPC_EINVAL, "... must precede"): it reads the H and dX (and, for LSTM dynamics, the curvature) those leave.  Any
+ * solve, gmpc_upper_loss or other call that drops the held solution voids them.
+ * lx = dL/dX [B][T+1][n] as passed to the bilevel call; NULL means the ctx's own lx buffer -- the one
+ * gmpc_bilevel_grad filled (L2 / JS), or the zeroed one gmpc_bilevel_grad_cotangent used for a NULL lx.  A caller
+ * who passed their own lx passes it again.  Either output may be NULL, not both.  A non-NULL grad_x0 on the
+ * step-major pipeline (n > 64 or m > 32: [A_t | B_t] is not kept) fails with GMPC_EINVAL; grad_goal works there.
+ * Read-only for every existing ctx buffer (Bvec, H, dX, grad_sum stay as they were). */
+int gmpc_bilevel_grad_inputs(gmpc_ctx* ctx, int B, const float* lx, float* grad_x0, float* grad_goal, void* stream);
+
 /* a13/a16 only: the upper-level loss [B] at the solution held by the ctx, without the gradient
  * (test-loss evaluation, norm/cost_trainer.py:13-21). */
 int gmpc_upper_loss(gmpc_ctx* ctx, int B, int loss_kind, const float* desired, const float* critic,
