@@ -22,6 +22,8 @@ void gmpc_launch_masks(int, int, int, int, const MlpDesc&, const float*, const f
                        hipStream_t);
 int gmpc_launch_linearize(int, int, int, int, const MlpDesc&, const uint32_t*, const int*, float*,
                           hipStream_t);
+int gmpc_launch_linearize_sparse(int, int, int, int, const MlpDesc&, const LinPad&, const uint32_t*, const int*,
+                                 float*, int, int, hipStream_t);
 int gmpc_launch_linearize_regs(int, int, int, int, const MlpDesc&, const LinPad&, const uint32_t*,
                                const int*, float*, int, int, hipStream_t);
 int gmpc_launch_linearize_mfma(int, int, int, int, const MlpDesc&, const LinPad&, const uint32_t*,
@@ -676,11 +678,19 @@ static int backward_pass(gmpc_ctx* c, int B, const float* X, const float* U, con
     ProfScope ps(c, PROF_LINEARIZE, s);
     // matrix-core chain; the VALU chain only serves shapes the MFMA tiling does not cover -- both are HIP
     // kernels of this library
-    // 1st choice: register-resident chain (compiled for the common equal-width shapes), 2nd: the
-    // LDS-operand chain (any shape), 3rd: VALU
+    // 1st choice: the chain over each sample's active relu units (200-wide hidden layers; bitwise the dense
+    // chain's result), 2nd: register-resident dense chain (compiled for the common equal-width shapes), 3rd: the
+    // LDS-operand chain (any shape), 4th: VALU.  GMPC_LIN=dense skips the first (read per call: the tests compare
+    // the two routes inside one process).
+    const char* lin_env = getenv("GMPC_LIN");
+    const bool lin_dense = lin_env != nullptr && strcmp(lin_env, "dense") == 0;
     if (c->dynl) {
       gmpc_launch_dynl_jac(B, sh.T, sh.T, 0, c->dl, X, U, active, AB, s);
       c->lin_kernel = "k_dynl_jac";
+    } else if (!lin_dense && gmpc_launch_linearize_sparse(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks,
+                                                          active, AB, 1, 0, s) == 0) {
+      c->lin_kernel = sh.n > 16 ? "k_linearize_sparse (rows 0..15) + k_linearize_regs (rows 16..n-1)"
+                                : "k_linearize_sparse";
     } else if (gmpc_launch_linearize_regs(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
                                           s) == 0) {
       snprintf(c->lin_kernel_buf, sizeof(c->lin_kernel_buf), "%s", gmpc_linearize_regs_last_name());

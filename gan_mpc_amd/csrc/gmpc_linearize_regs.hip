@@ -63,7 +63,7 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 template <int NT, int KS, int TAIL = 0, bool WIDE = false>
 __global__ __launch_bounds__(GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linearize_regs(
     int NSamp, int T, int n, int m, MlpDesc dyn, LinPad lp, const uint32_t* masks, const int* active,
-    float* AB, int ntiles, int samp_mul, int samp_add) {
+    float* AB, int ntiles, int samp_mul, int samp_add, int row0) {
   static_assert(NT <= 8 && 2 * KS <= 32 * NT + TAIL && (TAIL == 0 || TAIL == 8), "shape");
   constexpr bool AG = GMPC_REGS_OCC(NT, TAIL) == 1;      // register half of the accumulators (mfma_fence)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -71,7 +71,9 @@ __global__ __launch_bounds__(GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linea
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int half = lane >> 5, l31 = lane & 31;
   const int Lh = dyn.L - 1, nm = n + m;
-  const int Rtot = NSamp * n;
+  // row window: rows row0..n-1 of every sample (row0 > 0 only with k_linearize_sparse, which does the rest)
+  const int nr = n - row0;
+  const int Rtot = NSamp * nr;
   const int wl_floats = WIDE ? 4 * 32 * 33 : (dyn.dims[Lh] + GMPC_LIN_PADROWS) * n;   // WIDE: transpose tiles
   if (!WIDE)
     for (int e = threadIdx.x; e < wl_floats; e += blockDim.x) wl_s[e] = lp.WLP[e];
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linea
     int R = r0 + l31;                          // this lane's stacked Jacobian row
     const bool rvalid = R < Rtot;
     if (!rvalid) R = Rtot - 1;                 // clamped reads, no writes
-    const int s = R / n, irow = R - s * n;
+    const int s = R / nr, irow = row0 + (R - s * nr);
     size_t sid = (size_t)s * samp_mul + samp_add;
     if (active != nullptr) {
       const bool on = active[sid / T] != 0;
@@ -342,7 +344,7 @@ __global__ __launch_bounds__(GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linea
       GMPC_STAMP(3)
       mfma_fence<AG>(acc0);
       if (rvalid) {
-        float* dst = AB + (size_t)R * nm;
+        float* dst = AB + ((size_t)s * n + irow) * nm;
 #pragma unroll
         for (int rg = 0; rg < 16; ++rg) {
           const int c = (rg & 3) + 8 * (rg >> 2) + 4 * half;
@@ -365,8 +367,8 @@ const char* gmpc_linearize_regs_last_name() { return g_last_name; }
 template <int NT, int KS, int TAIL = 0, bool WIDE = false>
 static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                        const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
-                       hipStream_t s) {
-  const long Rtot = (long)NSamp * n;
+                       int row0, hipStream_t s) {
+  const long Rtot = (long)NSamp * (n - row0);
   if (Rtot >= (1L << 31) - 64) return -1;
   const int ntiles = (int)((Rtot + 31) / 32);
   const int Lh = dyn.L - 1;
@@ -384,15 +386,17 @@ static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const
   // (as rocprofv3's kernel trace prints the instantiation)
   snprintf(g_last_name, sizeof(g_last_name), "k_linearize_regs<%d, %d, %d, %s>", NT, KS, TAIL, WIDE ? "true" : "false");
   hipLaunchKernelGGL((k_linearize_regs<NT, KS, TAIL, WIDE>), dim3(grid), dim3(GMPC_THREADS), lds, s, NSamp, T, n, m,
-                     dyn, lp, masks, active, AB, ntiles, samp_mul, samp_add);
+                     dyn, lp, masks, active, AB, ntiles, samp_mul, samp_add, row0);
   return 0;
 }
 
+// rows row0..n-1 of every sample (row0 = 0: all of them; the wide form takes row0 = 0 only).
 // returns 0 on launch, -1 when the shape is not one this variant is compiled for
-int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
-                               const uint32_t* masks, const int* active, float* AB, int samp_mul,
-                               int samp_add, hipStream_t s) {
+int gmpc_launch_linearize_regs_rows(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                    const uint32_t* masks, const int* active, float* AB, int samp_mul,
+                                    int samp_add, int row0, hipStream_t s) {
   const int Lh = dyn.L - 1;
+  if (row0 < 0 || row0 >= n || (row0 > 0 && n + m > 32)) return -1;
   if (Lh < 2) return -1;
   const int H = dyn.dims[1];
   for (int l = 1; l <= Lh; ++l)
@@ -400,14 +404,20 @@ int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dy
   if (n + m > 32) {
     // wide inputs (large-state path): the 200-wide instantiation only
     if (H != 200 || lp.NT != 7 || 32 * lp.NTF * lp.NGF < ((n + m + 31) / 32 + 3) / 4 * 4 * 32) return -1;
-    return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
   }
   if (lp.NTF != 1 || lp.NGF != 1) return -1;
   if (H == 200 && lp.NT == 7)
-    return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
   if (H == 128 && lp.NT == 4)
-    return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
   if (H == 64 && lp.NT == 2)
-    return launch_regs<2, 32>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    return launch_regs<2, 32>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
   return -1;
+}
+
+int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                               const uint32_t* masks, const int* active, float* AB, int samp_mul,
+                               int samp_add, hipStream_t s) {
+  return gmpc_launch_linearize_regs_rows(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, 0, s);
 }

@@ -1,0 +1,243 @@
+// Dynamics Jacobian chain over each sample's ACTIVE relu units only (gfx950; hidden layers all 200 wide, n + m <= 32).
+//
+// Same product as k_linearize_regs -- [A_t | B_t] - [I | 0] = W_L^T D_{L-1} W_{L-1}^T ... D_1 W_1^T -- and the same
+// bits.  The dense chain contracts over all 200 units of a hidden layer; for an inactive unit the running product
+// holds an exact zero there, so its term is fma(w, +-0, c) == c (up to the sign of a zero sum).  Both chains issue
+// fp32 MFMAs, which accumulate as an fmaf chain in k order: dropping exactly-zero terms and keeping the order of
+// the rest reproduces every output.  Outputs of units the next mask zeroes are computed but never read.
+//
+// One wave per sample, rows 0..15 of its Jacobian on v_mfma_f32_16x16x4_f32: A = W_l^T (16 output units x 4
+// contracted units), B = S (4 contracted units x 16 Jacobian rows), the 4 contracted units of a k-step are four
+// consecutive entries of the sample's active list.  Rows 16..n-1 (n = 17: one row) stay on k_linearize_regs, which
+// takes a row window for them.
+//  - active lists: built per layer from the relu words with mbcnt (a prefix count, no scan), stored as 16-bit unit
+//    indices in the wave's LDS and padded with unit 200 -- a zero row of the padded W^T copies and a zero column of
+//    the S tile -- so the padded k-steps and the loads that run ahead of the last k-step read zeros, in bounds.
+//  - A operands: the lane-interleaved W_l^T rows of k_linearize_regs (LinPad::WTP, 1 KB per unit): the 12 full
+//    16-unit tiles are two 16-byte + two 8-byte buffer loads per lane and k-step; the voffset is the list entry
+//    << 10 plus a lane constant.  A k-step puts its 13 MFMAs beside two list reads and a handful of vector
+//    instructions (address of the weight rows, of the tail row and of the B operand; the 16-bit zero extensions).
+//  - tail units 192..199: the dense chain sums them on 4x4x1_16B as an even-k partial plus an odd-k partial.  The
+//    13th tile reproduces the split: rows 0..7 read unit 192 + r of the even list entries (odd ones -> zero row),
+//    rows 8..15 the same units of the odd ones; the two halves are added once per layer, as there.
+//  - S between layers: the accumulators go to a wave-private [16 rows][220] LDS tile, the next layer's B operands
+//    are read back at the list entries (four distinct units per read, no bank conflict inside a lane group).
+#include <cstdio>
+#include <type_traits>
+
+#include "gmpc_device.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+#define GMPC_LIN_PADROWS 24  // zero rows behind every padded copy (gmpc_linearize_mfma.hip)
+#define GMPC_SP_H 200        // hidden width of this form
+#define GMPC_SP_Z 200        // the zero unit padded list entries point at
+#define GMPC_SP_STR 220      // floats per Jacobian row of the S tile: units 0..199, zeros 200..207, odd partials 208..215
+#define GMPC_SP_CAP 216      // list entries: 200 + the 3 k-steps the prefetch runs ahead, rounded to 8
+#define GMPC_SP_WAVE_BYTES (16 * GMPC_SP_STR * 4 + 3 * GMPC_SP_CAP * 2)
+#define GMPC_SP_RD 3         // operand sets in flight: loads for k-step p + 2, list entries for p + 3
+
+// LDS: GMPC_SP_WAVE_BYTES per wave, 61.5 KB per workgroup -- two workgroups (eight waves) per CU
+__global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
+    int NSamp, int T, int n, int m, int Lh, LinPad lp, const uint32_t* masks, const int* active, float* AB,
+    int samp_mul, int samp_add) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4, l16 = lane & 15;
+  const int nm = n + m;
+  const int nrow = n < 16 ? n : 16;
+  char* wbase = smem + wave * GMPC_SP_WAVE_BYTES;
+  float* st = reinterpret_cast<float*>(wbase);                                      // S tile [16][STR]
+  unsigned short* lk = reinterpret_cast<unsigned short*>(wbase + 16 * GMPC_SP_STR * 4);   // unit list
+  unsigned short* lt = lk + GMPC_SP_CAP;                                            // [CAP][2]: even / odd only
+  // zero units 200..207 of the S tile (never written again)
+  if (lane < 16 * 8) st[(lane >> 3) * GMPC_SP_STR + GMPC_SP_H + (lane & 7)] = 0.f;
+  if (lane + 64 < 16 * 8) st[((lane + 64) >> 3) * GMPC_SP_STR + GMPC_SP_H + (lane & 7)] = 0.f;
+
+  // lane constants (bytes): A operand of unit 32 nt + l16 (+16) in a lane-interleaved W^T row; the tail tile's unit
+  // 192 + (l16 & 7); the S tile column of this lane's Jacobian row; its list half for the tail tile
+  const int lm = l16 * 32, ltl = ((l16 & 7) * 8 + 6) * 4;
+  const int ls = l16 * GMPC_SP_STR * 4;
+  const int tsel = l16 >= 8 ? 1 : 0;
+  const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(lp.WLP), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * n * (int)sizeof(float), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(lp.WTP[0]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * 32 * (int)sizeof(float), 0x00020000);
+  // seed operand: W_L[k][l16]; the rows past n read past the end of the buffer, which returns zero
+  const int lsn = l16 < n ? l16 * 4 : (1 << 28);
+
+  constexpr int WPB = GMPC_THREADS / 64;
+  for (int s = blockIdx.x * WPB + wave; s < NSamp; s += gridDim.x * WPB) {
+    const size_t sid = (size_t)s * samp_mul + samp_add;
+    if (active != nullptr && active[sid / T] == 0) continue;
+    const uint32_t* mrow = masks + sid * Lh * GMPC_MW;
+
+    // active list of hidden layer ml: returns its length
+    auto build = [&](int ml) -> int {
+      __builtin_amdgcn_wave_barrier();
+      for (int e = lane; e < GMPC_SP_CAP; e += 64) {
+        lk[e] = GMPC_SP_Z;
+        lt[2 * e] = GMPC_SP_Z;
+        lt[2 * e + 1] = GMPC_SP_Z;
+      }
+      int base = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const uint32_t lo = __builtin_amdgcn_readfirstlane(mrow[ml * GMPC_MW + 2 * c]);
+        uint32_t hi = c < 3 ? __builtin_amdgcn_readfirstlane(mrow[ml * GMPC_MW + 2 * c + 1]) : 0u;
+        const uint32_t lo_m = c < 3 ? lo : (lo & 0xFFu);     // units 192..199 of word 6
+        const uint32_t word = lane < 32 ? lo_m : hi;
+        const int pos = base + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo_m, 0u));
+        const int u = 64 * c + lane;
+        if ((word >> (lane & 31)) & 1u) {
+          lk[pos] = (unsigned short)u;
+          lt[2 * pos + (u & 1)] = (unsigned short)u;
+        }
+        base += __builtin_popcount(lo_m) + __builtin_popcount(hi);
+      }
+      __builtin_amdgcn_wave_barrier();
+      return base;
+    };
+
+    // ---- hidden GEMMs  S_{l-1} = W_l S_l over the active units of S_l,  l = Lh-1 .. 1 (seed: S = W_L)
+    auto layer = [&](int l, auto seedc) __attribute__((always_inline)) {
+      constexpr bool seed = decltype(seedc)::value;
+      const int np = (build(l) + 3) >> 2;
+      const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(lp.WTP[l]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * 1024, 0x00020000);
+      f32x4 acc[13];
+#pragma unroll
+      for (int t = 0; t < 13; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      struct Ops { float w[13]; float b; unsigned k, kt; };
+      Ops r[GMPC_SP_RD];
+      auto tables = [&](Ops& o, int p) {
+        o.k = lk[4 * p + g];
+        o.kt = lt[2 * (4 * p + g) + tsel];
+      };
+      auto loads = [&](Ops& o) {
+        const int vo = (int)(o.k << 10) + lm, vt = (int)(o.kt << 10) + ltl;
+        const v4u a0 = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo, 0, 0);
+        const v2u a1 = __builtin_amdgcn_raw_buffer_load_b64(wrs, vo + 16, 0, 0);
+        const v4u a2 = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo + 512, 0, 0);
+        const v2u a3 = __builtin_amdgcn_raw_buffer_load_b64(wrs, vo + 528, 0, 0);
+        // tile 2 nt + hh: units 32 nt + 16 hh + l16
+        o.w[0] = __uint_as_float(a0.x); o.w[2] = __uint_as_float(a0.y);
+        o.w[4] = __uint_as_float(a0.z); o.w[6] = __uint_as_float(a0.w);
+        o.w[8] = __uint_as_float(a1.x); o.w[10] = __uint_as_float(a1.y);
+        o.w[1] = __uint_as_float(a2.x); o.w[3] = __uint_as_float(a2.y);
+        o.w[5] = __uint_as_float(a2.z); o.w[7] = __uint_as_float(a2.w);
+        o.w[9] = __uint_as_float(a3.x); o.w[11] = __uint_as_float(a3.y);
+        o.w[12] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, vt, 0, 0));
+        if constexpr (seed) o.b = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)o.k * n * 4 + lsn, 0, 0));
+        else o.b = st[(ls >> 2) + o.k];
+      };
+      auto step = [&](int p, Ops& cur, Ops& ahead2) __attribute__((always_inline)) {
+        loads(ahead2);                 // k-step p + 2 (its list entries were read at k-step p - 1)
+        tables(cur, p + 3);            // cur's entries were last used for its loads at k-step p - 2
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < 13; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.w[t], cur.b, acc[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      tables(r[0], 0); tables(r[1], 1); tables(r[2], 2);
+      loads(r[0]); loads(r[1]);
+      for (int p = 0; p < np; p += 3) {
+        step(p, r[0], r[2]);
+        if (p + 1 >= np) break;
+        step(p + 1, r[1], r[0]);
+        if (p + 2 >= np) break;
+        step(p + 2, r[2], r[1]);
+      }
+      mfma_fence<false>(acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7], acc[8], acc[9], acc[10],
+                        acc[11], acc[12]);
+      __builtin_amdgcn_wave_barrier();
+      // accumulator rows 4 g + j of tile 2 nt + hh = units 32 nt + 16 hh + 4 g + j, column = this lane's row
+      float* srow = st + l16 * GMPC_SP_STR;
+#pragma unroll
+      for (int t = 0; t < 12; ++t)
+        *reinterpret_cast<f32x4*>(srow + 32 * (t >> 1) + 16 * (t & 1) + 4 * g) = acc[t];
+      // tail: rows 0..7 even-k partials of units 192..199, rows 8..15 the odd-k ones (to 208..215)
+      *reinterpret_cast<f32x4*>(srow + (g < 2 ? 192 : 200) + 4 * g) = acc[12];
+      __builtin_amdgcn_wave_barrier();
+      if (g < 2) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(srow + 192 + 4 * g);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(srow + 208 + 4 * g);
+        *reinterpret_cast<f32x4*>(srow + 192 + 4 * g) = x + y;
+      }
+      __builtin_amdgcn_wave_barrier();
+    };
+    layer(Lh - 1, std::true_type{});
+    for (int l = Lh - 2; l >= 1; --l) layer(l, std::false_type{});
+
+    // ---- input GEMM  out = W_1 S_1 over the active units of S_1: coordinates 16 t + l16 of W_1^T's 32-wide rows
+    {
+      const int np = (build(0) + 3) >> 2;
+      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+      const bool two = nm > 16;      // (both tiles always run: W_1^T rows are 32 wide, zero padded)
+      struct Ops0 { float w0, w1, b; unsigned k; };
+      Ops0 r[GMPC_SP_RD];
+      auto tables = [&](Ops0& o, int p) { o.k = lk[4 * p + g]; };
+      auto loads = [&](Ops0& o) {
+        const int vo = (int)(o.k << 7) + l16 * 4;
+        o.w0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs0, vo, 0, 0));
+        o.w1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs0, vo + 64, 0, 0));
+        o.b = st[(ls >> 2) + o.k];
+      };
+      auto step = [&](int p, Ops0& cur, Ops0& ahead2) __attribute__((always_inline)) {
+        loads(ahead2);
+        tables(cur, p + 3);
+        __builtin_amdgcn_sched_barrier(0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.w0, cur.b, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.w1, cur.b, acc1, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      tables(r[0], 0); tables(r[1], 1); tables(r[2], 2);
+      loads(r[0]); loads(r[1]);
+      for (int p = 0; p < np; p += 3) {
+        step(p, r[0], r[2]);
+        if (p + 1 >= np) break;
+        step(p + 1, r[1], r[0]);
+        if (p + 2 >= np) break;
+        step(p + 2, r[2], r[1]);
+      }
+      mfma_fence<false>(acc0, acc1);
+      if (l16 < nrow) {
+        float* dst = AB + ((size_t)s * n + l16) * nm;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = 4 * g + j;
+          if (c < nm) dst[c] = acc0[j] + (c == l16 ? 1.0f : 0.0f);
+          if (two && c + 16 < nm) dst[c + 16] = acc1[j] + (c + 16 == l16 ? 1.0f : 0.0f);
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+int gmpc_launch_linearize_regs_rows(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                    const uint32_t* masks, const int* active, float* AB, int samp_mul,
+                                    int samp_add, int row0, hipStream_t s);
+
+// returns 0 on launch, -1 when the shape is not one this form covers (the caller runs the dense chain)
+int gmpc_launch_linearize_sparse(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                 const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                                 hipStream_t s) {
+  const int Lh = dyn.L - 1;
+  if (Lh < 2 || n + m > 32 || n < 1 || lp.NT != 7 || lp.NTF != 1 || lp.NGF != 1) return -1;
+  for (int l = 1; l <= Lh; ++l)
+    if (dyn.dims[l] != GMPC_SP_H) return -1;
+  if (NSamp <= 0) return 0;
+  // rows 16..n-1 first (any error leaves nothing launched)
+  if (n > 16 && gmpc_launch_linearize_regs_rows(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, 16,
+                                                s) != 0)
+    return -1;
+  const size_t lds = (size_t)(GMPC_THREADS / 64) * GMPC_SP_WAVE_BYTES;
+  int grid = (NSamp + 3) / 4;
+  if (grid > 256 * 2) grid = 256 * 2;      // persistent: two workgroups per CU
+  hipLaunchKernelGGL(k_linearize_sparse, dim3(grid), dim3(GMPC_THREADS), lds, s, NSamp, T, n, m, Lh, lp, masks,
+                     active, AB, samp_mul, samp_add);
+  return 0;
+}
