@@ -10,13 +10,19 @@
 // contracted units), B = S (4 contracted units x 16 Jacobian rows), the 4 contracted units of a k-step are four
 // consecutive entries of the sample's active list.  Rows 16..n-1 (n = 17: one row) stay on k_linearize_regs, which
 // takes a row window for them.
-//  - active lists: built per layer from the relu words with mbcnt (a prefix count, no scan), stored as 16-bit unit
-//    indices in the wave's LDS and padded with unit 200 -- a zero row of the padded W^T copies and a zero column of
-//    the S tile -- so the padded k-steps and the loads that run ahead of the last k-step read zeros, in bounds.
+//  - active lists: built per layer from the relu words with mbcnt (a prefix count, no scan), stored as 32-bit unit
+//    indices in the wave's LDS (no 16-bit extensions on the vector port) and padded with unit 200 -- a zero row of
+//    the padded W^T copies and a zero column of the S tile -- so the padded k-steps and the loads that run ahead of
+//    the last k-step read zeros, in bounds.
 //  - A operands: the lane-interleaved W_l^T rows of k_linearize_regs (LinPad::WTP, 1 KB per unit): the 12 full
 //    16-unit tiles are two 16-byte + two 8-byte buffer loads per lane and k-step; the voffset is the list entry
-//    << 10 plus a lane constant.  A k-step puts its 13 MFMAs beside two list reads and a handful of vector
-//    instructions (address of the weight rows, of the tail row and of the B operand; the 16-bit zero extensions).
+//    << 10 plus a lane constant.  A k-step puts its 13 MFMAs beside three list / B reads and three vector
+//    instructions (address of the weight rows, of the tail row and of the B operand), plus one pointer increment
+//    per list every three k-steps.  (Structured buffer loads, vindex = list entry with the row stride in the
+//    resource, would drop the first two, but measured slower: more vector-L1 accesses for the same bytes.)
+//  - accumulators: the first k-step starts the chains from the constant zero and the k-loop runs whole groups of
+//    three k-steps before the last one or two, so the 52 accumulator registers stay in place: no zeroing and no
+//    copies out of the loop per layer.
 //  - tail units 192..199: the dense chain sums them on 4x4x1_16B as an even-k partial plus an odd-k partial.  The
 //    13th tile reproduces the split: rows 0..7 read unit 192 + r of the even list entries (odd ones -> zero row),
 //    rows 8..15 the same units of the odd ones; the two halves are added once per layer, as there.
@@ -36,10 +42,10 @@ typedef unsigned v2u __attribute__((ext_vector_type(2)));
 #define GMPC_SP_Z 200        // the zero unit padded list entries point at
 #define GMPC_SP_STR 220      // floats per Jacobian row of the S tile: units 0..199, zeros 200..207, odd partials 208..215
 #define GMPC_SP_CAP 216      // list entries: 200 + the 3 k-steps the prefetch runs ahead, rounded to 8
-#define GMPC_SP_WAVE_BYTES (16 * GMPC_SP_STR * 4 + 3 * GMPC_SP_CAP * 2)
+#define GMPC_SP_WAVE_BYTES (16 * GMPC_SP_STR * 4 + 3 * GMPC_SP_CAP * 4)
 #define GMPC_SP_RD 3         // operand sets in flight: loads for k-step p + 2, list entries for p + 3
 
-// LDS: GMPC_SP_WAVE_BYTES per wave, 61.5 KB per workgroup -- two workgroups (eight waves) per CU
+// LDS: GMPC_SP_WAVE_BYTES per wave, 65.1 KB per workgroup -- two workgroups (eight waves) per CU
 __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
     int NSamp, int T, int n, int m, int Lh, LinPad lp, const uint32_t* masks, const int* active, float* AB,
     int samp_mul, int samp_add) {
@@ -50,8 +56,9 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
   const int nrow = n < 16 ? n : 16;
   char* wbase = smem + wave * GMPC_SP_WAVE_BYTES;
   float* st = reinterpret_cast<float*>(wbase);                                      // S tile [16][STR]
-  unsigned short* lk = reinterpret_cast<unsigned short*>(wbase + 16 * GMPC_SP_STR * 4);   // unit list
-  unsigned short* lt = lk + GMPC_SP_CAP;                                            // [CAP][2]: even / odd only
+  // unit list (32-bit entries: no 16-bit extensions) and its [CAP][2] even / odd split for the tail tile
+  unsigned* lk = reinterpret_cast<unsigned*>(wbase + 16 * GMPC_SP_STR * 4);
+  unsigned* lt = lk + GMPC_SP_CAP;
   // zero units 200..207 of the S tile (never written again)
   if (lane < 16 * 8) st[(lane >> 3) * GMPC_SP_STR + GMPC_SP_H + (lane & 7)] = 0.f;
   if (lane + 64 < 16 * 8) st[((lane + 64) >> 3) * GMPC_SP_STR + GMPC_SP_H + (lane & 7)] = 0.f;
@@ -61,12 +68,14 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
   const int lm = l16 * 32, ltl = ((l16 & 7) * 8 + 6) * 4;
   const int ls = l16 * GMPC_SP_STR * 4;
   const int tsel = l16 >= 8 ? 1 : 0;
+  const unsigned* lkl = lk + g;                    // this lane's entry 4 p + g: lkl[4 p], its tail half: ltl_[8 p]
+  const unsigned* ltl_ = lt + 2 * g + tsel;
+  // seed operand: W_L[k][l16]; the rows past n read past the end of the buffer, which returns zero
+  const int lsn = l16 < n ? l16 * 4 : (1 << 28);
   const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(lp.WLP), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * n * (int)sizeof(float), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(lp.WTP[0]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * 32 * (int)sizeof(float), 0x00020000);
-  // seed operand: W_L[k][l16]; the rows past n read past the end of the buffer, which returns zero
-  const int lsn = l16 < n ? l16 * 4 : (1 << 28);
 
   constexpr int WPB = GMPC_THREADS / 64;
   for (int s = blockIdx.x * WPB + wave; s < NSamp; s += gridDim.x * WPB) {
@@ -74,14 +83,10 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
     if (active != nullptr && active[sid / T] == 0) continue;
     const uint32_t* mrow = masks + sid * Lh * GMPC_MW;
 
-    // active list of hidden layer ml: returns its length
+    // active list of hidden layer ml: returns its length.  Entries from the length on, as far as the k-steps and the
+    // loads that run ahead reach (4 np + 12), point at the zero unit
     auto build = [&](int ml) -> int {
       __builtin_amdgcn_wave_barrier();
-      for (int e = lane; e < GMPC_SP_CAP; e += 64) {
-        lk[e] = GMPC_SP_Z;
-        lt[2 * e] = GMPC_SP_Z;
-        lt[2 * e + 1] = GMPC_SP_Z;
-      }
       int base = 0;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -90,12 +95,17 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
         const uint32_t lo_m = c < 3 ? lo : (lo & 0xFFu);     // units 192..199 of word 6
         const uint32_t word = lane < 32 ? lo_m : hi;
         const int pos = base + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo_m, 0u));
-        const int u = 64 * c + lane;
+        const unsigned u = 64 * c + lane;
         if ((word >> (lane & 31)) & 1u) {
-          lk[pos] = (unsigned short)u;
-          lt[2 * pos + (u & 1)] = (unsigned short)u;
+          const bool odd = (u & 1u) != 0;
+          lk[pos] = u;
+          *reinterpret_cast<v2u*>(lt + 2 * pos) = v2u{odd ? GMPC_SP_Z : u, odd ? u : GMPC_SP_Z};
         }
         base += __builtin_popcount(lo_m) + __builtin_popcount(hi);
+      }
+      if (lane < 16) {
+        lk[base + lane] = GMPC_SP_Z;
+        *reinterpret_cast<v2u*>(lt + 2 * (base + lane)) = v2u{GMPC_SP_Z, GMPC_SP_Z};
       }
       __builtin_amdgcn_wave_barrier();
       return base;
@@ -108,16 +118,15 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<float*>(lp.WTP[l]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * 1024, 0x00020000);
       f32x4 acc[13];
-#pragma unroll
-      for (int t = 0; t < 13; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
       struct Ops { float w[13]; float b; unsigned k, kt; };
       Ops r[GMPC_SP_RD];
       auto tables = [&](Ops& o, int p) {
-        o.k = lk[4 * p + g];
-        o.kt = lt[2 * (4 * p + g) + tsel];
+        o.k = lkl[4 * p];
+        o.kt = ltl_[8 * p];
       };
       auto loads = [&](Ops& o) {
-        const int vo = (int)(o.k << 10) + lm, vt = (int)(o.kt << 10) + ltl;
+        const int k = (int)o.k, kt = (int)o.kt;
+        const int vo = (k << 10) + lm, vt = (kt << 10) + ltl;
         const v4u a0 = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo, 0, 0);
         const v2u a1 = __builtin_amdgcn_raw_buffer_load_b64(wrs, vo + 16, 0, 0);
         const v4u a2 = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo + 512, 0, 0);
@@ -130,8 +139,8 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
         o.w[5] = __uint_as_float(a2.z); o.w[7] = __uint_as_float(a2.w);
         o.w[9] = __uint_as_float(a3.x); o.w[11] = __uint_as_float(a3.y);
         o.w[12] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, vt, 0, 0));
-        if constexpr (seed) o.b = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, (int)o.k * n * 4 + lsn, 0, 0));
-        else o.b = st[(ls >> 2) + o.k];
+        if constexpr (seed) o.b = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, k * n * 4 + lsn, 0, 0));
+        else o.b = st[(ls >> 2) + k];
       };
       auto step = [&](int p, Ops& cur, Ops& ahead2) __attribute__((always_inline)) {
         loads(ahead2);                 // k-step p + 2 (its list entries were read at k-step p - 1)
@@ -141,14 +150,29 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
         for (int t = 0; t < 13; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.w[t], cur.b, acc[t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       };
-      tables(r[0], 0); tables(r[1], 1); tables(r[2], 2);
-      loads(r[0]); loads(r[1]);
-      for (int p = 0; p < np; p += 3) {
-        step(p, r[0], r[2]);
-        if (p + 1 >= np) break;
-        step(p + 1, r[1], r[0]);
-        if (p + 2 >= np) break;
-        step(p + 2, r[2], r[1]);
+      if (np == 0) {
+#pragma unroll
+        for (int t = 0; t < 13; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        tables(r[0], 0); tables(r[1], 1); tables(r[2], 2);
+        loads(r[0]); loads(r[1]);
+        // k-step 0 starts the chains from the constant zero (no accumulator initialisation on the vector port)
+        loads(r[2]);
+        tables(r[0], 3);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < 13; ++t)
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(r[0].w[t], r[0].b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        // whole groups of three k-steps with one exit, then the last one or two (the accumulators stay in place)
+        int p = 1;
+        for (; p + 3 <= np; p += 3) {
+          step(p, r[1], r[0]);
+          step(p + 1, r[2], r[1]);
+          step(p + 2, r[0], r[2]);
+        }
+        if (p < np) step(p, r[1], r[0]);
+        if (p + 1 < np) step(p + 1, r[2], r[1]);
       }
       mfma_fence<false>(acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7], acc[8], acc[9], acc[10],
                         acc[11], acc[12]);
@@ -178,7 +202,7 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       const bool two = nm > 16;      // (both tiles always run: W_1^T rows are 32 wide, zero padded)
       struct Ops0 { float w0, w1, b; unsigned k; };
       Ops0 r[GMPC_SP_RD];
-      auto tables = [&](Ops0& o, int p) { o.k = lk[4 * p + g]; };
+      auto tables = [&](Ops0& o, int p) { o.k = lkl[4 * p]; };
       auto loads = [&](Ops0& o) {
         const int vo = (int)(o.k << 7) + l16 * 4;
         o.w0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs0, vo, 0, 0));
@@ -195,13 +219,14 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       };
       tables(r[0], 0); tables(r[1], 1); tables(r[2], 2);
       loads(r[0]); loads(r[1]);
-      for (int p = 0; p < np; p += 3) {
+      int p = 0;
+      for (; p + 3 <= np; p += 3) {
         step(p, r[0], r[2]);
-        if (p + 1 >= np) break;
         step(p + 1, r[1], r[0]);
-        if (p + 2 >= np) break;
         step(p + 2, r[2], r[1]);
       }
+      if (p < np) step(p, r[0], r[2]);
+      if (p + 1 < np) step(p + 1, r[1], r[0]);
       mfma_fence<false>(acc0, acc1);
       if (l16 < nrow) {
         float* dst = AB + ((size_t)s * n + l16) * nm;
