@@ -360,6 +360,7 @@ struct LinPad {
   int NT, NTF, NGF;                     // column tiles: hidden GEMMs / input GEMM per group, groups
   const float* WLP;                     // [dims[Lh]+2][n]            rows >= dims[Lh] are zero
   const float* WTP[GMPC_MAX_LAYERS];    // l>=1: [dims[l+1]+2][32*NT]; l==0: [dims[1]+2][32*NTF]
+  const float* WSP[GMPC_MAX_LAYERS];    // 1 <= l < Lh: W_l^T packed for k_linearize_sparse (null for other shapes)
   unsigned long long* dbg;              // diagnostic: per-segment cycle sums (null in production)
 };
 

@@ -234,6 +234,10 @@ __global__ __launch_bounds__(GMPC_THREADS, 1) void k_linearize_mfma(
 }
 
 // ---------------------------------------------------------------------------------------------
+// packed copies of k_linearize_sparse (gmpc_linearize_sparse.hip: the one file that knows their format)
+size_t gmpc_linsparse_floats(int L, const int* dims, int n, int m);
+void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* out, hipStream_t s);
+
 size_t gmpc_linpad_floats(const gmpc_shape* sh) {
   const int L = sh->dyn_layers, Lh = L - 1;
   int wmax = 1;
@@ -243,7 +247,7 @@ size_t gmpc_linpad_floats(const gmpc_shape* sh) {
   size_t f = (size_t)(sh->dyn_dims[Lh] + GMPC_LIN_PADROWS) * sh->n;
   f += (size_t)(sh->dyn_dims[1] + GMPC_LIN_PADROWS) * 32 * NTF * NGF;
   for (int l = 1; l < Lh; ++l) f += (size_t)(sh->dyn_dims[l + 1] + GMPC_LIN_PADROWS) * 256;
-  return f + 64;
+  return f + 64 + gmpc_linsparse_floats(L, sh->dyn_dims, sh->n, sh->m);
 }
 
 // builds the padded copies; `pad` must hold gmpc_linpad_floats() floats
@@ -276,6 +280,7 @@ void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pa
                          dyn.W[l], p);
     p += (size_t)(outd + GMPC_LIN_PADROWS) * ldo;
   }
+  gmpc_linsparse_prepare(dyn, n, m, p, out, s);
 }
 
 template <int NT, int NTF>

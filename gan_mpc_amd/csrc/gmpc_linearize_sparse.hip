@@ -14,12 +14,15 @@
 //    indices in the wave's LDS (no 16-bit extensions on the vector port) and padded with unit 200 -- a zero row of
 //    the padded W^T copies and a zero column of the S tile -- so the padded k-steps and the loads that run ahead of
 //    the last k-step read zeros, in bounds.
-//  - A operands: the lane-interleaved W_l^T rows of k_linearize_regs (LinPad::WTP, 1 KB per unit): the 12 full
-//    16-unit tiles are two 16-byte + two 8-byte buffer loads per lane and k-step; the voffset is the list entry
-//    << 10 plus a lane constant.  A k-step puts its 13 MFMAs beside three list / B reads and three vector
-//    instructions (address of the weight rows, of the tail row and of the B operand), plus one pointer increment
-//    per list every three k-steps.  (Structured buffer loads, vindex = list entry with the row stride in the
-//    resource, would drop the first two, but measured slower: more vector-L1 accesses for the same bytes.)
+//  - A operands: a packed copy of W_l^T made for this kernel (LinPad::WSP, 1 KB per unit, see k_pack_sparse): the
+//    12 full 16-unit tiles are three 16-byte buffer loads per lane and k-step, each lane group reading 256
+//    contiguous bytes of its row (4 vector-L1 sectors of 64 B; the lane-interleaved rows of k_linearize_regs need 8
+//    for the same operands, and the vector L1 retires about one access per cycle); the tail tile is one 4-byte
+//    load, 32 contiguous bytes per row.  The voffset is the list entry << 10 plus a lane constant.  A k-step puts its 13 MFMAs beside three list / B
+//    reads and three vector instructions (address of the weight rows, of the tail row and of the B operand), plus
+//    one pointer increment per list every three k-steps.  (Structured buffer loads, vindex = list entry with the
+//    row stride in the resource, would drop the first two, but measured slower: more vector-L1 accesses for the
+//    same bytes.)
 //  - accumulators: the first k-step starts the chains from the constant zero and the k-loop runs whole groups of
 //    three k-steps before the last one or two, so the 52 accumulator registers stay in place: no zeroing and no
 //    copies out of the loop per layer.
@@ -44,6 +47,50 @@ typedef unsigned v2u __attribute__((ext_vector_type(2)));
 #define GMPC_SP_CAP 216      // list entries: 200 + the 3 k-steps the prefetch runs ahead, rounded to 8
 #define GMPC_SP_WAVE_BYTES (16 * GMPC_SP_STR * 4 + 3 * GMPC_SP_CAP * 4)
 #define GMPC_SP_RD 3         // operand sets in flight: loads for k-step p + 2, list entries for p + 3
+#define GMPC_SP_ROW 256      // floats per row of a packed copy (1 KB: the row address is the unit << 10)
+
+// The shapes this form covers: two or more hidden layers, all 200 wide, n + m <= 32 (one 32-wide input tile).
+static bool sparse_form(int L, const int* dims, int n, int m) {
+  const int Lh = L - 1;
+  if (Lh < 2 || n + m > 32 || n < 1) return false;
+  for (int l = 1; l <= Lh; ++l)
+    if (dims[l] != GMPC_SP_H) return false;
+  return true;
+}
+
+// Packed copy of hidden layer l's W_l^T (W: (200 x 200) row-major, [input unit i][output unit o]).  Row o (a unit of
+// layer l + 1, the contracted index) holds the A operands of its k-step as the lanes read them:
+//   [64 q + 4 l16 + j] = W[16 (4 q + j) + l16][o]   q = 0..2: tile 4 q + j, unit 16 (4 q + j) + l16 (units 0..191)
+//   [192 + u]          = W[192 + u][o]              u = 0..7: the tail tile
+// and zeros at 200..255.  Rows 200.. (the zero unit and the padding) stay zero.
+__global__ void k_pack_sparse(const float* W, float* dst) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= GMPC_SP_H * GMPC_SP_H) return;
+  const int i = e / GMPC_SP_H, o = e - i * GMPC_SP_H;
+  const int t = i >> 4;
+  const int slot = i < 192 ? 64 * (t >> 2) + 4 * (i & 15) + (t & 3) : i;
+  dst[(size_t)o * GMPC_SP_ROW + slot] = W[e];
+}
+
+// floats the packed copies add to the padded-weight buffer (gmpc_linpad_floats): 0 for shapes this form does not cover
+size_t gmpc_linsparse_floats(int L, const int* dims, int n, int m) {
+  if (!sparse_form(L, dims, n, m)) return 0;
+  // + one row to round the first copy up to 1 KB
+  return (size_t)(L - 2) * (GMPC_SP_H + GMPC_LIN_PADROWS) * GMPC_SP_ROW + GMPC_SP_ROW;
+}
+
+// builds the packed copies at `p` (zeroed, gmpc_linsparse_floats() floats) on every gmpc_set_params, beside the
+// padded copies of gmpc_linpad_prepare
+void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* out, hipStream_t s) {
+  for (int l = 0; l < GMPC_MAX_LAYERS; ++l) out->WSP[l] = nullptr;
+  if (!sparse_form(dyn.L, dyn.dims, n, m)) return;
+  p = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 1023) & ~(uintptr_t)1023);
+  for (int l = 1; l < dyn.L - 1; ++l) {
+    out->WSP[l] = p;
+    hipLaunchKernelGGL(k_pack_sparse, dim3((GMPC_SP_H * GMPC_SP_H + 255) / 256), dim3(256), 0, s, dyn.W[l], p);
+    p += (size_t)(GMPC_SP_H + GMPC_LIN_PADROWS) * GMPC_SP_ROW;
+  }
+}
 
 // LDS: GMPC_SP_WAVE_BYTES per wave, 65.1 KB per workgroup -- two workgroups (eight waves) per CU
 __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
@@ -63,9 +110,9 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
   if (lane < 16 * 8) st[(lane >> 3) * GMPC_SP_STR + GMPC_SP_H + (lane & 7)] = 0.f;
   if (lane + 64 < 16 * 8) st[((lane + 64) >> 3) * GMPC_SP_STR + GMPC_SP_H + (lane & 7)] = 0.f;
 
-  // lane constants (bytes): A operand of unit 32 nt + l16 (+16) in a lane-interleaved W^T row; the tail tile's unit
-  // 192 + (l16 & 7); the S tile column of this lane's Jacobian row; its list half for the tail tile
-  const int lm = l16 * 32, ltl = ((l16 & 7) * 8 + 6) * 4;
+  // lane constants (bytes): A operands of units 16 t + l16 in a packed W^T row; the tail tile's unit 192 + (l16 & 7);
+  // the S tile column of this lane's Jacobian row; its list half for the tail tile
+  const int lw = l16 * 16, lwt = (192 + (l16 & 7)) * 4;
   const int ls = l16 * GMPC_SP_STR * 4;
   const int tsel = l16 >= 8 ? 1 : 0;
   const unsigned* lkl = lk + g;                    // this lane's entry 4 p + g: lkl[4 p], its tail half: ltl_[8 p]
@@ -116,7 +163,7 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       constexpr bool seed = decltype(seedc)::value;
       const int np = (build(l) + 3) >> 2;
       const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<float*>(lp.WTP[l]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * 1024, 0x00020000);
+          const_cast<float*>(lp.WSP[l]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * GMPC_SP_ROW * 4, 0x00020000);
       f32x4 acc[13];
       struct Ops { float w[13]; float b; unsigned k, kt; };
       Ops r[GMPC_SP_RD];
@@ -126,18 +173,14 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       };
       auto loads = [&](Ops& o) {
         const int k = (int)o.k, kt = (int)o.kt;
-        const int vo = (k << 10) + lm, vt = (kt << 10) + ltl;
-        const v4u a0 = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo, 0, 0);
-        const v2u a1 = __builtin_amdgcn_raw_buffer_load_b64(wrs, vo + 16, 0, 0);
-        const v4u a2 = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo + 512, 0, 0);
-        const v2u a3 = __builtin_amdgcn_raw_buffer_load_b64(wrs, vo + 528, 0, 0);
-        // tile 2 nt + hh: units 32 nt + 16 hh + l16
-        o.w[0] = __uint_as_float(a0.x); o.w[2] = __uint_as_float(a0.y);
-        o.w[4] = __uint_as_float(a0.z); o.w[6] = __uint_as_float(a0.w);
-        o.w[8] = __uint_as_float(a1.x); o.w[10] = __uint_as_float(a1.y);
-        o.w[1] = __uint_as_float(a2.x); o.w[3] = __uint_as_float(a2.y);
-        o.w[5] = __uint_as_float(a2.z); o.w[7] = __uint_as_float(a2.w);
-        o.w[9] = __uint_as_float(a3.x); o.w[11] = __uint_as_float(a3.y);
+        const int vo = (k << 10) + lw, vt = (kt << 10) + lwt;
+        // tile 4 q + j: units 16 (4 q + j) + l16
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const v4u a = __builtin_amdgcn_raw_buffer_load_b128(wrs, vo + 256 * q, 0, 0);
+          o.w[4 * q] = __uint_as_float(a.x); o.w[4 * q + 1] = __uint_as_float(a.y);
+          o.w[4 * q + 2] = __uint_as_float(a.z); o.w[4 * q + 3] = __uint_as_float(a.w);
+        }
         o.w[12] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wrs, vt, 0, 0));
         if constexpr (seed) o.b = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, k * n * 4 + lsn, 0, 0));
         else o.b = st[(ls >> 2) + k];
@@ -251,9 +294,7 @@ int gmpc_launch_linearize_sparse(int NSamp, int T, int n, int m, const MlpDesc& 
                                  const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
                                  hipStream_t s) {
   const int Lh = dyn.L - 1;
-  if (Lh < 2 || n + m > 32 || n < 1 || lp.NT != 7 || lp.NTF != 1 || lp.NGF != 1) return -1;
-  for (int l = 1; l <= Lh; ++l)
-    if (dyn.dims[l] != GMPC_SP_H) return -1;
+  if (!sparse_form(dyn.L, dyn.dims, n, m) || lp.NT != 7 || lp.NTF != 1 || lp.NGF != 1) return -1;
   if (NSamp <= 0) return 0;
   // rows 16..n-1 first (any error leaves nothing launched)
   if (n > 16 && gmpc_launch_linearize_regs_rows(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, 16,
