@@ -83,6 +83,7 @@ SIGNATURES = {
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),
     "gmpc_bilevel_grad_inputs": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "gmpc_bilevel_grad_dynamics": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "gmpc_rollout_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_upper_loss": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "gmpc_expert_rollout": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(ExpertShape), _P, _P, _P, _P, _P]),
     "gmpc_expert_param_count": (C.c_long, [C.c_int, C.POINTER(ExpertShape)]),

@@ -89,6 +89,12 @@ void gmpc_launch_dyn_adjoints(int, int, int, int, int, const float*, const float
 int gmpc_dyn_rows_stride(const MlpDesc&);
 int gmpc_launch_dyn_rows(int, int, int, int, const MlpDesc&, const float*, const float*, const float*, const float*,
                          const float*, const float*, float*, float*, hipStream_t);
+int gmpc_rvjp_cost_stride(const MlpDesc&);
+void gmpc_launch_rvjp_sweep(int, int, int, int, const MlpDesc&, const MlpDesc&, const float*, const float*,
+                            const float*, const float*, const float*, const float*, const uint32_t*, float*, float*,
+                            float*, float*, float*, float*, float*, int, hipStream_t);
+void gmpc_launch_rvjp_acts(int, int, int, int, const MlpDesc&, const float*, const float*, float*, int, uint32_t*,
+                           hipStream_t);
 
 // LSTM dynamics variant (gmpc_dynl.hip)
 void gmpc_launch_dynl_rollout(DynlTrajArgs, hipStream_t);
@@ -270,6 +276,10 @@ struct gmpc_ctx {
   // dynamics-weight gradient (gmpc_bilevel_grad_dynamics): grown to the largest B seen, never shrunk
   float *dgw = nullptr, *dglam = nullptr, *dgacts = nullptr, *dgdels = nullptr;
   size_t dgw_cap = 0, dglam_cap = 0, dgacts_cap = 0, dgdels_cap = 0;
+  // rollout VJP (gmpc_rollout_vjp): its own relu masks, per-trajectory mpc_w terms, cost and dynamics rows; grown to
+  // the largest B seen, never shrunk
+  float *rvmask = nullptr, *rvgm = nullptr, *rvcact = nullptr, *rvcdel = nullptr, *rvacts = nullptr, *rvdels = nullptr;
+  size_t rvmask_cap = 0, rvgm_cap = 0, rvcact_cap = 0, rvcdel_cap = 0, rvacts_cap = 0, rvdels_cap = 0;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;
@@ -1694,6 +1704,82 @@ extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, f
     g += (long)M * N + N;
     aoff += M;
     doff += N;
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The VJP of the rollout and its costs at (X, U, goal) (gmpc_rollout_vjp.hip).  Stateless: the masks and rows live in
+// the call's own workspace, no held solution is dropped; the GEMMs' partials use the shared scratch.
+extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float* U, const float* goal, const float* gX,
+                                const float* gcost, float* grad_x0, float* grad_U, float* grad_goal,
+                                float* grad_theta_sum, float* grad_dyn_sum, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl)
+    return fail(GMPC_EINVAL, "rollout vjp: relu-MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
+  if (!X || !U || !goal) return fail(GMPC_EINVAL, "rollout vjp: X, U and goal must not be null");
+  if (!gX && !gcost) return fail(GMPC_EINVAL, "rollout vjp: gX and gcost are both null: no cotangent");
+  if (!grad_x0 && !grad_U && !grad_goal && !grad_theta_sum && !grad_dyn_sum)
+    return fail(GMPC_EINVAL, "rollout vjp: every output is null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = sh.n, m = sh.m, T = sh.T, Lh = sh.dyn_layers - 1;
+  const size_t steps = (size_t)B * T;
+  const bool want_theta = grad_theta_sum != nullptr && gcost != nullptr;
+  const size_t dstride = (size_t)gmpc_dyn_rows_stride(c->dyn), cstride = (size_t)gmpc_rvjp_cost_stride(c->cost);
+  // (uint32 mask words in a float allocation)
+  TRY(regrow(c, &c->rvmask, &c->rvmask_cap, steps * Lh * GMPC_MW));
+  if (want_theta) {
+    TRY(regrow(c, &c->rvgm, &c->rvgm_cap, (size_t)B * 3 + 8));
+    // the MFMA weight-gradient GEMM reads 8 rows past the end of both operands: keep them zero
+    TRY(regrow(c, &c->rvcact, &c->rvcact_cap, ((size_t)B + 8) * cstride));
+    TRY(regrow(c, &c->rvcdel, &c->rvcdel_cap, ((size_t)B + 8) * cstride));
+    HIP_TRY(hipMemsetAsync(c->rvcact + (size_t)B * cstride, 0, 8 * cstride * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(c->rvcdel + (size_t)B * cstride, 0, 8 * cstride * sizeof(float), s));
+  }
+  if (grad_dyn_sum) {
+    TRY(regrow(c, &c->rvacts, &c->rvacts_cap, (steps + 8) * dstride));
+    TRY(regrow(c, &c->rvdels, &c->rvdels_cap, (steps + 8) * dstride));
+    HIP_TRY(hipMemsetAsync(c->rvacts + steps * dstride, 0, 8 * dstride * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(c->rvdels + steps * dstride, 0, 8 * dstride * sizeof(float), s));
+  }
+  uint32_t* masks = reinterpret_cast<uint32_t*>(c->rvmask);
+  if (grad_dyn_sum)
+    gmpc_launch_rvjp_acts(B, n, m, T, c->dyn, X, U, c->rvacts, (int)dstride, masks, s);
+  else
+    gmpc_launch_masks(B, n, m, T, c->dyn, X, U, masks, s);
+  gmpc_launch_rvjp_sweep(B, n, m, T, c->dyn, c->cost, c->mpc_w, X, U, goal, gX, gcost, masks, grad_x0, grad_U,
+                         grad_goal, want_theta ? c->rvgm : nullptr, want_theta ? c->rvcact : nullptr,
+                         want_theta ? c->rvcdel : nullptr, grad_dyn_sum ? c->rvdels : nullptr, (int)dstride, s);
+  if (grad_theta_sum && !want_theta) {
+    // no cost cotangent: the costs' parameters get nothing
+    HIP_TRY(hipMemsetAsync(grad_theta_sum, 0, (3 + (size_t)mlp_count(sh.cost_layers, sh.cost_dims)) * sizeof(float),
+                           s));
+  } else if (want_theta) {
+    gmpc_launch_wgrad(B, 1, 3, c->rvgm, 0, c->rvgm, 3, c->rvgm + (size_t)B * 3, grad_theta_sum, B, c->wpart, 256, s,
+                      c->wpart_floats, false);
+    float* g = grad_theta_sum + 3;
+    int aoff = 0, doff = 0;
+    for (int l = 0; l < sh.cost_layers; ++l) {
+      const int M = sh.cost_dims[l], N = sh.cost_dims[l + 1];
+      gmpc_launch_wgrad(B, M, N, c->rvcact + aoff, (int)cstride, c->rvcdel + doff, (int)cstride, g, g + (long)M * N,
+                        B, c->wpart, 256, s, c->wpart_floats, true);
+      g += (long)M * N + N;
+      aoff += M;
+      doff += N;
+    }
+  }
+  if (grad_dyn_sum) {
+    float* g = grad_dyn_sum;
+    int aoff = 0, doff = 0;
+    for (int l = 0; l < sh.dyn_layers; ++l) {
+      const int M = sh.dyn_dims[l], N = sh.dyn_dims[l + 1];
+      gmpc_launch_wgrad((int)steps, M, N, c->rvacts + aoff, (int)dstride, c->rvdels + doff, (int)dstride, g,
+                        g + (long)M * N, (int)steps, c->wpart, 256, s, c->wpart_floats, true);
+      g += (long)M * N + N;
+      aoff += M;
+      doff += N;
+    }
   }
   HIP_TRY(hipGetLastError());
   return 0;

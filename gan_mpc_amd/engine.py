@@ -267,6 +267,27 @@ class Engine:
         _lib.check(self.lib.gmpc_bilevel_grad_dynamics(self.ctx, B, _ptr(lx), _ptr(grad_sum), self._stream()))
         return grad_sum
 
+    def rollout_vjp(self, X, U, goal, gX=None, gcost=None, want_x0=True, want_U=True, want_goal=True,
+                    want_theta=True, want_dyn=True):
+        """The VJP of the rollout and its costs at (X, U, goal) (gmpc_rollout_vjp): gX = dL/dX (B, T+1, n) and/or
+        gcost = dL/dcosts (B, T+1).  -> dict(x0 (B, n), U (B, T, m), goal (B, T+1, n), theta [3 + cost_count],
+        dyn [dyn_count]), None where not wanted; theta and dyn are summed over the batch.  Stateless: a held iLQR
+        solution stays valid.  Relu-MLP dynamics only."""
+        B = X.shape[0]
+        n, m, T = self.n, self.m, self.T
+        for name, t, shape in (("X", X, (B, T + 1, n)), ("U", U, (B, T, m)), ("goal", goal, (B, T + 1, self.nx)),
+                               ("gX", gX, (B, T + 1, n)), ("gcost", gcost, (B, T + 1))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"rollout_vjp: {name} must be {shape}, got {tuple(t.shape)}")
+        out = dict(x0=self.new(B, n) if want_x0 else None, U=self.new(B, T, m) if want_U else None,
+                   goal=self.new(B, T + 1, self.nx) if want_goal else None,
+                   theta=self.new(3 + self.cost_count) if want_theta else None,
+                   dyn=self.new(self.dyn_count) if want_dyn else None)
+        _lib.check(self.lib.gmpc_rollout_vjp(
+            self.ctx, B, _ptr(X), _ptr(U), _ptr(goal), _ptr(gX), _ptr(gcost), _ptr(out["x0"]), _ptr(out["U"]),
+            _ptr(out["goal"]), _ptr(out["theta"]), _ptr(out["dyn"]), self._stream()))
+        return out
+
     def upper_loss(self, B, loss_kind, desired=None, critic=None):
         loss = self.new(B)
         _lib.check(self.lib.gmpc_upper_loss(self.ctx, B, int(loss_kind), _ptr(desired), _ptr(critic),

@@ -15,11 +15,18 @@ section 12), and, with dynamics_grad=True, gmpc_bilevel_grad_dynamics dL/dtheta_
   - init_U receives none: at a stationary point the solution does not depend on the initial guess (away from the
     solver's stopping tolerance, where it does, but not differentiably).
   - The engine holds one solution at a time.  Backward must run before another solve on the same engine; otherwise it
-    raises instead of differentiating the wrong solution."""
+    raises instead of differentiating the wrong solution.
+
+(X, costs) = rollout_layer(policy, params, x0, U, goal) is the rollout and its per-step costs as a differentiable torch
+op: backward is one call of gmpc_rollout_vjp, the true derivative w.r.t. x0, U, goal and the
+mpc_weights / cost_params / dynamics_params ranges of params.flat (dynamics_grad=False leaves the last one out).  Its
+forward runs on a second engine of the policy bound to the same parameters, so an iLQR solution held for
+ilqr_layer's backward survives it.  Relu-MLP dynamics only (LSTM dynamics fail in forward)."""
 
 import torch
 
 from gan_mpc_amd._lib import GmpcError
+from gan_mpc_amd.engine import Engine
 from gan_mpc_amd.policy import optimizers as opt
 
 _THETA_KEYS = ("mpc_weights", "cost_params")
@@ -85,3 +92,72 @@ def ilqr_layer(policy, params, x0, goal, init_U, trajax_ilqr_kwargs=None, dynami
     dparams = policy.to_device_params(params)
     return ILQRFunction.apply(policy, dparams, trajax_ilqr_kwargs, dparams.flat, x0, goal, init_U,
                               bool(dynamics_grad))
+
+
+def _rollout_engine(policy, dparams, B):
+    """The policy's second engine (not the one holding its iLQR solution), sized for B and bound to dparams."""
+    n, m, nx, dyn_lstm = dparams.sizes_of_state()
+    if dyn_lstm:
+        raise GmpcError(f"rollout_layer: relu-MLP dynamics only (dyn_lstm_features = {dyn_lstm})")
+    key = policy._shape_key(dparams)
+    cached = getattr(policy, "_rollout_eng", None)
+    if cached is None or cached[0] != key or B > cached[1].max_batch:
+        if cached is not None:
+            cached[1].close()
+        eng = Engine(n, m, policy.config.mpc.horizon, dparams.meta["dyn_dims"], dparams.meta["cost_dims"],
+                     max_batch=max(B, 8), device=policy.device().index)
+        policy._rollout_eng = (key, eng)
+    eng = policy._rollout_eng[1]
+    eng.set_params(dparams.view("mpc_weights"), dparams.view("dynamics_params"), dparams.view("cost_params"))
+    return eng
+
+
+class RolloutFunction(torch.autograd.Function):
+    """forward(eng, dparams, flat, x0, U, goal, dynamics_grad) -> (X, costs); eng is bound to dparams."""
+
+    @staticmethod
+    def forward(ctx, eng, dparams, flat, x0, U, goal, dynamics_grad):
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+        U32, goal32 = f32(U), f32(goal)
+        X, costs = eng.rollout_cost(f32(x0), U32, goal32)
+        ctx.eng = eng
+        ctx.views = eng._bound
+        ctx.theta = dparams.range_of(_THETA_KEYS)
+        ctx.dyn = dparams.range_of(("dynamics_params",)) if dynamics_grad else None
+        ctx.flat_shape = flat.shape
+        ctx.save_for_backward(X, U32, goal32)
+        ctx.set_materialize_grads(False)
+        return X, costs
+
+    @staticmethod
+    def backward(ctx, gX, gc):
+        want_theta, want_x0, want_U, want_goal = ctx.needs_input_grad[2:6]
+        if (gX is None and gc is None) or not (want_theta or want_x0 or want_U or want_goal):
+            return (None,) * 7
+        eng = ctx.eng
+        X, U, goal = ctx.saved_tensors
+        if eng._bound is None or any(a.data_ptr() != b.data_ptr() for a, b in zip(eng._bound, ctx.views)):
+            eng.set_params(*ctx.views)      # another rollout_layer rebound the engine in between
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        out = eng.rollout_vjp(X, U, goal, f32(gX), f32(gc), want_x0=want_x0, want_U=want_U, want_goal=want_goal,
+                              want_theta=want_theta, want_dyn=want_theta and ctx.dyn is not None)
+        gflat = None
+        if want_theta:
+            lo, cnt = ctx.theta
+            gflat = torch.zeros(ctx.flat_shape, dtype=torch.float32, device=X.device)
+            gflat[lo:lo + cnt] = out["theta"]
+            if ctx.dyn is not None:
+                lo, cnt = ctx.dyn
+                gflat[lo:lo + cnt] = out["dyn"]
+        return None, None, gflat, out["x0"], out["U"], out["goal"], None
+
+
+def rollout_layer(policy, params, x0, U, goal, dynamics_grad=True):
+    """(X (B, T+1, n), costs (B, T+1)) = the rollout of (x0, U) under the policy's dynamics and its per-step costs
+    against goal (gmpc_rollout_cost), differentiable w.r.t. x0, U, goal and the mpc_weights / cost_params (and, with
+    dynamics_grad, dynamics_params) ranges of params.flat: the true derivative (see the module docstring).  params:
+    the policy's DeviceParams (a parameter tree is converted, and then is not differentiable); x0 (B, n), U (B, T, m),
+    goal (B, T+1, n): device tensors."""
+    dparams = policy.to_device_params(params)
+    eng = _rollout_engine(policy, dparams, x0.shape[0])
+    return RolloutFunction.apply(eng, dparams, dparams.flat, x0, U, goal, bool(dynamics_grad))

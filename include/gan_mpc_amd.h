@@ -19,7 +19,9 @@
  *    after a COMPLETED gmpc_ilqr_solve of the same batch size.  gmpc_set_params, gmpc_rollout_cost,
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
- *    ("must precede") instead of differentiating a stale linearisation.
+ *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp drops nothing: it
+ *    may run between a solve and its bilevel calls, or between a bilevel call and gmpc_bilevel_grad_inputs /
+ *    _dynamics.
  *
  * Parameter layouts (flat fp32 vectors, flax Dense order: kernel (in,out) row-major, then bias):
  *   dyn    : for l in 0..dyn_layers-1:  W_l[dims[l]][dims[l+1]], b_l[dims[l+1]]
@@ -221,6 +223,28 @@ int gmpc_bilevel_grad_inputs(gmpc_ctx* ctx, int B, const float* lx, float* grad_
  * reduction order, no atomics).  Workspace: about 2 B T (sum of the dyn widths) floats twice, allocated by the first
  * call that needs more than the ctx holds (a synchronising allocation) and kept for later calls. */
 int gmpc_bilevel_grad_dynamics(gmpc_ctx* ctx, int B, const float* lx, float* grad_dyn_sum, void* stream);
+
+/* The vector-Jacobian product of the rollout and its per-step costs (gmpc_rollout_cost's X and costs; trajax
+ * rollout / evaluate at policy/optimizers.py:24-31) for a caller's cotangents gX = dL/dX [B][T+1][n] and
+ * gcost = dL/dcosts [B][T+1] (either may be NULL, not both), taken at (X, U, goal) as passed: X must be the rollout
+ * of (X[:, 0], U) under the bound parameters.  The TRUE derivative (no bilevel step, no reference sign):
+ *   grad_x0 [B][n], grad_U [B][T][m], grad_goal [B][T+1][n] (row T is 0: the terminal cost does not read it) per
+ *   trajectory; grad_theta_sum [3 + cost_count] in gmpc_bilevel_grad's grad_sum layout (mpc_w, then the cost MLP)
+ *   and grad_dyn_sum [dyn param count] in gmpc_set_params' dyn layout, both SUMMED over the batch.
+ * Any output may be NULL (its work is skipped: no weight-gradient rows without grad_dyn_sum), not all of them.
+ * One reverse sweep through each step's relu MLP (the masks recomputed from (X, U) into the call's own workspace);
+ * no [A_t | B_t] is formed, so every shape the ctx accepts is covered, the step-major ones (n > 64 or m > 32)
+ * included.  Relu-MLP dynamics only: LSTM dynamics (dyn_lstm_features > 0), gX and gcost both NULL, every output
+ * NULL, a NULL X / U / goal, B outside [1, max_batch] or no gmpc_set_params fail with GMPC_EINVAL before any launch.
+ * Stateless and read-only for every existing ctx buffer: drops no held solution (see the ordering contract).
+ * Deterministic (fixed reduction order, no atomics); asynchronous, except that the first call needing more workspace
+ * than the ctx holds allocates it (a synchronising hipMalloc) and keeps it: B T (dyn hidden layers) 8 mask words,
+ * with grad_theta_sum 2 (B + 8) (summed cost widths) + 3 B floats, with grad_dyn_sum 2 (B T + 8) (summed dyn
+ * widths) floats. */
+int gmpc_rollout_vjp(gmpc_ctx* ctx, int B, const float* X, const float* U, const float* goal,
+                     const float* gX, const float* gcost,
+                     float* grad_x0, float* grad_U, float* grad_goal,
+                     float* grad_theta_sum, float* grad_dyn_sum, void* stream);
 
 /* a13/a16 only: the upper-level loss [B] at the solution held by the ctx, without the gradient
  * (test-loss evaluation, norm/cost_trainer.py:13-21). */
