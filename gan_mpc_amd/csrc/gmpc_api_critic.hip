@@ -1,0 +1,328 @@
+// C-ABI entry points of the critic and of what a training step does with gradients: the critic's loss / score, the
+// upper-level loss, the Adam and Polyak steps, the batched GEMM's test entry, the multi-GPU exchange.
+#include "gmpc_ctx.h"
+
+// critic ---------------------------------------------------------------------------------------
+static int bind_critic(gmpc_ctx* c, const float* critic, CriticDesc& cd, hipStream_t s, bool head_transpose = true) {
+  const gmpc_shape& sh = c->sh;
+  if (sh.lstm_features <= 0) return fail(GMPC_EINVAL, "this ctx was created without a critic");
+  const long n = c->nx, F = sh.lstm_features;      // the critic scores x sequences
+  cd.n = c->nx; cd.F = sh.lstm_features; cd.T1 = sh.T + 1;
+  cd.Wcat = critic;
+  cd.WcatT = c->critT;
+  cd.b = critic + (n + F) * 4 * F;
+  bind_mlp(cd.head, sh.head_layers, sh.head_dims, critic + (n + F) * 4 * F + 4 * F,
+           c->critT + (n + F) * 4 * F);
+  // the first-generation LSTM kernels read [Wx; Wh]^T; the second generation (n <= 32) and the head's forward
+  // layers read the parameters as they lie, the head's backward layers its transposed kernels (one launch)
+  if (!(c->lwp != nullptr && gmpc_lstm2_supported(cd)) || c->xT != nullptr)
+    gmpc_launch_transpose((int)(n + F), (int)(4 * F), cd.Wcat, c->critT, s);
+  if (head_transpose) gmpc_launch_mlp_transpose_all(cd.head, s);     // (else: the caller, beside the LSTM forward sweep)
+  return 0;
+}
+
+static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const float* label,
+                                   const float* critic, int loss_kind, float* dxseq, bool want_wgrad,
+                                   float* grad_sum, hipStream_t s, float* loss_sum = nullptr) {
+  // The side stream of the critic step (GMPC_CRITIC_SIDE=0: everything on the caller's stream): the transposed head
+  // kernels are built beside the LSTM forward sweep (only k_head2 reads them), the head's weight gradients and the
+  // loss sum run beside the BPTT sweep (they need k_head2's outputs only; the sweep is a latency chain at one wave
+  // per SIMD).
+  const char* side_env = getenv("GMPC_CRITIC_SIDE");
+  const bool side_on = !(side_env != nullptr && side_env[0] == '0') && c->xT == nullptr && c->lwp != nullptr;
+  if (side_on && !c->crit_side) {
+    HIP_TRY(hipStreamCreateWithFlags(&c->crit_side, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->crit_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->crit_join, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->crit_tr, hipEventDisableTiming));
+  }
+  // (an error return between a fork onto the side stream and its join must not leave work in flight there)
+  struct SideGuard {
+    hipStream_t st = nullptr;
+    ~SideGuard() { if (st) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); } }
+  } side_guard;
+  CriticDesc cd;
+  TRY(bind_critic(c, critic, cd, s, !side_on));
+  const bool tr_side = side_on && gmpc_lstm2_supported(cd);
+  if (side_on && !tr_side) gmpc_launch_mlp_transpose_all(cd.head, s);
+  if (tr_side) {
+    HIP_TRY(hipEventRecord(c->crit_fork, s));
+    HIP_TRY(hipStreamWaitEvent(c->crit_side, c->crit_fork, 0));
+    side_guard.st = c->crit_side;
+    gmpc_launch_mlp_transpose_all(cd.head, c->crit_side);
+    HIP_TRY(hipEventRecord(c->crit_tr, c->crit_side));
+  }
+  const gmpc_shape& sh = c->sh;
+  const int n = c->nx, F = sh.lstm_features, T1 = sh.T + 1;
+  // wide inputs (n + F > 256): x_t Wx for all steps is one MFMA GEMM up front and the LSTM kernels
+  // run on the recurrent half only (cr: n = 0, Wcat = Wh); dx comes back through a second GEMM
+  const bool widein = c->xT != nullptr;
+  const int R = Bc * T1, G4w = 4 * F;
+  CriticDesc cr = cd;
+  auto gemm1 = [&](int M, int N, int K, const float* X, int ldx, const float* Y, int ldy, float* Cp,
+                   int ldc) {
+    BgemmArgs g;
+    g.batch = 1; g.M = M; g.N = N; g.K = K;
+    g.X = X; g.sx = 0; g.ldx = ldx; g.Y = Y; g.sy = 0; g.ldy = ldy; g.C = Cp; g.sc = 0; g.ldc = ldc;
+    g.alpha = 1.f; g.beta = 0.f; g.active = nullptr;
+    gmpc_launch_bgemm_tn(g, s);
+  };
+  if (widein) {
+    cr.n = 0;
+    cr.Wcat = critic + (long)n * G4w;
+    cr.WcatT = c->WhT;
+    gmpc_launch_transpose(F, G4w, cr.Wcat, c->WhT, s);
+  }
+  const bool gen2 = !widein && c->lwp != nullptr && gmpc_lstm2_supported(cd);
+  if (gen2) {
+    ProfScope ps(c, PROF_LSTM_FWD, s);
+    gmpc_launch_lstm_fwd2(Bc, cd, xseq, c->gates, c->cs, c->hp, c->hT, s);
+  } else {
+    ProfScope ps(c, PROF_LSTM_FWD, s);
+    if (widein) {
+      gmpc_launch_transpose(R, n, xseq, c->xT, s);                       // [R][n] -> [n][R]
+      gemm1(R, G4w, n, c->xT, R, critic, G4w, c->xproj, G4w);             // xproj = x Wx
+    }
+    gmpc_launch_lstm_fwd(Bc, cr, xseq, c->gates, c->cs, c->hp, c->hT, widein ? c->xproj : nullptr, s);
+  }
+  if (tr_side) {
+    HIP_TRY(hipStreamWaitEvent(s, c->crit_tr, 0));
+    side_guard.st = nullptr;        // joined
+  }
+  {
+    ProfScope ps(c, PROF_HEAD, s);
+    gmpc_launch_head2(Bc, cd, loss_kind, c->hT, label, c->cscore, c->closs, c->hacts, c->hdels, c->plast, c->dhT,
+                      c->hstride, s);
+  }
+  hipStream_t sw = s;
+  bool forked = false;
+  if (gen2 && want_wgrad && side_on) {
+    HIP_TRY(hipEventRecord(c->crit_fork, s));
+    HIP_TRY(hipStreamWaitEvent(c->crit_side, c->crit_fork, 0));
+    sw = c->crit_side;
+    forked = true;
+    side_guard.st = c->crit_side;
+  }
+  float* gWx0 = grad_sum;
+  if (gen2 && (dxseq || want_wgrad)) {
+    // backward sweep with the LSTM weight gradients accumulated in registers (no dz in memory), then the
+    // reduction of the per-workgroup partials straight into grad_sum
+    ProfScope ps(c, PROF_LSTM_BWD, s);
+    float* gWh0 = want_wgrad ? gWx0 + (long)n * 4 * F : nullptr;
+    gmpc_launch_lstm_bwd2(Bc, cd, xseq, c->gates, c->cs, c->hp, c->dhT, want_wgrad ? c->lwp : nullptr, gWx0, gWh0,
+                          want_wgrad ? gWh0 + (long)F * 4 * F : nullptr, dxseq, s);
+  } else if (dxseq || want_wgrad) {
+    ProfScope ps(c, PROF_LSTM_BWD, s);
+    if (!widein) {
+      gmpc_launch_lstm_bwd(Bc, cd, c->gates, c->cs, c->dhT, want_wgrad ? c->dz : nullptr, dxseq, s);
+    } else {
+      gmpc_launch_lstm_bwd(Bc, cr, c->gates, c->cs, c->dhT, c->dz, nullptr, s);
+      if (dxseq) {
+        gmpc_launch_transpose(R, G4w, c->dz, c->xproj, s);               // dz^T: [4F][R]
+        gemm1(R, n, G4w, c->xproj, R, c->critT, n + F, dxseq, n);         // dx = dz Wx^T
+      }
+    }
+  }
+  if (want_wgrad) {
+    ProfScope ps(c, PROF_WGRAD, sw);
+    const int rows = Bc * T1, G4 = 4 * F;
+    float* gWx = grad_sum;
+    float* gWh = gWx + (long)n * G4;
+    float* gb = gWh + (long)F * G4;
+    // every problem with N % 256 == 0 goes into one batched launch (+ one reduction launch)
+    WgProb pr[GMPC_WG_MAX];
+    int np = 0;
+    auto add = [&](int r, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* Cw,
+                   float* cs, int cs_rows) {
+      WgProb q{};
+      q.rows = r; q.M = M; q.N = N; q.lda = lda; q.ldb = ldb; q.cs_rows = cs_rows;
+      q.A = A; q.B = Bm; q.C = Cw; q.colsum = cs;
+      pr[np++] = q;
+    };
+    struct Single { int r, M, N; const float* A; int lda; const float* Bm; int ldb; float* Cw; float* cs; int csr; };
+    Single single[GMPC_MAX_LAYERS + 2];
+    int ns = 0;
+    auto route = [&](int r, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* Cw,
+                     float* cs, int cs_rows) {
+      if (N % 256 == 0 && r >= 64 && np < GMPC_WG_MAX) add(r, M, N, A, lda, Bm, ldb, Cw, cs, cs_rows);
+      else single[ns++] = Single{r, M, N, A, lda, Bm, ldb, Cw, cs, cs_rows};
+    };
+    if (!gen2) {
+      route(rows, n, G4, xseq, n, c->dz, G4, gWx, nullptr, 0);
+      route(rows, F, G4, c->hp, F, c->dz, G4, gWh, gb, rows);
+    }
+    float* gh = gb + G4;
+    int aoff = 0, doff = 0;
+    for (int l = 0; l < sh.head_layers; ++l) {
+      const int M = sh.head_dims[l], N = sh.head_dims[l + 1];
+      if (l == sh.head_layers - 1 && np < GMPC_WG_MAX) {
+        // the last layer has one output: its weight gradient and its bias gradient are the column sums of
+        // k_head2's products [act * dscore | dscore] -- a problem without a GEMM part (M = 0)
+        add(Bc, 0, M + 1, c->plast, GMPC_HEAD2_LD, c->plast, GMPC_HEAD2_LD, gh, gh, Bc);
+      } else {
+        route(Bc, M, N, c->hacts + aoff, c->hstride, c->hdels + doff, c->hstride, gh, gh + (long)M * N, Bc);
+      }
+      gh += (long)M * N + N;
+      aoff += M;
+      doff += N;
+    }
+    if (np > 0 && !gmpc_launch_wgrad_batch(pr, np, c->wpart, c->wpart_floats, sw)) {
+      for (int i = 0; i < np; ++i)
+        single[ns++] = Single{pr[i].rows, pr[i].M, pr[i].N, pr[i].A, pr[i].lda, pr[i].B, pr[i].ldb, pr[i].C,
+                              pr[i].colsum, pr[i].cs_rows};
+    }
+    // the rest one by one, after the batch (they reuse the partial-sum buffer: stream order)
+    for (int i = 0; i < ns; ++i) {
+      if (single[i].M == 0)
+        gmpc_launch_colsum(single[i].csr, single[i].N, single[i].Bm, single[i].ldb, single[i].cs, c->wpart, sw);
+      else
+        gmpc_launch_wgrad(single[i].r, single[i].M, single[i].N, single[i].A, single[i].lda, single[i].Bm,
+                          single[i].ldb, single[i].Cw, single[i].cs, single[i].csr, c->wpart, 256, sw,
+                          c->wpart_floats, true);
+    }
+  }
+  if (loss_sum) gmpc_launch_sum(Bc, c->closs, loss_sum, 0, sw);
+  if (forked) {
+    HIP_TRY(hipEventRecord(c->crit_join, sw));
+    HIP_TRY(hipStreamWaitEvent(s, c->crit_join, 0));
+    side_guard.st = nullptr;        // joined
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmpc_critic_loss_grad(gmpc_ctx* c, int Bc, const float* xseq, const float* label,
+                                     const float* critic, float* loss_sum, float* grad_sum,
+                                     void* stream) {
+  if (!c) return fail(GMPC_EINVAL, "ctx is null");
+  if (Bc < 1 || Bc > 2 * c->maxB) return fail(GMPC_EINVAL, "Bc=%d outside [1, 2*max_batch]", Bc);
+  if (!xseq || !label || !critic || !loss_sum || !grad_sum) return fail(GMPC_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TRY(critic_forward_backward(c, Bc, xseq, label, critic, 0, nullptr, true, grad_sum, s, loss_sum));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmpc_critic_score_vjp(gmpc_ctx* c, int Bc, const float* xseq, const float* critic,
+                                     float* score, float* dxseq, void* stream) {
+  if (!c) return fail(GMPC_EINVAL, "ctx is null");
+  if (Bc < 1 || Bc > 2 * c->maxB) return fail(GMPC_EINVAL, "Bc=%d outside [1, 2*max_batch]", Bc);
+  if (!xseq || !critic || !score) return fail(GMPC_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TRY(critic_forward_backward(c, Bc, xseq, nullptr, critic, 2, dxseq, false, nullptr, s));
+  HIP_TRY(hipMemcpyAsync(score, c->cscore, Bc * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// upper-level loss only, at the solution held by the ctx (norm/cost_trainer.py:13-21 test loss)
+int upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired, const float* critic,
+                      float* loss, bool want_lx, hipStream_t s) {
+  const gmpc_shape& sh = c->sh;
+  if (loss_kind == 0) {
+    if (!desired) return fail(GMPC_EINVAL, "desired is null");
+    gmpc_launch_l2loss(B, sh.T, sh.n, c->nx, c->Xs, desired, loss, c->lx, s);
+  } else if (loss_kind == 1) {
+    if (!critic) return fail(GMPC_EINVAL, "critic is null");
+    if (c->dynl) {
+      // the critic sees the x columns of xc (gan/js_policy.py:64-65); its input gradient goes back into
+      // those columns, zero on the carry
+      const long rows = (long)B * (sh.T + 1);
+      gmpc_launch_cols_gather(rows, sh.n, c->nx, c->Xs, c->xg, s);
+      TRY(critic_forward_backward(c, B, c->xg, nullptr, critic, 1, want_lx ? c->lxg : nullptr, false,
+                                  nullptr, s));
+      if (want_lx) gmpc_launch_cols_scatter(rows, sh.n, c->nx, c->lxg, c->lx, s);
+    } else
+    TRY(critic_forward_backward(c, B, c->Xs, nullptr, critic, 1, want_lx ? c->lx : nullptr, false,
+                                nullptr, s));
+    HIP_TRY(hipMemcpyAsync(loss, c->closs, B * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else {
+    return fail(GMPC_EINVAL, "loss_kind must be 0 (L2) or 1 (JS)");
+  }
+  return 0;
+}
+
+extern "C" int gmpc_upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired,
+                               const float* critic, float* loss, void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
+  if (!loss) return fail(GMPC_EINVAL, "null argument");
+  c->gradB = 0;   // the L2 loss rewrites the ctx's lx, which gmpc_bilevel_grad_inputs would read
+  TRY(upper_loss(c, B, loss_kind, desired, critic, loss, false, static_cast<hipStream_t>(stream)));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmpc_polyak(gmpc_ctx* c, long count, const float* prev, const float* cur, double factor,
+                           float* out, void* stream) {
+  if (!c || !prev || !cur || !out || count < 1) return fail(GMPC_EINVAL, "bad argument");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  gmpc_launch_polyak(count, prev, cur, factor, out, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmpc_adam_clip_step(gmpc_ctx* c, long count, float* params, const float* grad,
+                                   float* m, float* v, float grad_scale, int step, double lr,
+                                   double max_norm, double b1, double b2, double eps, void* stream) {
+  if (!c || !params || !grad || !m || !v) return fail(GMPC_EINVAL, "null argument");
+  if (count < 1 || step < 1) return fail(GMPC_EINVAL, "count and step must be positive");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  {
+    ProfScope ps(c, PROF_ADAM, s);
+    gmpc_launch_adam(count, params, grad, m, v, grad_scale, step, lr, max_norm, b1, b2, eps,
+                     c->scratch, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// Batched TN GEMM used by the large-state Riccati path, exported for its unit test:
+// C[b] = alpha * X[b]^T Y[b] + beta * C[b] with X[b] K x M, Y[b] K x N, C[b] M x N, all row-major
+// and densely packed per batch element.  Y must be followed by >= 8 readable rows.
+extern "C" int gmpc_bgemm_tn(gmpc_ctx* c, int batch, int M, int N, int K, const float* X, const float* Y,
+                             float* C, float alpha, float beta, void* stream) {
+  if (!c || !X || !Y || !C || batch < 1 || M < 1 || N < 1 || K < 1) return fail(GMPC_EINVAL, "bad argument");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  BgemmArgs a;
+  a.batch = batch; a.M = M; a.N = N; a.K = K;
+  a.X = X; a.sx = (long)K * M; a.ldx = M;
+  a.Y = Y; a.sy = (long)K * N; a.ldy = N;
+  a.C = C; a.sc = (long)M * N; a.ldc = N;
+  a.alpha = alpha; a.beta = beta; a.active = nullptr;
+  gmpc_launch_bgemm_tn(a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// multi-GPU exchange -----------------------------------------------------------------------------
+extern "C" int gmpc_comm_unique_id(char* id128) {
+  if (!id128) return fail(GMPC_EINVAL, "null argument");
+  return gmpc_comm_unique_id_impl(id128);
+}
+
+extern "C" int gmpc_comm_init(gmpc_ctx* c, int world_size, int rank, const char* id128) {
+  if (!c || !id128) return fail(GMPC_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(c->device));
+  return gmpc_comm_init_impl(&c->comm, world_size, rank, id128);
+}
+
+extern "C" int gmpc_allreduce_grads(gmpc_ctx* c, float* packed, long count, void* stream) {
+  if (!c || !packed || count < 1) return fail(GMPC_EINVAL, "bad argument");
+  HIP_TRY(hipSetDevice(c->device));
+  return gmpc_comm_allreduce_impl(&c->comm, packed, count, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gmpc_comm_world(gmpc_ctx* c, int* world_size, int* rank) {
+  if (!c || !world_size || !rank) return fail(GMPC_EINVAL, "null argument");
+  *world_size = c->comm.world;
+  *rank = c->comm.rank;
+  return 0;
+}

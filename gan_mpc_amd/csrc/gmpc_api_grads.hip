@@ -1,0 +1,368 @@
+// C-ABI entry points of the gradients that end in weight sums: the bilevel tail and what follows it, the rollout VJP,
+// the dynamics regression, the expert model.
+#include "gmpc_ctx.h"
+
+// bilevel ----------------------------------------------------------------------------------------
+// a8-a11 from the loss's cotangents at the solution held by the ctx: lx = dL/dX [B][T+1][n] (never null here),
+// lu = dL/dU [B][T][m] or null (a loss of X only).  Writes Bvec, H, dX and grad_sum.
+static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const float* lu, float sign,
+                                   float* grad_sum, hipStream_t s) {
+  const gmpc_shape& sh = c->sh;
+  const int n = sh.n, m = sh.m, T = sh.T;
+  c->gradB = 0;
+  // a8: Bvec; a9+solve: structured Hessian solve; a11: cost_vjp
+  if (c->big) {
+    // step-major: the loss adjoint (Bvec) and the Riccati sweep of the Hessian solve share one
+    // backward pass over re-linearised steps, the tangent roll is a second, forward pass
+    if (gmpc_big_backward(c->bw, B, c->dyn, c->lp, c->masks, c->Xs, c->Us, c->goals, c->mpc_w, c->QT,
+                          c->qT, nullptr, c->Ks, c->ks, nullptr, nullptr, lx, c->Bvec, s,
+                          c->dynl ? &c->dl : nullptr, c->dynl ? c->adjs : nullptr, lu) != 0 ||
+        gmpc_big_forward_tangent(c->bw, B, c->dyn, c->lp, c->masks, c->Ks, c->ks, c->Hout, c->dX, s,
+                                 c->dynl ? &c->dl : nullptr, c->Xs, c->Us) != 0)
+      return fail(GMPC_EINVAL, "large-state bilevel: Jacobian kernel does not cover this shape");
+  } else {
+    RiccatiArgs r;
+    memset(&r, 0, sizeof(r));
+    r.B = B; r.n = n; r.ng = c->nx; r.m = m; r.T = T; r.mode = 1;
+    r.X = c->Xs; r.U = c->Us; r.goal = c->goals; r.mpc_w = c->mpc_w; r.AB = c->AB; r.QT = c->QT;
+    r.qT = c->qT; r.K = c->Ks; r.k = c->ks; r.Bvec = c->Bvec; r.Hout = c->Hout; r.dX = c->dX;
+    if (!c->dynl && gmpc_riccati_w2h_shape(r)) {
+      // two waves per trajectory, products on the matrix pipe, the loss adjoint (a8) in the same sweep
+      ProfScope ps(c, PROF_RICCATI, s);      // (bench.py: secondary.bilevel.kernel_ms)
+      gmpc_launch_riccati_w2h(r, lx, lu, c->Bvec, s);
+    } else {
+      gmpc_launch_bvec(B, T, n, m, c->AB, lx, lu, c->Bvec, s);
+      if (c->dynl) {
+        // smooth dynamics: the dense Hessian the reference solves with carries lam_{t+1} . d^2 f (oracle
+        // second_order_lqr); lam = the adjoints of the solve's last backward pass
+        gmpc_launch_dynl_curv(B, T, T, 0, c->dl, c->Xs, c->Us, c->adjs, nullptr, c->phi, s);
+        r.Phi = c->phi;
+      }
+      ProfScope ps(c, PROF_RICCATI, s);      // (bench.py: secondary.bilevel.kernel_ms)
+      gmpc_launch_riccati(r, s);
+    }
+  }
+  gmpc_launch_costvjp(B, T, n, m, c->cost, c->mpc_w, sign, c->Xs, c->Us, c->goals, c->nx, c->Hout, c->dX,
+                      c->gmpc, c->cact, c->cdel, c->cstride, s);
+  // sums over the batch: mpc_w (3 columns of gmpc) and the cost layers
+  gmpc_launch_wgrad(B, 1, 3, c->gmpc, 0, c->gmpc, 3, c->scratch + 512, grad_sum, B, c->wpart, 256, s, c->wpart_floats, false);
+  gmpc_launch_wgrad_mlp(2 * B, B, sh.cost_layers, sh.cost_dims, c->cact, c->cdel, c->cstride, grad_sum + 3, c->wpart,
+                        c->wpart_floats, s);
+  c->gradB = B;   // H, dX (and Phi) now belong to the held solution: gmpc_bilevel_grad_inputs may follow
+  return 0;
+}
+
+extern "C" int gmpc_bilevel_grad(gmpc_ctx* c, int B, int loss_kind, const float* desired,
+                                 const float* critic, float sign, float* loss, float* grad_sum,
+                                 void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
+  if (!loss || !grad_sum) return fail(GMPC_EINVAL, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  c->gradB = 0;   // the loss below rewrites the ctx's lx
+  TRY(upper_loss(c, B, loss_kind, desired, critic, loss, true, s));
+  TRY(bilevel_from_cotangents(c, B, c->lx, nullptr, sign, grad_sum, s));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// a caller-defined upper-level loss (reference policy/optimizers.py:34-83 takes any `loss`): the caller has
+// differentiated it; the kernels read its lx / lu directly.  A null lx is a loss of U only: c->lx is zeroed.
+extern "C" int gmpc_bilevel_grad_cotangent(gmpc_ctx* c, int B, const float* lx, const float* lu, float sign,
+                                           float* grad_sum, void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B) return fail(GMPC_EINVAL, "gmpc_ilqr_solve with B=%d must precede this call", B);
+  if (!grad_sum) return fail(GMPC_EINVAL, "null argument");
+  if (!lx && !lu) return fail(GMPC_EINVAL, "lx and lu are both null: the loss has no cotangent");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!lx) {
+    HIP_TRY(hipMemsetAsync(c->lx, 0, (size_t)B * (c->sh.T + 1) * c->sh.n * sizeof(float), s));
+    lx = c->lx;
+  }
+  TRY(bilevel_from_cotangents(c, B, lx, lu, sign, grad_sum, s));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// dL/dx0 and dL/dgoal of the loss whose bilevel gradient the ctx has just computed (gmpc_input_grads.hip): the
+// implicit-function gradient through the held solution, from the H, dX (and Phi) the bilevel tail left.  Read-only
+// for every other ctx buffer.
+extern "C" int gmpc_bilevel_grad_inputs(gmpc_ctx* c, int B, const float* lx, float* grad_x0, float* grad_goal,
+                                        void* stream) {
+  TRY(check_call(c, B));
+  if (c->solB != B || c->gradB != B)
+    return fail(GMPC_EINVAL, "gmpc_bilevel_grad or gmpc_bilevel_grad_cotangent with B=%d on the held solution must "
+                "precede this call", B);
+  if (!grad_x0 && !grad_goal) return fail(GMPC_EINVAL, "grad_x0 and grad_goal are both null");
+  if (grad_x0 && c->big)
+    return fail(GMPC_EINVAL, "grad_x0: the step-major pipeline (n=%d > 64 or m=%d > 32) keeps no [A_t | B_t] of the "
+                "solution; only grad_goal is available for this shape", c->sh.n, c->sh.m);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const gmpc_shape& sh = c->sh;
+  if (!lx) lx = c->lx;
+  if (grad_x0) {
+    if (gmpc_launch_input_grads(B, sh.T, sh.n, c->nx, sh.m, c->mpc_w, c->Xs, c->goals, c->dX, c->Hout, lx, c->AB,
+                                c->QT, c->dynl ? c->phi : nullptr, grad_x0, grad_goal, s) != 0)
+      return fail(GMPC_EINVAL, "grad_x0: shape n=%d m=%d not covered", sh.n, sh.m);
+  } else {
+    gmpc_launch_goal_grad(B, sh.T, sh.n, c->nx, c->mpc_w, c->Xs, c->goals, c->dX, grad_goal, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// dL/dtheta_dyn of the loss whose bilevel gradient the ctx has just computed (gmpc_dyn_grads.hip): the adjoint
+// sweeps give w = mu - nu and lam per step, the row kernel the layer inputs and deltas of 2 B T rows, and the weight
+// GEMMs sum them over the batch.  Read-only for every other ctx buffer (the GEMMs' partials use the shared scratch).
+extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, float* grad_dyn_sum, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl)
+    return fail(GMPC_EINVAL, "dynamics gradient: relu-MLP dynamics only (dyn_lstm_features = %d)",
+                sh.dyn_lstm_features);
+  if (c->big)
+    return fail(GMPC_EINVAL, "dynamics gradient: the step-major pipeline (n=%d > 64 or m=%d > 32) keeps no "
+                "[A_t | B_t] of the solution; n <= 64 and m <= 32 only", sh.n, sh.m);
+  if (!grad_dyn_sum) return fail(GMPC_EINVAL, "grad_dyn_sum is null");
+  if (c->solB != B || c->gradB != B)
+    return fail(GMPC_EINVAL, "gmpc_bilevel_grad or gmpc_bilevel_grad_cotangent with B=%d on the held solution must "
+                "precede this call", B);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = sh.n, m = sh.m, T = sh.T;
+  if (!lx) lx = c->lx;
+  const size_t steps = (size_t)B * T, rows = 2 * steps;
+  const size_t stride = (size_t)gmpc_dyn_rows_stride(c->dyn);
+  TRY(c->dgw.grow(c, steps * n));
+  TRY(c->dglam.grow(c, steps * n));
+  TRY(c->dgacts.reserve(c, rows, stride, s));
+  TRY(c->dgdels.reserve(c, rows, stride, s));
+  gmpc_launch_dyn_adjoints(B, T, n, c->nx, m, c->mpc_w, c->Xs, c->goals, c->dX, lx, c->AB, c->QT, c->qT, c->dgw.p,
+                           c->dglam.p, s);
+  if (gmpc_launch_dyn_rows(B, T, n, m, c->dyn, c->Xs, c->Us, c->dX, c->Hout, c->dgw.p, c->dglam.p, c->dgacts.p,
+                           c->dgdels.p, s) != 0)
+    return fail(GMPC_EINVAL, "dynamics gradient: layer widths above 256");
+  // gW_l = sum over the 2 B T rows of [a; -a']^T [delta(w); delta(lam)], gb_l = sum of the primal half's deltas
+  gmpc_launch_wgrad_mlp((int)rows, (int)steps, sh.dyn_layers, sh.dyn_dims, c->dgacts.p, c->dgdels.p, (int)stride,
+                        grad_dyn_sum, c->wpart, c->wpart_floats, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The VJP of the rollout and its costs at (X, U, goal) (gmpc_rollout_vjp.hip).  Stateless: the masks and rows live in
+// the call's own workspace, no held solution is dropped; the GEMMs' partials use the shared scratch.
+extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float* U, const float* goal, const float* gX,
+                                const float* gcost, float* grad_x0, float* grad_U, float* grad_goal,
+                                float* grad_theta_sum, float* grad_dyn_sum, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl)
+    return fail(GMPC_EINVAL, "rollout vjp: relu-MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
+  if (!X || !U || !goal) return fail(GMPC_EINVAL, "rollout vjp: X, U and goal must not be null");
+  if (!gX && !gcost) return fail(GMPC_EINVAL, "rollout vjp: gX and gcost are both null: no cotangent");
+  if (!grad_x0 && !grad_U && !grad_goal && !grad_theta_sum && !grad_dyn_sum)
+    return fail(GMPC_EINVAL, "rollout vjp: every output is null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = sh.n, m = sh.m, T = sh.T, Lh = sh.dyn_layers - 1;
+  const size_t steps = (size_t)B * T;
+  const bool want_theta = grad_theta_sum != nullptr && gcost != nullptr;
+  const size_t dstride = (size_t)gmpc_dyn_rows_stride(c->dyn), cstride = (size_t)gmpc_rvjp_cost_stride(c->cost);
+  // (uint32 mask words in a float allocation)
+  TRY(c->rvmask.grow(c, steps * Lh * GMPC_MW));
+  if (want_theta) {
+    TRY(c->rvgm.grow(c, (size_t)B * 3 + 8));      // [B][3] and the 1 x 3 product its column sum's launch leaves behind
+    TRY(c->rvcact.reserve(c, B, cstride, s));
+    TRY(c->rvcdel.reserve(c, B, cstride, s));
+  }
+  if (grad_dyn_sum) {
+    TRY(c->rvacts.reserve(c, steps, dstride, s));
+    TRY(c->rvdels.reserve(c, steps, dstride, s));
+  }
+  uint32_t* masks = reinterpret_cast<uint32_t*>(c->rvmask.p);
+  if (grad_dyn_sum)
+    gmpc_launch_rvjp_acts(B, n, m, T, c->dyn, X, U, c->rvacts.p, (int)dstride, masks, s);
+  else
+    gmpc_launch_masks(B, n, m, T, c->dyn, X, U, masks, s);
+  gmpc_launch_rvjp_sweep(B, n, m, T, c->dyn, c->cost, c->mpc_w, X, U, goal, gX, gcost, masks, grad_x0, grad_U,
+                         grad_goal, want_theta ? c->rvgm.p : nullptr, want_theta ? c->rvcact.p : nullptr,
+                         want_theta ? c->rvcdel.p : nullptr, grad_dyn_sum ? c->rvdels.p : nullptr, (int)dstride, s);
+  if (grad_theta_sum && !want_theta) {
+    // no cost cotangent: the costs' parameters get nothing
+    HIP_TRY(hipMemsetAsync(grad_theta_sum, 0, (3 + (size_t)mlp_count(sh.cost_layers, sh.cost_dims)) * sizeof(float),
+                           s));
+  } else if (want_theta) {
+    gmpc_launch_wgrad(B, 1, 3, c->rvgm.p, 0, c->rvgm.p, 3, c->rvgm.p + (size_t)B * 3, grad_theta_sum, B, c->wpart, 256,
+                      s, c->wpart_floats, false);
+    gmpc_launch_wgrad_mlp(B, B, sh.cost_layers, sh.cost_dims, c->rvcact.p, c->rvcdel.p, (int)cstride,
+                          grad_theta_sum + 3, c->wpart, c->wpart_floats, s);
+  }
+  if (grad_dyn_sum)
+    gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, c->rvacts.p, c->rvdels.p, (int)dstride,
+                          grad_dyn_sum, c->wpart, c->wpart_floats, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// dynamics regression (N3) ---------------------------------------------------------------------
+extern "C" int gmpc_dynamics_loss_grad(gmpc_ctx* c, int B, int S, const float* xseq, const float* useq,
+                                       const float* next_xseq, double discount, int teacher_forcing,
+                                       float* loss_sum, float* grad_sum, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  if (S < 1 || S > sh.T) return fail(GMPC_EINVAL, "S=%d outside [1, T=%d]", S, sh.T);
+  if (!xseq || !useq || !next_xseq || !loss_sum || !grad_sum) return fail(GMPC_EINVAL, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!c->dfacts) {
+    // (zeroed whole, once: the pad rows of the weight-gradient GEMM's operands stay finite whatever B * S a call has)
+    const size_t rows = (size_t)c->maxB * sh.T, padded = rows + GMPC_WGRAD_PAD;
+    c->dfstride = c->dynl ? (int)gmpc_dynl_fit_stride(c->dl) : (int)gmpc_dynfit_stride(&sh);
+    int rc = dalloc(c, &c->dfpred, rows * c->nx);
+    if (!rc) rc = dalloc(c, &c->dfacts, padded * c->dfstride);
+    if (!rc) rc = dalloc(c, &c->dfdels, padded * c->dfstride);
+    if (!rc && c->dynl) rc = dalloc(c, &c->dfsave, rows * 6 * c->dl.F);
+    if (!rc) rc = dalloc(c, &c->dfloss, c->maxB);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->dfacts, 0, padded * c->dfstride * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(c->dfdels, 0, padded * c->dfstride * sizeof(float), s));
+  }
+  const int rows = B * S;
+  if (c->dynl) {
+    // LSTM variant: BPTT through the cell and the tail (gmpc_dynl.hip); gradient layout Wx | Wh | b | tail
+    const DynlDesc& d = c->dl;
+    const long Fd = d.F, kin = d.nx + d.m, G4 = 4 * Fd;
+    gmpc_launch_dynl_fit(B, S, d, xseq, useq, next_xseq, (float)discount, teacher_forcing != 0, c->dfpred,
+                         c->dfacts, c->dfdels, c->dfstride, c->dfsave, c->dfloss, s);
+    float* gWx = grad_sum;
+    float* gWh = gWx + kin * G4;
+    float* gb = gWh + Fd * G4;
+    gmpc_launch_wgrad(rows, (int)kin, (int)G4, c->dfacts, c->dfstride, c->dfdels, c->dfstride, gWx, nullptr, 0,
+                      c->wpart, 256, s, c->wpart_floats, true);
+    gmpc_launch_wgrad(rows, (int)Fd, (int)G4, c->dfacts + kin, c->dfstride, c->dfdels, c->dfstride, gWh, gb, rows,
+                      c->wpart, 256, s, c->wpart_floats, true);
+    gmpc_launch_wgrad_mlp(rows, rows, d.tail.L, d.tail.dims, c->dfacts + kin + Fd, c->dfdels + G4, c->dfstride,
+                          gb + G4, c->wpart, c->wpart_floats, s);
+  } else {
+    if (gmpc_launch_dynfit(B, S, sh.n, sh.m, c->dyn, xseq, useq, next_xseq, (float)discount,
+                           teacher_forcing != 0, c->dfpred, c->dfacts, c->dfdels, c->dfstride, c->dfloss,
+                           s) != 0)
+      return fail(GMPC_EINVAL, "dynamics regression: unsupported layer width");
+    gmpc_launch_wgrad_mlp(rows, rows, sh.dyn_layers, sh.dyn_dims, c->dfacts, c->dfdels, c->dfstride, grad_sum,
+                          c->wpart, c->wpart_floats, s);
+  }
+  gmpc_launch_sum(B, c->dfloss, loss_sum, 0, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// expert sequence model (N2) --------------------------------------------------------------------
+
+static int check_expert_shape(const gmpc_expert_shape* es, int n, int m) {
+  if (!es) return fail(GMPC_EINVAL, "expert shape is null");
+  if (es->head_layers < 1 || es->head_layers > GMPC_MAX_LAYERS)
+    return fail(GMPC_EINVAL, "expert head_layers=%d outside [1, %d]", es->head_layers, GMPC_MAX_LAYERS);
+  if (es->lstm_features < 0 || es->lstm_features > 128)
+    return fail(GMPC_EINVAL, "expert lstm_features=%d outside [0, 128]", es->lstm_features);
+  const int L = es->head_layers;
+  if (es->head_dims_x[L] != n || es->head_dims_u[L] != m)
+    return fail(GMPC_EINVAL, "expert heads must end in n=%d and m=%d", n, m);
+  if (es->head_dims_x[0] != es->head_dims_u[0] ||
+      (es->lstm_features > 0 && es->head_dims_x[0] != es->lstm_features))
+    return fail(GMPC_EINVAL, "expert heads must start at the width of y");
+  for (int l = 0; l <= L; ++l)
+    if (es->head_dims_x[l] < 1 || es->head_dims_x[l] > 1024 || es->head_dims_u[l] < 1 ||
+        es->head_dims_u[l] > 1024)
+      return fail(GMPC_EINVAL, "expert head widths must be in [1, 1024]");
+  return 0;
+}
+
+extern "C" long gmpc_expert_param_count(int n, const gmpc_expert_shape* es) {
+  if (!es || es->head_layers < 1 || es->head_layers > GMPC_MAX_LAYERS) return -1;
+  const long F = es->lstm_features, h = es->head_dims_x[0];
+  long cnt = F > 0 ? (n + F) * 4 * F + 4 * F : (long)n * h + h;
+  return cnt + mlp_count(es->head_layers, es->head_dims_x) + mlp_count(es->head_layers, es->head_dims_u);
+}
+
+extern "C" int gmpc_expert_rollout(gmpc_ctx* c, int B, int hist, const gmpc_expert_shape* es,
+                                   const float* expert, const float* history, float* goal, float* init_U,
+                                   void* stream) {
+  TRY(check_call(c, B, false));     // the expert model has its own parameters
+  const gmpc_shape& sh = c->sh;
+  const int nx = c->nx;     // the expert model predicts x sequences (goals have x_size columns)
+  TRY(check_expert_shape(es, nx, sh.m));
+  if (hist < 1) return fail(GMPC_EINVAL, "hist=%d: at least one history row is needed (yaml: history >= 1)", hist);
+  if (!expert || !history || !goal || !init_U) return fail(GMPC_EINVAL, "null argument");
+  ExpertArgs a;
+  a.B = B; a.n = nx; a.m = sh.m; a.T = sh.T; a.hist = hist; a.F = es->lstm_features;
+  const long F = a.F, h = es->head_dims_x[0];
+  a.Wcat = expert;
+  a.bcat = expert + (F > 0 ? (nx + F) * 4 * F : (long)nx * h);
+  const float* heads = a.bcat + (F > 0 ? 4 * F : h);
+  bind_mlp(a.hx, es->head_layers, es->head_dims_x, heads, nullptr);
+  bind_mlp(a.hu, es->head_layers, es->head_dims_u, heads + mlp_count(es->head_layers, es->head_dims_x),
+           nullptr);
+  a.history = history; a.goal = goal; a.U = init_U;
+  if (gmpc_launch_expert(a, static_cast<hipStream_t>(stream)) != 0)
+    return fail(GMPC_EINVAL, "expert kernel: unsupported shape");
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// expert model training --------------------------------------------------------------------------
+
+extern "C" int gmpc_expert_loss_grad(gmpc_ctx* c, int B, int S, const gmpc_expert_shape* es, const float* expert,
+                                     const float* xseq, const float* useq, const float* next_xseq, double discount,
+                                     int teacher_forcing, float* loss_sum, float* grad_sum, void* stream) {
+  TRY(check_call(c, B, false));     // the expert model has its own parameters
+  const int nx = c->nx, m = c->sh.m;
+  TRY(check_expert_shape(es, nx, m));
+  if (S < 1) return fail(GMPC_EINVAL, "S=%d: at least one step is needed", S);
+  if ((long)B * S > (1L << 30)) return fail(GMPC_EINVAL, "B*S=%ld rows: too many", (long)B * S);
+  if (es->lstm_features == 0 && es->head_dims_x[0] > 512)
+    return fail(GMPC_EINVAL, "expert MLP first width %d > 512", es->head_dims_x[0]);
+  if (!expert || !xseq || !useq || !next_xseq || !loss_sum) return fail(GMPC_EINVAL, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ExpertFitArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.S = S; a.n = nx; a.m = m; a.F = es->lstm_features; a.Y = es->head_dims_x[0];
+  const long F = a.F, Y = a.Y, L = es->head_layers;
+  a.Wcat = expert;
+  a.bcat = expert + (F > 0 ? (nx + F) * 4 * F : (long)nx * Y);
+  const float* heads = a.bcat + (F > 0 ? 4 * F : Y);
+  bind_mlp(a.hx, (int)L, es->head_dims_x, heads, nullptr);
+  bind_mlp(a.hu, (int)L, es->head_dims_u, heads + mlp_count((int)L, es->head_dims_x), nullptr);
+  a.xseq = xseq; a.useq = useq; a.yseq = next_xseq;
+  a.gamma = (float)discount;
+  a.teacher_forcing = teacher_forcing != 0;
+  a.grad = grad_sum != nullptr;
+  const size_t stride = (size_t)gmpc_expert_fit_layout(a);
+  const size_t rows = (size_t)B * S;
+  if (!c->efloss) TRY(dalloc(c, &c->efloss, c->maxB));
+  a.loss = c->efloss;
+  if (a.grad) {
+    TRY(c->efacts.reserve(c, rows, stride, s));
+    TRY(c->efdels.reserve(c, rows, stride, s));
+    TRY(c->efsave.grow(c, rows * a.sstride));
+    a.acts = c->efacts.p; a.dels = c->efdels.p; a.save = c->efsave.p;
+  }
+  gmpc_launch_expert_fit(a, s);
+  if (a.grad) {
+    const int R = (int)rows;
+    float* g = grad_sum;
+    const int M0 = F > 0 ? (int)(nx + F) : nx, N0 = F > 0 ? (int)(4 * F) : (int)Y;
+    gmpc_launch_wgrad(R, M0, N0, a.acts, (int)stride, a.dels, (int)stride, g, g + (long)M0 * N0, R, c->wpart,
+                      256, s, c->wpart_floats, true);
+    g += (long)M0 * N0 + N0;
+    for (int h = 0; h < 2; ++h) {
+      const MlpDesc& d = h == 0 ? a.hx : a.hu;
+      for (int l = 0; l < d.L; ++l) {
+        const int M = d.dims[l], N = d.dims[l + 1];
+        const int ao = h == 0 ? a.ax[l] : a.au[l], dof = h == 0 ? a.dx[l] : a.du[l];
+        gmpc_launch_wgrad(R, M, N, a.acts + ao, (int)stride, a.dels + dof, (int)stride, g, g + (long)M * N, R,
+                          c->wpart, 256, s, c->wpart_floats, true);
+        g += (long)M * N + N;
+      }
+    }
+  }
+  gmpc_launch_sum(B, c->efloss, loss_sum, 0, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

@@ -4,7 +4,7 @@
 // Reference arithmetic: trajax linearize / quadratize / lqr_step / tvlqr / adjoint as run inside
 // trajax ilqr (reference call sites policy/optimizers.py:19,55) on dynamics/nn.py:27-34 and
 // cost/cost_model.py:20-42, cost/nn.py:23-29.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // k_linearize: [A_t | B_t] = I + W_L^T D_{L-1} W_{L-1}^T ... D_1 W_1^T for SP samples (b,t) per pass.
@@ -680,9 +680,6 @@ int gmpc_launch_terminal(int B, int T, int n, const MlpDesc& cm, const float* mp
     default: return -1;
   }
 }
-
-bool gmpc_riccati_w_shape(const RiccatiArgs& a);
-void gmpc_launch_riccati_w(const RiccatiArgs& a, hipStream_t s);
 
 void gmpc_launch_riccati(const RiccatiArgs& a, hipStream_t s) {
   if (gmpc_riccati_w_shape(a)) {          // two waves per trajectory, products on the matrix pipe

@@ -3,7 +3,7 @@
 // Reference arithmetic: policy/optimizers.py:61-73,78-105 (loss_grad_wrt_control, the dense
 // Hessian solve -- here the equivalent structured solve, see k_riccati mode 1 -- and cost_vjp),
 // norm/l2_policy.py:12-18.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 // L2 loss  sum_dims mean_t (x - x*)^2  and its gradient wrt X.  `desired` has ng <= n columns: the loss sees
 // the x part of xc (reference norm/l2_policy.py:15-16 splits xcseq at x_size), the gradient is zero on the rest.

@@ -7,12 +7,10 @@
 // caller gets /opt/rocm's.  A ctx that never called gmpc_comm_init is a world of one and the exchange
 // is a no-op, so single-GPU callers need no RCCL at all.
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
-
 #include <cstdio>
 #include <cstring>
 
-#include "../../include/gan_mpc_amd.h"
+#include "gmpc_launch.h"
 
 namespace {
 struct NcclId { char internal[128]; };           // ncclUniqueId (NCCL_UNIQUE_ID_BYTES = 128)
@@ -61,11 +59,6 @@ Rccl* rccl() {
   return &r;
 }
 }  // namespace
-
-// error plumbing shared with gmpc_api.hip
-int gmpc_fail(int code, const char* fmt, ...);
-
-struct GmpcComm { NcclComm comm = nullptr; int world = 1, rank = 0; };
 
 int gmpc_comm_unique_id_impl(char* id128) {
   Rccl* r = rccl();

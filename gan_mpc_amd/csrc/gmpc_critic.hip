@@ -10,7 +10,7 @@
 // produces gate pre-activation j (4F = 256 with the reference's F = 64) for all SB sequences from
 // the concatenated kernel Wcat = [Wx; Wh] ((n+F) x 4F, exactly the flat critic layout), the cell
 // update runs as thread (unit, wave).  Saved per (sequence, step): activated gates, c_t, h_{t-1}.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 
 // NXR > 0: the input size n is known at compile time and thread j keeps column j of [Wx; Wh]
@@ -697,14 +697,8 @@ void gmpc_launch_lstm_bwd(int Bc, const CriticDesc& cd, const float* gates, cons
                        dhT, dz, dxseq, stage_w);
 }
 
-// C[M][N] = sum_r A[r][:M]^T B[r][:N]; colsum[N] = sum_{r < cs_rows} B[r][:N] (optional).
-// part must hold nsplit*(M*N + N) floats.
-bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb,
-                            float* C, float* colsum, int cs_rows, float* part, long part_floats,
-                            hipStream_t s);
 __global__ void k_colsum(int cs_rows, int N, const float* Bm, int ldb, int rows_per_chunk, float* part);
 
-// part holds part_floats floats (at least max_split*(M*N + N)); mfma_ok: B has >= 8 zero pad rows
 void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb,
                        float* C, float* colsum, int cs_rows, float* part, int max_split,
                        hipStream_t s, long part_floats, bool mfma_ok) {
@@ -748,6 +742,20 @@ void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const fl
                        colsum);
 }
 
+float* gmpc_launch_wgrad_mlp(int rows, int cs_rows, int L, const int* dims, const float* acts, const float* dels,
+                             int stride, float* g, float* part, long part_floats, hipStream_t s) {
+  int aoff = 0, doff = 0;
+  for (int l = 0; l < L; ++l) {
+    const int M = dims[l], N = dims[l + 1];
+    gmpc_launch_wgrad(rows, M, N, acts + aoff, stride, dels + doff, stride, g, g + (long)M * N, cs_rows, part, 256, s,
+                      part_floats, true);
+    g += (long)M * N + N;
+    aoff += M;
+    doff += N;
+  }
+  return g;
+}
+
 void gmpc_launch_sum(int count, const float* v, float* out, int square, hipStream_t s) {
   hipLaunchKernelGGL(k_sum, dim3(1), dim3(1024), 0, s, count, v, out, square);
 }
@@ -774,8 +782,8 @@ void gmpc_launch_polyak(long count, const float* prev, const float* cur, double 
 // read straight from global memory in their natural row-major layout (the MFMA A operand of k-step
 // r is row r of A, the B operand row r of B: both coalesced).  One wavefront owns a 32 x 32*NTW
 // strip of C over one chunk of rows; partial strips are summed in chunk order (deterministic).
-// Requires N % (32*NTW) == 0 and B padded with >= 8 zero rows; A is clamped (it may be a caller's
-// buffer).  v_mfma_f32_32x32x2_f32 = k-ordered exact fp32 fmaf chain.
+// Requires N % (32*NTW) == 0 and B followed by GMPC_WGRAD_PAD allocated, finite rows (gmpc_launch.h: they meet a
+// zero A operand); A is clamped (it may be a caller's buffer).  v_mfma_f32_32x32x2_f32 = k-ordered exact fp32 fmaf chain.
 // ---------------------------------------------------------------------------------------------
 template <int NTW>
 __global__ __launch_bounds__(GMPC_THREADS) void k_wgrad_mfma(int rows, int M, int N, const float* A,
@@ -1020,7 +1028,6 @@ __global__ __launch_bounds__(256) void k_reduce_batch(WgBatch bt, const float* p
   if (seg == 0 && e < count) out[e] = (sh[0][el] + sh[1][el]) + (sh[2][el] + sh[3][el]);
 }
 
-// colsum[N] = sum_{r < rows} B[r][:N] on its own (two launches; `part` holds the chunk sums)
 void gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum, float* part, hipStream_t s) {
   int cchunks = (rows + 63) / 64;
   if (cchunks > 2048) cchunks = 2048;
@@ -1031,7 +1038,6 @@ void gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum
   hipLaunchKernelGGL(k_reduce_splits, dim3((N + 63) / 64), dim3(256), 0, s, N, cchunks, part, colsum);
 }
 
-// returns false when a problem does not qualify (the caller then issues them one by one)
 bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_floats, hipStream_t s) {
   if (np < 1 || np > GMPC_WG_MAX) return false;
   WgBatch bt;
@@ -1101,7 +1107,6 @@ bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_float
   return true;
 }
 
-// MFMA path of gmpc_launch_wgrad; returns false when the shape does not qualify.
 bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb,
                             float* C, float* colsum, int cs_rows, float* part, long part_floats,
                             hipStream_t s) {

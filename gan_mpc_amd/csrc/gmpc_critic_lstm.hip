@@ -24,7 +24,7 @@
 //
 // Saved by the forward sweep for the backward one (internal layouts, one float per thread and step, coalesced):
 // the activated gates AFTER the transpose (4 planes), c_t, h_t.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
 
@@ -362,7 +362,6 @@ static int lstm2_nx(const CriticDesc& cd) {
 
 bool gmpc_lstm2_supported(const CriticDesc& cd) { return lstm2_nx(cd) != 0; }
 
-// floats of the weight-gradient partial buffer for Bc sequences
 long gmpc_lstm2_wpart_floats(const CriticDesc& cd, int Bc) {
   const int nx = lstm2_nx(cd);
   return nx ? (long)((Bc + 3) / 4) * GMPC_LSTM2_ROWS(nx) * 256 : 0;
@@ -403,7 +402,6 @@ static void launch_bwd2(int Bc, const CriticDesc& cd, const float* xseq, const f
   }
 }
 
-// Wp != null: weight gradients -> gWx, gWh, gb (sums over the Bc sequences); dxseq != null: input gradient
 bool gmpc_launch_lstm_bwd2(int Bc, const CriticDesc& cd, const float* xseq, const float* G, const float* Cst,
                            const float* Hst, const float* dhT, float* Wp, float* gWx, float* gWh, float* gb,
                            float* dxseq, hipStream_t s) {
@@ -435,7 +433,6 @@ bool gmpc_launch_lstm_bwd2(int Bc, const CriticDesc& cd, const float* xseq, cons
 // layer's input (`acts`) and delta (`dels`) row-major, and for the last layer (one output) the products
 // act[row][k] * dscore[row] with dscore in column K: its weight and bias gradients are column sums (`plast`).
 // ---------------------------------------------------------------------------------------------------------------
-#define GMPC_HEAD2_LD 264     // leading dimension of plast: 256 products + dscore, padded to a multiple of 8
 #ifndef GMPC_HEAD_RING
 #define GMPC_HEAD_RING 3       // weight chunks of head_layer in flight + 1
 #endif

@@ -1,0 +1,164 @@
+// The context behind the C ABI and what the files of its entry points share (gmpc_api*.hip; none of them has a kernel).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "gmpc_launch.h"
+
+enum { PROF_ROLLOUT = 0, PROF_LINEARIZE, PROF_TERMINAL, PROF_RICCATI, PROF_LINESEARCH, PROF_LSTM_FWD,
+       PROF_HEAD, PROF_LSTM_BWD, PROF_WGRAD, PROF_ADAM };
+
+// error handling -------------------------------------------------------------------------------
+static constexpr auto& fail = gmpc_fail;     // the entry points' name for the library's one error record
+#define HIP_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return fail(GMPC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
+                  __LINE__);                                                                \
+  } while (0)
+#define TRY(expr) do { int r_ = (expr); if (r_ != 0) return r_; } while (0)
+
+#define GMPC_POLL_DEPTH 4   // iterations the host may enqueue ahead of the convergence flags it has seen
+
+// A workspace buffer that an entry point sizes per call: grown to the largest size seen, never shrunk (the only
+// allocations after gmpc_create)
+struct GrowBuf {
+  float* p = nullptr;
+  size_t cap = 0;     // floats
+  int grow(gmpc_ctx* c, size_t floats);
+};
+// Operand rows of the weight-gradient GEMM, [rows + GMPC_WGRAD_PAD][stride]: reserve() grows the buffer and zeroes the
+// pad rows on `s` (the kernels that fill the buffer write the first `rows` rows only)
+struct PadRows : GrowBuf {
+  int reserve(gmpc_ctx* c, size_t rows, size_t stride, hipStream_t s);
+};
+
+struct gmpc_ctx {
+  gmpc_shape sh;
+  GmpcComm comm;
+  int nx = 0;            // x part of xc (= n unless the dynamics carry rides in xc)
+  bool dynl = false;     // LSTM dynamics variant
+  DynlDesc dl{};
+  float *xg = nullptr, *lxg = nullptr;   // x columns of Xs / d loss / dx (critic-facing, dynl only)
+  float* phi = nullptr;                  // dynl, small-state path: [B][T][n+m][n+m] curvature for the bilevel solve
+  int maxB, device;
+  std::vector<void*> allocs;
+  // bound parameters
+  const float* mpc_w = nullptr;
+  MlpDesc dyn{}, cost{};
+  float *dynT = nullptr, *costT = nullptr, *linpad = nullptr;
+  size_t linpad_floats = 0;
+  LinPad lp{};
+  bool params_set = false;
+  // trajectory workspace
+  uint32_t *masks, *maskc;
+  float *Xc, *Uc, *AB, *QT, *qT;
+  float *Xs, *Us, *goals, *Ks, *ks, *grads, *adjs;
+  float *obj, *alpha, *obj_step, *U_step;
+  int *iters, *cont;
+  int* hcont = nullptr;                       // pinned ring of continuation flags (gmpc_ilqr_solve)
+  float* fzcand = nullptr;                    // line-search candidates of gmpc_ilqr_solve_fused (shapes it covers)
+  hipEvent_t poll_ev[GMPC_POLL_DEPTH] = {};
+  int solB = 0;
+  // batch size whose Bvec / H / dX (and Phi) a completed bilevel tail left for the held solution (0: none); every
+  // change of the held solution clears it
+  int gradB = 0;
+  // bilevel workspace
+  float *lx, *Bvec, *Hout, *dX, *gmpc, *cact, *cdel, *bl_loss;
+  int cstride;
+  // critic workspace
+  float *critT, *gates, *cs, *hp, *hT, *dz, *hacts, *hdels, *dhT, *cscore, *closs;
+  float* lwp = nullptr;        // weight-gradient partials of k_lstm_bwd2, one [85][256] block per 4 sequences
+  // k_head2: last layer's act * dscore products and dscore, [Bc + GMPC_WGRAD_PAD][GMPC_HEAD2_LD]
+  float* plast = nullptr;
+  int hstride;
+  LsWork lsw{};
+  // large-state (n > 64) backward pass
+  bool big = false;
+  BigWork bw{};
+  float *WhT = nullptr, *xT = nullptr, *xproj = nullptr;   // wide-input critic (n + F > 256)
+  // dynamics regression (allocated on first use)
+  float *dfpred = nullptr, *dfacts = nullptr, *dfdels = nullptr, *dfloss = nullptr, *dfsave = nullptr;
+  int dfstride = 0;
+  // expert model training (gmpc_expert_loss_grad)
+  PadRows efacts, efdels;
+  GrowBuf efsave;
+  float* efloss = nullptr;
+  // dynamics-weight gradient (gmpc_bilevel_grad_dynamics)
+  GrowBuf dgw, dglam;
+  PadRows dgacts, dgdels;
+  // rollout VJP (gmpc_rollout_vjp): its own relu masks, per-trajectory mpc_w terms, cost and dynamics rows
+  GrowBuf rvmask, rvgm;
+  PadRows rvcact, rvcdel, rvacts, rvdels;
+  // shared scratch
+  float *wpart, *scratch;
+  long wpart_floats;
+  // optional per-kernel timing with HIP events on the launch stream (gmpc_profile_*)
+  bool prof = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[GMPC_PROF_SLOTS];
+  const char* lin_kernel = "";      // kernel the last Jacobian chain ran on (gmpc_profile_kernel_name)
+  char lin_kernel_buf[96] = "";     // name of the chain instantiation this ctx launched last (copied at launch time)
+  hipEvent_t lin_event = nullptr;   // caller's event, recorded after the Jacobian chain (gmpc_set_linearize_event)
+  // the critic's head weight gradients run beside the BPTT sweep (critic_forward_backward): a context-owned side
+  // stream forked after k_head2 and joined behind the sweep
+  hipStream_t crit_side = nullptr;
+  hipEvent_t crit_fork = nullptr, crit_join = nullptr, crit_tr = nullptr;
+};
+
+// RAII bracket: records a start/stop event pair around one kernel launch when profiling is on
+struct ProfScope {
+  gmpc_ctx* c; int slot; hipStream_t s; hipEvent_t e1 = nullptr;
+  ProfScope(gmpc_ctx* c_, int slot_, hipStream_t s_) : c(c_), slot(slot_), s(s_) {
+    if (!c->prof) return;
+    hipEvent_t e0;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { e1 = nullptr; return; }
+    (void)hipEventRecord(e0, s);
+    c->prof_ev[slot].push_back({e0, e1});
+  }
+  ~ProfScope() { if (e1) (void)hipEventRecord(e1, s); }
+};
+
+template <typename Tp>
+static int dalloc(gmpc_ctx* c, Tp** p, size_t count) {
+  void* q = nullptr;
+  if (count == 0) count = 1;
+  hipError_t e = hipMalloc(&q, count * sizeof(Tp));
+  if (e != hipSuccess)
+    return fail(GMPC_ENOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(Tp),
+                hipGetErrorString(e));
+  c->allocs.push_back(q);
+  *p = static_cast<Tp*>(q);
+  return 0;
+}
+
+static long mlp_count(int L, const int* dims) {
+  long c = 0;
+  for (int l = 0; l < L; ++l) c += (long)dims[l] * dims[l + 1] + dims[l + 1];
+  return c;
+}
+
+static void bind_mlp(MlpDesc& d, int L, const int* dims, const float* flat, float* flatT) {
+  d.L = L;
+  for (int l = 0; l <= L; ++l) d.dims[l] = dims[l];
+  long off = 0;
+  for (int l = 0; l < L; ++l) {
+    d.W[l] = flat + off;
+    d.WT[l] = flatT ? flatT + off : nullptr;
+    off += (long)dims[l] * dims[l + 1];
+    d.b[l] = flat + off;
+    off += dims[l + 1];
+  }
+}
+
+// gmpc_api.hip: argument and state checks every entry point starts with
+int check_call(gmpc_ctx* c, int B, bool need_params = true);
+// gmpc_api_critic.hip: the upper-level loss at the solution held by the ctx (and, with want_lx, its gradient in c->lx)
+int upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired, const float* critic, float* loss, bool want_lx,
+               hipStream_t s);

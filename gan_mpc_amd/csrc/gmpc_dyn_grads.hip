@@ -17,7 +17,7 @@
 //   k_dyn_adjoints  one workgroup per trajectory: the three backward sweeps -> w, lam planes [B][T][n]
 //   k_dyn_rows      16 steps per workgroup on v_mfma_f32_16x16x4_f32: the layer inputs [a; -a'] and deltas
 //                   [delta(w); delta(lam)] as 2 B T rows, whose column sums (k_wgrad*) are the weight gradient.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 #include <cstring>
 
@@ -298,7 +298,6 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_rows(DgRowArgs a) {
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-// The adjoint planes w, lam [B][T][n]; n <= 64, m <= 32 (the caller checks).
 void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X,
                               const float* goal, const float* dX, const float* lx, const float* AB, const float* QT,
                               const float* qT, float* w, float* lam, hipStream_t s) {
@@ -316,14 +315,12 @@ void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* m
                        dX, lx, AB, QT, qT, w, lam);
 }
 
-// The row layout of gmpc_launch_dyn_rows: floats per row (the larger of the input and the output columns).
 int gmpc_dyn_rows_stride(const MlpDesc& d) {
   int in = 0, out = 0;
   for (int l = 0; l < d.L; ++l) { in += d.dims[l]; out += d.dims[l + 1]; }
   return in > out ? in : out;
 }
 
-// acts / dels: 2 B T rows of gmpc_dyn_rows_stride floats.  Widths up to 256; returns 1 otherwise.
 int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const float* X, const float* U,
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
                          hipStream_t s) {

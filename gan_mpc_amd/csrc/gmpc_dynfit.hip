@@ -8,7 +8,7 @@
 // the C4 / C5 state sizes), activations of the
 // current step in LDS, layer inputs / deltas of every (sequence, step) written to HBM as the row
 // operands of the weight-gradient GEMMs (k_wgrad_mfma, the same kernel the critic uses).
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 struct DynFitArgs {
   int B, S, n, m;

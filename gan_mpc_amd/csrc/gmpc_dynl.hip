@@ -11,7 +11,7 @@
 // u = U_t + alpha k_t + K_t (x_new - X_t)), and the Jacobian kernel (forward recompute at (xc_t, u_t), then
 // the chain rule through the cell and the tail).  One 256-thread workgroup per trajectory / sample; the
 // reference's default is the MLP variant (yaml `use: "mlp"`), so these are written for clarity, not tuned.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 namespace {
 

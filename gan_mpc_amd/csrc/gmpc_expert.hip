@@ -11,7 +11,7 @@
 // gate pre-activation j (4F <= 512), the cell update runs as (unit, sequence), then the two heads run
 // side by side, the state head on threads 0..255, the action head on 256..511, each thread taking the
 // neurons j, j + 256, ... of its head's layer (widths and n up to 1024: the C4 / C5 state sizes).
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 #define GMPC_EX_THREADS 512
 

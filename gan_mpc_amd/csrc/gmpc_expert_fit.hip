@@ -18,7 +18,7 @@
 // The weight gradients are then sum_r acts^T dels on the matrix cores (gmpc_launch_wgrad: k_wgrad_mfma,
 // fixed chunk order), written straight into the flat expert layout.  No atomics anywhere: identical calls
 // give identical bits.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 __device__ __forceinline__ float efit_block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -241,7 +241,6 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
   }
 }
 
-// acts / dels row layout of one shape (see the header of this file); returns the row stride
 int gmpc_expert_fit_layout(ExpertFitArgs& a) {
   const int L = a.hx.L;
   int off = a.n + a.F + a.Y;              // head inputs a_1.. follow y

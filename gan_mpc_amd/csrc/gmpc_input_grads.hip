@@ -11,7 +11,7 @@
 //          nu_T = QT dX_T, nu_t = Q_t dX_t + Phi_x(x,u),t [dX_t; H_t] + A_t^T nu_{t+1}   (nu_0 = d/dx0 [H . grad_U J])
 //          dL/dx0 = mu_0 - nu_0.
 // Q_t is formed from x_t and g_t in closed form (the stage Hessian k_riccati builds), never stored.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 #define GMPC_IG_THREADS 256
 #define GMPC_IG_CHUNK_FLOATS 15872   // LDS for the staged steps (62 KB; the adjoints add 1 KB)

@@ -23,7 +23,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // C[b] = alpha * sum_{k<K} X[b][k][0:M]^T (x) Y[b][k][0:N]  (+ beta * C[b]);  one wave per
@@ -1395,20 +1395,6 @@ __global__ void k_big_cont(int B, int T, int m, const float* U, const float* gn2
 // ------------------------------------------------------------------------------------------------
 // host driver of one backward pass
 // ------------------------------------------------------------------------------------------------
-int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
-                               const uint32_t* masks, const int* active, float* AB, int samp_mul,
-                               int samp_add, hipStream_t s);
-int gmpc_launch_linearize_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
-                               const uint32_t* masks, const int* active, float* AB, int samp_mul,
-                               int samp_add, hipStream_t s);
-
-// LSTM dynamics variant (gmpc_dynl.hip): the per-step Jacobians come from its kernel instead of the chain
-void gmpc_launch_dynl_jac(int, int, int, int, const DynlDesc&, const float*, const float*, const int*, float*,
-                          hipStream_t);
-void gmpc_launch_dynl_curv(int, int, int, int, const DynlDesc&, const float*, const float*, const float*, const int*,
-                           float*, hipStream_t);
-void gmpc_launch_add_phi(int, int, int, const float*, float*, float*, hipStream_t);
-
 static void big_lowrank_factors(const BigWork& w, int B, const MlpDesc& dyn, const uint32_t* masks, int t,
                                 const int* active, hipStream_t s);
 // out[b][c][r] = in[b][r][c], 64 x 64 tiles through LDS

@@ -1,0 +1,211 @@
+// Every host function that is defined in one .hip file and called from another, by defining file; that file includes
+// this header too, so each definition is checked against what its callers see.  Default arguments live here only.
+// (gmpc_fused_solve.h keeps the one-launch solve's argument block and limits beside its two prototypes.)
+#pragma once
+#include "gmpc_device.h"     // (and with it the device helpers: a kernel file needs this include only)
+
+// gmpc_api.hip: the thread's error record behind gmpc_last_error(); returns `code`
+int gmpc_fail(int code, const char* fmt, ...);
+
+// gmpc_traj.hip ------------------------------------------------------------------------------------------------------
+void gmpc_launch_rollout(const TrajArgs& a, hipStream_t s);
+// `eval` (optional): another evaluator of the candidates of a round -- the LSTM dynamics variant (gmpc_dynl.hip) --
+// behind the same work list and the same decide / commit kernels; `user` is handed back to it
+typedef void (*gmpc_ls_eval_fn)(void* user, const TrajArgs&, int max_items, hipStream_t);
+int gmpc_launch_linesearch(const TrajArgs& a, const LsWork& w, hipStream_t s, gmpc_ls_eval_fn eval = nullptr,
+                           void* user = nullptr);
+// masks: [B][T][Lh][GMPC_MW] relu bits of the dynamics' hidden layers at (X_t, U_t)
+void gmpc_launch_masks(int B, int n, int m, int T, const MlpDesc& dyn, const float* X, const float* U,
+                       uint32_t* masks, hipStream_t s);
+// gmpc_traj_rw.hip: the register-weight trajectory kernel
+bool gmpc_traj_rw_shape(const TrajArgs& a);
+// LDS of one workgroup; sets the sizing fields of `a` (aw is set by the caller: widest layer of both networks)
+size_t gmpc_traj_rw_lds(TrajArgs& a);
+void gmpc_launch_traj_rw(const TrajArgs& a, bool ls, int grid, size_t lds, hipStream_t s);
+// gmpc_ls16.hip / gmpc_ls32.hip: 16 / 32 line-search candidates per workgroup
+bool gmpc_ls16_shape(const TrajArgs& a);
+int gmpc_ls16_split();     // work lists shorter than this stay on k_traj_rw
+bool gmpc_ls32_shape(const TrajArgs& a);
+int gmpc_ls32_split();     // work lists of at least this many items go to k_ls32 (0: never)
+// one workgroup per 16 / 32 work-list items; `max_items` bounds the list (the kernel reads the actual count)
+void gmpc_launch_ls16(const TrajArgs& a, long max_items, hipStream_t s);
+void gmpc_launch_ls32(const TrajArgs& a, long max_items, int min_items, hipStream_t s);
+
+// gmpc_backward.hip ---------------------------------------------------------------------------------------------------
+// VALU Jacobian chain; non-zero when the row count of n is not instantiated
+int gmpc_launch_linearize(int B, int T, int n, int m, const MlpDesc& dyn, const uint32_t* masks, const int* active,
+                          float* AB, hipStream_t s);
+// terminal quadratisation QT [B][n][n], qT [B][n]; non-zero on an unsupported cost fout
+int gmpc_launch_terminal(int B, int T, int n, const MlpDesc& cm, const float* mpc_w, const float* X, const int* active,
+                         float* QT, float* qT, hipStream_t s);
+void gmpc_launch_riccati(const RiccatiArgs& a, hipStream_t s);
+// gmpc_riccati_w.hip: the two-wave sweep
+bool gmpc_riccati_w_shape(const RiccatiArgs& a);      // mode 0 only; GMPC_RICCATI=valu keeps k_riccati
+bool gmpc_riccati_w2h_shape(const RiccatiArgs& a);    // mode 1 with the loss adjoint folded in (MLP dynamics)
+void gmpc_launch_riccati_w(const RiccatiArgs& a, hipStream_t s);
+void gmpc_launch_riccati_w2h(const RiccatiArgs& a, const float* lx, const float* lu, float* bvec_out, hipStream_t s);
+
+// Jacobian chains (gmpc_linearize_*.hip) -----------------------------------------------------------------------------
+// All of them: Jacobians of NSamp samples; sample s is sample s*samp_mul + samp_add of `masks`.  They return 0 on
+// launch and -1 when the shape is not one the form covers (the caller takes the next form).
+int gmpc_launch_linearize_sparse(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                 const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                                 hipStream_t s);
+int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                               const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                               hipStream_t s);
+// rows row0..n-1 of every sample (row0 = 0: all of them; the wide form takes row0 = 0 only)
+int gmpc_launch_linearize_regs_rows(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                    const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                                    int row0, hipStream_t s);
+const char* gmpc_linearize_regs_last_name();   // instantiation the last gmpc_launch_linearize_regs* launched
+int gmpc_launch_linearize_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                               const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                               hipStream_t s);
+// padded weight copies of the chains: floats of the buffer, and the build on every gmpc_set_params
+size_t gmpc_linpad_floats(const gmpc_shape* sh);
+void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pad_floats, LinPad* out, hipStream_t s);
+// k_linearize_sparse's packed copies inside that buffer: floats they add (0: shape not covered), build at `p` (zeroed)
+size_t gmpc_linsparse_floats(int L, const int* dims, int n, int m);
+void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* out, hipStream_t s);
+
+// gmpc_large.hip: the step-major pipeline (n > 64 or m > 32) ---------------------------------------------------------
+void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s);
+// one backward pass, non-zero when no Jacobian kernel covers the shape; lx / Bvec (lu optional): the bilevel tail's
+int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad& lp, const uint32_t* masks,
+                      const float* X, const float* U, const float* goal, const float* mpc_w, const float* QT,
+                      const float* qT, const int* active, float* K, float* k, float* grad, float* adj, const float* lx,
+                      float* Bvec, hipStream_t s, const DynlDesc* dl = nullptr, const float* lam_sol = nullptr,
+                      const float* lu = nullptr);
+// the bilevel tail's forward tangent roll; X / U: the solution, read by the LSTM variant (dl) only
+int gmpc_big_forward_tangent(const BigWork& w, int B, const MlpDesc& dyn, const LinPad& lp, const uint32_t* masks,
+                             const float* K, const float* k, float* Hout, float* dX, hipStream_t s,
+                             const DynlDesc* dl = nullptr, const float* X = nullptr, const float* U = nullptr);
+void gmpc_launch_big_cont(int B, int T, int m, const float* U, const float* gn2, const int* iters, const float* obj,
+                          const float* alpha, const float* obj_step, const float* U_step, const gmpc_ilqr_opts& opts,
+                          const int* active, int* cont, hipStream_t s);
+
+// gmpc_critic.hip -----------------------------------------------------------------------------------------------------
+void gmpc_launch_transpose(int R, int C, const float* in, float* out, hipStream_t s);   // in [R][C] -> out [C][R]
+void gmpc_launch_lstm_fwd(int Bc, const CriticDesc& cd, const float* xseq, float* gates, float* cs, float* hp,
+                          float* hT, const float* xproj, hipStream_t s);
+void gmpc_launch_lstm_bwd(int Bc, const CriticDesc& cd, const float* gates, const float* cs, const float* dhT,
+                          float* dz, float* dxseq, hipStream_t s);
+void gmpc_launch_sum(int count, const float* v, float* out, int square, hipStream_t s);
+void gmpc_launch_adam(long count, float* p, const float* g, float* m, float* v, float scale, int step, double lr,
+                      double max_norm, double b1, double b2, double eps, float* scratch /* >= 257 */, hipStream_t s);
+void gmpc_launch_polyak(long count, const float* prev, const float* cur, double f, float* out, hipStream_t s);
+
+// The weight-gradient GEMM: C[M][N] = sum_r A[r][:M]^T B[r][:N]; colsum[N] = sum_{r < cs_rows} B[r][:N] (optional).
+// Its matrix-core kernels (k_wgrad_mfma, k_wgrad_batch) read B up to GMPC_WGRAD_PAD rows past `rows`; A is clamped to
+// its last row and masked to zero there, so those rows of B only have to be allocated and finite.
+#define GMPC_WGRAD_PAD 8
+// part holds part_floats floats (at least max_split*(M*N + N)); mfma_ok: B has its GMPC_WGRAD_PAD pad rows
+void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
+                       float* colsum, int cs_rows, float* part, int max_split, hipStream_t s, long part_floats,
+                       bool mfma_ok);
+// MFMA path of gmpc_launch_wgrad; returns false when the shape does not qualify
+bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
+                            float* colsum, int cs_rows, float* part, long part_floats, hipStream_t s);
+// One MLP's rows summed into its packed gradient g = W_0 | b_0 | W_1 | b_1 | ... (the layout of a parameter vector):
+// layer l's inputs are columns sum(dims[0..l-1]).. of `acts`, its deltas columns sum(dims[1..l]).. of `dels`, both
+// [rows + GMPC_WGRAD_PAD][stride]; the biases sum the first cs_rows rows.  Returns g behind the last layer.
+float* gmpc_launch_wgrad_mlp(int rows, int cs_rows, int L, const int* dims, const float* acts, const float* dels,
+                             int stride, float* g, float* part, long part_floats, hipStream_t s);
+// all problems in one launch (+ one reduction); false when one does not qualify (the caller issues them one by one)
+bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_floats, hipStream_t s);
+// colsum[N] = sum_{r < rows} B[r][:N] on its own (two launches; `part` holds the chunk sums)
+void gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum, float* part, hipStream_t s);
+
+// gmpc_critic_lstm.hip: second-generation LSTM kernels (n <= 32) and the head ----------------------------------------
+bool gmpc_lstm2_supported(const CriticDesc& cd);
+long gmpc_lstm2_wpart_floats(const CriticDesc& cd, int Bc);   // floats of the weight-gradient partial buffer
+bool gmpc_launch_lstm_fwd2(int Bc, const CriticDesc& cd, const float* xseq, float* G, float* Cst, float* Hst, float* hT,
+                           hipStream_t s);
+// Wp != null: weight gradients -> gWx, gWh, gb (sums over the Bc sequences); dxseq != null: input gradient
+bool gmpc_launch_lstm_bwd2(int Bc, const CriticDesc& cd, const float* xseq, const float* G, const float* Cst,
+                           const float* Hst, const float* dhT, float* Wp, float* gWx, float* gWh, float* gb,
+                           float* dxseq, hipStream_t s);
+void gmpc_launch_mlp_transpose_all(const MlpDesc& d, hipStream_t s);   // every W[l] -> WT[l] in one launch
+#define GMPC_HEAD2_LD 264     // leading dimension of plast: 256 products + dscore, padded to a multiple of 8
+void gmpc_launch_head2(int Bc, const CriticDesc& cd, int loss_kind, const float* hT, const float* label, float* score,
+                       float* loss, float* acts, float* dels, float* plast, float* dhT, int act_stride, hipStream_t s);
+
+// gmpc_bilevel.hip ----------------------------------------------------------------------------------------------------
+void gmpc_launch_l2loss(int B, int T, int n, int ng, const float* X, const float* desired, float* loss, float* lx,
+                        hipStream_t s);
+void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* lx, const float* lu, float* Bvec,
+                      hipStream_t s);
+void gmpc_launch_costvjp(int B, int T, int n, int m, const MlpDesc& cm, const float* mpc_w, float sign, const float* X,
+                         const float* U, const float* goal, int ng, const float* Hc, const float* dX, float* gmpc,
+                         float* cact, float* cdel, int stride, hipStream_t s);
+void gmpc_launch_get_cost(int B, int n, int ng, int m, const MlpDesc& cm, const float* mpc_w, const float* x,
+                          const float* u, const float* goal_row, int terminal, float* out, hipStream_t s);
+
+// gmpc_input_grads.hip ------------------------------------------------------------------------------------------------
+// x0 (and, with ggoal, the goal) gradient: n <= 64, m <= 32 (the caller checks); 0 on success
+int gmpc_launch_input_grads(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X, const float* goal,
+                            const float* dX, const float* H, const float* lx, const float* AB, const float* QT,
+                            const float* Phi, float* gx0, float* ggoal, hipStream_t s);
+void gmpc_launch_goal_grad(int B, int T, int n, int ng, const float* mpc_w, const float* X, const float* goal,
+                           const float* dX, float* ggoal, hipStream_t s);
+
+// gmpc_dyn_grads.hip --------------------------------------------------------------------------------------------------
+// the adjoint planes w, lam [B][T][n]; n <= 64, m <= 32 (the caller checks)
+void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X, const float* goal,
+                              const float* dX, const float* lx, const float* AB, const float* QT, const float* qT,
+                              float* w, float* lam, hipStream_t s);
+// the row layout of gmpc_launch_dyn_rows: floats per row (the larger of the input and the output columns)
+int gmpc_dyn_rows_stride(const MlpDesc& d);
+// acts / dels: 2 B T rows of gmpc_dyn_rows_stride floats.  Widths up to 256; returns 1 otherwise.
+int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const float* X, const float* U,
+                         const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
+                         hipStream_t s);
+
+// gmpc_rollout_vjp.hip ------------------------------------------------------------------------------------------------
+int gmpc_rvjp_cost_stride(const MlpDesc& c);   // floats per cost row (the larger of the summed input / output widths)
+// masks: [B][T][Lh][GMPC_MW] relu bits at (X_t, U_t).  Null outputs are skipped; cacts / cdels ([B][cost stride]) and
+// gm go together; dels: B T rows of dstride floats in gmpc_dyn_rows_stride's layout.
+void gmpc_launch_rvjp_sweep(int B, int n, int m, int T, const MlpDesc& dyn, const MlpDesc& cost, const float* mpc_w,
+                            const float* X, const float* U, const float* goal, const float* gX, const float* gc,
+                            const uint32_t* masks, float* gx0, float* gU, float* ggoal, float* gm, float* cacts,
+                            float* cdels, float* dels, int dstride, hipStream_t s);
+// acts: B T rows of dstride floats (the layer inputs at gmpc_dyn_rows_stride's offsets); masks as k_masks writes them
+void gmpc_launch_rvjp_acts(int B, int n, int m, int T, const MlpDesc& dyn, const float* X, const float* U, float* acts,
+                           int dstride, uint32_t* masks, hipStream_t s);
+
+// gmpc_dynfit.hip: dynamics regression --------------------------------------------------------------------------------
+size_t gmpc_dynfit_stride(const gmpc_shape* s);   // floats per acts / dels row
+int gmpc_launch_dynfit(int B, int S, int n, int m, const MlpDesc& dyn, const float* xseq, const float* useq,
+                       const float* yseq, float gamma, int teacher_forcing, float* pred, float* acts, float* dels,
+                       int stride, float* loss, hipStream_t s);
+
+// gmpc_dynl.hip: LSTM dynamics variant --------------------------------------------------------------------------------
+void gmpc_launch_dynl_rollout(DynlTrajArgs a, hipStream_t s);
+void gmpc_launch_dynl_candidates(DynlTrajArgs a, int max_items, hipStream_t s);
+// [A_t | B_t] / the curvature term Phi_t = lam_{t+1} . d^2 f of steps t0 .. t0 + nt - 1 of a T-step horizon
+void gmpc_launch_dynl_jac(int B, int T, int nt, int t0, const DynlDesc& d, const float* X, const float* U,
+                          const int* active, float* AB, hipStream_t s);
+void gmpc_launch_dynl_curv(int B, int T, int nt, int t0, const DynlDesc& d, const float* X, const float* U,
+                           const float* adj, const int* active, float* Phi, hipStream_t s);
+void gmpc_launch_add_phi(int B, int n, int m, const float* Phi, float* HG, float* T1, hipStream_t s);
+// the first nx of n columns of every row: src [rows][n] -> dst [rows][nx], and back (zero on the other columns)
+void gmpc_launch_cols_gather(long rows, int n, int nx, const float* src, float* dst, hipStream_t s);
+void gmpc_launch_cols_scatter(long rows, int n, int nx, const float* src, float* dst, hipStream_t s);
+size_t gmpc_dynl_fit_stride(const DynlDesc& d);   // floats per acts / dels row
+void gmpc_launch_dynl_fit(int B, int S, const DynlDesc& d, const float* xseq, const float* useq, const float* yseq,
+                          float gamma, int teacher_forcing, float* pred, float* acts, float* dels, int stride,
+                          float* save, float* loss, hipStream_t s);
+
+// gmpc_expert.hip / gmpc_expert_fit.hip -------------------------------------------------------------------------------
+int gmpc_launch_expert(const ExpertArgs& a, hipStream_t s);   // non-zero on an unsupported shape
+// acts / dels row layout of one shape (see the header of gmpc_expert_fit.hip); returns the row stride
+int gmpc_expert_fit_layout(ExpertFitArgs& a);
+void gmpc_launch_expert_fit(const ExpertFitArgs& a, hipStream_t s);
+
+// gmpc_comm.hip: multi-GPU exchange -----------------------------------------------------------------------------------
+struct GmpcComm { void* comm = nullptr; int world = 1, rank = 0; };   // comm: the ncclComm_t, null in a world of one
+int gmpc_comm_unique_id_impl(char* id128);
+int gmpc_comm_init_impl(GmpcComm* gc, int world, int rank, const char* id128);
+int gmpc_comm_allreduce_impl(GmpcComm* gc, float* packed, long count, hipStream_t s);
+void gmpc_comm_destroy_impl(GmpcComm* gc);

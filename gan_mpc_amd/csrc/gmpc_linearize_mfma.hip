@@ -16,7 +16,7 @@
 //   - C: NT accumulators of 16 registers (32 x 32*NT columns), masked with the relu bits of the
 //     layer below in the epilogue and written back to G as the next A operand.
 // Waves never talk to each other: no workgroup barrier in the kernel.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 
 
@@ -234,10 +234,6 @@ __global__ __launch_bounds__(GMPC_THREADS, 1) void k_linearize_mfma(
 }
 
 // ---------------------------------------------------------------------------------------------
-// packed copies of k_linearize_sparse (gmpc_linearize_sparse.hip: the one file that knows their format)
-size_t gmpc_linsparse_floats(int L, const int* dims, int n, int m);
-void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* out, hipStream_t s);
-
 size_t gmpc_linpad_floats(const gmpc_shape* sh) {
   const int L = sh->dyn_layers, Lh = L - 1;
   int wmax = 1;
@@ -250,7 +246,6 @@ size_t gmpc_linpad_floats(const gmpc_shape* sh) {
   return f + 64 + gmpc_linsparse_floats(L, sh->dyn_dims, sh->n, sh->m);
 }
 
-// builds the padded copies; `pad` must hold gmpc_linpad_floats() floats
 void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pad_floats, LinPad* out,
                          hipStream_t s) {
   const int Lh = dyn.L - 1;
@@ -317,8 +312,6 @@ static int launch_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const
   return 0;
 }
 
-// Jacobians of NSamp samples; sample s is sample s*samp_mul + samp_add of `masks`.
-// returns 0 on launch, -1 if the shape does not fit this kernel (caller uses the VALU chain)
 int gmpc_launch_linearize_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                const uint32_t* masks, const int* active, float* AB, int samp_mul,
                                int samp_add, hipStream_t s) {

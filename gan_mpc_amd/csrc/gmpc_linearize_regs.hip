@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <cstdio>
 
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 #ifndef GMPC_LIN_RD0
 #define GMPC_LIN_RD0 3      // k-steps of W_1^T fragments in flight + 1 in the wide form's input GEMM (5 or 8: C4 97 vs 91 ms)
 #endif
@@ -390,8 +390,6 @@ static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const
   return 0;
 }
 
-// rows row0..n-1 of every sample (row0 = 0: all of them; the wide form takes row0 = 0 only).
-// returns 0 on launch, -1 when the shape is not one this variant is compiled for
 int gmpc_launch_linearize_regs_rows(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                     const uint32_t* masks, const int* active, float* AB, int samp_mul,
                                     int samp_add, int row0, hipStream_t s) {

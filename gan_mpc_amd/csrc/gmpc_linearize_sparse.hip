@@ -34,7 +34,7 @@
 #include <cstdio>
 #include <type_traits>
 
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -72,15 +72,12 @@ __global__ void k_pack_sparse(const float* W, float* dst) {
   dst[(size_t)o * GMPC_SP_ROW + slot] = W[e];
 }
 
-// floats the packed copies add to the padded-weight buffer (gmpc_linpad_floats): 0 for shapes this form does not cover
 size_t gmpc_linsparse_floats(int L, const int* dims, int n, int m) {
   if (!sparse_form(L, dims, n, m)) return 0;
   // + one row to round the first copy up to 1 KB
   return (size_t)(L - 2) * (GMPC_SP_H + GMPC_LIN_PADROWS) * GMPC_SP_ROW + GMPC_SP_ROW;
 }
 
-// builds the packed copies at `p` (zeroed, gmpc_linsparse_floats() floats) on every gmpc_set_params, beside the
-// padded copies of gmpc_linpad_prepare
 void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* out, hipStream_t s) {
   for (int l = 0; l < GMPC_MAX_LAYERS; ++l) out->WSP[l] = nullptr;
   if (!sparse_form(dyn.L, dyn.dims, n, m)) return;
@@ -285,11 +282,6 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
   }
 }
 
-int gmpc_launch_linearize_regs_rows(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
-                                    const uint32_t* masks, const int* active, float* AB, int samp_mul,
-                                    int samp_add, int row0, hipStream_t s);
-
-// returns 0 on launch, -1 when the shape is not one this form covers (the caller runs the dense chain)
 int gmpc_launch_linearize_sparse(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                  const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
                                  hipStream_t s) {

@@ -29,7 +29,7 @@
 //
 // Reference arithmetic: dynamics/nn.py:27-34, cost/cost_model.py:20-42, cost/nn.py:23-29, trajax
 // line_search_ddp / ddp_rollout (u = U + alpha k + K (x - X)) as called from policy/optimizers.py:19.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -571,7 +571,6 @@ __global__ __launch_bounds__(LS16_THREADS, 1) void k_ls16(TrajArgs a) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-bool gmpc_traj_rw_shape(const TrajArgs& a);
 static size_t ls16_lds(int nob, int T);
 
 // shapes k_ls16 is instantiated for: the register-weight shapes with n + m <= 24, m <= 8 and a cost network
@@ -622,7 +621,6 @@ static void ls16_launch_kh(const TrajArgs& a, int grid, hipStream_t s) {
   }
 }
 
-// one workgroup per 16 work-list items; `max_items` bounds the list (the kernel reads the actual count)
 void gmpc_launch_ls16(const TrajArgs& a, long max_items, hipStream_t s) {
   const int grid = (int)((max_items + LS16_C - 1) / LS16_C);
   switch (a.dyn.dims[1]) {

@@ -27,7 +27,7 @@
 //
 // Reference arithmetic: dynamics/nn.py:27-34, cost/cost_model.py:20-42, cost/nn.py:23-29, trajax
 // line_search_ddp / ddp_rollout (u = U + alpha k + K (x - X)) as called from policy/optimizers.py:19.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -710,8 +710,6 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-bool gmpc_ls16_shape(const TrajArgs& a);
-
 static size_t ls32_lds(int n, int m) {
   const int k0s = (n + m + 3) / 4;
   const int fl = n > 16 ? Ls32Lay<6, 2>::TOTAL : k0s <= 4 ? Ls32Lay<4, 1>::TOTAL : Ls32Lay<6, 1>::TOTAL;
@@ -750,7 +748,6 @@ static void ls32_launch(const TrajArgs& a, int grid, int min_items, hipStream_t 
   hipLaunchKernelGGL((k_ls32<K0S, NOB>), dim3(grid), dim3(LS32_THREADS), ls32_lds(a.n, a.m), s, a, min_items);
 }
 
-// one workgroup per 32 work-list items; `max_items` bounds the list (the kernel reads the actual count)
 void gmpc_launch_ls32(const TrajArgs& a, long max_items, int min_items, hipStream_t s) {
   const int per = LS32_NG * LS32_C;
   const int grid = (int)((max_items + per - 1) / per);

@@ -3,7 +3,7 @@
 // Same recursion as k_riccati (trajax lqr_step / tvlqr with delta = 1e-8, adjoint); the association of the
 // products differs (A^T (P A) instead of (A^T P) A, the K terms through V), the results agree to rounding.
 // Reference arithmetic: trajax tvlqr as called from policy/optimizers.py:19,41; cost/cost_model.py:20-31.
-#include "gmpc_device.h"
+#include "gmpc_launch.h"
 #include <cstdlib>
 #include <cstring>
 

@@ -18,6 +18,7 @@
 //                 mpc_w terms, the cost layers' input / delta rows and (grad_dyn_sum) the dynamics' delta rows.
 // The batch sums (mpc_w, cost and dynamics weights) are the weight-gradient GEMMs of gmpc_critic.hip.
 #include "gmpc_traj_layers.h"
+#include "gmpc_launch.h"
 
 #include <cstring>
 
@@ -312,15 +313,12 @@ static int rv_width(int n, int m, const MlpDesc& d, const MlpDesc* d2) {
   return (w + 3) & ~3;
 }
 
-// Floats per cost row (the larger of the summed input and output widths).
 int gmpc_rvjp_cost_stride(const MlpDesc& c) {
   int in = 0, out = 0;
   for (int l = 0; l < c.L; ++l) { in += c.dims[l]; out += c.dims[l + 1]; }
   return in > out ? in : out;
 }
 
-// masks: [B][T][Lh][GMPC_MW] relu bits at (X_t, U_t).  Null outputs are skipped; cacts / cdels ([B][cost stride]) and
-// gm go together; dels: B T rows of dstride floats in gmpc_dyn_rows_stride's layout.
 void gmpc_launch_rvjp_sweep(int B, int n, int m, int T, const MlpDesc& dyn, const MlpDesc& cost, const float* mpc_w,
                             const float* X, const float* U, const float* goal, const float* gX, const float* gc,
                             const uint32_t* masks, float* gx0, float* gU, float* ggoal, float* gm, float* cacts,
@@ -349,7 +347,6 @@ void gmpc_launch_rvjp_sweep(int B, int n, int m, int T, const MlpDesc& dyn, cons
   hipLaunchKernelGGL(k_rvjp_sweep, dim3((B + 3) / 4), dim3(GMPC_THREADS), lds, s, a);
 }
 
-// acts: B T rows of dstride floats (the layer inputs at gmpc_dyn_rows_stride's offsets); masks as k_masks writes them.
 void gmpc_launch_rvjp_acts(int B, int n, int m, int T, const MlpDesc& dyn, const float* X, const float* U, float* acts,
                            int dstride, uint32_t* masks, hipStream_t s) {
   RvjpArgs a;

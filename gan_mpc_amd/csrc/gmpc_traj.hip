@@ -13,6 +13,7 @@
 // cost/nn.py:23-29, trajax rollout / evaluate / ddp_rollout / line_search_ddp as called from
 // policy/optimizers.py:19,26-29,55.
 #include "gmpc_traj_layers.h"
+#include "gmpc_launch.h"
 
 #ifndef GMPC_TRAJ_MINW
 #define GMPC_TRAJ_MINW 4
@@ -491,16 +492,6 @@ static void traj_attr(KernelT k) {
   (void)hipGetLastError();
 }
 
-bool gmpc_traj_rw_shape(const TrajArgs& a);
-size_t gmpc_traj_rw_lds(TrajArgs& a);
-void gmpc_launch_traj_rw(const TrajArgs& a, bool ls, int grid, size_t lds, hipStream_t s);
-bool gmpc_ls16_shape(const TrajArgs& a);
-int gmpc_ls16_split();
-void gmpc_launch_ls16(const TrajArgs& a, long max_items, hipStream_t s);
-bool gmpc_ls32_shape(const TrajArgs& a);
-int gmpc_ls32_split();
-void gmpc_launch_ls32(const TrajArgs& a, long max_items, int min_items, hipStream_t s);
-
 void gmpc_launch_rollout(const TrajArgs& a0, hipStream_t s) {
   TrajArgs a = a0;
   if (gmpc_traj_rw_shape(a)) {
@@ -515,9 +506,7 @@ void gmpc_launch_rollout(const TrajArgs& a0, hipStream_t s) {
   const int grid = (a.B + GMPC_TB - 1) / GMPC_TB;
   hipLaunchKernelGGL(k_traj<false>, dim3(grid), dim3(GMPC_TRAJ_THREADS), lds, s, a);
 }
-// `eval` (optional): another evaluator of the candidates of a round -- the LSTM dynamics variant
-// (gmpc_dynl.hip) -- behind the same work list and the same decide / commit kernels.
-typedef void (*gmpc_ls_eval_fn)(void* user, const TrajArgs&, int max_items, hipStream_t);
+
 int gmpc_launch_linesearch(const TrajArgs& a0, const LsWork& w, hipStream_t s, gmpc_ls_eval_fn eval,
                            void* user) {
   TrajArgs a = a0;

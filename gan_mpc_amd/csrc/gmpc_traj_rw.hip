@@ -6,6 +6,7 @@
 // Reference arithmetic as in gmpc_traj.hip: dynamics/nn.py:27-34, cost/cost_model.py:20-42, cost/nn.py:23-29,
 // trajax rollout / evaluate / ddp_rollout as called from policy/optimizers.py:19,26-29,55.
 #include "gmpc_traj_layers.h"
+#include "gmpc_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // Register-weight MFMA form of the dynamics network (k_traj<LS, H, NHL, K0Q>, 256 threads).
@@ -479,7 +480,6 @@ static int rw_width(const TrajArgs& a) {
 }
 bool gmpc_traj_rw_shape(const TrajArgs& a) { return rw_width(a) != 0; }
 
-// LDS of one workgroup; sets the sizing fields of `a` (aw is set by the caller: widest layer of both networks)
 size_t gmpc_traj_rw_lds(TrajArgs& a) {
   const int H = rw_width(a);
   a.pw = GMPC_RW_THREADS;
