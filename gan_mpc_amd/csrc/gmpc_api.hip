@@ -108,6 +108,7 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
   c->sh = *shape;
   c->maxB = max_batch;
   c->device = device;
+  if (hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) c->ncu = 256;
   const gmpc_shape& s = c->sh;
   const size_t B = max_batch, n = s.n, m = s.m, T = s.T, nm = n + m, Lh = s.dyn_layers - 1;
   c->dynl = s.dyn_lstm_features > 0;

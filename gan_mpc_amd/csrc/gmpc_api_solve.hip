@@ -216,6 +216,10 @@ extern "C" int gmpc_ilqr_solve(gmpc_ctx* c, int B, const float* x0, const float*
   ls.Xc = c->Xc; ls.Uc = c->Uc; ls.maskc = c->maskc; ls.active = c->cont; ls.alpha = c->alpha;
   ls.obj_step = c->obj_step; ls.U_step = c->U_step; ls.iters = c->iters;
   ls.alpha_0 = opts->alpha_0; ls.alpha_min = opts->alpha_min;
+  // which kernels evaluate the line searches' candidates, how many rounds: fixed for the solve
+  LsPlan plan;
+  if (gmpc_ls_plan(ls, c->ncu, c->dynl, &plan) != 0 && opts->maxiter > 0)
+    return fail(GMPC_EINVAL, "line search: alpha_0 / alpha_min need more than %d rounds", GMPC_LS_ROUNDS_MAX);
   // a fresh solve starts its first line search with a single full step per trajectory
   HIP_TRY(hipMemsetAsync(c->lsw.prevk, 0, B * sizeof(int), s));
   HIP_TRY(hipMemsetAsync(c->lsw.counts + GMPC_LS_ROUNDS_MAX, 0, (1 + GMPC_LS_STATS) * sizeof(int), s));
@@ -242,9 +246,7 @@ extern "C" int gmpc_ilqr_solve(gmpc_ctx* c, int B, const float* x0, const float*
     HIP_TRY(hipEventRecord(c->poll_ev[slot], s));
     {
       ProfScope ps(c, PROF_LINESEARCH, s);
-      if (gmpc_launch_linesearch(ls, c->lsw, s, c->dynl ? &dynl_ls_eval : nullptr, c) != 0)
-        return fail(GMPC_EINVAL, "line search: alpha_0 / alpha_min need more than %d rounds",
-                    GMPC_LS_ROUNDS_MAX);
+      gmpc_launch_linesearch(ls, plan, c->lsw, s, c->dynl ? &dynl_ls_eval : nullptr, c);
     }
     TRY(backward_pass(c, B, c->Xs, c->Us, c->goals, c->cont, c->Ks, c->ks, c->grads, c->adjs, c->AB,
                       c->cont, opts, s));
@@ -276,8 +278,7 @@ extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const 
   if (c->big)
     return fail(GMPC_EINVAL, "fused solve: n <= 64 and m <= 32 only (n=%d m=%d)", sh.n, sh.m);
   if (sh.T > GMPC_FZ_MAX_T) return fail(GMPC_EINVAL, "fused solve: T <= %d only (T=%d)", GMPC_FZ_MAX_T, sh.T);
-  int k_max = 0;   // step sizes alpha_0 / 2^k above alpha_min (the line search's loop, as gmpc_launch_linesearch counts)
-  for (float al = opts->alpha_0; al > opts->alpha_min && k_max <= GMPC_FZ_MAX_HALVINGS; al *= 0.5f) ++k_max;
+  const int k_max = gmpc_ls_halvings(opts->alpha_0, opts->alpha_min, GMPC_FZ_MAX_HALVINGS + 1);
   if (k_max > GMPC_FZ_MAX_HALVINGS)
     return fail(GMPC_EINVAL, "fused solve: alpha_0 / alpha_min allow more than %d halvings", GMPC_FZ_MAX_HALVINGS);
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -49,6 +49,7 @@ struct gmpc_ctx {
   float *xg = nullptr, *lxg = nullptr;   // x columns of Xs / d loss / dx (critic-facing, dynl only)
   float* phi = nullptr;                  // dynl, small-state path: [B][T][n+m][n+m] curvature for the bilevel solve
   int maxB, device;
+  int ncu = 0;           // compute units of `device` (the line search's plan sizes a pass over the chip with it)
   std::vector<void*> allocs;
   // bound parameters
   const float* mpc_w = nullptr;

@@ -192,16 +192,15 @@ struct TrajArgs {
   // candidate i writes Xc / Uc / maskc / objc at index i
   const int* item_b; const int* item_k; const int* nitems;
   float* objc;
-  // work lists of at least ls_split items are k_ls16's, shorter ones k_traj_rw's (0: no split, see
-  // gmpc_ls16.hip); both kernels are launched and read the round's count
-  int ls_split;
-  // ... and lists of at least ls32_split items k_ls32's (two groups of 16 per workgroup, gmpc_ls32.hip; 0: never)
-  int ls32_split;
+  // which kernel evaluates a round, by the round's count: k_ls32 from ls32_split items on, k_ls16 from ls_split on,
+  // k_traj_rw below (0: that kernel does not take part).  All of them are launched and read the count; the guard is
+  // ls_round_form (gmpc_ls_common.h), the thresholds come from gmpc_ls_plan with ls_split <= ls32_split.
+  int ls_split, ls32_split;
 };
 
 #define GMPC_LS_ITEMS 8   // candidates per trajectory held at once by the line search
 
-// device workspace of the round-based line search (gmpc_traj.hip)
+// device workspace of the round-based line search (gmpc_linesearch.hip)
 struct LsWork {
   int* item_b[2]; int* item_k[2];   // ping-pong work lists [maxB * GMPC_LS_ITEMS]
   int* first; int* cnt; int* kfirst;   // [maxB] this round's candidates of trajectory b: cnt halvings

@@ -7,7 +7,7 @@
 // and the staging cost / L2 loss / critic see xc[:nx] only (their `ng` argument).
 //
 // Two kernels: the trajectory kernel (rollout + per-step costs; as line-search candidate evaluator it takes
-// the (trajectory, halving) work list of gmpc_traj.hip's k_ls_place and applies the DDP feedback
+// the (trajectory, halving) work list of gmpc_linesearch.hip's k_ls_place and applies the DDP feedback
 // u = U_t + alpha k_t + K_t (x_new - X_t)), and the Jacobian kernel (forward recompute at (xc_t, u_t), then
 // the chain rule through the cell and the tail).  One 256-thread workgroup per trajectory / sample; the
 // reference's default is the MLP variant (yaml `use: "mlp"`), so these are written for clarity, not tuned.

@@ -9,27 +9,45 @@ int gmpc_fail(int code, const char* fmt, ...);
 
 // gmpc_traj.hip ------------------------------------------------------------------------------------------------------
 void gmpc_launch_rollout(const TrajArgs& a, hipStream_t s);
-// `eval` (optional): another evaluator of the candidates of a round -- the LSTM dynamics variant (gmpc_dynl.hip) --
-// behind the same work list and the same decide / commit kernels; `user` is handed back to it
-typedef void (*gmpc_ls_eval_fn)(void* user, const TrajArgs&, int max_items, hipStream_t);
-int gmpc_launch_linesearch(const TrajArgs& a, const LsWork& w, hipStream_t s, gmpc_ls_eval_fn eval = nullptr,
-                           void* user = nullptr);
+// the general trajectory kernel: one workgroup per 4 trajectories (ls = false) / work-list items (ls = true)
+void gmpc_launch_traj(const TrajArgs& a, bool ls, int grid, hipStream_t s);
 // masks: [B][T][Lh][GMPC_MW] relu bits of the dynamics' hidden layers at (X_t, U_t)
 void gmpc_launch_masks(int B, int n, int m, int T, const MlpDesc& dyn, const float* X, const float* U,
                        uint32_t* masks, hipStream_t s);
 // gmpc_traj_rw.hip: the register-weight trajectory kernel
 bool gmpc_traj_rw_shape(const TrajArgs& a);
-// LDS of one workgroup; sets the sizing fields of `a` (aw is set by the caller: widest layer of both networks)
+// LDS of one workgroup; sets the sizing fields of `a`
 size_t gmpc_traj_rw_lds(TrajArgs& a);
 void gmpc_launch_traj_rw(const TrajArgs& a, bool ls, int grid, size_t lds, hipStream_t s);
-// gmpc_ls16.hip / gmpc_ls32.hip: 16 / 32 line-search candidates per workgroup
+// gmpc_ls16.hip / gmpc_ls32.hip: 16 / 32 line-search candidates per workgroup; the shapes they are instantiated for
 bool gmpc_ls16_shape(const TrajArgs& a);
-int gmpc_ls16_split();     // work lists shorter than this stay on k_traj_rw
 bool gmpc_ls32_shape(const TrajArgs& a);
-int gmpc_ls32_split();     // work lists of at least this many items go to k_ls32 (0: never)
 // one workgroup per 16 / 32 work-list items; `max_items` bounds the list (the kernel reads the actual count)
 void gmpc_launch_ls16(const TrajArgs& a, long max_items, hipStream_t s);
-void gmpc_launch_ls32(const TrajArgs& a, long max_items, int min_items, hipStream_t s);
+void gmpc_launch_ls32(const TrajArgs& a, long max_items, hipStream_t s);
+
+// gmpc_linesearch.hip -------------------------------------------------------------------------------------------------
+// step sizes alpha_0 / 2^k, k = 0, 1, .., that stay above alpha_min (trajax' loop), counted up to `cap`
+int gmpc_ls_halvings(float alpha_0, float alpha_min, int cap);
+// The route of a solve's line searches: everything about them that its shape, options and the GMPC_LS* variables fix.
+struct LsPlan {
+  bool rw, ls16, ls32;      // kernels that evaluate candidates beside a custom evaluator's / k_traj<true>: k_traj_rw<true>,
+                            // and with it k_ls16, and with that k_ls32
+  int split16, split32;     // TrajArgs::ls_split / ls32_split (0: form not taking part; else 1 <= split16 <= split32)
+  int k_max;                // gmpc_ls_halvings
+  int first_min;            // least size of a trajectory's first round
+  int rounds;               // rounds enqueued per line search (the worst case)
+  int aw, pw, sw0, swl;     // k_traj_rw's LDS sizing (the TrajArgs fields) and bytes
+  size_t lds;
+};
+// `a`: B, shape, networks, alpha_0 / alpha_min; ncu: compute units of the device; non-zero: more than
+// GMPC_LS_ROUNDS_MAX rounds
+int gmpc_ls_plan(const TrajArgs& a, int ncu, bool custom_eval, LsPlan* p);
+// `eval` (optional, custom_eval of the plan): another evaluator of the candidates of a round -- the LSTM dynamics
+// variant (gmpc_dynl.hip) -- behind the same work list and the same decide / commit kernels; `user` is handed back to it
+typedef void (*gmpc_ls_eval_fn)(void* user, const TrajArgs&, int max_items, hipStream_t);
+void gmpc_launch_linesearch(const TrajArgs& a, const LsPlan& p, const LsWork& w, hipStream_t s,
+                            gmpc_ls_eval_fn eval = nullptr, void* user = nullptr);
 
 // gmpc_backward.hip ---------------------------------------------------------------------------------------------------
 // VALU Jacobian chain; non-zero when the row count of n is not instantiated

@@ -27,27 +27,15 @@
 //
 // Reference arithmetic: dynamics/nn.py:27-34, cost/cost_model.py:20-42, cost/nn.py:23-29, trajax
 // line_search_ddp / ddp_rollout (u = U + alpha k + K (x - X)) as called from policy/optimizers.py:19.
+#include "gmpc_ls_common.h"
 #include "gmpc_launch.h"
-#include <cstdlib>
-#include <cstring>
 
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
 #define LS32_THREADS 512         // two teams of 256
 #define LS32_NG 2           // groups per workgroup
-#define LS32_C 16           // candidates per group
-#define LS32_KH 200         // hidden width
-#define LS32_KS 50          // k-steps of a hidden layer
-#define LS32_GS 80          // floats between groups of 4 activation rows
-#define LS32_ROWS 208       // activation rows (13 blocks)
-#define LS32_ACT ((LS32_ROWS / 4) * LS32_GS)
+#define LS32_ACT ((LS_ROWS / 4) * LS_GS)
 #define LS32_LDS_MAX (159 * 1024)   // (the kernel also holds 512 bytes of static LDS)
-
-__device__ __forceinline__ f32x4_t ls32_mfma(float a, float b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// float index of activation row k, candidate c
-__device__ __forceinline__ int ls32_at(int k, int c) { return (k >> 2) * LS32_GS + (k & 3) * 16 + c; }
 
 // epilogue of row block nb < 12 (the bias is in the accumulator): relu, the next layer's activations, and the relu
 // bits of the block in the candidate's mask image of this layer -- 32 bytes per candidate and layer in the layout of
@@ -114,20 +102,20 @@ struct Ls32Lay {
   // one group: its small buffers, then its two activation buffers -- ONE contiguous region per group, so that a
   // slot of the time loop can hand the two groups to the phases as two __restrict__ pointers (see `slots` in the kernel)
   static constexpr int XCUR = 0;                                  // rows x ; u ; 0 (layer-0 input), 8 groups of 4 rows
-  static constexpr int DXS = XCUR + 8 * LS32_GS;                  // x - X_nominal in the layout of xcur
-  static constexpr int PART = DXS + 8 * LS32_GS;                  // [4 waves][NOB][4][64] output-layer partials
+  static constexpr int DXS = XCUR + 8 * LS_GS;                    // x - X_nominal in the layout of xcur
+  static constexpr int PART = DXS + 8 * LS_GS;                    // [4 waves][NOB][4][64] output-layer partials
   static constexpr int P12 = PART + 4 * NOB * 256;                // [2][4 waves][4][32] block-12 partials
   static constexpr int MASK = P12 + 2 * 4 * 4 * 32;               // [16][3 layers][32 bytes] mask image = [16][24] words
-  static constexpr int KS = MASK + LS32_C * 24;                   // gains [16][MNX]
-  static constexpr int KUS = KS + LS32_C * MNX;                   // k and U, [16][8] each
-  static constexpr int DUMMY = KUS + 2 * LS32_C * 8;              // [64] where the stores of lanes without a role land
+  static constexpr int KS = MASK + LS_C * 24;                     // gains [16][MNX]
+  static constexpr int KUS = KS + LS_C * MNX;                     // k and U, [16][8] each
+  static constexpr int DUMMY = KUS + 2 * LS_C * 8;                // [64] where the stores of lanes without a role land
   static constexpr int ACTA = DUMMY + 64;
   static constexpr int ACTB = ACTA + LS32_ACT;                    // (after the horizon: the stage costs [16][T])
   static constexpr int GSZ = ACTB + LS32_ACT;                     // (group gi starts at gi * GSZ)
   // shared tables (read-only inside the time loop), relative to TB0
   static constexpr int TB0 = LS32_NG * GSZ;
   static constexpr int BIAS = 0;                                  // [3][208] hidden biases, [32] output bias
-  static constexpr int WXL = BIAS + 3 * LS32_ROWS + 32;           // [2 layers][52 k-steps][4 g][8]: A fragments of block 12
+  static constexpr int WXL = BIAS + 3 * LS_ROWS + 32;             // [2 layers][52 k-steps][4 g][8]: A fragments of block 12
   static constexpr int WOL = WXL + 2 * 52 * 32;                   // [4 waves][13][64] A fragments of output block 0
   static constexpr int WOL1 = WOL + 4 * 13 * 64;                  // [4 waves][13][4 g][NV8] A fragments of output block 1
   static constexpr int TOTAL = TB0 + WOL1 + 4 * 13 * 4 * NV8;
@@ -135,7 +123,7 @@ struct Ls32Lay {
 
 // K0S: k-steps of layer 0 (n + m <= 4 K0S); NOB: 16-row blocks of the output layer (n <= 16 NOB)
 template <int K0S, int NOB>
-__global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items) {
+__global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a) {
   constexpr int NG = LS32_NG;
   extern __shared__ __attribute__((aligned(16))) char smem_ls32[];
   // tt: thread of its team; wave: wave of its team (the row blocks / k-steps it owns are those of k_ls16's wave)
@@ -174,42 +162,36 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
   };
   auto gbase = [&](int gi) -> float* { return smf + gi * GSZ; };
   auto grp = [&](int gi) -> Grp { return grp_at(gbase(gi)); };
-  __shared__ float s_alpha[NG][LS32_C], s_obj[NG][LS32_C];
-  __shared__ int s_bi[NG][LS32_C], s_in[NG][LS32_C];
+  __shared__ float s_alpha[NG][LS_C], s_obj[NG][LS_C];
+  __shared__ int s_bi[NG][LS_C], s_in[NG][LS_C];
 
   const int cnt = *a.nitems;
-  if (cnt < min_items) return;                  // shorter work lists: k_ls16 / k_traj_rw (their launches return here)
-  const int b0 = blockIdx.x * (NG * LS32_C);
+  if (ls_round_form(cnt, a) != LS_FORM_32) return;
+  const int b0 = blockIdx.x * (NG * LS_C);
   if (b0 >= cnt) return;
-  if (tid < NG * LS32_C) {
-    const int it = min(b0 + tid, cnt - 1);
-    s_bi[tid >> 4][tid & 15] = a.item_b[it];
-    s_in[tid >> 4][tid & 15] = (b0 + tid) < cnt;
-    float al = a.alpha_0;
-    for (int k = a.item_k[it]; k > 0; --k) al *= 0.5f;
-    s_alpha[tid >> 4][tid & 15] = al;
-  }
+  if (tid < NG * LS_C)     // (the tables indexed [group][candidate], not as one flat array: see ls_terminal_cost)
+    ls_candidate(a, cnt, b0 + tid, &s_bi[tid >> 4][tid & 15], &s_in[tid >> 4][tid & 15], &s_alpha[tid >> 4][tid & 15]);
   constexpr int Lh = 3;
   const size_t mstride = (size_t)T * Lh * GMPC_MW;
   const float w0 = sigmoidf_(a.mpc_w[0]), w1 = sigmoidf_(a.mpc_w[1]), w2 = sigmoidf_(a.mpc_w[2]);
 
   // ---- weights: registers for the whole horizon.  Team A: layer 1 (row blocks wave, wave + 4, wave + 8; block 12 is
   // split over the waves by k-step, k-steps wave + 4 j, fragments in LDS) and layer 0; team B: layer 2.
-  float wr[3][LS32_KS];
+  float wr[3][LS_KS];
   {
     const float* Wl = a.dyn.W[team + 1];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       const int nn = 16 * (wave + 4 * r) + c16;
 #pragma unroll
-      for (int ks = 0; ks < LS32_KS; ++ks) wr[r][ks] = Wl[(size_t)(4 * ks + g) * LS32_KH + nn];
+      for (int ks = 0; ks < LS_KS; ++ks) wr[r][ks] = Wl[(size_t)(4 * ks + g) * LS_KH + nn];
     }
   }
   for (int hl = 0; hl < 2; ++hl) {
     const float* Wl = a.dyn.W[hl + 1];
     for (int e = tid; e < 52 * 32; e += LS32_THREADS) {
       const int ks = e >> 5, gg = (e >> 3) & 3, cc = e & 7;
-      wxl[hl * 52 * 32 + e] = ks < LS32_KS ? Wl[(size_t)(4 * ks + gg) * LS32_KH + 192 + cc] : 0.f;
+      wxl[hl * 52 * 32 + e] = ks < LS_KS ? Wl[(size_t)(4 * ks + gg) * LS_KH + 192 + cc] : 0.f;
     }
   }
   // One register set, two uses: team A keeps layer 0's fragments in it (w0r[r][ks] = shr[r K0S + ks], block 12's
@@ -224,36 +206,27 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
 #pragma unroll
       for (int ks = 0; ks < K0S; ++ks) {
         const int k = 4 * ks + g;
-        shr[r * K0S + ks] = k < n + m ? a.dyn.W[0][(size_t)k * LS32_KH + nn] : 0.f;
+        shr[r * K0S + ks] = k < n + m ? a.dyn.W[0][(size_t)k * LS_KH + nn] : 0.f;
       }
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int k = 4 * (wave + 4 * q) + g, nn = 192 + c16;
-      shr[3 * K0S + q] = (k < n + m && nn < LS32_KH) ? a.dyn.W[0][(size_t)k * LS32_KH + nn] : 0.f;
+      shr[3 * K0S + q] = (k < n + m && nn < LS_KH) ? a.dyn.W[0][(size_t)k * LS_KH + nn] : 0.f;
     }
   }
   // output layer (k-steps 13 wave + j of wave `wave`): fragments in LDS
   for (int e = tid; e < 4 * 13 * 64; e += LS32_THREADS) {
     const int l = e & 63, j = (e >> 6) % 13, wv = (e >> 6) / 13;
     const int ks = 13 * wv + j, no = l & 15;
-    wol[e] = (ks < LS32_KS && no < n) ? a.dyn.W[Lh][(size_t)(4 * ks + (l >> 4)) * n + no] : 0.f;
+    wol[e] = (ks < LS_KS && no < n) ? a.dyn.W[Lh][(size_t)(4 * ks + (l >> 4)) * n + no] : 0.f;
   }
   if constexpr (NOB > 1)
     for (int e = tid; e < 4 * 13 * 4 * NV8; e += LS32_THREADS) {
       const int cc = e % NV8, gg = (e / NV8) & 3, ks = e / (4 * NV8);      // ks = 13 wave + j
-      wol1[e] = (ks < LS32_KS && cc < NV) ? a.dyn.W[Lh][(size_t)(4 * ks + gg) * n + 16 + cc] : 0.f;
+      wol1[e] = (ks < LS_KS && cc < NV) ? a.dyn.W[Lh][(size_t)(4 * ks + gg) * n + 16 + cc] : 0.f;
     }
-  for (int e = tid; e < 3 * LS32_ROWS + 32; e += LS32_THREADS) {
-    float v = 0.f;
-    if (e < 3 * LS32_ROWS) {
-      const int l = e / LS32_ROWS, j = e - l * LS32_ROWS;
-      if (j < LS32_KH) v = a.dyn.b[l][j];
-    } else if (e - 3 * LS32_ROWS < n) {
-      v = a.dyn.b[Lh][e - 3 * LS32_ROWS];
-    }
-    bias_s[e] = v;
-  }
+  ls_fill_bias(bias_s, a.dyn, LS_KH, n, tid, LS32_THREADS);
   // every per-group buffer starts at zero (xcur rows >= n + m, activation rows 192.., mask words, dxs = x_0 - X_0)
   for (int e = tid; e < NG * GSZ; e += LS32_THREADS) smf[e] = 0.f;
   __syncthreads();
@@ -261,13 +234,13 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
   auto INB = [&](int gi, int c) -> bool { return s_in[gi][c] != 0; };
   // (candidate index; the per-step global accesses below index with 32-bit offsets from the uniform buffer pointers --
   // gmpc_ls32_shape checks that the buffers are that small -- so that an address costs one register, not two)
-  auto CI = [&](int gi, int c) -> unsigned { return (unsigned)(b0 + gi * LS32_C + c); };
+  auto CI = [&](int gi, int c) -> unsigned { return (unsigned)(b0 + gi * LS_C + c); };
   // ---- initial state: the nominal trajectory's x_0
   for (int gi = 0; gi < NG; ++gi) {
     float* xc = grp(gi).xcur;
-    for (int e = tid; e < LS32_C * n; e += LS32_THREADS) {
+    for (int e = tid; e < LS_C * n; e += LS32_THREADS) {
       const int c = e / n, i = e - c * n;
-      xc[ls32_at(i, c)] = a.X[(size_t)BI(gi, c) * (T + 1) * n + i];
+      xc[ls_at(i, c)] = a.X[(size_t)BI(gi, c) * (T + 1) * n + i];
     }
   }
 
@@ -277,7 +250,7 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
   // integer instructions per phase -- left to itself hipcc hoists some seventy such values out of the time loop and
   // spills them.  Kept: the (candidate, control) pair of the controls phase (a division by m).
   constexpr int PE = 2 * K0S;
-  const int cc = min((tt >> 1) / m, LS32_C - 1), cj = (tt >> 1) - ((tt >> 1) / m) * m;
+  const int cc = min((tt >> 1) / m, LS_C - 1), cj = (tt >> 1) - ((tt >> 1) / m) * m;
   constexpr int KQ = K0S == 4 ? 4 : 8;          // m n <= 16 KQ
   static_assert(KQ + 4 <= 3 * K0S + 2, "the operand registers share layer 0's");
 #define LS32_LANE()                                                                                   \
@@ -311,7 +284,7 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
     for (int q = 0; q < KQ; ++q) kd[16 * q] = shr[q];
     if (kl < 8) {
       G.kUs[kc * 8 + kl] = shr[KQ];
-      G.kUs[LS32_C * 8 + kc * 8 + kl] = shr[KQ + 1];
+      G.kUs[LS_C * 8 + kc * 8 + kl] = shr[KQ + 1];
     }
   };
   // step 0's operands of both groups
@@ -333,20 +306,15 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
   const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(a.maskc, 0, 0x7FFFFFF0, 0x00020000);
   // (LDS-only barrier: the global stores of a phase are not read inside the horizon)
 #define LS32_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#ifdef GMPC_TRAJ_STAMPS
-  // diagnostic build: cycles per half-step spent in each of the four segments (work) and at its barrier (wait)
-  unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp_ = __builtin_readcyclecounter();
-#define TS_(i) { const unsigned long long t_ = __builtin_readcyclecounter(); st_[i] += t_ - tp_; tp_ = t_; }
-#else
-#define TS_(i)
-#endif
+  // (diagnostic build: cycles per half-step spent in each of the four segments (work) and at its barrier (wait))
+  TS_BEGIN();
 #define LS32_SEG_END(i) do { TS_(2 * (i)) LS32_BAR(); TS_(2 * (i) + 1) } while (0)
   // ================= the six phases of a group's step (gb: the group's region; tb: the shared tables) =================
   auto phaseC = [&](int gi, float* gb, int t) __attribute__((always_inline)) {
     const Grp G = grp_at(gb);
     LS32_LANE();
     const int cp = tq >> 1, chalf = tq & 1;
-    const bool con = cp < LS32_C * m;
+    const bool con = cp < LS_C * m;
     // (lanes without a (candidate, control) pair run the same instructions on pair 0's operands and store nowhere)
     const float* kcb = G.Ks + (con ? cc * LY::MNX + cj * n : 0) + chalf;
     const float* dcb = G.dxs + chalf * 16 + cc;
@@ -354,16 +322,16 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
 #pragma unroll
     for (int e = 0; e < PE; ++e) {
       // row i = chalf + 2 e of dxs: group e / 2, row (e & 1) 2 + chalf of the group
-      const float dx = dcb[(e >> 1) * LS32_GS + (e & 1) * 32];
+      const float dx = dcb[(e >> 1) * LS_GS + (e & 1) * 32];
       du = fmaf(kcb[2 * e], chalf + 2 * e < n ? dx : 0.f, du);
     }
     du += __shfl_xor(du, 1);
     const int cq = cc * 8 + cj;
-    const float u = G.kUs[LS32_C * 8 + cq] + fmaf(s_alpha[gi][cc], G.kUs[cq], du);
+    const float u = G.kUs[LS_C * 8 + cq] + fmaf(s_alpha[gi][cc], G.kUs[cq], du);
     if (con && chalf == 0) {
       ls32_store_if(rsU, (CI(gi, cc) * (unsigned)T + (unsigned)t) * (unsigned)m + (unsigned)cj, __float_as_uint(u),
-                    b0 + gi * LS32_C + cc < cnt);
-      G.xcur[ls32_at(n + cj, cc)] = u;
+                    b0 + gi * LS_C + cc < cnt);
+      G.xcur[ls_at(n + cj, cc)] = u;
     }
   };
   auto phaseL0 = [&](float* gb, const float* tb) __attribute__((always_inline)) {
@@ -378,19 +346,19 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
     }
     float bf[K0S];
 #pragma unroll
-    for (int ks = 0; ks < K0S; ++ks) bf[ks] = G.xcur[ks * LS32_GS + lane];
-    const float* xw = G.xcur + ls32_opq(wave * LS32_GS + lane);
-    const float bx0 = xw[0], bx1 = xw[4 * LS32_GS];
+    for (int ks = 0; ks < K0S; ++ks) bf[ks] = G.xcur[ks * LS_GS + lane];
+    const float* xw = G.xcur + ls32_opq(wave * LS_GS + lane);
+    const float bx0 = xw[0], bx1 = xw[4 * LS_GS];
 #pragma unroll
     for (int ks = 0; ks < K0S; ++ks)
 #pragma unroll
-      for (int r = 0; r < 3; ++r) d[r] = ls32_mfma(shr[r * K0S + ks], bf[ks], d[r]);
-    dx = ls32_mfma(shr[3 * K0S], bx0, dx);
-    dx = ls32_mfma(shr[3 * K0S + 1], bx1, dx);
+      for (int r = 0; r < 3; ++r) d[r] = ls_mfma(shr[r * K0S + ks], bf[ks], d[r]);
+    dx = ls_mfma(shr[3 * K0S], bx0, dx);
+    dx = ls_mfma(shr[3 * K0S + 1], bx1, dx);
     {
-      const int ob = ls32_opq((4 * wave + g) * LS32_GS + c16), mo = ls32_opq(c16 * 96 + 2 * wave + (g >> 1));
+      const int ob = ls32_opq((4 * wave + g) * LS_GS + c16), mo = ls32_opq(c16 * 96 + 2 * wave + (g >> 1));
 #pragma unroll
-      for (int r = 0; r < 3; ++r) ls32_epilogue(d[r], G.actA + ob + 16 * r * LS32_GS, G.mask + mo + 8 * r, lane);
+      for (int r = 0; r < 3; ++r) ls32_epilogue(d[r], G.actA + ob + 16 * r * LS_GS, G.mask + mo + 8 * r, lane);
     }
     if (lane < 32) {
       float* pl = G.p12 + ls32_opq(wave * 128 + lane);
@@ -408,29 +376,29 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
     const float* wxl = tb + LY::WXL;
     const float* hin = hl == 0 ? G.actA : G.actB;
     float* hout = hl == 0 ? G.actB : G.actA;
-    const float2 tail = ls32_tail(G.p12 + (hl & 1) * 512, bias_s + hl * LS32_ROWS + 192, G.mask + hl * 32, lane);
+    const float2 tail = ls32_tail(G.p12 + (hl & 1) * 512, bias_s + hl * LS_ROWS + 192, G.mask + hl * 32, lane);
     f32x4_t d[3], dx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      const float4 bv = *reinterpret_cast<const float4*>(bias_s + (hl + 1) * LS32_ROWS + 16 * (wave + 4 * r) + 4 * g);
+      const float4 bv = *reinterpret_cast<const float4*>(bias_s + (hl + 1) * LS_ROWS + 16 * (wave + 4 * r) + 4 * g);
       d[r] = f32x4_t{bv.x, bv.y, bv.z, bv.w};
     }
     // chunks of 4 k-steps, operands of chunk j + 1 read while chunk j multiplies: 4 B fragments, and the A / B
     // fragments of this wave's block-12 k-step 4 j + wave
     const float* wx = wxl + hl * 52 * 32 + ls32_opq(wave * 32 + g * 8 + (c16 & 7));
-    const float* hx = hin + ls32_opq(wave * LS32_GS + lane);
+    const float* hx = hin + ls32_opq(wave * LS_GS + lane);
     float bq[2][4], ax[2], bx[2];
     auto load_chunk = [&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int ks = 4 * j + e;
-        if (ks < 48) bq[j & 1][e] = hin[ks * LS32_GS + lane];
+        if (ks < 48) bq[j & 1][e] = hin[ks * LS_GS + lane];
       }
       // (lanes c16 >= 8 read the fragment of lane c16 - 8: rows 200 .. 207 of the product come out as copies of rows
       // 192 .. 199 and are never stored)
       ax[j & 1] = wx[4 * j * 32];
-      if (j < 12) bx[j & 1] = hx[4 * j * LS32_GS];
+      if (j < 12) bx[j & 1] = hx[4 * j * LS_GS];
     };
     load_chunk(std::integral_constant<int, 0>{});
     rw_static_for<13>([&](auto jc) __attribute__((always_inline)) {
@@ -444,22 +412,22 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
       rw_static_for<4>([&](auto ec) __attribute__((always_inline)) {
         constexpr int e = decltype(ec)::value;
         constexpr int ks = 4 * j + e;
-        if constexpr (ks < LS32_KS) {
-          d[0] = ls32_mfma(wr[0][ks], bq[j & 1][e], d[0]);
-          d[1] = ls32_mfma(wr[1][ks], bq[j & 1][e], d[1]);
-          d[2] = ls32_mfma(wr[2][ks], bq[j & 1][e], d[2]);
+        if constexpr (ks < LS_KS) {
+          d[0] = ls_mfma(wr[0][ks], bq[j & 1][e], d[0]);
+          d[1] = ls_mfma(wr[1][ks], bq[j & 1][e], d[1]);
+          d[2] = ls_mfma(wr[2][ks], bq[j & 1][e], d[2]);
         }
-        if constexpr (e == 1) dx = ls32_mfma(ax[j & 1], bx[j & 1], dx);
+        if constexpr (e == 1) dx = ls_mfma(ax[j & 1], bx[j & 1], dx);
       });
       __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);                 // the next chunk's LDS reads
       __builtin_amdgcn_sched_group_barrier(0x008, j < 12 ? 13 : 7, 0);   // this chunk's MFMAs
       if constexpr (j == 6) LS32_SEG_END(hl == 0 ? 2 : 0);
     });
     {
-      const int ob = ls32_opq((4 * wave + g) * LS32_GS + c16), mo = ls32_opq(c16 * 96 + 2 * wave + (g >> 1));
+      const int ob = ls32_opq((4 * wave + g) * LS_GS + c16), mo = ls32_opq(c16 * 96 + 2 * wave + (g >> 1));
 #pragma unroll
       for (int r = 0; r < 3; ++r)
-        ls32_epilogue(d[r], hout + ob + 16 * r * LS32_GS, G.mask + (hl + 1) * 32 + mo + 8 * r, lane);
+        ls32_epilogue(d[r], hout + ob + 16 * r * LS_GS, G.mask + (hl + 1) * 32 + mo + 8 * r, lane);
     }
     if (lane < 32) {
       float* pl = G.p12 + ((hl + 1) & 1) * 512 + ls32_opq(wave * 128 + lane);
@@ -475,17 +443,17 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
     const float* wol = tb + LY::WOL;
     const float* wol1 = tb + LY::WOL1;
     const float* hin = G.actA;
-    const float2 tail = ls32_tail(G.p12, bias_s + 2 * LS32_ROWS + 192, G.mask + 2 * 32, lane);
+    const float2 tail = ls32_tail(G.p12, bias_s + 2 * LS_ROWS + 192, G.mask + 2 * 32, lane);
     f32x4_t d[NOB];
 #pragma unroll
     for (int blk = 0; blk < NOB; ++blk) d[blk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float bf[13], wo[NOB][13];
-    const float* hl_ = hin + ls32_opq(13 * wave * LS32_GS + lane);                   // (52 groups)
+    const float* hl_ = hin + ls32_opq(13 * wave * LS_GS + lane);                     // (52 groups)
     const float* wl_ = wol + ls32_opq(wave * 13 * 64 + lane);
     const float* w1_ = wol1 + ls32_opq((wave * 13 * 4 + g) * NV8 + (c16 & 7));
 #pragma unroll
     for (int j = 0; j < 13; ++j) {
-      bf[j] = hl_[j * LS32_GS];
+      bf[j] = hl_[j * LS_GS];
       wo[0][j] = wl_[j * 64];
       if (NOB > 1) wo[NOB - 1][j] = w1_[j * 4 * NV8];                               // (rows >= 24: copies, never read)
     }
@@ -494,7 +462,7 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
 #pragma unroll
     for (int j = 0; j < 13; ++j)
 #pragma unroll
-      for (int blk = 0; blk < NOB; ++blk) d[blk] = ls32_mfma(wo[blk][j], bf[j], d[blk]);
+      for (int blk = 0; blk < NOB; ++blk) d[blk] = ls_mfma(wo[blk][j], bf[j], d[blk]);
     float* pl = G.part + ls32_opq(wave * NOB * 256 + lane);
 #pragma unroll
     for (int blk = 0; blk < NOB; ++blk)
@@ -508,14 +476,14 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
     const Grp G = grp_at(gb);
     LS32_LANE();
     const float* part = G.part;
-    const unsigned ci0 = (unsigned)(b0 + gi * LS32_C);                 // first candidate of the group
+    const unsigned ci0 = (unsigned)(b0 + gi * LS_C);                   // first candidate of the group
     const unsigned left = (unsigned)max(cnt - (int)ci0, 0);           // candidates of the group that exist
     // thread (wave i, lane (g, c)) owns coordinate 4 g + i of candidate c (output block 0); threads < 16 (n - 16) also
     // own coordinate 16 + tq / 16 of candidate tq & 15 (output block 1)
     const int no1 = 4 * g + wave, q2 = tq >> 4;
     const bool on1 = no1 < n, on2 = NOB > 1 && 16 + q2 < n;
-    const int x1 = ls32_at(no1, c16), x2 = ls32_at(on2 ? 16 + q2 : 0, c16);
-    const float bo1 = tb[LY::BIAS + 3 * LS32_ROWS + no1];                            // (0 past n)
+    const int x1 = ls_at(no1, c16), x2 = ls_at(on2 ? 16 + q2 : 0, c16);
+    const float bo1 = tb[LY::BIAS + 3 * LS_ROWS + no1];                              // (0 past n)
     // (coordinates past n: the same sums on in-range addresses, stored nowhere)
     const float v1 = (((part[tq] + part[NOB * 256 + tq]) + (part[2 * NOB * 256 + tq] + part[3 * NOB * 256 + tq])) + bo1) + G.xcur[x1];
     const unsigned xo = ((ci0 + (unsigned)c16) * (unsigned)(T + 1) + (unsigned)(t + 1)) * (unsigned)n;
@@ -527,7 +495,7 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
     ls32_store_if(rsX, xo + (unsigned)no1, __float_as_uint(v1), in16 && on1);
     if constexpr (NOB > 1) {
       const int pi2 = 256 + (q2 & 3) * 64 + 16 * ((q2 >> 2) & 3) + c16;
-      const float bo2 = tb[LY::BIAS + 3 * LS32_ROWS + 16 + q2];
+      const float bo2 = tb[LY::BIAS + 3 * LS_ROWS + 16 + q2];
       const float v2 = (((part[pi2] + part[NOB * 256 + pi2]) + (part[2 * NOB * 256 + pi2] + part[3 * NOB * 256 + pi2])) + bo2) + G.xcur[x2];
       if (on2) {
         G.xcur[x2] = v2;
@@ -543,7 +511,7 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
       const unsigned mc1 = (unsigned)tq / 24u, mc2 = (unsigned)(tq + 256) / 24u;      // (mc2 > 15: past the block)
       ls32_store_if(rsM, tw + mc1 * (ms - 24u) + (unsigned)tq, img[tq], mc1 < left);   // (mc1 <= 10)
       ls32_store_if(rsM, tw + mc2 * (ms - 24u) + (unsigned)(tq + 256), img[(tq + 256) & 511],
-                    mc2 < (unsigned)LS32_C && mc2 < left);
+                    mc2 < (unsigned)LS_C && mc2 < left);
     }
   };
 
@@ -602,160 +570,40 @@ __global__ __launch_bounds__(LS32_THREADS) void k_ls32(TrajArgs a, int min_items
 #endif
   __syncthreads();
 
-  // ---- stage costs (team = group): 4 lanes per (candidate, step) pair, 64 pairs per sweep; summed per candidate in
-  // step order
-  {
-    const int gi = team;
-    const Grp G = grp(gi);
-    float* cst = G.actB;
-    const float al = GMPC_ALPHA;
-    const int q = tt & 3;
-    for (int p = tt >> 2; p < LS32_C * T; p += 64) {
-      const int c = p / T, t = p - c * T;
-      const int bc = BI(gi, c);
-      const size_t ci = INB(gi, c) ? (size_t)CI(gi, c) : 0;  // (unused candidates read item 0's rows: in bounds, discarded)
-      const float* xr = t > 0 ? a.Xc + (ci * (T + 1) + t) * n : a.X + (size_t)bc * (T + 1) * n;
-      const float* ur = a.Uc + (ci * T + t) * m;
-      const float* gl = a.goal + ((size_t)bc * (T + 1) + t) * n;
-      float xv[8], gv[8], uv[2];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int i = min(q + 4 * e, n - 1);
-        xv[e] = xr[i];
-        gv[e] = gl[i];
-      }
-#pragma unroll
-      for (int e = 0; e < 2; ++e) uv[e] = ur[min(q + 4 * e, m - 1)];
-      float dd = 0.f, uu = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float dx = q + 4 * e < n ? xv[e] - gv[e] : 0.f;
-        dd = fmaf(dx, dx, dd);
-      }
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const float u = q + 4 * e < m ? uv[e] : 0.f;
-        uu = fmaf(u, u, uu);
-      }
-      dd += __shfl_xor(dd, 1); dd += __shfl_xor(dd, 2);
-      uu += __shfl_xor(uu, 1); uu += __shfl_xor(uu, 2);
-      if (q == 0) cst[p] = INB(gi, c) ? w0 * (sqrtf(uu + al * al) - al) + w1 * (sqrtf(dd + al * al) - al) : 0.f;
-    }
-  }
+  // ---- after the horizon (team = group; gmpc_ls_common.h): stage costs in the group's actB, summed per candidate in
+  // step order, then the terminal cost network
+  const int gi = team;
+  const Grp G = grp(gi);
+  auto INBg = [&](int c) -> bool { return INB(gi, c); };
+  auto CIg = [&](int c) -> unsigned { return CI(gi, c); };
+  ls_stage_costs(a, tt, w0, w1, G.actB, [&](int c) -> int { return BI(gi, c); }, INBg, CIg);
   __syncthreads();
-  if (tid < NG * LS32_C) {
-    const float* cst = smf + (tid >> 4) * GSZ + LY::ACTB + (tid & 15) * T;      // group's actB
-    float acc = 0.f;
-    for (int t = 0; t < T; ++t) acc += cst[t];
-    s_obj[tid >> 4][tid & 15] = acc;
-  }
+  if (tid < NG * LS_C) s_obj[tid >> 4][tid & 15] = ls_cost_sum(smf + (tid >> 4) * GSZ + LY::ACTB + (tid & 15) * T, T);
   __syncthreads();            // (the stage costs have been read: actB is a layer buffer again)
-  // ---- terminal cost w2 |cost_mlp(x_T)|^2 on the matrix pipe as well (team = group): activations [k][16] in actA /
-  // actB, weight fragments straight from global memory (row blocks nb = wave, wave + 4, ..)
-  {
-    const int gi = team;
-    const Grp G = grp(gi);
-    float* in = G.actA;
-    float* out = G.actB;
-    for (int e = tt; e < LS32_C * ((n + 3) & ~3); e += 256) {
-      const int i = e >> 4, c = e & 15;
-      in[ls32_at(i, c)] = i < n ? G.xcur[ls32_at(i, c)] : 0.f;
-    }
-    __syncthreads();
-    const int Lc = a.cost.L - 1;
-    for (int l = 0; l <= Lc; ++l) {
-      const int fi = a.cost.dims[l], fo = a.cost.dims[l + 1];
-      const float* W = a.cost.W[l];
-      const float* bv = a.cost.b[l];
-      const int nks = (fi + 3) >> 2;
-      for (int nb = wave; 16 * nb < fo; nb += 4) {
-        const int col = 16 * nb + c16;
-        const bool colok = col < fo;
-        f32x4_t acc;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = 16 * nb + 4 * g + i < fo ? bv[16 * nb + 4 * g + i] : 0.f;
-        const float* wp = W + (colok ? col : 0);
-        for (int k0 = 0; k0 < nks; k0 += 8) {        // 8 fragments in flight (k-steps past the last: zero weights)
-          float wv[8], bq[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int ks = min(k0 + e, nks - 1), k = 4 * ks + g;
-            const float w = wp[(size_t)min(k, fi - 1) * fo];
-            wv[e] = (k0 + e < nks && k < fi && colok) ? w : 0.f;
-            bq[e] = in[ks * LS32_GS + lane];
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc = ls32_mfma(wv[e], bq[e], acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float v = l < Lc ? fmaxf(acc[i], 0.f) : acc[i];
-          if (16 * nb + 4 * g + i >= fo) v = 0.f;
-          out[(4 * nb + g) * LS32_GS + i * 16 + c16] = v;
-        }
-      }
-      __syncthreads();
-      float* tmp = in; in = out; out = tmp;
-    }
-    if (tt < LS32_C && INB(gi, tt)) {
-      const int fo = a.cost.dims[Lc + 1];
-      float yy = 0.f;
-      for (int r = 0; r < fo; ++r) {
-        const float y = in[ls32_at(r, tt)];
-        yy = fmaf(y, y, yy);
-      }
-      a.objc[CI(gi, tt)] = s_obj[gi][tt] + w2 * yy;
-    }
-  }
+  ls_terminal_cost(a, tt, wave, lane, w2, G.xcur, G.actA, G.actB, s_obj[gi], INBg, CIg);
 }
 
 // ---- host side --------------------------------------------------------------------------------------
 static size_t ls32_lds(int n, int m) {
-  const int k0s = (n + m + 3) / 4;
-  const int fl = n > 16 ? Ls32Lay<6, 2>::TOTAL : k0s <= 4 ? Ls32Lay<4, 1>::TOTAL : Ls32Lay<6, 1>::TOTAL;
+  int fl = 0;
+  ls_pick_k0s_nob(n, m, [&](auto k0s, auto nob) { fl = Ls32Lay<decltype(k0s)::value, decltype(nob)::value>::TOTAL; });
   return (size_t)fl * sizeof(float);
 }
 // shapes k_ls32 is instantiated for: k_ls16's with at most 8 rows in output block 1, a gain block that fits its LDS
 // slot, stage costs that fit an activation buffer and candidate buffers a 32-bit index reaches
 bool gmpc_ls32_shape(const TrajArgs& a) {
-  const char* e = getenv("GMPC_LS");        // read per call: the tests switch forms inside one process
-  if (e != nullptr && (strcmp(e, "rw") == 0 || strcmp(e, "ls16") == 0)) return false;
-  if (!gmpc_ls16_shape(a) || a.dyn.dims[1] != LS32_KH) return false;      // (the 200-wide form only)
+  if (!gmpc_ls16_shape(a) || a.dyn.dims[1] != LS_KH) return false;        // (the 200-wide form only)
   const int k0s = (a.n + a.m + 3) / 4;
   const long items = (long)a.B * GMPC_LS_ITEMS;
   return a.n <= 24 && a.m * a.n <= (k0s <= 4 && a.n <= 16 ? 64 : 128) && ls32_lds(a.n, a.m) <= LS32_LDS_MAX &&
-         LS32_C * a.T <= LS32_ACT && items * (a.T + 1) * a.n < (1L << 31) && items * a.T * 3 * GMPC_MW < (1L << 31);
-}
-// work lists of at least this many candidates are k_ls32's: more than one pass of k_ls16 over the 256 CUs (4096
-// candidates).  Measured in round 4 at C3 (profiles/EXPERIMENTS.md): the 8192 candidates of a first round take one pass
-// of this kernel 0.79 ms against 0.92 ms for two passes of k_ls16; a list of 4096 or fewer is one k_ls16 pass (0.46 ms)
-// and would be half a chip of this kernel for 0.79 ms.  GMPC_LS32_SPLIT overrides the threshold (0: never; the tests
-// set 1 to send every round here).
-int gmpc_ls32_split() {
-  const char* e = getenv("GMPC_LS32_SPLIT");
-  return e != nullptr ? atoi(e) : 4097;
+         LS_C * a.T <= LS32_ACT && items * (a.T + 1) * a.n < (1L << 31) && items * a.T * 3 * GMPC_MW < (1L << 31);
 }
 
-template <int K0S, int NOB>
-static void ls32_launch(const TrajArgs& a, int grid, int min_items, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ls32<K0S, NOB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LS32_LDS_MAX);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  hipLaunchKernelGGL((k_ls32<K0S, NOB>), dim3(grid), dim3(LS32_THREADS), ls32_lds(a.n, a.m), s, a, min_items);
-}
-
-void gmpc_launch_ls32(const TrajArgs& a, long max_items, int min_items, hipStream_t s) {
-  const int per = LS32_NG * LS32_C;
+void gmpc_launch_ls32(const TrajArgs& a, long max_items, hipStream_t s) {
+  const int per = LS32_NG * LS_C;
   const int grid = (int)((max_items + per - 1) / per);
-  const int k0s = (a.n + a.m + 3) / 4;
-  if (a.n <= 16) {
-    if (k0s <= 4) ls32_launch<4, 1>(a, grid, min_items, s);
-    else ls32_launch<6, 1>(a, grid, min_items, s);
-  } else {
-    ls32_launch<6, 2>(a, grid, min_items, s);
-  }
+  ls_pick_k0s_nob(a.n, a.m, [&](auto k0s, auto nob) {
+    ls_launch<&k_ls32<decltype(k0s)::value, decltype(nob)::value>>(LS32_LDS_MAX, grid, LS32_THREADS, ls32_lds(a.n, a.m), s,
+                                                                    a);
+  });
 }

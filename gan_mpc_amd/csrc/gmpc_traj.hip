@@ -1,7 +1,7 @@
-// Sequential-in-time trajectory kernels: rollout + cost, and the DDP line search.  This file holds the
-// general (any network shape) VALU form, the line-search bookkeeping kernels and the launchers; the
-// reference's default dynamics network (3 x 200) takes the register-weight MFMA form of
-// gmpc_traj_rw.hip.
+// Sequential-in-time trajectory kernels: rollout + cost, and the candidates of the DDP line search.  This file holds
+// the general (any network shape) VALU form, the mask-only forward pass and their launchers; the reference's default
+// dynamics network (3 x 200) takes the register-weight MFMA form of gmpc_traj_rw.hip, and the line search's rounds
+// (work list, decide, commit, and which kernel evaluates a round) are gmpc_linesearch.hip.
 //
 // One 256-thread workgroup owns GMPC_TB = 4 trajectories for the whole horizon.  The state and
 // control of the current step live in LDS as float4 (one component per trajectory), every layer is
@@ -13,6 +13,7 @@
 // cost/nn.py:23-29, trajax rollout / evaluate / ddp_rollout / line_search_ddp as called from
 // policy/optimizers.py:19,26-29,55.
 #include "gmpc_traj_layers.h"
+#include "gmpc_ls_common.h"
 #include "gmpc_launch.h"
 
 #ifndef GMPC_TRAJ_MINW
@@ -44,12 +45,7 @@ __global__ __launch_bounds__(GMPC_TRAJ_THREADS, GMPC_TRAJ_MINW) void k_traj(Traj
     const int cnt = *a.nitems;
     if (b0 >= cnt) return;
     if (tid < GMPC_TB) {
-      const int it = min(b0 + tid, cnt - 1);
-      s_bi[tid] = a.item_b[it];
-      s_in[tid] = (b0 + tid) < cnt;
-      float al = a.alpha_0;
-      for (int k = a.item_k[it]; k > 0; --k) al *= 0.5f;
-      s_alpha[tid] = al;
+      ls_candidate(a, cnt, b0 + tid, &s_bi[tid], &s_in[tid], &s_alpha[tid]);
       // the objective to beat: stage and terminal costs are non-negative, so a candidate whose
       // running sum has reached it can no longer be accepted (NaN compares false: dead as well)
       float oo = a.obj[s_bi[tid]];
@@ -106,12 +102,7 @@ __global__ __launch_bounds__(GMPC_TRAJ_THREADS, GMPC_TRAJ_MINW) void k_traj(Traj
     float gnext = 0.f;
     if (n <= 64 && wave < GMPC_TB && lane < n) gnext = a.goal[(size_t)BI(wave) * (T + 1) * n + lane];
     __syncthreads();
-#ifdef GMPC_TRAJ_STAMPS
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp_ = __builtin_readcyclecounter();
-#define TS_(i) { const unsigned long long t_ = __builtin_readcyclecounter(); st_[i] += t_ - tp_; tp_ = t_; }
-#else
-#define TS_(i)
-#endif
+    TS_BEGIN();
 
     bool aborted = false;
     for (int t = 0; t < T; ++t) {
@@ -268,165 +259,6 @@ __global__ __launch_bounds__(GMPC_TRAJ_THREADS, GMPC_TRAJ_MINW) void k_traj(Traj
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Round-based backtracking line search (trajax line_search_ddp: alpha = alpha_0, alpha_0/2, ... while
-// alpha > alpha_min, the first candidate whose objective decreases is taken).  The halvings of one
-// trajectory are independent rollouts, so a round evaluates several of them speculatively
-// (k_traj<true> over a work list of (trajectory, halving count) candidates) and k_ls_decide picks,
-// per trajectory, the LARGEST accepted step of the round -- the candidate the sequential loop would
-// have stopped at -- commits it, or queues the next 4 halvings (8 from the third round on).  The first round of a trajectory
-// covers the halvings up to the one its previous line search accepted (1 candidate for a
-// well-conditioned problem that takes full steps, up to 8 for one that backtracks deeply), so the
-// rollouts stay close to the sequential loop's count while the launches drop from up to 15
-// dependent rollouts to 1-3 rounds.  Nothing is read back by the host.
-// ------------------------------------------------------------------------------------------------
-#define GMPC_LS_NEXT 4   // candidates queued per trajectory after a round without an accepted step
-
-__global__ void k_ls_init(int B, const int* active, float alpha_0, float alpha_min, int k_max, int first_min, int* iters,
-                          int* run, int* cnt, int* kfirst, const int* prevk, float* alpha, float* U_step,
-                          float* obj_step) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  cnt[b] = 0;
-  if (active != nullptr && active[b] == 0) { run[b] = 0; return; }
-  iters[b] += 1;
-  if (alpha_0 > alpha_min) {
-    int R = prevk[b] + 1;
-    R = R < first_min ? first_min : R;      // (first_min >= 1: see gmpc_launch_linesearch)
-    R = R > GMPC_LS_ITEMS ? GMPC_LS_ITEMS : R;
-    R = R > k_max ? k_max : R;
-    run[b] = 1;
-    cnt[b] = R;
-    kfirst[b] = 0;
-  } else {
-    run[b] = 0;
-    alpha[b] = alpha_0;
-    U_step[b] = 0.f;
-    obj_step[b] = 0.f;
-  }
-}
-
-// Work list of a round, ordered by candidate number first and trajectory second: the four slots of a
-// k_traj<true> workgroup then hold the SAME halving count of four trajectories.  Large steps are
-// rejected early in the horizon (their running cost passes the objective to beat within a few
-// steps), and a workgroup whose four candidates are all dead stops -- which only happens when
-// candidates of similar fate sit together.  One workgroup; cnt[b] candidates for trajectory b.
-__global__ __launch_bounds__(1024) void k_ls_place(int B, const int* cnt, const int* kfirst, int* item_b,
-                                                   int* item_k, int* slot, int* count, int* total,
-                                                   int* round_total) {
-  __shared__ int s_n[GMPC_LS_ITEMS], s_base[GMPC_LS_ITEMS], s_fill[GMPC_LS_ITEMS];
-  const int tid = threadIdx.x;
-  if (tid < GMPC_LS_ITEMS) { s_n[tid] = 0; s_fill[tid] = 0; }
-  __syncthreads();
-  for (int b = tid; b < B; b += blockDim.x) {
-    const int c = cnt[b];
-    for (int j = 0; j < c; ++j) atomicAdd(&s_n[j], 1);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int j = 0; j < GMPC_LS_ITEMS; ++j) { s_base[j] = acc; acc += s_n[j]; }
-    *count = acc;
-    *total += acc;          // candidate rollouts since the solve began (one workgroup: no race)
-    *round_total += acc;
-  }
-  __syncthreads();
-  for (int b = tid; b < B; b += blockDim.x) {
-    const int c = cnt[b], k0 = kfirst[b];
-    for (int j = 0; j < c; ++j) {
-      const int pos = s_base[j] + atomicAdd(&s_fill[j], 1);
-      item_b[pos] = b;
-      item_k[pos] = k0 + j;
-      slot[b * GMPC_LS_ITEMS + j] = pos;
-    }
-  }
-}
-
-struct LsDecideArgs {
-  int n, m, T, Lh, k_max;
-  int next;              // candidates queued for the next round when this one accepts nothing
-  float alpha_0;
-  const int* slot; int* cnt; int* kfirst; int* prevk; int* run;
-  const float* objc; const float* Xc; const float* Uc; const uint32_t* maskc;
-  float* X; float* U; uint32_t* masks;
-  float* obj; float* obj_step; float* U_step; float* alpha;
-  int* stats;            // LsWork::counts + GMPC_LS_ROUNDS_MAX + 1
-};
-
-__global__ __launch_bounds__(GMPC_THREADS) void k_ls_decide(LsDecideArgs a) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  if (a.run[b] == 0) return;
-  __shared__ int s_acc;
-  __shared__ float s_us[GMPC_THREADS / 64];
-  const int* sl = a.slot + (size_t)b * GMPC_LS_ITEMS;
-  __shared__ int s_item;
-  if (tid == 0) {
-    float oo = a.obj[b];
-    if (isnan(oo)) oo = INFINITY;
-    const int R = a.cnt[b], k0 = a.kfirst[b];
-    int acc = -1;
-    float on_acc = 0.f;
-    for (int j = 0; j < R; ++j) {
-      float on = a.objc[sl[j]];
-      if (isnan(on)) on = oo;
-      if (on < oo) { acc = j; on_acc = on; break; }
-    }
-    s_item = acc >= 0 ? sl[acc] : 0;
-    auto halved = [&](int k) { float al = a.alpha_0; for (; k > 0; --k) al *= 0.5f; return al; };
-    if (acc >= 0) {
-      a.obj[b] = on_acc;
-      a.obj_step[b] = fabsf(on_acc - oo);
-      a.alpha[b] = halved(k0 + acc + 1);
-      a.prevk[b] = k0 + acc;
-      a.run[b] = 0;
-      a.cnt[b] = 0;
-      atomicAdd(a.stats + min(k0 + acc, 15), 1);
-      atomicMax(a.stats + 17, k0 + acc);       // deepest halving accepted since the solve began
-    } else if (k0 + R >= a.k_max) {      // every step size down to alpha_min failed
-      a.alpha[b] = halved(a.k_max);
-      a.U_step[b] = 0.f;
-      a.obj_step[b] = 0.f;
-      a.prevk[b] = a.k_max - 1;
-      a.run[b] = 0;
-      a.cnt[b] = 0;
-      atomicAdd(a.stats + 16, 1);
-    } else {                               // queue the next GMPC_LS_NEXT halvings (k_ls_place)
-      // (round 4, measured and not kept: a second round that reaches the deepest halving any trajectory of the batch
-      // has accepted so far -- the third round it was meant to remove only exists in a solve's first iteration, and
-      // the longer second round cost 0.2 ms per iteration)
-      const int left = a.k_max - (k0 + R);
-      a.cnt[b] = left < a.next ? left : a.next;
-      a.kfirst[b] = k0 + R;
-    }
-    s_acc = acc;
-  }
-  __syncthreads();
-  const int acc = s_acc;
-  if (acc < 0) return;
-  // commit the accepted candidate as the new iterate
-  const size_t it = (size_t)s_item;
-  const int n = a.n, m = a.m, T = a.T;
-  float* Xd = a.X + (size_t)b * (T + 1) * n;
-  const float* Xs = a.Xc + it * (T + 1) * n;
-  for (int e = n + tid; e < (T + 1) * n; e += blockDim.x) Xd[e] = Xs[e];
-  float us = 0.f;
-  float* Ud = a.U + (size_t)b * T * m;
-  const float* Us = a.Uc + it * T * m;
-  for (int e = tid; e < T * m; e += blockDim.x) {
-    const float un = Us[e], d = un - Ud[e];
-    us = fmaf(d, d, us);
-    Ud[e] = un;
-  }
-  const size_t mw = (size_t)T * a.Lh * GMPC_MW;
-  uint32_t* Md = a.masks + (size_t)b * mw;
-  const uint32_t* Ms = a.maskc + it * mw;
-  for (size_t e = tid; e < mw; e += blockDim.x) Md[e] = Ms[e];
-  us = wave_sum(us);
-  if ((tid & 63) == 0) s_us[tid >> 6] = us;
-  __syncthreads();
-  if (tid == 0) a.U_step[b] = sqrtf((s_us[0] + s_us[1]) + (s_us[2] + s_us[3]));
-}
-
 // Forward pass at given (x, u) pairs, masks only: used when gmpc_lqr_backward is handed a
 // trajectory that did not come from this context's rollout.  4 samples per workgroup.
 __global__ __launch_bounds__(GMPC_THREADS) void k_masks(int NS, int n, int m, int T, MlpDesc dyn,
@@ -465,12 +297,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_masks(int NS, int n, int m, in
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-static int traj_aw(int n, int m, const MlpDesc& d1, const MlpDesc* d2) {
-  int w = n + m > GMPC_THREADS ? n + m : GMPC_THREADS;
-  for (int l = 0; l <= d1.L; ++l) w = d1.dims[l] > w ? d1.dims[l] : w;
-  if (d2) for (int l = 0; l <= d2->L; ++l) w = d2->dims[l] > w ? d2->dims[l] : w;
-  return (w + 3) & ~3;
-}
+// (traj_aw, the activation width both forms size their LDS with: gmpc_traj_layers.h)
 static size_t traj_lds(TrajArgs& a) {
   a.aw = traj_aw(a.n, a.m, a.dyn, &a.cost);
   a.pw = a.n > GMPC_TRAJ_THREADS ? a.n : GMPC_TRAJ_THREADS;
@@ -483,102 +310,38 @@ static size_t traj_lds(TrajArgs& a) {
   if (bytes + wl * sizeof(float) <= 64 * 1024) { a.swl = (int)wl; bytes += wl * sizeof(float); }
   return bytes;
 }
-// dynamic LDS above the default 64 KB needs the attribute; the kernels also hold a few hundred bytes
-// of static LDS, so the full 160 KB cannot be requested
-template <typename KernelT>
-static void traj_attr(KernelT k) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            128 * 1024);
-  (void)hipGetLastError();
+
+// the general form: one workgroup per 4 trajectories (ls = false) / work-list items (ls = true: `grid` covers the
+// largest possible work list, the kernel reads the actual count); sizes its own LDS
+void gmpc_launch_traj(const TrajArgs& a0, bool ls, int grid, hipStream_t s) {
+  TrajArgs a = a0;
+  const size_t lds = traj_lds(a);
+  static bool attr = false;
+  if (!attr) {
+    // dynamic LDS above the default 64 KB needs the attribute; the kernels also hold a few hundred bytes
+    // of static LDS, so the full 160 KB cannot be requested
+    const void* ks[] = {reinterpret_cast<const void*>(&k_traj<false>), reinterpret_cast<const void*>(&k_traj<true>)};
+    for (const void* k : ks) {
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      (void)hipGetLastError();
+    }
+    attr = true;
+  }
+  if (!ls) hipLaunchKernelGGL(k_traj<false>, dim3(grid), dim3(GMPC_TRAJ_THREADS), lds, s, a);
+  else hipLaunchKernelGGL(k_traj<true>, dim3(grid), dim3(GMPC_TRAJ_THREADS), lds, s, a);
 }
 
 void gmpc_launch_rollout(const TrajArgs& a0, hipStream_t s) {
-  TrajArgs a = a0;
-  if (gmpc_traj_rw_shape(a)) {
-    a.aw = traj_aw(a.n, a.m, a.dyn, &a.cost);
+  const int grid = (a0.B + GMPC_TB - 1) / GMPC_TB;
+  if (gmpc_traj_rw_shape(a0)) {
+    TrajArgs a = a0;
     const size_t rlds = gmpc_traj_rw_lds(a);
-    gmpc_launch_traj_rw(a, false, (a.B + GMPC_TB - 1) / GMPC_TB, rlds, s);
-    return;
+    gmpc_launch_traj_rw(a, false, grid, rlds, s);
+  } else {
+    gmpc_launch_traj(a0, false, grid, s);
   }
-  const size_t lds = traj_lds(a);
-  static bool attr = false;
-  if (!attr) { traj_attr(&k_traj<false>); attr = true; }
-  const int grid = (a.B + GMPC_TB - 1) / GMPC_TB;
-  hipLaunchKernelGGL(k_traj<false>, dim3(grid), dim3(GMPC_TRAJ_THREADS), lds, s, a);
 }
 
-int gmpc_launch_linesearch(const TrajArgs& a0, const LsWork& w, hipStream_t s, gmpc_ls_eval_fn eval,
-                           void* user) {
-  TrajArgs a = a0;
-  const bool rw = eval == nullptr && gmpc_traj_rw_shape(a);
-  if (rw) a.aw = traj_aw(a.n, a.m, a.dyn, &a.cost);
-  const bool ls16 = rw && gmpc_ls16_shape(a);
-  a.ls_split = ls16 ? gmpc_ls16_split() : 0;
-  const bool ls32 = ls16 && gmpc_ls32_split() > 0 && gmpc_ls32_shape(a) && (long)a.B * GMPC_LS_ITEMS >= gmpc_ls32_split();
-  a.ls32_split = ls32 ? gmpc_ls32_split() : 0;
-  const size_t lds = eval ? 0 : rw ? gmpc_traj_rw_lds(a) : traj_lds(a);
-  static bool attr = false;
-  if (!attr && !eval) { traj_attr(&k_traj<true>); attr = true; }
-  // halvings allowed by trajax' loop: candidate k runs while alpha_0 / 2^k > alpha_min
-  int k_max = 0;
-  for (float al = a.alpha_0; al > a.alpha_min && k_max < 4096; al *= 0.5f) ++k_max;
-  // Size of the first round: one more candidate than the previous search accepted -- or, where a round of 16- or
-  // 32-candidate workgroups runs anyway and has room, all GMPC_LS_ITEMS of them: a pass of k_ls32 over the chip holds
-  // 8192 candidates (k_ls16: 4096) and takes the same time half empty.  At C3 the previous rule filled it to 7965 and
-  // left ~10 trajectories per iteration whose step size had grown by more than four halvings with a THIRD round of
-  // their own (a k_traj_rw pass, 0.2 - 0.4 ms for 80 candidates, in most iterations); with the full first round a
-  // third round needs 13 halvings (20 of 102,400 searches).  Which candidate is accepted does not change.
-  int first_min = 1;
-  if (ls16) {
-    static const int ncu = []() {
-      int v = 256;
-      (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, 0);
-      return v;
-    }();
-    const long all = (long)a.B * GMPC_LS_ITEMS;
-    const long pass = all >= a.ls32_split && ls32 ? (long)ncu * 32 : (long)ncu * 16;
-    if (all >= a.ls_split && all <= pass) first_min = GMPC_LS_ITEMS;
-  }
-  // worst case: a first round of first_min candidates, a second of GMPC_LS_NEXT, then GMPC_LS_ITEMS per round (a third
-  // round is rare and every round enqueued costs four launches whether it finds work or not: the later rounds take all
-  // they can hold; trajax' 15 step sizes are 4 rounds after a one-candidate first round, 3 after a full one)
-  int rounds = 0;
-  for (int left = k_max, r = 0; left > 0; ++r, ++rounds) left -= r == 0 ? first_min : r == 1 ? GMPC_LS_NEXT : GMPC_LS_ITEMS;
-  if (rounds > GMPC_LS_ROUNDS_MAX) return -1;
-  hipLaunchKernelGGL(k_ls_init, dim3((a.B + 255) / 256), dim3(256), 0, s, a.B, a.active, a.alpha_0,
-                     a.alpha_min, k_max, first_min, a.iters, w.run, w.cnt, w.kfirst, w.prevk, a.alpha, a.U_step,
-                     a.obj_step);
-  for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(k_ls_place, dim3(1), dim3(1024), 0, s, a.B, w.cnt, w.kfirst, w.item_b[0], w.item_k[0],
-                       w.slot, w.counts + r, w.counts + GMPC_LS_ROUNDS_MAX,
-                       w.counts + GMPC_LS_ROUNDS_MAX + 1 + 24 + (r < GMPC_LS_STATS - 24 ? r : GMPC_LS_STATS - 25));
-    a.item_b = w.item_b[0]; a.item_k = w.item_k[0]; a.nitems = w.counts + r; a.objc = w.objc;
-    const long max_items = (long)a.B * (r == 1 ? GMPC_LS_NEXT : GMPC_LS_ITEMS);
-    const int lsgrid = (int)((max_items + GMPC_TB - 1) / GMPC_TB);
-    if (eval)
-      eval(user, a, (int)max_items, s);
-    else if (rw) {
-      // short lists: 4 candidates per workgroup; long lists: 16 (each kernel returns on the other's rounds)
-      // (three forms, each launch returns at once when the round's count is another form's: 4 candidates per
-      // workgroup for short lists, 16 up to one pass over the chip, two groups of 16 beyond)
-      gmpc_launch_traj_rw(a, true, lsgrid, lds, s);
-      if (ls16) gmpc_launch_ls16(a, max_items, s);
-      if (ls32) gmpc_launch_ls32(a, max_items, a.ls32_split, s);
-    } else
-      hipLaunchKernelGGL(k_traj<true>, dim3((unsigned)lsgrid), dim3(GMPC_TRAJ_THREADS), lds, s, a);
-    LsDecideArgs d;
-    d.n = a.n; d.m = a.m; d.T = a.T; d.Lh = a.dyn.L - 1; d.k_max = k_max;
-    d.next = r == 0 ? GMPC_LS_NEXT : GMPC_LS_ITEMS;      // size of round r + 1
-    d.alpha_0 = a.alpha_0;
-    d.slot = w.slot; d.cnt = w.cnt; d.kfirst = w.kfirst; d.prevk = w.prevk; d.run = w.run;
-    d.objc = w.objc; d.Xc = a.Xc; d.Uc = a.Uc; d.maskc = a.maskc;
-    d.X = a.X; d.U = a.Uio; d.masks = a.masks;
-    d.obj = a.obj; d.obj_step = a.obj_step; d.U_step = a.U_step; d.alpha = a.alpha;
-    d.stats = w.counts + GMPC_LS_ROUNDS_MAX + 1;
-    hipLaunchKernelGGL(k_ls_decide, dim3(a.B), dim3(GMPC_THREADS), 0, s, d);
-  }
-  return 0;
-}
 void gmpc_launch_masks(int B, int n, int m, int T, const MlpDesc& dyn, const float* X,
                        const float* U, uint32_t* masks, hipStream_t s) {
   const int NS = B * T;

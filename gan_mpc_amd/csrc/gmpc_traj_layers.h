@@ -1,10 +1,18 @@
-// Layer routines shared by the trajectory kernels (gmpc_traj.hip: general VALU form, line search
-// bookkeeping; gmpc_traj_rw.hip: register-weight MFMA form).  4 trajectories ("slots") per workgroup,
-// activations in LDS as float4 (one component per slot).
+// Layer routines shared by the trajectory kernels (gmpc_traj.hip: general VALU form; gmpc_traj_rw.hip:
+// register-weight MFMA form).  4 trajectories ("slots") per workgroup, activations in LDS as float4 (one
+// component per slot).
 #pragma once
 #include "gmpc_device.h"
 
 #define GMPC_TRAJ_THREADS_ 512   // workgroup size of the general k_traj
+
+// float4 rows of one activation buffer: the widest layer of the network(s) the kernel evaluates (host side)
+static int traj_aw(int n, int m, const MlpDesc& d1, const MlpDesc* d2) {
+  int w = n + m > GMPC_THREADS ? n + m : GMPC_THREADS;
+  for (int l = 0; l <= d1.L; ++l) w = d1.dims[l] > w ? d1.dims[l] : w;
+  if (d2) for (int l = 0; l <= d2->L; ++l) w = d2->dims[l] > w ? d2->dims[l] : w;
+  return (w + 3) & ~3;
+}
 
 // One hidden layer for the 4 trajectories of the block: z = act_in . W + b; mask bits; relu.
 // mbase points at mask word 0 of (trajectory 0, this step, this layer); trajectory c sits

@@ -1,11 +1,12 @@
 // Register-weight MFMA form of the trajectory kernels (rollout + cost, line-search candidates) for the
 // reference's default dynamics network: three hidden layers of 200 (dynamics/nn.py:27-34, yaml
-// num_layers 4 / num_hidden_units 200).  gmpc_traj.hip holds the general form, the line-search
-// bookkeeping kernels and the launchers that choose between the two.
+// num_layers 4 / num_hidden_units 200).  gmpc_traj.hip holds the general form and the rollout's launcher that
+// chooses between the two, gmpc_linesearch.hip the line search's.
 //
 // Reference arithmetic as in gmpc_traj.hip: dynamics/nn.py:27-34, cost/cost_model.py:20-42, cost/nn.py:23-29,
 // trajax rollout / evaluate / ddp_rollout as called from policy/optimizers.py:19,26-29,55.
 #include "gmpc_traj_layers.h"
+#include "gmpc_ls_common.h"
 #include "gmpc_launch.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -160,15 +161,8 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
   const int b0 = blockIdx.x * GMPC_TB;
   if (LS) {
     const int cnt = *a.nitems;
-    if (b0 >= cnt || (a.ls_split > 0 && cnt >= a.ls_split)) return;   // (long work lists: k_ls16)
-    if (tid < GMPC_TB) {
-      const int it = min(b0 + tid, cnt - 1);
-      s_bi[tid] = a.item_b[it];
-      s_in[tid] = (b0 + tid) < cnt;
-      float al = a.alpha_0;
-      for (int k = a.item_k[it]; k > 0; --k) al *= 0.5f;
-      s_alpha[tid] = al;
-    }
+    if (b0 >= cnt || ls_round_form(cnt, a) != LS_FORM_RW) return;   // (long work lists: k_ls16 / k_ls32)
+    if (tid < GMPC_TB) ls_candidate(a, cnt, b0 + tid, &s_bi[tid], &s_in[tid], &s_alpha[tid]);
   } else if (tid < GMPC_TB) {
     s_bi[tid] = min(b0 + tid, a.B - 1);
     s_in[tid] = (b0 + tid) < a.B;
@@ -247,12 +241,7 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
   }
   float objacc = 0.f;  // lane 0 of wave c accumulates trajectory c
   __syncthreads();
-#ifdef GMPC_TRAJ_STAMPS
-  unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp_ = __builtin_readcyclecounter();
-#define TS_(i) { const unsigned long long t_ = __builtin_readcyclecounter(); st_[i] += t_ - tp_; tp_ = t_; }
-#else
-#define TS_(i)
-#endif
+  TS_BEGIN();
 
   // The operands of the step's controls are loaded one step ahead (every global round trip inside the step
   // is ~1k cycles of a ~8k-cycle step).  Plain rollout: thread (c, j) holds u_t[j] of slot c.  Line search:
@@ -482,6 +471,7 @@ bool gmpc_traj_rw_shape(const TrajArgs& a) { return rw_width(a) != 0; }
 
 size_t gmpc_traj_rw_lds(TrajArgs& a) {
   const int H = rw_width(a);
+  a.aw = traj_aw(a.n, a.m, a.dyn, &a.cost);
   a.pw = GMPC_RW_THREADS;
   a.sw0 = 0;                                             // W_0 lives in registers
   a.swl = a.n * rw_khp(H);                               // transposed W_L

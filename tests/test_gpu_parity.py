@@ -503,6 +503,26 @@ def test_linesearch_two_group_form_is_bit_identical_on_random_shapes(seed, monke
         eng.close()
 
 
+def test_linesearch_two_group_threshold_never_below_the_16_candidate_forms(monkeypatch):
+    """GMPC_LS32_SPLIT=1 alone asks k_ls32 for every work list while k_ls16's threshold stays at 1537: the plan raises
+    k_ls32's threshold to k_ls16's, so on this batch (21 x 8 candidates at most) every round is still k_traj_rw's and
+    the solve returns the bits of the solve with no variable set.  (Unclamped, k_traj_rw AND k_ls32 evaluated such
+    rounds and k_ls32's values -- k_ls16's bits, not k_traj_rw's -- were the ones kept.)"""
+    pb, pb64, eng = _setup("ls16-ragged")
+    d = eng.to_dev
+    kw = {"maxiter": 3}
+    for var in ("GMPC_LS", "GMPC_LS16_SPLIT", "GMPC_LS32_SPLIT"):
+        monkeypatch.delenv(var, raising=False)
+    ref = eng.ilqr_solve(d(pb["x0"]), d(pb["U"]), d(pb["goal"]), kw)
+    ncand = eng.linesearch_candidates()
+    snap = {key: ref[key].cpu().numpy().copy() for key in ("X", "U", "obj", "grad", "iterations")}
+    monkeypatch.setenv("GMPC_LS32_SPLIT", "1")
+    out = eng.ilqr_solve(d(pb["x0"]), d(pb["U"]), d(pb["goal"]), kw)
+    assert eng.linesearch_candidates() == ncand
+    for key in snap:
+        np.testing.assert_array_equal(out[key].cpu().numpy(), snap[key], err_msg=key)
+
+
 def test_unsupported_shape_fails_loudly():
     from gan_mpc_amd import GmpcError
     from gan_mpc_amd.engine import Engine
