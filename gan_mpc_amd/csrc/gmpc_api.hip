@@ -58,7 +58,7 @@ static int check_shape(const gmpc_shape* s) {
     if (s->cost_dims[l] < 1 || s->cost_dims[l] > GMPC_THREADS)
       return fail(GMPC_EINVAL, "cost hidden width must be in [1, %d]", GMPC_THREADS);
   if (s->lstm_features != 0) {
-    // (64: the register-weight kernels of gmpc_critic_lstm.hip / gmpc_critic.hip; other counts: k_lstm_fwd_g / _bwd_g)
+    // (64: gmpc_critic_lstm.hip's kernels and k_lstm_fwd / _bwd of gmpc_critic.hip; other counts: k_lstm_fwd_g / _bwd_g)
     if (s->lstm_features < 1 || s->lstm_features > 128)
       return fail(GMPC_EINVAL, "unsupported shape: critic lstm_features = %d outside [1, 128]", s->lstm_features);
     if (s->head_layers < 1 || s->head_layers > GMPC_MAX_LAYERS)

@@ -177,7 +177,7 @@ static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const
         gmpc_launch_colsum(single[i].csr, single[i].N, single[i].Bm, single[i].ldb, single[i].cs, c->wpart, sw);
       else
         gmpc_launch_wgrad(single[i].r, single[i].M, single[i].N, single[i].A, single[i].lda, single[i].Bm,
-                          single[i].ldb, single[i].Cw, single[i].cs, single[i].csr, c->wpart, 256, sw,
+                          single[i].ldb, single[i].Cw, single[i].cs, single[i].csr, c->wpart, sw,
                           c->wpart_floats, true);
     }
   }

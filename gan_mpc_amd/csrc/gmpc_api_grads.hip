@@ -45,7 +45,7 @@ static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const fl
   gmpc_launch_costvjp(B, T, n, m, c->cost, c->mpc_w, sign, c->Xs, c->Us, c->goals, c->nx, c->Hout, c->dX,
                       c->gmpc, c->cact, c->cdel, c->cstride, s);
   // sums over the batch: mpc_w (3 columns of gmpc) and the cost layers
-  gmpc_launch_wgrad(B, 1, 3, c->gmpc, 0, c->gmpc, 3, c->scratch + 512, grad_sum, B, c->wpart, 256, s, c->wpart_floats, false);
+  gmpc_launch_wgrad(B, 1, 3, c->gmpc, 0, c->gmpc, 3, c->scratch + 512, grad_sum, B, c->wpart, s, c->wpart_floats, false);
   gmpc_launch_wgrad_mlp(2 * B, B, sh.cost_layers, sh.cost_dims, c->cact, c->cdel, c->cstride, grad_sum + 3, c->wpart,
                         c->wpart_floats, s);
   c->gradB = B;   // H, dX (and Phi) now belong to the held solution: gmpc_bilevel_grad_inputs may follow
@@ -190,8 +190,8 @@ extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float*
     HIP_TRY(hipMemsetAsync(grad_theta_sum, 0, (3 + (size_t)mlp_count(sh.cost_layers, sh.cost_dims)) * sizeof(float),
                            s));
   } else if (want_theta) {
-    gmpc_launch_wgrad(B, 1, 3, c->rvgm.p, 0, c->rvgm.p, 3, c->rvgm.p + (size_t)B * 3, grad_theta_sum, B, c->wpart, 256,
-                      s, c->wpart_floats, false);
+    gmpc_launch_wgrad(B, 1, 3, c->rvgm.p, 0, c->rvgm.p, 3, c->rvgm.p + (size_t)B * 3, grad_theta_sum, B, c->wpart, s,
+                      c->wpart_floats, false);
     gmpc_launch_wgrad_mlp(B, B, sh.cost_layers, sh.cost_dims, c->rvcact.p, c->rvcdel.p, (int)cstride,
                           grad_theta_sum + 3, c->wpart, c->wpart_floats, s);
   }
@@ -235,9 +235,9 @@ extern "C" int gmpc_dynamics_loss_grad(gmpc_ctx* c, int B, int S, const float* x
     float* gWh = gWx + kin * G4;
     float* gb = gWh + Fd * G4;
     gmpc_launch_wgrad(rows, (int)kin, (int)G4, c->dfacts, c->dfstride, c->dfdels, c->dfstride, gWx, nullptr, 0,
-                      c->wpart, 256, s, c->wpart_floats, true);
+                      c->wpart, s, c->wpart_floats, true);
     gmpc_launch_wgrad(rows, (int)Fd, (int)G4, c->dfacts + kin, c->dfstride, c->dfdels, c->dfstride, gWh, gb, rows,
-                      c->wpart, 256, s, c->wpart_floats, true);
+                      c->wpart, s, c->wpart_floats, true);
     gmpc_launch_wgrad_mlp(rows, rows, d.tail.L, d.tail.dims, c->dfacts + kin + Fd, c->dfdels + G4, c->dfstride,
                           gb + G4, c->wpart, c->wpart_floats, s);
   } else {
@@ -349,7 +349,7 @@ extern "C" int gmpc_expert_loss_grad(gmpc_ctx* c, int B, int S, const gmpc_exper
     float* g = grad_sum;
     const int M0 = F > 0 ? (int)(nx + F) : nx, N0 = F > 0 ? (int)(4 * F) : (int)Y;
     gmpc_launch_wgrad(R, M0, N0, a.acts, (int)stride, a.dels, (int)stride, g, g + (long)M0 * N0, R, c->wpart,
-                      256, s, c->wpart_floats, true);
+                      s, c->wpart_floats, true);
     g += (long)M0 * N0 + N0;
     for (int h = 0; h < 2; ++h) {
       const MlpDesc& d = h == 0 ? a.hx : a.hu;
@@ -357,7 +357,7 @@ extern "C" int gmpc_expert_loss_grad(gmpc_ctx* c, int B, int S, const gmpc_exper
         const int M = d.dims[l], N = d.dims[l + 1];
         const int ao = h == 0 ? a.ax[l] : a.au[l], dof = h == 0 ? a.dx[l] : a.du[l];
         gmpc_launch_wgrad(R, M, N, a.acts + ao, (int)stride, a.dels + dof, (int)stride, g, g + (long)M * N, R,
-                          c->wpart, 256, s, c->wpart_floats, true);
+                          c->wpart, s, c->wpart_floats, true);
         g += (long)M * N + N;
       }
     }

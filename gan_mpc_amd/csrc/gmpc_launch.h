@@ -103,25 +103,30 @@ void gmpc_launch_big_cont(int B, int T, int m, const float* U, const float* gn2,
                           const float* alpha, const float* obj_step, const float* U_step, const gmpc_ilqr_opts& opts,
                           const int* active, int* cont, hipStream_t s);
 
-// gmpc_critic.hip -----------------------------------------------------------------------------------------------------
-void gmpc_launch_transpose(int R, int C, const float* in, float* out, hipStream_t s);   // in [R][C] -> out [C][R]
+// gmpc_critic.hip: the critic LSTM sweeps outside gmpc_critic_lstm.hip's shapes (F = 64 with n > 32 or on the wide-input
+// path, where cd.n == 0 and xproj holds x_t Wx; any other F <= 128) ---------------------------------------------------
 void gmpc_launch_lstm_fwd(int Bc, const CriticDesc& cd, const float* xseq, float* gates, float* cs, float* hp,
                           float* hT, const float* xproj, hipStream_t s);
 void gmpc_launch_lstm_bwd(int Bc, const CriticDesc& cd, const float* gates, const float* cs, const float* dhT,
                           float* dz, float* dxseq, hipStream_t s);
+
+// gmpc_optim.hip: optimiser and utility kernels ----------------------------------------------------------------------
+void gmpc_launch_transpose(int R, int C, const float* in, float* out, hipStream_t s);   // in [R][C] -> out [C][R]
 void gmpc_launch_sum(int count, const float* v, float* out, int square, hipStream_t s);
 void gmpc_launch_adam(long count, float* p, const float* g, float* m, float* v, float scale, int step, double lr,
                       double max_norm, double b1, double b2, double eps, float* scratch /* >= 257 */, hipStream_t s);
 void gmpc_launch_polyak(long count, const float* prev, const float* cur, double f, float* out, hipStream_t s);
 
+// gmpc_wgrad.hip -----------------------------------------------------------------------------------------------------
 // The weight-gradient GEMM: C[M][N] = sum_r A[r][:M]^T B[r][:N]; colsum[N] = sum_{r < cs_rows} B[r][:N] (optional).
 // Its matrix-core kernels (k_wgrad_mfma, k_wgrad_batch) read B up to GMPC_WGRAD_PAD rows past `rows`; A is clamped to
 // its last row and masked to zero there, so those rows of B only have to be allocated and finite.
 #define GMPC_WGRAD_PAD 8
-// part holds part_floats floats (at least max_split*(M*N + N)); mfma_ok: B has its GMPC_WGRAD_PAD pad rows
+#define GMPC_WGRAD_MAX_SPLIT 256   // most row chunks of the VALU form (k_wgrad)
+// part holds part_floats floats: up to GMPC_WGRAD_MAX_SPLIT partial sums of M*N + N floats, fewer where they would not
+// fit; mfma_ok: B has its GMPC_WGRAD_PAD pad rows
 void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
-                       float* colsum, int cs_rows, float* part, int max_split, hipStream_t s, long part_floats,
-                       bool mfma_ok);
+                       float* colsum, int cs_rows, float* part, hipStream_t s, long part_floats, bool mfma_ok);
 // MFMA path of gmpc_launch_wgrad; returns false when the shape does not qualify
 bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
                             float* colsum, int cs_rows, float* part, long part_floats, hipStream_t s);

@@ -16,7 +16,7 @@
 //                 the cost MLP, then per step the backward pass of v_{t+1} through the dynamics MLP with that step's
 //                 masks, the staging-cost terms in closed form.  Writes grad_U, grad_x0, grad_goal, the per-trajectory
 //                 mpc_w terms, the cost layers' input / delta rows and (grad_dyn_sum) the dynamics' delta rows.
-// The batch sums (mpc_w, cost and dynamics weights) are the weight-gradient GEMMs of gmpc_critic.hip.
+// The batch sums (mpc_w, cost and dynamics weights) are the weight-gradient GEMMs of gmpc_wgrad.hip.
 #include "gmpc_traj_layers.h"
 #include "gmpc_launch.h"
 

@@ -25,8 +25,8 @@ def critic_route(n, F):
     """Mirror of critic_forward_backward (gmpc_api_critic.hip).  gmpc_create allocates the wide-input buffers (xT, xproj)
     when n + F > GMPC_THREADS, and `widein = c->xT != nullptr`; `gen2 = !widein && c->lwp != nullptr &&
     gmpc_lstm2_supported(cd)`, where lwp exists exactly when lstm2_nx() != 0; otherwise gmpc_launch_lstm_fwd /
-    gmpc_launch_lstm_bwd (gmpc_critic.hip) run k_lstm_fwd / k_lstm_bwd at F = 64 and the strided k_lstm_fwd_g /
-    k_lstm_bwd_g at every other F."""
+    gmpc_launch_lstm_bwd (gmpc_critic.hip) run k_lstm_fwd / k_lstm_bwd (run-time n, one form for every n) at F = 64
+    and the strided k_lstm_fwd_g / k_lstm_bwd_g at every other F."""
     if n + F > THREADS:
         return ("wide",)
     nx = lstm2_nx(n, F)

@@ -1,8 +1,9 @@
 """The critic step (critic_loss_grad, critic_score_vjp) over every dispatch cell of critic_forward_backward against the
-fp64 oracle: the register-weight kernels at each x width NX (exact and padded), short and long sequences, batches
-around the backward sweep's groups and the head's 8-row workgroups, the first-generation and generic-F kernels, the
-wide-input GEMMs, head widths that leave a wave with one neuron and the deepest head.  The case table and the route
-mirror are tests/critic_cases.py (checked without a GPU by tests/test_critic_cases.py).
+fp64 oracle: the register-weight kernels of gmpc_critic_lstm.hip at each x width NX (exact and padded), short and
+long sequences, batches around the backward sweep's groups and the head's 8-row workgroups, the run-time-n F = 64
+kernels and the generic-F kernels of gmpc_critic.hip (routes "gen1", "generic"), the wide-input GEMMs, head widths
+that leave a wave with one neuron and the deepest head.  The case table and the route mirror are
+tests/critic_cases.py (checked without a GPU by tests/test_critic_cases.py).
 
 Then bit-for-bit: an engine reused with a smaller batch after a larger one against a fresh engine, the side-stream
 schedule against everything on the caller's stream, and two identical calls."""
