@@ -366,3 +366,90 @@ extern "C" int gmpc_expert_loss_grad(gmpc_ctx* c, int B, int S, const gmpc_exper
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+// The VJP of gmpc_expert_rollout at (expert, history) (gmpc_expert_vjp.hip).  Stateless: rows, save rows and the
+// transposed weight copies live in the call's own workspace, no held solution is dropped; the GEMMs' partials use
+// the shared scratch.
+extern "C" int gmpc_expert_vjp(gmpc_ctx* c, int B, int hist, const gmpc_expert_shape* es, const float* expert,
+                               const float* history, const float* g_goal, const float* g_U, float* grad_expert_sum,
+                               float* grad_history, void* stream) {
+  TRY(check_call(c, B, false));     // the expert model has its own parameters
+  const int nx = c->nx, m = c->sh.m, T = c->sh.T;
+  TRY(check_expert_shape(es, nx, m));
+  if (hist < 1) return fail(GMPC_EINVAL, "hist=%d: at least one history row is needed (yaml: history >= 1)", hist);
+  if (es->lstm_features == 0 && es->head_dims_x[0] > 512)
+    return fail(GMPC_EINVAL, "expert MLP first width %d > 512", es->head_dims_x[0]);
+  if (!expert || !history) return fail(GMPC_EINVAL, "expert vjp: expert and history must not be null");
+  if (!g_goal && !g_U) return fail(GMPC_EINVAL, "expert vjp: g_goal and g_U are both null: no cotangent");
+  if (!grad_expert_sum && !grad_history) return fail(GMPC_EINVAL, "expert vjp: every output is null");
+  if ((long)B * (hist + T) > (1L << 30)) return fail(GMPC_EINVAL, "B*(hist+T)=%ld rows: too many", (long)B * (hist + T));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long F = es->lstm_features, Y = es->head_dims_x[0];
+  const int L = es->head_layers;
+  const long count = gmpc_expert_param_count(nx, es);
+  TRY(c->evT.grow(c, (size_t)count));      // each matrix's transposed copy at the matrix's own offset
+  ExpertVjpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.T = T; a.hist = hist; a.n = nx; a.m = m; a.F = (int)F; a.Y = (int)Y;
+  a.st0 = F > 0 ? 0 : hist;
+  const long first = F > 0 ? (nx + F) * 4 * F : (long)nx * Y, nb = F > 0 ? 4 * F : Y;
+  a.Wcat = expert;
+  a.bcat = expert + first;
+  a.WcatT = c->evT.p;
+  const long hx_off = first + nb, hu_off = hx_off + mlp_count(L, es->head_dims_x);
+  bind_mlp(a.hx, L, es->head_dims_x, expert + hx_off, c->evT.p + hx_off);
+  bind_mlp(a.hu, L, es->head_dims_u, expert + hu_off, c->evT.p + hu_off);
+  {
+    // the row layout is k_expert_fit's
+    ExpertFitArgs f;
+    memset(&f, 0, sizeof(f));
+    f.n = nx; f.m = m; f.F = (int)F; f.Y = (int)Y; f.hx = a.hx; f.hu = a.hu;
+    a.stride = gmpc_expert_fit_layout(f);
+    a.hw = f.hw;
+    for (int l = 0; l < L; ++l) { a.ax[l] = f.ax[l]; a.au[l] = f.au[l]; a.dx[l] = f.dx[l]; a.du[l] = f.du[l]; }
+  }
+  a.sstride = (F > 0 ? 6 * (int)F : 0) + m;
+  ExpertVjpMats mats;
+  memset(&mats, 0, sizeof(mats));
+  auto add_mat = [&](int R, int C, const float* in, const float* out) {
+    mats.R[mats.nm] = R; mats.C[mats.nm] = C; mats.in[mats.nm] = in; mats.out[mats.nm] = const_cast<float*>(out);
+    ++mats.nm;
+  };
+  add_mat(F > 0 ? (int)(nx + F) : nx, (int)nb, a.Wcat, a.WcatT);
+  for (int l = 0; l < L; ++l) {
+    add_mat(a.hx.dims[l], a.hx.dims[l + 1], a.hx.W[l], a.hx.WT[l]);
+    add_mat(a.hu.dims[l], a.hu.dims[l + 1], a.hu.W[l], a.hu.WT[l]);
+  }
+  const size_t rows = (size_t)B * (hist + T - a.st0), head0 = (size_t)B * (hist - a.st0), stride = (size_t)a.stride;
+  TRY(c->evacts.reserve(c, rows, stride, s));
+  if (grad_expert_sum) TRY(c->evdels.reserve(c, rows, stride, s));
+  TRY(c->evsave.grow(c, gmpc_expert_vjp_save_floats(a)));
+  a.history = history; a.g_goal = g_goal; a.g_U = g_U;
+  a.acts = c->evacts.p;
+  a.dels = grad_expert_sum ? c->evdels.p : nullptr;
+  a.save = reinterpret_cast<float4*>(c->evsave.p);
+  a.grad_history = grad_history;
+  if (gmpc_launch_expert_vjp(a, mats, s) != 0) return fail(GMPC_EINVAL, "expert vjp kernel: unsupported shape");
+  if (grad_expert_sum) {
+    // [Wx | Wh] (or W_first) over every row the kernel ran; the heads over the rows with head deltas (st >= hist) only
+    float* g = grad_expert_sum;
+    const int R = (int)rows, Rh = B * T, M0 = F > 0 ? (int)(nx + F) : nx, N0 = (int)nb;
+    gmpc_launch_wgrad(R, M0, N0, a.acts, (int)stride, a.dels, (int)stride, g, g + (long)M0 * N0, R, c->wpart, s,
+                      c->wpart_floats, true);
+    g += (long)M0 * N0 + N0;
+    const float* hacts = a.acts + head0 * stride;
+    const float* hdels = a.dels + head0 * stride;
+    for (int h = 0; h < 2; ++h) {
+      const MlpDesc& d = h == 0 ? a.hx : a.hu;
+      for (int l = 0; l < L; ++l) {
+        const int M = d.dims[l], N = d.dims[l + 1];
+        const int ao = h == 0 ? a.ax[l] : a.au[l], dof = h == 0 ? a.dx[l] : a.du[l];
+        gmpc_launch_wgrad(Rh, M, N, hacts + ao, (int)stride, hdels + dof, (int)stride, g, g + (long)M * N, Rh, c->wpart,
+                          s, c->wpart_floats, true);
+        g += (long)M * N + N;
+      }
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

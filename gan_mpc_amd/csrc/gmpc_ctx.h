@@ -98,6 +98,9 @@ struct gmpc_ctx {
   // rollout VJP (gmpc_rollout_vjp): its own relu masks, per-trajectory mpc_w terms, cost and dynamics rows
   GrowBuf rvmask, rvgm;
   PadRows rvcact, rvcdel, rvacts, rvdels;
+  // expert rollout VJP (gmpc_expert_vjp): its rows, the kernel's save rows, the transposed weight copies
+  PadRows evacts, evdels;
+  GrowBuf evsave, evT;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;

@@ -270,6 +270,31 @@ struct ExpertFitArgs {
   float* loss;                   // [B]
 };
 
+// VJP of the expert rollout (gmpc_expert_vjp.hip): the rollout's schedule, cotangents of goal and init_U in
+struct ExpertVjpArgs {
+  int B, T, hist, n, m, F, Y, hw; // F == 0: the MLP variant; Y = width of y; hw = widest head layer
+  int st0;                       // first step the kernel runs: 0 (LSTM), hist (MLP: no carry through the history)
+  const float* Wcat;             // LSTM: [(n+F)][4F] (Wx rows, then Wh rows);  MLP: [n][Y]
+  const float* bcat;             // LSTM: [4F];  MLP: [Y]
+  const float* WcatT;            // the transposed copy of Wcat
+  MlpDesc hx, hu;                // heads, dims[0] = Y; WT[l]: the transposed copies
+  int ax[GMPC_MAX_LAYERS], au[GMPC_MAX_LAYERS];    // acts offsets of the heads' layer inputs
+  int dx[GMPC_MAX_LAYERS], du[GMPC_MAX_LAYERS];    // dels offsets of the heads' layer output deltas
+  const float* history;          // [B][hist+1][n]
+  const float* g_goal;           // [B][T+1][n] or null (zero)
+  const float* g_U;              // [B][T][m] or null (zero)
+  float* acts; float* dels; int stride;   // rows (st - st0) B + b; dels null: no parameter gradient wanted
+  float4* save; int sstride;     // per (workgroup, step - st0): sstride float4
+  float* grad_history;           // [B][hist+1][n] or null
+};
+// the matrices k_expert_transpose_all turns in one launch: in [R][C] -> out [C][R]
+struct ExpertVjpMats {
+  int nm;
+  int R[2 * GMPC_MAX_LAYERS + 1], C[2 * GMPC_MAX_LAYERS + 1];
+  const float* in[2 * GMPC_MAX_LAYERS + 1];
+  float* out[2 * GMPC_MAX_LAYERS + 1];
+};
+
 // batched "TN" GEMM of the large-state path (gmpc_large.hip)
 struct BgemmArgs {
   int batch, M, N, K;

@@ -226,6 +226,11 @@ int gmpc_launch_expert(const ExpertArgs& a, hipStream_t s);   // non-zero on an 
 int gmpc_expert_fit_layout(ExpertFitArgs& a);
 void gmpc_launch_expert_fit(const ExpertFitArgs& a, hipStream_t s);
 
+// gmpc_expert_vjp.hip: floats of the save rows of one call; the transposes and the sweep (non-zero on an unsupported
+// shape, before any launch)
+size_t gmpc_expert_vjp_save_floats(const ExpertVjpArgs& a);
+int gmpc_launch_expert_vjp(const ExpertVjpArgs& a, const ExpertVjpMats& mats, hipStream_t s);
+
 // gmpc_comm.hip: multi-GPU exchange -----------------------------------------------------------------------------------
 struct GmpcComm { void* comm = nullptr; int world = 1, rank = 0; };   // comm: the ncclComm_t, null in a world of one
 int gmpc_comm_unique_id_impl(char* id128);

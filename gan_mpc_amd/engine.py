@@ -323,6 +323,25 @@ class Engine:
             float(discount), int(bool(teacher_forcing)), _ptr(loss_sum), _ptr(grad_sum), self._stream()))
         return loss_sum, grad_sum
 
+    def expert_vjp(self, history, expert_flat, expert_shape, g_goal=None, g_U=None, want_params=True,
+                   want_history=True):
+        """The VJP of expert_rollout at (expert_flat, history) (gmpc_expert_vjp): g_goal = dL/dgoal (B, T+1, nx) and/or
+        g_U = dL/dinit_U (B, T, m).  -> dict(params [expert count], summed over the batch, history (B, hist+1, nx)),
+        None where not wanted.  Stateless: a held iLQR solution and its bilevel tail stay valid."""
+        B, hist = history.shape[0], history.shape[1] - 1
+        count = self.lib.gmpc_expert_param_count(self.nx, C.byref(expert_shape))
+        assert expert_flat.numel() == count, (expert_flat.numel(), count)
+        for name, t, shape in (("history", history, (B, hist + 1, self.nx)), ("g_goal", g_goal, (B, self.T + 1, self.nx)),
+                               ("g_U", g_U, (B, self.T, self.m))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"expert_vjp: {name} must be {shape}, got {tuple(t.shape)}")
+        out = dict(params=self.new(count) if want_params else None,
+                   history=self.new(B, hist + 1, self.nx) if want_history else None)
+        _lib.check(self.lib.gmpc_expert_vjp(
+            self.ctx, B, hist, C.byref(expert_shape), _ptr(expert_flat), _ptr(history), _ptr(g_goal), _ptr(g_U),
+            _ptr(out["params"]), _ptr(out["history"]), self._stream()))
+        return out
+
     def dynamics_loss_grad(self, xseq, useq, next_xseq, discount, teacher_forcing, loss_sum=None,
                            grad_sum=None):
         """-> (loss_sum[1], grad_sum[dyn_count]) of the multi-step prediction loss over the batch."""

@@ -126,6 +126,11 @@ class ExpertModel(ExpertProtocol):
             self._packed = (expert_params, engine.to_dev(flat), make_expert_shape(F, dx, du))
         return self._packed[1], self._packed[2]
 
+    def device_params(self, expert_params, engine):
+        """(flat, shape): the cached fp32 device vector in params.pack_expert's layout -- the leaf
+        policy.differentiable.expert_layer differentiates -- and its gmpc_expert_shape."""
+        return self._device_params(expert_params, engine)
+
     def get_goal_states_init_actions(self, history_X, expert_params, engine=None):
         """Batched policy/eval.py:87-107 on the GPU -> device tensors goal (B, T+1, n), init_U (B, T, m)."""
         if engine is None:

@@ -21,7 +21,16 @@ section 12), and, with dynamics_grad=True, gmpc_bilevel_grad_dynamics dL/dtheta_
 op: backward is one call of gmpc_rollout_vjp, the true derivative w.r.t. x0, U, goal and the
 mpc_weights / cost_params / dynamics_params ranges of params.flat (dynamics_grad=False leaves the last one out).  Its
 forward runs on a second engine of the policy bound to the same parameters, so an iLQR solution held for
-ilqr_layer's backward survives it.  Relu-MLP dynamics only (LSTM dynamics fail in forward)."""
+ilqr_layer's backward survives it.  Relu-MLP dynamics only (LSTM dynamics fail in forward).
+
+(goal, init_U) = expert_layer(policy, expert_flat, expert_shape, history) is the expert sequence model's rollout
+(gmpc_expert_rollout on the policy's engine) as a differentiable torch op: backward is one call of gmpc_expert_vjp
+(DESIGN.md section 15), the true derivative w.r.t. expert_flat -- a device fp32 vector in params.pack_expert's layout,
+e.g. ExpertModel.device_params' -- summed over the batch, and w.r.t. history per window.  The expert's parameters are
+not part of params.flat: expert_flat is their leaf, and this layer is the one way a task loss reaches them
+(ilqr_layer's dL/dgoal, rollout_layer's dL/dU).  Both its forward and its backward leave a held iLQR solution and its
+bilevel tail alone, so it composes with the other two layers in one backward():
+expert_layer -> ilqr_layer -> loss (init_U gets no cotangent) and expert_layer -> rollout_layer(U=init_U) -> loss."""
 
 import torch
 
@@ -161,3 +170,47 @@ def rollout_layer(policy, params, x0, U, goal, dynamics_grad=True):
     dparams = policy.to_device_params(params)
     eng = _rollout_engine(policy, dparams, x0.shape[0])
     return RolloutFunction.apply(eng, dparams, dparams.flat, x0, U, goal, bool(dynamics_grad))
+
+
+class ExpertFunction(torch.autograd.Function):
+    """forward(eng, expert_shape, expert_flat, history) -> (goal, init_U)."""
+
+    @staticmethod
+    def forward(ctx, eng, expert_shape, expert_flat, history):
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+        flat32, hist32 = f32(expert_flat), f32(history)
+        goal, init_U = eng.expert_rollout(hist32, flat32, expert_shape)
+        ctx.eng, ctx.shape = eng, expert_shape
+        ctx.save_for_backward(flat32, hist32)
+        ctx.set_materialize_grads(False)
+        return goal, init_U
+
+    @staticmethod
+    def backward(ctx, g_goal, g_U):
+        want_params, want_history = ctx.needs_input_grad[2:4]
+        if (g_goal is None and g_U is None) or not (want_params or want_history):
+            return (None,) * 4
+        eng = ctx.eng
+        if eng.ctx is None:
+            raise RuntimeError("expert_layer backward: the engine of the forward has been closed (the policy rebuilt "
+                               "it for another shape or a larger batch)")
+        flat, history = ctx.saved_tensors
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        out = eng.expert_vjp(history, flat, ctx.shape, f32(g_goal), f32(g_U), want_params=want_params,
+                             want_history=want_history)
+        return None, None, out["params"], out["history"]
+
+
+def expert_layer(policy, expert_flat, expert_shape, history):
+    """(goal (B, T+1, x_size), init_U (B, T, m)) of the expert sequence model on the policy's engine, differentiable
+    w.r.t. expert_flat (device fp32 vector in params.pack_expert's layout; gradient summed over the batch) and history
+    (B, hist+1, x_size) (see the module docstring).  expert_shape: the model's gmpc_expert_shape
+    (engine.make_expert_shape, or ExpertModel.device_params)."""
+    B = history.shape[0]
+    eng = policy._engine
+    if eng is None or B > eng.max_batch:
+        if policy._bound is None:
+            raise GmpcError(f"expert_layer: the policy has no engine for a batch of {B} yet; bind its parameters first "
+                            "(policy.bind(params, batch))")
+        eng = policy.engine_for(B)
+    return ExpertFunction.apply(eng, expert_shape, expert_flat, history)

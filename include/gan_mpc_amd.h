@@ -19,9 +19,9 @@
  *    after a COMPLETED gmpc_ilqr_solve of the same batch size.  gmpc_set_params, gmpc_rollout_cost,
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
- *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp drops nothing: it
- *    may run between a solve and its bilevel calls, or between a bilevel call and gmpc_bilevel_grad_inputs /
- *    _dynamics.
+ *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp and gmpc_expert_vjp
+ *    drop nothing: they may run between a solve and its bilevel calls, or between a bilevel call and
+ *    gmpc_bilevel_grad_inputs / _dynamics.
  *
  * Parameter layouts (flat fp32 vectors, flax Dense order: kernel (in,out) row-major, then bias):
  *   dyn    : for l in 0..dyn_layers-1:  W_l[dims[l]][dims[l+1]], b_l[dims[l+1]]
@@ -329,6 +329,27 @@ long gmpc_expert_param_count(int n, const gmpc_expert_shape* es);
 int gmpc_expert_loss_grad(gmpc_ctx* ctx, int B, int S, const gmpc_expert_shape* es, const float* expert,
                           const float* xseq, const float* useq, const float* next_xseq, double discount,
                           int teacher_forcing, float* loss_sum, float* grad_sum, void* stream);
+
+/* The vector-Jacobian product of gmpc_expert_rollout at (expert, history) for a caller's cotangents
+ * g_goal = dL/dgoal [B][T+1][x_size] and g_U = dL/dinit_U [B][T][m] (either may be NULL, not both; a NULL one is zero):
+ *   grad_expert_sum [gmpc_expert_param_count] in the flat layout of gmpc_expert_rollout, SUMMED over the batch and
+ *   overwritten; grad_history [B][hist+1][x_size] per window.  Either output may be NULL (its work is skipped: no
+ *   weight-gradient rows or GEMMs without grad_expert_sum), not both.
+ * The schedule is the rollout's: steps st = 0 .. hist+T-1, the input of step st is history[st] for st <= hist and the
+ * previous step's next_x after that, goal[st-hist+1] = next_x_st and init_U[st-hist] = u_st for st >= hist,
+ * goal[0] = history[hist].  So g_goal[:, 0] goes straight into grad_history[:, hist]; the teacher-forced steps
+ * st < hist receive gradient through the LSTM carry only, and for the MLP variant (no carry) rows < hist of
+ * grad_history are exactly zero.  The action head is differentiated through its tanh.  T is the ctx's horizon.
+ * Caps as gmpc_expert_rollout (F <= 128, x_size, m and head widths <= 1024, the MLP variant's first width <= 512),
+ * hist >= 1, 1 <= B <= max_batch; anything else, both cotangents NULL or both outputs NULL fail with GMPC_EINVAL
+ * before any launch.  Stateless and read-only for every existing ctx buffer: drops no held solution and no bilevel
+ * tail (see the ordering contract), so it may run between a solve, its bilevel call and the inputs / dynamics calls.
+ * Deterministic (fixed reduction order, no atomics); asynchronous, except that the first call needing more workspace
+ * than the ctx holds allocates it (a synchronising hipMalloc) and keeps it: up to 2 (B (hist+T) + 8) row strides
+ * (gmpc_expert_loss_grad's rows), B (hist+T) (6F + m) save floats and one transposed copy of the weights. */
+int gmpc_expert_vjp(gmpc_ctx* ctx, int B, int hist, const gmpc_expert_shape* es, const float* expert,
+                    const float* history, const float* g_goal, const float* g_U,
+                    float* grad_expert_sum, float* grad_history, void* stream);
 
 /* N3: dynamics-model regression, norm/dynamics_trainer.py:14-47 (predict_loss) and
  * :62-86 (batch mean + value_and_grad) with utils.py:230-240 (discounted_sum).  For each of the B
