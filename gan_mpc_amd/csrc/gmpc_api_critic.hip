@@ -218,6 +218,30 @@ extern "C" int gmpc_critic_score_vjp(gmpc_ctx* c, int Bc, const float* xseq, con
   return 0;
 }
 
+// The VJP of the score for a caller's output delta g_score = d loss / d score (k_head2 loss_kind 3): one forward
+// sweep, one head pass, one backward pass on whichever route the shape takes.  Stateless: the critic's own workspace
+// and the caller's outputs only.
+extern "C" int gmpc_critic_vjp(gmpc_ctx* c, int Bc, const float* xseq, const float* critic, const float* g_score,
+                               float* score, float* grad_xseq, float* grad_critic_sum, void* stream) {
+  if (!c) return fail(GMPC_EINVAL, "ctx is null");
+  if (c->sh.lstm_features <= 0) return fail(GMPC_EINVAL, "gmpc_critic_vjp: this ctx was created without a critic");
+  if (Bc < 1 || Bc > 2 * c->maxB)
+    return fail(GMPC_EINVAL, "gmpc_critic_vjp: Bc=%d outside [1, 2*max_batch=%d]", Bc, 2 * c->maxB);
+  if (!xseq) return fail(GMPC_EINVAL, "gmpc_critic_vjp: xseq is null");
+  if (!critic) return fail(GMPC_EINVAL, "gmpc_critic_vjp: critic is null");
+  if (!g_score) return fail(GMPC_EINVAL, "gmpc_critic_vjp: g_score is null");
+  if (!grad_xseq && !grad_critic_sum)
+    return fail(GMPC_EINVAL, "gmpc_critic_vjp: grad_xseq and grad_critic_sum are both null");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TRY(critic_forward_backward(c, Bc, xseq, g_score, critic, 3, grad_xseq, grad_critic_sum != nullptr,
+                              grad_critic_sum, s));
+  if (score) HIP_TRY(hipMemcpyAsync(score, c->cscore, Bc * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // upper-level loss only, at the solution held by the ctx (norm/cost_trainer.py:13-21 test loss)
 int upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired, const float* critic,
                       float* loss, bool want_lx, hipStream_t s) {

@@ -138,8 +138,10 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_lstm_fwd2(int Bc, CriticDes
 // back: the transposed weights (64 registers) and the gradient accumulators (84) are shared, one group's LDS round
 // trips and transcendentals sit under the other's MFMAs, the workgroup needs ONE wave per SIMD -- it fits beside the
 // one-wave Riccati sweep (176 registers) where two 200-register waves did not -- and leaves half the partials.
+// WANT_W and WANT_DX together (gmpc_critic_vjp): one sweep, the arithmetic of either form alone; the accumulators and
+// both transposed weight halves need one wave per SIMD at NG = 1 as well.
 template <int NX, bool WANT_W, bool WANT_DX, int NG>
-__global__ __launch_bounds__(GMPC_THREADS, NG == 1 ? 2 : 1) void k_lstm_bwd2(
+__global__ __launch_bounds__(GMPC_THREADS, (NG == 1 && !(WANT_W && WANT_DX)) ? 2 : 1) void k_lstm_bwd2(
     int Bc, CriticDesc cd, const float* __restrict__ xseq, const float* __restrict__ G, const float* __restrict__ Cst,
     const float* __restrict__ Hst, const float* __restrict__ dhT, float* __restrict__ Wp, float* __restrict__ dxseq) {
   constexpr int KG = (64 + NX + 3) / 4;          // row groups of the weight gradient
@@ -387,7 +389,13 @@ static void launch_bwd2(int Bc, const CriticDesc& cd, const float* xseq, const f
                         const float* Hst, const float* dhT, float* Wp, float* dxseq, hipStream_t s) {
   const int ng = bwd2_groups(Bc);
   const dim3 grid((Bc + 4 * ng - 1) / (4 * ng)), blk(GMPC_THREADS);
-  // (both wanted is not a combination the API asks for today: two sweeps)
+  if (Wp && dxseq) {     // gmpc_critic_vjp with both gradients: one sweep
+    if (ng == 2)
+      hipLaunchKernelGGL((k_lstm_bwd2<NX, true, true, 2>), grid, blk, 0, s, Bc, cd, xseq, G, Cst, Hst, dhT, Wp, dxseq);
+    else
+      hipLaunchKernelGGL((k_lstm_bwd2<NX, true, true, 1>), grid, blk, 0, s, Bc, cd, xseq, G, Cst, Hst, dhT, Wp, dxseq);
+    return;
+  }
   if (Wp) {
     if (ng == 2)
       hipLaunchKernelGGL((k_lstm_bwd2<NX, true, false, 2>), grid, blk, 0, s, Bc, cd, xseq, G, Cst, Hst, dhT, Wp, nullptr);
@@ -580,6 +588,10 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
       const float p = sigmoidf_(sc);
       ls = -logf(p) + logf(1.f - p);
       ds = -1.f;
+    } else if (loss_kind == 3) {
+      // the caller's output delta d loss / d score (gmpc_critic_vjp), in the label slot
+      ls = 0.f;
+      ds = label[min(row, Bc - 1)];
     } else {
       ls = 0.f;
       ds = 1.f;

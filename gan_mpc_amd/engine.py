@@ -378,6 +378,26 @@ class Engine:
                                                   _ptr(dx), self._stream()))
         return score, dx
 
+    def critic_vjp(self, xseq, critic, g_score, want_dx=True, want_params=True, grad_sum=None):
+        """The VJP of the critic's scores at (critic, xseq) for g_score = dL/dscore (Bc,) (gmpc_critic_vjp).
+        -> dict(score (Bc,), dx (Bc, T+1, nx) = g_b dscore_b/dxseq_b, params [critic_count] = sum_b g_b dscore_b/dtheta
+        in critic_loss_grad's layout), None where not wanted.  grad_sum: optional caller-owned [critic_count] view
+        (e.g. of a packed all-reduce buffer) for params.  Stateless: a held iLQR solution and its bilevel tail stay
+        valid."""
+        Bc = xseq.shape[0]
+        for name, t, shape in (("xseq", xseq, (Bc, self.T + 1, self.nx)), ("critic", critic, (self.critic_count,)),
+                               ("g_score", g_score, (Bc,))):
+            if tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"critic_vjp: {name} must be {shape}, got {tuple(t.shape)}")
+        if grad_sum is not None and (not want_params or tuple(grad_sum.shape) != (self.critic_count,)):
+            raise _lib.GmpcError(f"critic_vjp: grad_sum must be ({self.critic_count},) and goes with want_params, got "
+                                 f"{tuple(grad_sum.shape)}, want_params={want_params}")
+        out = dict(score=self.new(Bc), dx=self.new(Bc, self.T + 1, self.nx) if want_dx else None,
+                   params=(self.new(self.critic_count) if grad_sum is None else grad_sum) if want_params else None)
+        _lib.check(self.lib.gmpc_critic_vjp(self.ctx, Bc, _ptr(xseq), _ptr(critic), _ptr(g_score), _ptr(out["score"]),
+                                            _ptr(out["dx"]), _ptr(out["params"]), self._stream()))
+        return out
+
     def adam_clip_step(self, params, grad, m, v, step, lr, grad_scale=1.0, max_norm=100.0, b1=0.9,
                        b2=0.999, eps=1e-8):
         _lib.check(self.lib.gmpc_adam_clip_step(

@@ -41,9 +41,19 @@ class BaseMPC(eval_policy.EvalMPC):
         LOSS_KIND None overrides it with torch operations that torch.func can vmap and differentiate."""
         raise NotImplementedError
 
+    def batch_cotangents(self, X, U, dparams, loss_args, want_grad=True):
+        """Optional: the upper-level loss of the WHOLE batch and its cotangents, (loss [B], lx (B, T+1, n) or None,
+        lu (B, T, m) or None) as contiguous fp32 device tensors (lx, lu None without want_grad; a cotangent that is
+        identically zero is None).  A subclass that overrides it is asked here instead of LOSS_KIND / loss(): for
+        losses that go through another layer (gan/gan_policy.py: the critic) rather than per-trajectory torch code."""
+        raise NotImplementedError
+
+    def _batched_loss(self):
+        return type(self).batch_cotangents is not BaseMPC.batch_cotangents
+
     def _custom_loss(self):
         """True for the subclass's own torch loss; NotImplementedError when there is no loss at all."""
-        if self.LOSS_KIND is not None:
+        if self.LOSS_KIND is not None or self._batched_loss():
             return False
         if type(self).loss is BaseMPC.loss:
             raise NotImplementedError(f"{type(self).__name__} sets no LOSS_KIND and does not override loss()")
@@ -57,7 +67,9 @@ class BaseMPC(eval_policy.EvalMPC):
         if B > 0:            # an empty shard still joins the exchange, with count 0
             dparams, sol = self._solve(dparams, history_X)
             eng = self._engine
-            if custom:       # the reference's jax.vmap(policy.loss, in_axes=(0, 0, None, 0))
+            if self._batched_loss():
+                loss, _, _ = self.batch_cotangents(sol["X"], sol["U"], dparams, (desired,), want_grad=False)
+            elif custom:       # the reference's jax.vmap(policy.loss, in_axes=(0, 0, None, 0))
                 loss, _, _ = opt.loss_cotangents(self.loss, sol["X"], sol["U"], dparams, (desired,),
                                                  (0 if desired is not None else None,), want_grad=False)
             else:
@@ -87,7 +99,12 @@ class BaseMPC(eval_policy.EvalMPC):
             x0 = d(hx[:, -1])
             if eng.n > eng.nx:       # xc = concat[x, carry], the training policy's carry is zero (:31-38, :101-102)
                 x0 = torch.cat([x0, d(self.get_dynamics_carry(hx))], dim=1).contiguous()
-            if custom:       # loss(xcseq, useq, params, *batch_loss_args), vmapped over (0, 0, None) + loss_vmap
+            if self._batched_loss():
+                args = tuple(batch_loss_args or ())
+                loss, _, _, _ = opt.bilevel_optimization(
+                    self, dparams, x0, d(init_U), d(goal), None, sign=self.bilevel_sign, grad_sum=packed[1:-1],
+                    cotangents=lambda X, U: self.batch_cotangents(X, U, dparams, args))
+            elif custom:     # loss(xcseq, useq, params, *batch_loss_args), vmapped over (0, 0, None) + loss_vmap
                 loss, _, _, _ = opt.bilevel_optimization(
                     self, dparams, x0, d(init_U), d(goal), self.loss, sign=self.bilevel_sign,
                     grad_sum=packed[1:-1], loss_args=tuple(batch_loss_args or ()), loss_vmap=self.loss_vmap)

@@ -8,7 +8,8 @@ section 12), and, with dynamics_grad=True, gmpc_bilevel_grad_dynamics dL/dtheta_
   - params: a DeviceParams; its flat vector `params.flat` is the differentiable leaf.  Its mpc_weights and
     cost_params ranges receive gradient, summed over the batch.  The dynamics_params range receives gradient only
     with dynamics_grad=True (relu-MLP dynamics, n <= 64 and m <= 32: anything else fails in forward); by default it
-    gets none, as in the reference.  Critic and expert parameters get none.
+    gets none, as in the reference.  Critic and expert parameters get none (critic_layer and expert_layer are
+    their layers).
   - x0 (B, n) -- xc, carry columns included for LSTM dynamics -- and goal (B, T+1, x_size) receive per-sample
     gradients.  dL/dx0 is not available on the step-major pipeline (n > 64 or m > 32): asking for it (x0 requiring
     grad) fails in forward.
@@ -30,7 +31,16 @@ e.g. ExpertModel.device_params' -- summed over the batch, and w.r.t. history per
 not part of params.flat: expert_flat is their leaf, and this layer is the one way a task loss reaches them
 (ilqr_layer's dL/dgoal, rollout_layer's dL/dU).  Both its forward and its backward leave a held iLQR solution and its
 bilevel tail alone, so it composes with the other two layers in one backward():
-expert_layer -> ilqr_layer -> loss (init_U gets no cotangent) and expert_layer -> rollout_layer(U=init_U) -> loss."""
+expert_layer -> ilqr_layer -> loss (init_U gets no cotangent) and expert_layer -> rollout_layer(U=init_U) -> loss.
+
+score = critic_layer(policy, params, xseq) is the critic's score of Bc state sequences (gmpc_critic_score_vjp on the
+policy's engine) as a differentiable torch op: backward is one call of gmpc_critic_vjp with the
+incoming dL/dscore, the true derivative w.r.t. xseq per sequence and w.r.t. the critic_params range of params.flat,
+summed over the batch (zeros on every other range).  Any objective of the scores written in torch -- Wasserstein,
+least squares, hinge, label smoothing, per-sequence weights -- so reaches the discriminator's parameters, and the
+generator loss runs through expert_layer -> ilqr_layer -> critic_layer -> loss in one backward(): neither its forward
+nor its backward touches a held iLQR solution or its bilevel tail.  xseq has x_size columns (with LSTM dynamics the
+caller slices X[..., :x_size]); it never rebuilds the policy's engine, so Bc <= 2 max_batch of the bound engine."""
 
 import torch
 
@@ -214,3 +224,53 @@ def expert_layer(policy, expert_flat, expert_shape, history):
                             "(policy.bind(params, batch))")
         eng = policy.engine_for(B)
     return ExpertFunction.apply(eng, expert_shape, expert_flat, history)
+
+
+class CriticFunction(torch.autograd.Function):
+    """forward(eng, dparams, flat, xseq) -> score; flat is dparams.flat."""
+
+    @staticmethod
+    def forward(ctx, eng, dparams, flat, xseq):
+        xs = xseq.detach().to(torch.float32).contiguous()
+        crit = dparams.view("critic_params")
+        score, _ = eng.critic_score_vjp(xs, crit, want_dx=False)
+        ctx.eng, ctx.crit = eng, crit
+        ctx.range = dparams.range_of(("critic_params",))
+        ctx.flat_shape = flat.shape
+        ctx.save_for_backward(xs)
+        ctx.set_materialize_grads(False)
+        return score
+
+    @staticmethod
+    def backward(ctx, g_score):
+        want_params, want_dx = ctx.needs_input_grad[2:4]
+        if g_score is None or not (want_params or want_dx):
+            return (None,) * 4
+        eng = ctx.eng
+        if eng.ctx is None:
+            raise RuntimeError("critic_layer backward: the engine of the forward has been closed (the policy rebuilt "
+                               "it for another shape or a larger batch)")
+        xs, = ctx.saved_tensors
+        gflat = None
+        if want_params:
+            lo, cnt = ctx.range
+            gflat = torch.zeros(ctx.flat_shape, dtype=torch.float32, device=xs.device)
+        out = eng.critic_vjp(xs, ctx.crit, g_score.to(torch.float32).contiguous(), want_dx=want_dx,
+                             want_params=want_params, grad_sum=gflat[lo:lo + cnt] if want_params else None)
+        return None, None, gflat, out["dx"]
+
+
+def critic_layer(policy, params, xseq):
+    """score (Bc,) of the policy's critic on xseq (Bc, T+1, x_size), differentiable w.r.t. xseq and the critic_params
+    range of params.flat (see the module docstring).  params: the policy's DeviceParams (a parameter tree is converted,
+    and then is not differentiable); runs on the policy's engine as it is."""
+    dparams = policy.to_device_params(params)
+    Bc = xseq.shape[0]
+    eng = policy._engine
+    if eng is None:
+        raise GmpcError(f"critic_layer: the policy has no engine for a batch of {Bc} yet; bind its parameters first "
+                        "(policy.bind(params, batch))")
+    if Bc > 2 * eng.max_batch:
+        raise GmpcError(f"critic_layer: Bc = {Bc} sequences exceed 2 * max_batch = {2 * eng.max_batch} of the policy's "
+                        f"engine (max_batch = {eng.max_batch}); bind the policy for a larger batch first")
+    return CriticFunction.apply(eng, dparams, dparams.flat, xseq)

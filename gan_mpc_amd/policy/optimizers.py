@@ -22,7 +22,8 @@ def ilqr_solve(policy, dparams, x0, U, goal, trajax_ilqr_kwargs=None):
 
 
 def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=None,
-                         trajax_ilqr_kwargs=None, sign=1.0, grad_sum=None, loss_args=(), loss_vmap=None):
+                         trajax_ilqr_kwargs=None, sign=1.0, grad_sum=None, loss_args=(), loss_vmap=None,
+                         cotangents=None):
     """reference policy/optimizers.py:34-75, batched, WITHOUT the batch mean: returns
     (loss [B], low_level_grad [B,T,m], grad_sum [3 + cost_count] summed over the batch, itr [B]).
     sign=+1 reproduces the reference as written.
@@ -30,12 +31,19 @@ def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=N
     loss_kind 0 (L2, against `desired`) and 1 (JS, the policy's critic) run on the kernels' own losses.  A
     callable is the reference's `loss(X, U, params, *loss_args)` of ONE trajectory: it is evaluated and
     differentiated per trajectory under torch.func.vmap (loss_cotangents; loss_vmap: the in_dims of loss_args,
-    default 0 for each), its cotangents go to gmpc_bilevel_grad_cotangent."""
+    default 0 for each), its cotangents go to gmpc_bilevel_grad_cotangent.
+
+    cotangents (loss_kind is then ignored): a callable (X, U) -> (loss [B], lx (B, T+1, n) or None, lu (B, T, m) or
+    None) for the whole batch at once, for a loss that is not a vmap of per-trajectory torch code (BaseMPC.
+    batch_cotangents); a None cotangent is passed on as NULL, not as zeros."""
     B = x0.shape[0]
     eng = policy.bind(dparams, B)
     sol = _solver(policy, eng)(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
-    if callable(loss_kind):
-        loss, lx, lu = loss_cotangents(loss_kind, sol["X"], sol["U"], dparams, loss_args, loss_vmap)
+    if cotangents is not None or callable(loss_kind):
+        if cotangents is not None:
+            loss, lx, lu = cotangents(sol["X"], sol["U"])
+        else:
+            loss, lx, lu = loss_cotangents(loss_kind, sol["X"], sol["U"], dparams, loss_args, loss_vmap)
         grad_sum = eng.bilevel_grad_cotangent(B, lx, lu, sign=sign, grad_sum=grad_sum)
         return loss, sol["grad"], grad_sum, sol["iterations"]
     critic = dparams.view("critic_params") if loss_kind == 1 else None

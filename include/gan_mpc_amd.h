@@ -19,8 +19,8 @@
  *    after a COMPLETED gmpc_ilqr_solve of the same batch size.  gmpc_set_params, gmpc_rollout_cost,
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
- *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp and gmpc_expert_vjp
- *    drop nothing: they may run between a solve and its bilevel calls, or between a bilevel call and
+ *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp, gmpc_expert_vjp and
+ *    gmpc_critic_vjp drop nothing: they may run between a solve and its bilevel calls, or between a bilevel call and
  *    gmpc_bilevel_grad_inputs / _dynamics.
  *
  * Parameter layouts (flat fp32 vectors, flax Dense order: kernel (in,out) row-major, then bias):
@@ -266,6 +266,28 @@ int gmpc_critic_loss_grad(gmpc_ctx* ctx, int Bc, const float* xseq, const float*
  *   -> score [Bc]; dxseq [Bc][T+1][n] or NULL. */
 int gmpc_critic_score_vjp(gmpc_ctx* ctx, int Bc, const float* xseq, const float* critic,
                           float* score, float* dxseq, void* stream);
+
+/* The vector-Jacobian product of the critic's scores at (critic, xseq) for a caller's output delta
+ * g_score = dL/dscore [Bc]: any discriminator or generator objective is a function of the scores, and everything
+ * behind the head's scalar output is linear in g_score.
+ *   xseq [Bc][T+1][x_size], critic the flat parameters (layout above), g_score [Bc]
+ *   -> score [Bc]; grad_xseq [Bc][T+1][x_size] = g_b * d score_b / d xseq_b per sequence; grad_critic_sum
+ *      [critic_count] = sum_b g_b * d score_b / d theta in gmpc_critic_loss_grad's layout, SUMMED over the batch and
+ *      overwritten.  Any output may be NULL (its work is skipped: no weight-gradient accumulation or GEMMs without
+ *      grad_critic_sum, no dx without grad_xseq), but not both gradients.
+ * The true derivative: no reference sign applies.  g = 1 gives gmpc_critic_score_vjp's dxseq, g = the BCE delta
+ * gmpc_critic_loss_grad's grad_sum, g = -1 the generator cotangent of gmpc_bilevel_grad(loss_kind = 1).
+ * One forward sweep, one head pass and one backward pass on every dispatch route of the critic step (register-weight
+ * n <= 32 at F = 64, run-time n at F = 64, any other F <= 128, wide input n + F > 256); with both gradients the
+ * register-weight backward sweep accumulates the LSTM weight gradient and writes dx in the same pass.
+ * A NULL xseq, critic or g_score, both gradient outputs NULL, Bc outside [1, 2 max_batch] or a ctx created without a
+ * critic fail with GMPC_EINVAL before any launch.
+ * Stateless: it writes the critic step's own workspace and the caller's outputs only -- none of Bvec, H, dX or the
+ * ctx's lx -- and drops neither a held solution nor a bilevel tail (see the ordering contract), so it may run between
+ * a solve, its bilevel call and the inputs / dynamics calls.  Deterministic (fixed reduction order, no atomics):
+ * identical calls give identical bits.  Asynchronous; no allocation. */
+int gmpc_critic_vjp(gmpc_ctx* ctx, int Bc, const float* xseq, const float* critic, const float* g_score,
+                    float* score, float* grad_xseq, float* grad_critic_sum, void* stream);
 
 /* a18: optax.chain(clip_by_global_norm(max_norm), adam(lr)) on one contiguous trainable range
  * (gan/runner.py:51-63).  grad is scaled by grad_scale first (1/B for a batch sum).
