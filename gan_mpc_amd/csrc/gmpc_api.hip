@@ -213,16 +213,15 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
   A_(iters, B); A_(cont, B);
   if (!c->dynl && !c->big && s.T <= GMPC_FZ_MAX_T) A_(fzcand, B * GMPC_FZ_NC * ((T + 1) * n + T * m));
   // bilevel
-  int cin = 0, cout_ = 0;
-  for (int l = 0; l < s.cost_layers; ++l) { cin += s.cost_dims[l]; cout_ += s.cost_dims[l + 1]; }
-  c->cstride = cin > cout_ ? cin : cout_;
+  c->drows = mlp_rows(s.dyn_layers, s.dyn_dims);
+  c->crows = mlp_rows(s.cost_layers, s.cost_dims);
   A_(lx, B * (T + 1) * n);
   A_(Bvec, B * T * m);
   A_(Hout, B * T * m);
   A_(dX, B * (T + 1) * n);
   A_(gmpc, B * 3);
-  A_(cact, (2 * B + GMPC_WGRAD_PAD) * c->cstride);
-  A_(cdel, (2 * B + GMPC_WGRAD_PAD) * c->cstride);
+  A_(cact, (2 * B + GMPC_WGRAD_PAD) * c->crows.stride);
+  A_(cdel, (2 * B + GMPC_WGRAD_PAD) * c->crows.stride);
   A_(bl_loss, B);
   // critic
   long wmax = 0;
@@ -230,7 +229,6 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
     long w = (long)s.cost_dims[l] * s.cost_dims[l + 1] + s.cost_dims[l + 1];
     if (w > wmax) wmax = w;
   }
-  c->hstride = 1;
   if (c->dynl) {
     A_(xg, B * (T + 1) * c->nx);
     A_(lxg, B * (T + 1) * c->nx);
@@ -243,9 +241,7 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
   if (s.lstm_features > 0) {
     // (the saves of the LSTM kernels are laid out per workgroup of 4 sequences: round the batch up)
     const size_t Bc = (2 * B + 3) / 4 * 4, F = s.lstm_features, T1 = T + 1, n = c->nx;   // the critic scores x sequences
-    int hin = 0, hout = 0;
-    for (int l = 0; l < s.head_layers; ++l) { hin += s.head_dims[l]; hout += s.head_dims[l + 1]; }
-    c->hstride = hin > hout ? hin : hout;
+    c->hrows = mlp_rows(s.head_layers, s.head_dims);
     A_(critT, (n + F) * 4 * F + mlp_count(s.head_layers, s.head_dims));
     A_(gates, Bc * T1 * 4 * F);
     A_(cs, Bc * T1 * F);
@@ -263,8 +259,8 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
       if (gmpc_lstm2_supported(probe)) A_(lwp, gmpc_lstm2_wpart_floats(probe, (int)Bc));
     }
     A_(plast, (Bc + GMPC_WGRAD_PAD) * GMPC_HEAD2_LD);
-    A_(hacts, (Bc + GMPC_WGRAD_PAD) * c->hstride);
-    A_(hdels, (Bc + GMPC_WGRAD_PAD) * c->hstride);
+    A_(hacts, (Bc + GMPC_WGRAD_PAD) * c->hrows.stride);
+    A_(hdels, (Bc + GMPC_WGRAD_PAD) * c->hrows.stride);
     A_(dhT, Bc * F);
     A_(cscore, Bc);
     A_(closs, Bc);
@@ -281,12 +277,12 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
   A_(scratch, 1024);
 #undef A_
   // operands of the weight-gradient GEMM: its pad rows must be finite (GMPC_WGRAD_PAD)
-  if (!rc && c->cdel) (void)hipMemset(c->cdel, 0, (2 * B + GMPC_WGRAD_PAD) * c->cstride * sizeof(float));
-  if (!rc && c->cact) (void)hipMemset(c->cact, 0, (2 * B + GMPC_WGRAD_PAD) * c->cstride * sizeof(float));
+  if (!rc && c->cdel) (void)hipMemset(c->cdel, 0, (2 * B + GMPC_WGRAD_PAD) * c->crows.stride * sizeof(float));
+  if (!rc && c->cact) (void)hipMemset(c->cact, 0, (2 * B + GMPC_WGRAD_PAD) * c->crows.stride * sizeof(float));
   if (!rc && s.lstm_features > 0) {
     (void)hipMemset(c->dz, 0, ((size_t)2 * B * (T + 1) + GMPC_WGRAD_PAD) * 4 * s.lstm_features * sizeof(float));
-    (void)hipMemset(c->hdels, 0, ((size_t)2 * B + GMPC_WGRAD_PAD) * c->hstride * sizeof(float));
-    (void)hipMemset(c->hacts, 0, ((size_t)2 * B + GMPC_WGRAD_PAD) * c->hstride * sizeof(float));
+    (void)hipMemset(c->hdels, 0, ((size_t)2 * B + GMPC_WGRAD_PAD) * c->hrows.stride * sizeof(float));
+    (void)hipMemset(c->hacts, 0, ((size_t)2 * B + GMPC_WGRAD_PAD) * c->hrows.stride * sizeof(float));
     (void)hipMemset(c->plast, 0, ((size_t)2 * B + GMPC_WGRAD_PAD) * GMPC_HEAD2_LD * sizeof(float));
   }
   if (!rc) (void)hipMemset(c->Ks, 0, (B * T * m * n + 16 * nm) * sizeof(float));

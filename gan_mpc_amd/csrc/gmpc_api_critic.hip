@@ -92,7 +92,7 @@ static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const
   {
     ProfScope ps(c, PROF_HEAD, s);
     gmpc_launch_head2(Bc, cd, loss_kind, c->hT, label, c->cscore, c->closs, c->hacts, c->hdels, c->plast, c->dhT,
-                      c->hstride, s);
+                      c->hrows, s);
   }
   hipStream_t sw = s;
   bool forked = false;
@@ -152,7 +152,6 @@ static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const
       route(rows, F, G4, c->hp, F, c->dz, G4, gWh, gb, rows);
     }
     float* gh = gb + G4;
-    int aoff = 0, doff = 0;
     for (int l = 0; l < sh.head_layers; ++l) {
       const int M = sh.head_dims[l], N = sh.head_dims[l + 1];
       if (l == sh.head_layers - 1 && np < GMPC_WG_MAX) {
@@ -160,11 +159,10 @@ static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const
         // k_head2's products [act * dscore | dscore] -- a problem without a GEMM part (M = 0)
         add(Bc, 0, M + 1, c->plast, GMPC_HEAD2_LD, c->plast, GMPC_HEAD2_LD, gh, gh, Bc);
       } else {
-        route(Bc, M, N, c->hacts + aoff, c->hstride, c->hdels + doff, c->hstride, gh, gh + (long)M * N, Bc);
+        route(Bc, M, N, c->hacts + c->hrows.aoff[l], c->hrows.stride, c->hdels + c->hrows.doff[l], c->hrows.stride, gh,
+              gh + (long)M * N, Bc);
       }
       gh += (long)M * N + N;
-      aoff += M;
-      doff += N;
     }
     if (np > 0 && !gmpc_launch_wgrad_batch(pr, np, c->wpart, c->wpart_floats, sw)) {
       for (int i = 0; i < np; ++i)

@@ -43,10 +43,10 @@ static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const fl
     }
   }
   gmpc_launch_costvjp(B, T, n, m, c->cost, c->mpc_w, sign, c->Xs, c->Us, c->goals, c->nx, c->Hout, c->dX,
-                      c->gmpc, c->cact, c->cdel, c->cstride, s);
+                      c->gmpc, c->cact, c->cdel, c->crows, s);
   // sums over the batch: mpc_w (3 columns of gmpc) and the cost layers
   gmpc_launch_wgrad(B, 1, 3, c->gmpc, 0, c->gmpc, 3, c->scratch + 512, grad_sum, B, c->wpart, s, c->wpart_floats, false);
-  gmpc_launch_wgrad_mlp(2 * B, B, sh.cost_layers, sh.cost_dims, c->cact, c->cdel, c->cstride, grad_sum + 3, c->wpart,
+  gmpc_launch_wgrad_mlp(2 * B, B, sh.cost_layers, sh.cost_dims, c->cact, c->cdel, c->crows, grad_sum + 3, c->wpart,
                         c->wpart_floats, s);
   c->gradB = B;   // H, dX (and Phi) now belong to the held solution: gmpc_bilevel_grad_inputs may follow
   return 0;
@@ -113,7 +113,7 @@ extern "C" int gmpc_bilevel_grad_inputs(gmpc_ctx* c, int B, const float* lx, flo
 
 // dL/dtheta_dyn of the loss whose bilevel gradient the ctx has just computed (gmpc_dyn_grads.hip): the adjoint
 // sweeps give w = mu - nu and lam per step, the row kernel the layer inputs and deltas of 2 B T rows, and the weight
-// GEMMs sum them over the batch.  Read-only for every other ctx buffer (the GEMMs' partials use the shared scratch).
+// GEMMs sum them over the batch.  Read-only for every ctx buffer but the call workspace and the GEMMs' shared scratch.
 extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, float* grad_dyn_sum, void* stream) {
   TRY(check_call(c, B));
   const gmpc_shape& sh = c->sh;
@@ -131,25 +131,25 @@ extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, f
   const int n = sh.n, m = sh.m, T = sh.T;
   if (!lx) lx = c->lx;
   const size_t steps = (size_t)B * T, rows = 2 * steps;
-  const size_t stride = (size_t)gmpc_dyn_rows_stride(c->dyn);
-  TRY(c->dgw.grow(c, steps * n));
-  TRY(c->dglam.grow(c, steps * n));
-  TRY(c->dgacts.reserve(c, rows, stride, s));
-  TRY(c->dgdels.reserve(c, rows, stride, s));
-  gmpc_launch_dyn_adjoints(B, T, n, c->nx, m, c->mpc_w, c->Xs, c->goals, c->dX, lx, c->AB, c->QT, c->qT, c->dgw.p,
-                           c->dglam.p, s);
-  if (gmpc_launch_dyn_rows(B, T, n, m, c->dyn, c->Xs, c->Us, c->dX, c->Hout, c->dgw.p, c->dglam.p, c->dgacts.p,
-                           c->dgdels.p, s) != 0)
+  CallWork& k = c->cw;     // aux, aux2: the adjoint planes w, lam
+  TRY(k.aux.grow(c, steps * n));
+  TRY(k.aux2.grow(c, steps * n));
+  TRY(k.acts.reserve(c, rows, c->drows.stride, s));
+  TRY(k.dels.reserve(c, rows, c->drows.stride, s));
+  gmpc_launch_dyn_adjoints(B, T, n, c->nx, m, c->mpc_w, c->Xs, c->goals, c->dX, lx, c->AB, c->QT, c->qT, k.aux.p,
+                           k.aux2.p, s);
+  if (gmpc_launch_dyn_rows(B, T, n, m, c->dyn, c->Xs, c->Us, c->dX, c->Hout, k.aux.p, k.aux2.p, k.acts.p, k.dels.p,
+                           c->drows, s) != 0)
     return fail(GMPC_EINVAL, "dynamics gradient: layer widths above 256");
   // gW_l = sum over the 2 B T rows of [a; -a']^T [delta(w); delta(lam)], gb_l = sum of the primal half's deltas
-  gmpc_launch_wgrad_mlp((int)rows, (int)steps, sh.dyn_layers, sh.dyn_dims, c->dgacts.p, c->dgdels.p, (int)stride,
-                        grad_dyn_sum, c->wpart, c->wpart_floats, s);
+  gmpc_launch_wgrad_mlp((int)rows, (int)steps, sh.dyn_layers, sh.dyn_dims, k.acts.p, k.dels.p, c->drows, grad_dyn_sum,
+                        c->wpart, c->wpart_floats, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
 // The VJP of the rollout and its costs at (X, U, goal) (gmpc_rollout_vjp.hip).  Stateless: the masks and rows live in
-// the call's own workspace, no held solution is dropped; the GEMMs' partials use the shared scratch.
+// the call workspace, no held solution is dropped; the GEMMs' partials use the shared scratch.
 extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float* U, const float* goal, const float* gX,
                                 const float* gcost, float* grad_x0, float* grad_U, float* grad_goal,
                                 float* grad_theta_sum, float* grad_dyn_sum, void* stream) {
@@ -165,38 +165,40 @@ extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float*
   const int n = sh.n, m = sh.m, T = sh.T, Lh = sh.dyn_layers - 1;
   const size_t steps = (size_t)B * T;
   const bool want_theta = grad_theta_sum != nullptr && gcost != nullptr;
-  const size_t dstride = (size_t)gmpc_dyn_rows_stride(c->dyn), cstride = (size_t)gmpc_rvjp_cost_stride(c->cost);
-  // (uint32 mask words in a float allocation)
-  TRY(c->rvmask.grow(c, steps * Lh * GMPC_MW));
+  CallWork& k = c->cw;     // acts / dels: the dynamics rows, acts2 / dels2: the cost rows
+  // aux: the call's own relu masks (uint32 words in a float allocation)
+  TRY(k.aux.grow(c, steps * Lh * GMPC_MW));
   if (want_theta) {
-    TRY(c->rvgm.grow(c, (size_t)B * 3 + 8));      // [B][3] and the 1 x 3 product its column sum's launch leaves behind
-    TRY(c->rvcact.reserve(c, B, cstride, s));
-    TRY(c->rvcdel.reserve(c, B, cstride, s));
+    // aux2: the per-trajectory mpc_w terms [B][3] and the 1 x 3 product their column sum's launch leaves behind
+    TRY(k.aux2.grow(c, (size_t)B * 3 + 8));
+    TRY(k.acts2.reserve(c, B, c->crows.stride, s));
+    TRY(k.dels2.reserve(c, B, c->crows.stride, s));
   }
   if (grad_dyn_sum) {
-    TRY(c->rvacts.reserve(c, steps, dstride, s));
-    TRY(c->rvdels.reserve(c, steps, dstride, s));
+    TRY(k.acts.reserve(c, steps, c->drows.stride, s));
+    TRY(k.dels.reserve(c, steps, c->drows.stride, s));
   }
-  uint32_t* masks = reinterpret_cast<uint32_t*>(c->rvmask.p);
+  uint32_t* masks = reinterpret_cast<uint32_t*>(k.aux.p);
+  float* gm = k.aux2.p;
   if (grad_dyn_sum)
-    gmpc_launch_rvjp_acts(B, n, m, T, c->dyn, X, U, c->rvacts.p, (int)dstride, masks, s);
+    gmpc_launch_rvjp_acts(B, n, m, T, c->dyn, X, U, k.acts.p, c->drows, masks, s);
   else
     gmpc_launch_masks(B, n, m, T, c->dyn, X, U, masks, s);
   gmpc_launch_rvjp_sweep(B, n, m, T, c->dyn, c->cost, c->mpc_w, X, U, goal, gX, gcost, masks, grad_x0, grad_U,
-                         grad_goal, want_theta ? c->rvgm.p : nullptr, want_theta ? c->rvcact.p : nullptr,
-                         want_theta ? c->rvcdel.p : nullptr, grad_dyn_sum ? c->rvdels.p : nullptr, (int)dstride, s);
+                         grad_goal, want_theta ? gm : nullptr, want_theta ? k.acts2.p : nullptr,
+                         want_theta ? k.dels2.p : nullptr, grad_dyn_sum ? k.dels.p : nullptr, c->drows, c->crows, s);
   if (grad_theta_sum && !want_theta) {
     // no cost cotangent: the costs' parameters get nothing
     HIP_TRY(hipMemsetAsync(grad_theta_sum, 0, (3 + (size_t)mlp_count(sh.cost_layers, sh.cost_dims)) * sizeof(float),
                            s));
   } else if (want_theta) {
-    gmpc_launch_wgrad(B, 1, 3, c->rvgm.p, 0, c->rvgm.p, 3, c->rvgm.p + (size_t)B * 3, grad_theta_sum, B, c->wpart, s,
-                      c->wpart_floats, false);
-    gmpc_launch_wgrad_mlp(B, B, sh.cost_layers, sh.cost_dims, c->rvcact.p, c->rvcdel.p, (int)cstride,
-                          grad_theta_sum + 3, c->wpart, c->wpart_floats, s);
+    gmpc_launch_wgrad(B, 1, 3, gm, 0, gm, 3, gm + (size_t)B * 3, grad_theta_sum, B, c->wpart, s, c->wpart_floats,
+                      false);
+    gmpc_launch_wgrad_mlp(B, B, sh.cost_layers, sh.cost_dims, k.acts2.p, k.dels2.p, c->crows, grad_theta_sum + 3,
+                          c->wpart, c->wpart_floats, s);
   }
   if (grad_dyn_sum)
-    gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, c->rvacts.p, c->rvdels.p, (int)dstride,
+    gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, k.acts.p, k.dels.p, c->drows,
                           grad_dyn_sum, c->wpart, c->wpart_floats, s);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -214,7 +216,7 @@ extern "C" int gmpc_dynamics_loss_grad(gmpc_ctx* c, int B, int S, const float* x
   if (!c->dfacts) {
     // (zeroed whole, once: the pad rows of the weight-gradient GEMM's operands stay finite whatever B * S a call has)
     const size_t rows = (size_t)c->maxB * sh.T, padded = rows + GMPC_WGRAD_PAD;
-    c->dfstride = c->dynl ? (int)gmpc_dynl_fit_stride(c->dl) : (int)gmpc_dynfit_stride(&sh);
+    c->dfstride = c->dynl ? (int)gmpc_dynl_fit_stride(c->dl) : c->drows.stride;
     int rc = dalloc(c, &c->dfpred, rows * c->nx);
     if (!rc) rc = dalloc(c, &c->dfacts, padded * c->dfstride);
     if (!rc) rc = dalloc(c, &c->dfdels, padded * c->dfstride);
@@ -229,8 +231,10 @@ extern "C" int gmpc_dynamics_loss_grad(gmpc_ctx* c, int B, int S, const float* x
     // LSTM variant: BPTT through the cell and the tail (gmpc_dynl.hip); gradient layout Wx | Wh | b | tail
     const DynlDesc& d = c->dl;
     const long Fd = d.F, kin = d.nx + d.m, G4 = 4 * Fd;
+    MlpRows tail = c->drows;     // the tail's columns, in rows that start with the cell's
+    tail.stride = c->dfstride;
     gmpc_launch_dynl_fit(B, S, d, xseq, useq, next_xseq, (float)discount, teacher_forcing != 0, c->dfpred,
-                         c->dfacts, c->dfdels, c->dfstride, c->dfsave, c->dfloss, s);
+                         c->dfacts, c->dfdels, tail, c->dfsave, c->dfloss, s);
     float* gWx = grad_sum;
     float* gWh = gWx + kin * G4;
     float* gb = gWh + Fd * G4;
@@ -238,14 +242,14 @@ extern "C" int gmpc_dynamics_loss_grad(gmpc_ctx* c, int B, int S, const float* x
                       c->wpart, s, c->wpart_floats, true);
     gmpc_launch_wgrad(rows, (int)Fd, (int)G4, c->dfacts + kin, c->dfstride, c->dfdels, c->dfstride, gWh, gb, rows,
                       c->wpart, s, c->wpart_floats, true);
-    gmpc_launch_wgrad_mlp(rows, rows, d.tail.L, d.tail.dims, c->dfacts + kin + Fd, c->dfdels + G4, c->dfstride,
+    gmpc_launch_wgrad_mlp(rows, rows, d.tail.L, d.tail.dims, c->dfacts + kin + Fd, c->dfdels + G4, tail,
                           gb + G4, c->wpart, c->wpart_floats, s);
   } else {
     if (gmpc_launch_dynfit(B, S, sh.n, sh.m, c->dyn, xseq, useq, next_xseq, (float)discount,
-                           teacher_forcing != 0, c->dfpred, c->dfacts, c->dfdels, c->dfstride, c->dfloss,
+                           teacher_forcing != 0, c->dfpred, c->dfacts, c->dfdels, c->drows, c->dfloss,
                            s) != 0)
       return fail(GMPC_EINVAL, "dynamics regression: unsupported layer width");
-    gmpc_launch_wgrad_mlp(rows, rows, sh.dyn_layers, sh.dyn_dims, c->dfacts, c->dfdels, c->dfstride, grad_sum,
+    gmpc_launch_wgrad_mlp(rows, rows, sh.dyn_layers, sh.dyn_dims, c->dfacts, c->dfdels, c->drows, grad_sum,
                           c->wpart, c->wpart_floats, s);
   }
   gmpc_launch_sum(B, c->dfloss, loss_sum, 0, s);
@@ -281,6 +285,27 @@ extern "C" long gmpc_expert_param_count(int n, const gmpc_expert_shape* es) {
   return cnt + mlp_count(es->head_layers, es->head_dims_x) + mlp_count(es->head_layers, es->head_dims_u);
 }
 
+// The expert's weight gradient in the flat layout: the first matrix ([Wx; Wh] or W_first) and its bias over `rows`
+// rows, then head_x's and head_u's layers over `head_rows` rows (k_expert_vjp has head deltas on its last rows only).
+static void expert_wgrad(gmpc_ctx* c, const ExpertNet& e, const float* acts, const float* dels, int rows,
+                         const float* head_acts, const float* head_dels, int head_rows, float* g, hipStream_t s) {
+  const int M0 = e.n + e.F, N0 = e.F > 0 ? 4 * e.F : e.Y;
+  gmpc_launch_wgrad(rows, M0, N0, acts, e.stride, dels, e.stride, g, g + (long)M0 * N0, rows, c->wpart, s,
+                    c->wpart_floats, true);
+  g += (long)M0 * N0 + N0;
+  for (int h = 0; h < 2; ++h) {
+    const MlpDesc& d = h == 0 ? e.hx : e.hu;
+    const int* ao = h == 0 ? e.ax : e.au;
+    const int* dof = h == 0 ? e.dx : e.du;
+    for (int l = 0; l < d.L; ++l) {
+      const int M = d.dims[l], N = d.dims[l + 1];
+      gmpc_launch_wgrad(head_rows, M, N, head_acts + ao[l], e.stride, head_dels + dof[l], e.stride, g, g + (long)M * N,
+                        head_rows, c->wpart, s, c->wpart_floats, true);
+      g += (long)M * N + N;
+    }
+  }
+}
+
 extern "C" int gmpc_expert_rollout(gmpc_ctx* c, int B, int hist, const gmpc_expert_shape* es,
                                    const float* expert, const float* history, float* goal, float* init_U,
                                    void* stream) {
@@ -290,15 +315,9 @@ extern "C" int gmpc_expert_rollout(gmpc_ctx* c, int B, int hist, const gmpc_expe
   TRY(check_expert_shape(es, nx, sh.m));
   if (hist < 1) return fail(GMPC_EINVAL, "hist=%d: at least one history row is needed (yaml: history >= 1)", hist);
   if (!expert || !history || !goal || !init_U) return fail(GMPC_EINVAL, "null argument");
-  ExpertArgs a;
-  a.B = B; a.n = nx; a.m = sh.m; a.T = sh.T; a.hist = hist; a.F = es->lstm_features;
-  const long F = a.F, h = es->head_dims_x[0];
-  a.Wcat = expert;
-  a.bcat = expert + (F > 0 ? (nx + F) * 4 * F : (long)nx * h);
-  const float* heads = a.bcat + (F > 0 ? 4 * F : h);
-  bind_mlp(a.hx, es->head_layers, es->head_dims_x, heads, nullptr);
-  bind_mlp(a.hu, es->head_layers, es->head_dims_u, heads + mlp_count(es->head_layers, es->head_dims_x),
-           nullptr);
+  ExpertArgs a{};
+  a.B = B; a.T = sh.T; a.hist = hist;
+  bind_expert(a.net, nx, sh.m, es, expert, nullptr);
   a.history = history; a.goal = goal; a.U = init_U;
   if (gmpc_launch_expert(a, static_cast<hipStream_t>(stream)) != 0)
     return fail(GMPC_EINVAL, "expert kernel: unsupported shape");
@@ -322,53 +341,32 @@ extern "C" int gmpc_expert_loss_grad(gmpc_ctx* c, int B, int S, const gmpc_exper
   hipStream_t s = static_cast<hipStream_t>(stream);
   ExpertFitArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = B; a.S = S; a.n = nx; a.m = m; a.F = es->lstm_features; a.Y = es->head_dims_x[0];
-  const long F = a.F, Y = a.Y, L = es->head_layers;
-  a.Wcat = expert;
-  a.bcat = expert + (F > 0 ? (nx + F) * 4 * F : (long)nx * Y);
-  const float* heads = a.bcat + (F > 0 ? 4 * F : Y);
-  bind_mlp(a.hx, (int)L, es->head_dims_x, heads, nullptr);
-  bind_mlp(a.hu, (int)L, es->head_dims_u, heads + mlp_count((int)L, es->head_dims_x), nullptr);
+  a.B = B; a.S = S;
+  bind_expert(a.net, nx, m, es, expert, nullptr);
   a.xseq = xseq; a.useq = useq; a.yseq = next_xseq;
   a.gamma = (float)discount;
   a.teacher_forcing = teacher_forcing != 0;
   a.grad = grad_sum != nullptr;
-  const size_t stride = (size_t)gmpc_expert_fit_layout(a);
+  a.sstride = (a.net.F > 0 ? 6 * a.net.F : 0) + nx + m;
   const size_t rows = (size_t)B * S;
   if (!c->efloss) TRY(dalloc(c, &c->efloss, c->maxB));
   a.loss = c->efloss;
   if (a.grad) {
-    TRY(c->efacts.reserve(c, rows, stride, s));
-    TRY(c->efdels.reserve(c, rows, stride, s));
-    TRY(c->efsave.grow(c, rows * a.sstride));
-    a.acts = c->efacts.p; a.dels = c->efdels.p; a.save = c->efsave.p;
+    CallWork& k = c->cw;
+    TRY(k.acts.reserve(c, rows, a.net.stride, s));
+    TRY(k.dels.reserve(c, rows, a.net.stride, s));
+    TRY(k.save.grow(c, rows * a.sstride));
+    a.acts = k.acts.p; a.dels = k.dels.p; a.save = k.save.p;
   }
   gmpc_launch_expert_fit(a, s);
-  if (a.grad) {
-    const int R = (int)rows;
-    float* g = grad_sum;
-    const int M0 = F > 0 ? (int)(nx + F) : nx, N0 = F > 0 ? (int)(4 * F) : (int)Y;
-    gmpc_launch_wgrad(R, M0, N0, a.acts, (int)stride, a.dels, (int)stride, g, g + (long)M0 * N0, R, c->wpart,
-                      s, c->wpart_floats, true);
-    g += (long)M0 * N0 + N0;
-    for (int h = 0; h < 2; ++h) {
-      const MlpDesc& d = h == 0 ? a.hx : a.hu;
-      for (int l = 0; l < d.L; ++l) {
-        const int M = d.dims[l], N = d.dims[l + 1];
-        const int ao = h == 0 ? a.ax[l] : a.au[l], dof = h == 0 ? a.dx[l] : a.du[l];
-        gmpc_launch_wgrad(R, M, N, a.acts + ao, (int)stride, a.dels + dof, (int)stride, g, g + (long)M * N, R,
-                          c->wpart, s, c->wpart_floats, true);
-        g += (long)M * N + N;
-      }
-    }
-  }
+  if (a.grad) expert_wgrad(c, a.net, a.acts, a.dels, (int)rows, a.acts, a.dels, (int)rows, grad_sum, s);
   gmpc_launch_sum(B, c->efloss, loss_sum, 0, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
 // The VJP of gmpc_expert_rollout at (expert, history) (gmpc_expert_vjp.hip).  Stateless: rows, save rows and the
-// transposed weight copies live in the call's own workspace, no held solution is dropped; the GEMMs' partials use
+// transposed weight copies live in the call workspace, no held solution is dropped; the GEMMs' partials use
 // the shared scratch.
 extern "C" int gmpc_expert_vjp(gmpc_ctx* c, int B, int hist, const gmpc_expert_shape* es, const float* expert,
                                const float* history, const float* g_goal, const float* g_U, float* grad_expert_sum,
@@ -384,72 +382,28 @@ extern "C" int gmpc_expert_vjp(gmpc_ctx* c, int B, int hist, const gmpc_expert_s
   if (!grad_expert_sum && !grad_history) return fail(GMPC_EINVAL, "expert vjp: every output is null");
   if ((long)B * (hist + T) > (1L << 30)) return fail(GMPC_EINVAL, "B*(hist+T)=%ld rows: too many", (long)B * (hist + T));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const long F = es->lstm_features, Y = es->head_dims_x[0];
-  const int L = es->head_layers;
-  const long count = gmpc_expert_param_count(nx, es);
-  TRY(c->evT.grow(c, (size_t)count));      // each matrix's transposed copy at the matrix's own offset
+  CallWork& k = c->cw;     // aux: each matrix's transposed copy at the matrix's own offset
+  TRY(k.aux.grow(c, (size_t)gmpc_expert_param_count(nx, es)));
   ExpertVjpArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = B; a.T = T; a.hist = hist; a.n = nx; a.m = m; a.F = (int)F; a.Y = (int)Y;
-  a.st0 = F > 0 ? 0 : hist;
-  const long first = F > 0 ? (nx + F) * 4 * F : (long)nx * Y, nb = F > 0 ? 4 * F : Y;
-  a.Wcat = expert;
-  a.bcat = expert + first;
-  a.WcatT = c->evT.p;
-  const long hx_off = first + nb, hu_off = hx_off + mlp_count(L, es->head_dims_x);
-  bind_mlp(a.hx, L, es->head_dims_x, expert + hx_off, c->evT.p + hx_off);
-  bind_mlp(a.hu, L, es->head_dims_u, expert + hu_off, c->evT.p + hu_off);
-  {
-    // the row layout is k_expert_fit's
-    ExpertFitArgs f;
-    memset(&f, 0, sizeof(f));
-    f.n = nx; f.m = m; f.F = (int)F; f.Y = (int)Y; f.hx = a.hx; f.hu = a.hu;
-    a.stride = gmpc_expert_fit_layout(f);
-    a.hw = f.hw;
-    for (int l = 0; l < L; ++l) { a.ax[l] = f.ax[l]; a.au[l] = f.au[l]; a.dx[l] = f.dx[l]; a.du[l] = f.du[l]; }
-  }
-  a.sstride = (F > 0 ? 6 * (int)F : 0) + m;
-  ExpertVjpMats mats;
-  memset(&mats, 0, sizeof(mats));
-  auto add_mat = [&](int R, int C, const float* in, const float* out) {
-    mats.R[mats.nm] = R; mats.C[mats.nm] = C; mats.in[mats.nm] = in; mats.out[mats.nm] = const_cast<float*>(out);
-    ++mats.nm;
-  };
-  add_mat(F > 0 ? (int)(nx + F) : nx, (int)nb, a.Wcat, a.WcatT);
-  for (int l = 0; l < L; ++l) {
-    add_mat(a.hx.dims[l], a.hx.dims[l + 1], a.hx.W[l], a.hx.WT[l]);
-    add_mat(a.hu.dims[l], a.hu.dims[l + 1], a.hu.W[l], a.hu.WT[l]);
-  }
-  const size_t rows = (size_t)B * (hist + T - a.st0), head0 = (size_t)B * (hist - a.st0), stride = (size_t)a.stride;
-  TRY(c->evacts.reserve(c, rows, stride, s));
-  if (grad_expert_sum) TRY(c->evdels.reserve(c, rows, stride, s));
-  TRY(c->evsave.grow(c, gmpc_expert_vjp_save_floats(a)));
+  a.B = B; a.T = T; a.hist = hist;
+  bind_expert(a.net, nx, m, es, expert, k.aux.p);
+  a.st0 = a.net.F > 0 ? 0 : hist;
+  a.sstride = (a.net.F > 0 ? 6 * a.net.F : 0) + m;
+  const size_t rows = (size_t)B * (hist + T - a.st0), head0 = (size_t)B * (hist - a.st0), stride = (size_t)a.net.stride;
+  TRY(k.acts.reserve(c, rows, stride, s));
+  if (grad_expert_sum) TRY(k.dels.reserve(c, rows, stride, s));
+  TRY(k.save.grow(c, gmpc_expert_vjp_save_floats(a)));
   a.history = history; a.g_goal = g_goal; a.g_U = g_U;
-  a.acts = c->evacts.p;
-  a.dels = grad_expert_sum ? c->evdels.p : nullptr;
-  a.save = reinterpret_cast<float4*>(c->evsave.p);
+  a.acts = k.acts.p;
+  a.dels = grad_expert_sum ? k.dels.p : nullptr;
+  a.save = reinterpret_cast<float4*>(k.save.p);
   a.grad_history = grad_history;
-  if (gmpc_launch_expert_vjp(a, mats, s) != 0) return fail(GMPC_EINVAL, "expert vjp kernel: unsupported shape");
-  if (grad_expert_sum) {
-    // [Wx | Wh] (or W_first) over every row the kernel ran; the heads over the rows with head deltas (st >= hist) only
-    float* g = grad_expert_sum;
-    const int R = (int)rows, Rh = B * T, M0 = F > 0 ? (int)(nx + F) : nx, N0 = (int)nb;
-    gmpc_launch_wgrad(R, M0, N0, a.acts, (int)stride, a.dels, (int)stride, g, g + (long)M0 * N0, R, c->wpart, s,
-                      c->wpart_floats, true);
-    g += (long)M0 * N0 + N0;
-    const float* hacts = a.acts + head0 * stride;
-    const float* hdels = a.dels + head0 * stride;
-    for (int h = 0; h < 2; ++h) {
-      const MlpDesc& d = h == 0 ? a.hx : a.hu;
-      for (int l = 0; l < L; ++l) {
-        const int M = d.dims[l], N = d.dims[l + 1];
-        const int ao = h == 0 ? a.ax[l] : a.au[l], dof = h == 0 ? a.dx[l] : a.du[l];
-        gmpc_launch_wgrad(Rh, M, N, hacts + ao, (int)stride, hdels + dof, (int)stride, g, g + (long)M * N, Rh, c->wpart,
-                          s, c->wpart_floats, true);
-        g += (long)M * N + N;
-      }
-    }
-  }
+  if (gmpc_launch_expert_vjp(a, s) != 0) return fail(GMPC_EINVAL, "expert vjp kernel: unsupported shape");
+  // [Wx | Wh] (or W_first) over every row the kernel ran; the heads over the rows with head deltas (st >= hist) only
+  if (grad_expert_sum)
+    expert_wgrad(c, a.net, a.acts, a.dels, (int)rows, a.acts + head0 * stride, a.dels + head0 * stride, B * T,
+                 grad_expert_sum, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_costvjp(int B, int T, int n, i
                                                           const float* X, const float* U,
                                                           const float* goal, int ng, const float* Hc,
                                                           const float* dX, float* gmpc /*[B][3]*/,
-                                                          float* cact, float* cdel, int stride) {
+                                                          float* cact, float* cdel, MlpRows rows) {
   // bufA holds the terminal state (n rows, may exceed the 256-wide layers); dynamic LDS
   extern __shared__ __attribute__((aligned(16))) char smem_cv[];
   float4* bufA = reinterpret_cast<float4*>(smem_cv);
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_costvjp(int B, int T, int n, i
   __shared__ float red[2][GMPC_THREADS / 64];
   __shared__ float yv[2][64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int b = blockIdx.x;
+  const int b = blockIdx.x, stride = rows.stride;
   const float al = GMPC_ALPHA;
   const float r0 = mpc_w[0], r1 = mpc_w[1], r2 = mpc_w[2];
   const float w0 = sigmoidf_(r0), w1 = sigmoidf_(r1), w2 = sigmoidf_(r2);
@@ -118,9 +118,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_costvjp(int B, int T, int n, i
     cact[(size_t)(B + b) * stride + i] = dX[xi];
   }
   __syncthreads();
-  int aoff = n;
   for (int l = 0; l < Lc; ++l) {
-    const int K = cm.dims[l], N = cm.dims[l + 1];
+    const int K = cm.dims[l], N = cm.dims[l + 1], aoff = rows.aoff[l + 1];
     float4 acc[1] = {make_float4(tid < N ? cm.b[l][tid] : 0.f, 0.f, 0.f, 0.f)};
     dense_rows<1>(cm.W[l], K, N, tid, in, acc);
     if (tid < N) {
@@ -131,7 +130,6 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_costvjp(int B, int T, int n, i
       cact[(size_t)b * stride + aoff + tid] = pa;
       cact[(size_t)(B + b) * stride + aoff + tid] = ta;
     }
-    aoff += N;
     __syncthreads();
     float4* tmp = in; in = out; out = tmp;
   }
@@ -159,10 +157,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_costvjp(int B, int T, int n, i
   }
   // ---- backward: adjoints of (y, ydot) are (ydot, y) * 2 w2 * sign
   const float scale = 2.f * w2 * sign;
-  int doff = 0;
-  for (int l = 0; l <= Lc; ++l) doff += cm.dims[l + 1];
-  doff -= fo;
   if (tid < fo) {
+    const int doff = rows.doff[Lc];
     const float yb = yv[1][tid] * scale, ydb = yv[0][tid] * scale;
     out[tid] = make_float4(yb, ydb, 0.f, 0.f);
     cdel[(size_t)b * stride + doff + tid] = yb;
@@ -173,8 +169,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_costvjp(int B, int T, int n, i
     const int K = cm.dims[l + 1], N = cm.dims[l];
     float4 acc[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
     dense_rows<1>(cm.WT[l], K, N, tid, out, acc);
-    doff -= N;
     if (tid < N) {
+      const int doff = rows.doff[l - 1];
       const float mk = zpos[l - 1][tid];
       const float zb = acc[0].x * mk, zdb = acc[0].y * mk;
       in[tid] = make_float4(zb, zdb, 0.f, 0.f);
@@ -199,10 +195,10 @@ void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* 
 void gmpc_launch_costvjp(int B, int T, int n, int m, const MlpDesc& cm, const float* mpc_w,
                          float sign, const float* X, const float* U, const float* goal, int ng,
                          const float* Hc, const float* dX, float* gmpc, float* cact, float* cdel,
-                         int stride, hipStream_t s) {
+                         const MlpRows& rows, hipStream_t s) {
   const size_t lds = ((size_t)(n > GMPC_THREADS ? n : GMPC_THREADS) + GMPC_THREADS) * sizeof(float4);
   hipLaunchKernelGGL(k_costvjp, dim3(B), dim3(GMPC_THREADS), lds, s, B, T, n, m, cm, mpc_w, sign, X, U,
-                     goal, ng, Hc, dX, gmpc, cact, cdel, stride);
+                     goal, ng, Hc, dX, gmpc, cact, cdel, rows);
 }
 
 // a4: cost_model.get_cost(x, u, t, ...) for one (x, u) per workgroup, outside a rollout (reference

@@ -499,13 +499,13 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
                                                            const float* __restrict__ label, float* __restrict__ score,
                                                            float* __restrict__ loss, float* __restrict__ acts,
                                                            float* __restrict__ dels, float* __restrict__ plast,
-                                                           float* __restrict__ dhT, int act_stride) {
+                                                           float* __restrict__ dhT, MlpRows rows) {
   constexpr int R = 4 * G;
   __shared__ __attribute__((aligned(16))) float img[2][G * 1024];     // [buffer][group][k][4 rows]
   __shared__ float red[4][R];
   __shared__ float dsc[R];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-  const int s0 = blockIdx.x * R;
+  const int s0 = blockIdx.x * R, act_stride = rows.stride;
   const MlpDesc& hd = cd.head;
   const int L = hd.L;
   // layer-0 input: the final LSTM state (F0 = lstm_features values per sequence), rows clamped; the image is read in
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
   }
   __syncthreads();
   unsigned zmask[GMPC_MAX_LAYERS];       // bit 4 g + s: relu open for row (g, s) of this thread's neuron
-  int in = 0, aoff = F0;
+  int in = 0;
 #pragma unroll
   for (int lay = 0; lay < GMPC_MAX_LAYERS; ++lay) {
     zmask[lay] = 0;
@@ -549,12 +549,11 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
           zm |= open ? (1u << (4 * g + s)) : 0u;
           r[s] = open ? z : 0.f;
           const int row = s0 + 4 * g + s;
-          if (tid < N && row < Bc) acts[(size_t)row * act_stride + aoff + tid] = r[s];
+          if (tid < N && row < Bc) acts[(size_t)row * act_stride + rows.aoff[lay + 1] + tid] = r[s];
         }
         if (tid < Npad) *reinterpret_cast<float4*>(&out[g * 1024 + tid * 4]) = make_float4(r[0], r[1], r[2], r[3]);
       }
       zmask[lay] = zm;
-      aoff += N;
       in ^= 1;
       __syncthreads();
     }
@@ -605,9 +604,6 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
   }
   __syncthreads();
   // delta of the last layer, its gradient products, and the delta handed to the layer below
-  int doff = 0;
-  for (int lay = 0; lay < L; ++lay) doff += hd.dims[lay + 1];
-  doff -= 1;
   {
     float* out = img[in ^ 1];
     const int Kpad = (KL + 15) & ~15;
@@ -622,7 +618,7 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
           if (tid < KL) plast[(size_t)row * GMPC_HEAD2_LD + tid] = av[g][s] * ds;
           if (tid == 0) {
             plast[(size_t)row * GMPC_HEAD2_LD + KL] = ds;
-            dels[(size_t)row * act_stride + doff] = ds;
+            dels[(size_t)row * act_stride + rows.doff[L - 1]] = ds;
           }
         }
         const bool open = L == 1 || ((zmask[(L + GMPC_MAX_LAYERS - 2) % GMPC_MAX_LAYERS] >> (4 * g + s)) & 1u);
@@ -637,8 +633,7 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
 #pragma unroll
   for (int lay = GMPC_MAX_LAYERS - 2; lay >= 0; --lay) {
     if (lay < L - 1) {
-      const int K = hd.dims[lay], N = hd.dims[lay + 1];
-      doff -= N;
+      const int K = hd.dims[lay], N = hd.dims[lay + 1], doff = rows.doff[lay];
       // this layer's delta for the weight gradients
       if (tid < N) {
 #pragma unroll
@@ -697,41 +692,15 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_head2(int Bc, CriticDesc cd
   }
 }
 
-// all transposes of an MLP's kernels in one launch: blockIdx.z = layer, 32 x 32 tiles through LDS
-__global__ __launch_bounds__(256) void k_mlp_transpose_all(MlpDesc d) {
-  __shared__ float tile[32][33];
-  const int lay = blockIdx.z;
-  const int R = d.dims[lay], C = d.dims[lay + 1];
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-  if (r0 >= R || c0 >= C) return;
-  const float* in = d.W[lay];
-  float* out = const_cast<float*>(d.WT[lay]);
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8)
-    if (r0 + r < R && c0 + tx < C) tile[r][tx] = in[(size_t)(r0 + r) * C + c0 + tx];
-  __syncthreads();
-  for (int cc = ty; cc < 32; cc += 8)
-    if (c0 + cc < C && r0 + tx < R) out[(size_t)(c0 + cc) * R + r0 + tx] = tile[tx][cc];
-}
-
-void gmpc_launch_mlp_transpose_all(const MlpDesc& d, hipStream_t s) {
-  int rmax = 1, cmax = 1;
-  for (int l = 0; l < d.L; ++l) {
-    rmax = d.dims[l] > rmax ? d.dims[l] : rmax;
-    cmax = d.dims[l + 1] > cmax ? d.dims[l + 1] : cmax;
-  }
-  hipLaunchKernelGGL(k_mlp_transpose_all, dim3((cmax + 31) / 32, (rmax + 31) / 32, d.L), dim3(256), 0, s, d);
-}
-
 // rows per workgroup = 4 G with G = 2.  Measured (C3, 2048 sequences, head 3 x 256, alone): G = 2 0.049 ms, 3 0.056,
 // 4 0.063 -- the layer chain is latency-bound per workgroup, more workgroups beat more rows per weight load
 int gmpc_head2_rows() { return 8; }
 
 void gmpc_launch_head2(int Bc, const CriticDesc& cd, int loss_kind, const float* hT, const float* label, float* score,
-                       float* loss, float* acts, float* dels, float* plast, float* dhT, int act_stride,
+                       float* loss, float* acts, float* dels, float* plast, float* dhT, const MlpRows& rows,
                        hipStream_t s) {
   const int R = gmpc_head2_rows();
   const dim3 grid((Bc + R - 1) / R), blk(GMPC_THREADS);
   hipLaunchKernelGGL(k_head2<2>, grid, blk, 0, s, Bc, cd, loss_kind, hT, label, score, loss, acts, dels, plast, dhT,
-                     act_stride);
+                     rows);
 }

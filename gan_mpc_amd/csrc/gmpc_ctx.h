@@ -40,6 +40,17 @@ struct PadRows : GrowBuf {
   int reserve(gmpc_ctx* c, size_t rows, size_t stride, hipStream_t s);
 };
 
+// The workspace of one call of a gradient entry point (gmpc_expert_loss_grad, gmpc_bilevel_grad_dynamics,
+// gmpc_rollout_vjp, gmpc_expert_vjp): each reserves what it needs at its top.  The contents are dead when the entry
+// point returns, and calls on one context are stream-ordered (as the shared wpart / scratch already require), so every
+// call may take all of it.  PadRows::reserve zeroes the pad rows on every call: that, not a first allocation, is what
+// keeps them finite behind whatever an earlier call with other rows and another stride left there.
+struct CallWork {
+  PadRows acts, dels;     // the rows of the call's main network
+  PadRows acts2, dels2;   // a second network's (gmpc_rollout_vjp: the cost MLP's)
+  GrowBuf save, aux, aux2;
+};
+
 struct gmpc_ctx {
   gmpc_shape sh;
   GmpcComm comm;
@@ -73,13 +84,13 @@ struct gmpc_ctx {
   int gradB = 0;
   // bilevel workspace
   float *lx, *Bvec, *Hout, *dX, *gmpc, *cact, *cdel, *bl_loss;
-  int cstride;
+  // acts / dels rows of the dynamics MLP (dynl: its tail), the cost MLP and the critic head
+  MlpRows drows{}, crows{}, hrows{};
   // critic workspace
   float *critT, *gates, *cs, *hp, *hT, *dz, *hacts, *hdels, *dhT, *cscore, *closs;
   float* lwp = nullptr;        // weight-gradient partials of k_lstm_bwd2, one [85][256] block per 4 sequences
   // k_head2: last layer's act * dscore products and dscore, [Bc + GMPC_WGRAD_PAD][GMPC_HEAD2_LD]
   float* plast = nullptr;
-  int hstride;
   LsWork lsw{};
   // large-state (n > 64) backward pass
   bool big = false;
@@ -88,19 +99,8 @@ struct gmpc_ctx {
   // dynamics regression (allocated on first use)
   float *dfpred = nullptr, *dfacts = nullptr, *dfdels = nullptr, *dfloss = nullptr, *dfsave = nullptr;
   int dfstride = 0;
-  // expert model training (gmpc_expert_loss_grad)
-  PadRows efacts, efdels;
-  GrowBuf efsave;
-  float* efloss = nullptr;
-  // dynamics-weight gradient (gmpc_bilevel_grad_dynamics)
-  GrowBuf dgw, dglam;
-  PadRows dgacts, dgdels;
-  // rollout VJP (gmpc_rollout_vjp): its own relu masks, per-trajectory mpc_w terms, cost and dynamics rows
-  GrowBuf rvmask, rvgm;
-  PadRows rvcact, rvcdel, rvacts, rvdels;
-  // expert rollout VJP (gmpc_expert_vjp): its rows, the kernel's save rows, the transposed weight copies
-  PadRows evacts, evdels;
-  GrowBuf evsave, evT;
+  float* efloss = nullptr;     // per-window losses of gmpc_expert_loss_grad
+  CallWork cw;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;
@@ -158,6 +158,36 @@ static void bind_mlp(MlpDesc& d, int L, const int* dims, const float* flat, floa
     off += (long)dims[l] * dims[l + 1];
     d.b[l] = flat + off;
     off += dims[l + 1];
+  }
+}
+
+// The expert model of shape `es` in the flat vector `expert` = Wcat | bcat | head_x | head_u (expertT: the same layout
+// for the transposed copies, or null), and the acts / dels row layout of its kernels.
+static void bind_expert(ExpertNet& e, int nx, int m, const gmpc_expert_shape* es, const float* expert, float* expertT) {
+  const int L = es->head_layers;
+  e.n = nx; e.m = m; e.F = es->lstm_features; e.Y = es->head_dims_x[0];
+  const long first = e.F > 0 ? (long)(nx + e.F) * 4 * e.F : (long)nx * e.Y, nb = e.F > 0 ? 4 * e.F : e.Y;
+  const long hx_off = first + nb, hu_off = hx_off + mlp_count(L, es->head_dims_x);
+  e.Wcat = expert;
+  e.bcat = expert + first;
+  e.WcatT = expertT;
+  bind_mlp(e.hx, L, es->head_dims_x, expert + hx_off, expertT ? expertT + hx_off : nullptr);
+  bind_mlp(e.hu, L, es->head_dims_u, expert + hu_off, expertT ? expertT + hu_off : nullptr);
+  // acts row: [x_in | h_prev | y | head_x inputs a_1.. | head_u inputs a_1..]; dels row: [dz or d y_pre | head_x output
+  // deltas | head_u output deltas]
+  int off = nx + e.F + e.Y;
+  e.ax[0] = e.au[0] = nx + e.F;
+  for (int l = 1; l < L; ++l) { e.ax[l] = off; off += e.hx.dims[l]; }
+  for (int l = 1; l < L; ++l) { e.au[l] = off; off += e.hu.dims[l]; }
+  const int in_w = off;
+  off = (int)nb;
+  for (int l = 0; l < L; ++l) { e.dx[l] = off; off += e.hx.dims[l + 1]; }
+  for (int l = 0; l < L; ++l) { e.du[l] = off; off += e.hu.dims[l + 1]; }
+  e.stride = in_w > off ? in_w : off;
+  e.hw = 1;
+  for (int l = 0; l <= L; ++l) {
+    e.hw = e.hx.dims[l] > e.hw ? e.hx.dims[l] : e.hw;
+    e.hw = e.hu.dims[l] > e.hw ? e.hu.dims[l] : e.hw;
   }
 }
 

@@ -22,6 +22,21 @@ struct MlpDesc {
   const float* b[GMPC_MAX_LAYERS];
 };
 
+// The acts / dels rows of one MLP, the operands of its weight-gradient GEMMs (gmpc_launch_wgrad_mlp): layer l's inputs
+// are columns aoff[l].. of an acts row, its output deltas columns doff[l].. of a dels row, both `stride` floats long
+// (the larger of the summed input and the summed output widths).
+struct MlpRows { int aoff[GMPC_MAX_LAYERS], doff[GMPC_MAX_LAYERS], stride; };
+inline MlpRows mlp_rows(int L, const int* dims) {
+  MlpRows r{};
+  int in = 0, out = 0;
+  for (int l = 0; l < L; ++l) {
+    r.aoff[l] = in; r.doff[l] = out;
+    in += dims[l]; out += dims[l + 1];
+  }
+  r.stride = in > out ? in : out;
+  return r;
+}
+
 // Sum over the 64 lanes, result in every lane.  Data-parallel-primitive moves instead of
 // __shfl_xor: the shuffle compiles to ds_bpermute_b32, a round trip through the LDS crossbar (~150
 // cycles each, six per sum), DPP row operations are plain VALU modifiers.  Steps: within quads, within
@@ -242,53 +257,55 @@ struct WgProb {
 #define GMPC_WG_MAX 8
 struct WgBatch { int np; int gemm_blocks; WgProb p[GMPC_WG_MAX]; };
 
-// expert sequence model (gmpc_expert.hip)
+// The expert sequence model as its three kernels see it (bind_expert, gmpc_ctx.h), and the column layout of the acts /
+// dels rows that k_expert_fit and k_expert_vjp emit (see the header of gmpc_expert_fit.hip)
+struct ExpertNet {
+  int n, m, F, Y, hw;            // F == 0: the MLP variant (first = Dense(n -> Y) + relu); Y = width of y; hw = widest
+                                 // head layer
+  const float* Wcat;             // LSTM: [(n+F)][4F] (Wx rows, then Wh rows);  MLP: first.W [n][Y]
+  const float* bcat;             // LSTM: [4F];  MLP: first.b [Y]
+  const float* WcatT;            // the transposed copy of Wcat, or null
+  MlpDesc hx, hu;                // heads: dims[0] = Y ... dims[L] = n / m; WT[l]: the transposed copies, or null
+  int ax[GMPC_MAX_LAYERS], au[GMPC_MAX_LAYERS];    // acts offsets of the heads' layer inputs
+  int dx[GMPC_MAX_LAYERS], du[GMPC_MAX_LAYERS];    // dels offsets of the heads' layer output deltas
+  int stride;                    // floats per acts / dels row
+};
+
+// expert sequence model inference (gmpc_expert.hip)
 struct ExpertArgs {
-  int B, n, m, T, hist, F;       // F == 0: the MLP variant (first = Dense(n -> h) + relu)
-  const float* Wcat;             // LSTM: [(n+F)][4F];  MLP: first.W [n][h]
-  const float* bcat;             // LSTM: [4F];         MLP: first.b [h]
-  MlpDesc hx, hu;                // heads: dims[0] = F (or h) ... dims[L] = n / m
+  int B, T, hist;
+  ExpertNet net;                 // hw: raised by the launcher to the LDS activations per head it sizes
   const float* history;          // [B][hist+1][n]
   float* goal;                   // [B][T+1][n]
   float* U;                      // [B][T][m]
-  int hw;                        // set by the launcher: LDS activations per head (>= every head width)
 };
 
 // expert sequence model training (gmpc_expert_fit.hip): one minibatch of windows, loss and BPTT
 struct ExpertFitArgs {
-  int B, S, n, m, F, Y, hw;      // F == 0: the MLP variant; Y = width of y; hw = widest head layer
-  const float* Wcat;             // LSTM: [(n+F)][4F] (Wx rows, then Wh rows);  MLP: [n][Y]
-  const float* bcat;             // LSTM: [4F];  MLP: [Y]
-  MlpDesc hx, hu;                // heads, dims[0] = Y
-  int ax[GMPC_MAX_LAYERS], au[GMPC_MAX_LAYERS];    // acts offsets of the heads' layer inputs
-  int dx[GMPC_MAX_LAYERS], du[GMPC_MAX_LAYERS];    // dels offsets of the heads' layer output deltas
+  int B, S;
+  ExpertNet net;
   const float* xseq; const float* useq; const float* yseq;   // [B][S][n], [B][S][m], [B][S][n]
   float gamma;
   int teacher_forcing, grad;
-  float* acts; float* dels; int stride;
+  float* acts; float* dels;
   float* save; int sstride;
   float* loss;                   // [B]
 };
 
 // VJP of the expert rollout (gmpc_expert_vjp.hip): the rollout's schedule, cotangents of goal and init_U in
 struct ExpertVjpArgs {
-  int B, T, hist, n, m, F, Y, hw; // F == 0: the MLP variant; Y = width of y; hw = widest head layer
+  int B, T, hist;
   int st0;                       // first step the kernel runs: 0 (LSTM), hist (MLP: no carry through the history)
-  const float* Wcat;             // LSTM: [(n+F)][4F] (Wx rows, then Wh rows);  MLP: [n][Y]
-  const float* bcat;             // LSTM: [4F];  MLP: [Y]
-  const float* WcatT;            // the transposed copy of Wcat
-  MlpDesc hx, hu;                // heads, dims[0] = Y; WT[l]: the transposed copies
-  int ax[GMPC_MAX_LAYERS], au[GMPC_MAX_LAYERS];    // acts offsets of the heads' layer inputs
-  int dx[GMPC_MAX_LAYERS], du[GMPC_MAX_LAYERS];    // dels offsets of the heads' layer output deltas
+  ExpertNet net;                 // with the transposed copies
   const float* history;          // [B][hist+1][n]
   const float* g_goal;           // [B][T+1][n] or null (zero)
   const float* g_U;              // [B][T][m] or null (zero)
-  float* acts; float* dels; int stride;   // rows (st - st0) B + b; dels null: no parameter gradient wanted
+  float* acts; float* dels;      // rows (st - st0) B + b; dels null: no parameter gradient wanted
   float4* save; int sstride;     // per (workgroup, step - st0): sstride float4
   float* grad_history;           // [B][hist+1][n] or null
 };
-// the matrices k_expert_transpose_all turns in one launch: in [R][C] -> out [C][R]
-struct ExpertVjpMats {
+// the matrices k_transpose_all (gmpc_optim.hip) turns in one launch: in [R][C] -> out [C][R]
+struct TransposeList {
   int nm;
   int R[2 * GMPC_MAX_LAYERS + 1], C[2 * GMPC_MAX_LAYERS + 1];
   const float* in[2 * GMPC_MAX_LAYERS + 1];

@@ -194,11 +194,11 @@ __device__ __forceinline__ void dg_gemm(const float* A, int K, int N, const floa
 
 // rows: B T steps, r = b T + t.  acts / dels: [2 rows][stride]; row r holds the primal layer inputs a_0 .. a_{L-1}
 // and delta_1(w) .. delta_L(w), row rows + r the negated tangent inputs -a'_0 .. -a'_{L-1} and delta_1(lam) ..
-// delta_L(lam).  aoff[l] / doff[l]: the column of a_l / delta_{l+1} in a row.
+// delta_L(lam).  lay: the column of a_l / delta_{l+1} in a row, and the row stride.
 struct DgRowArgs {
-  int rows, T, n, m, stride;
+  int rows, T, n, m;
   MlpDesc dyn;
-  int aoff[GMPC_MAX_LAYERS], doff[GMPC_MAX_LAYERS];
+  MlpRows lay;
   const float *X, *U, *dX, *H, *w, *lam;
   float *acts, *dels;
 };
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_rows(DgRowArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
   const int n = a.n, m = a.m, nm = n + m, L = a.dyn.L, T = a.T;
   const int r0 = blockIdx.x * GMPC_DG_ROWS;
-  const size_t st = a.stride, tro = (size_t)a.rows;   // the tangent row of step r is tro + r
+  const size_t st = a.lay.stride, tro = (size_t)a.rows;   // the tangent row of step r is tro + r
   // ---- layer 0 inputs: [x_t; u_t] and [dX_t; H_t]
   for (int e = tid; e < GMPC_DG_ROWS * nm; e += GMPC_DG_THREADS) {
     const int i = e / nm, c = e - i * nm, r = r0 + i;
@@ -250,8 +250,8 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_rows(DgRowArgs a) {
         Ab[(16 + i) * GMPC_DG_LDA + j] = q;
         ml[i * 256 + j] = on ? 1 : 0;
         if (r < a.rows) {
-          a.acts[(size_t)r * st + a.aoff[l + 1] + j] = p;
-          a.acts[(tro + r) * st + a.aoff[l + 1] + j] = -q;
+          a.acts[(size_t)r * st + a.lay.aoff[l + 1] + j] = p;
+          a.acts[(tro + r) * st + a.lay.aoff[l + 1] + j] = -q;
         }
       }
     }
@@ -264,8 +264,8 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_rows(DgRowArgs a) {
     if (r < a.rows) {
       p = a.w[(size_t)r * n + c];
       q = a.lam[(size_t)r * n + c];
-      a.dels[(size_t)r * st + a.doff[L - 1] + c] = p;
-      a.dels[(tro + r) * st + a.doff[L - 1] + c] = q;
+      a.dels[(size_t)r * st + a.lay.doff[L - 1] + c] = p;
+      a.dels[(tro + r) * st + a.lay.doff[L - 1] + c] = q;
     }
     Ab[i * GMPC_DG_LDA + c] = p;
     Ab[(16 + i) * GMPC_DG_LDA + c] = q;
@@ -288,8 +288,8 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_rows(DgRowArgs a) {
         Ab[i * GMPC_DG_LDA + j] = p;
         Ab[(16 + i) * GMPC_DG_LDA + j] = q;
         if (r < a.rows) {
-          a.dels[(size_t)r * st + a.doff[l - 1] + j] = p;
-          a.dels[(tro + r) * st + a.doff[l - 1] + j] = q;
+          a.dels[(size_t)r * st + a.lay.doff[l - 1] + j] = p;
+          a.dels[(tro + r) * st + a.lay.doff[l - 1] + j] = q;
         }
       }
     }
@@ -315,26 +315,14 @@ void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* m
                        dX, lx, AB, QT, qT, w, lam);
 }
 
-int gmpc_dyn_rows_stride(const MlpDesc& d) {
-  int in = 0, out = 0;
-  for (int l = 0; l < d.L; ++l) { in += d.dims[l]; out += d.dims[l + 1]; }
-  return in > out ? in : out;
-}
-
 int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const float* X, const float* U,
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
-                         hipStream_t s) {
+                         const MlpRows& lay, hipStream_t s) {
   DgRowArgs a;
   memset(&a, 0, sizeof(a));
   for (int l = 0; l <= dyn.L; ++l)
     if (dyn.dims[l] > 256) return 1;
-  a.rows = B * T; a.T = T; a.n = n; a.m = m; a.dyn = dyn;
-  a.stride = gmpc_dyn_rows_stride(dyn);
-  int ao = 0, dof = 0;
-  for (int l = 0; l < dyn.L; ++l) {
-    a.aoff[l] = ao; a.doff[l] = dof;
-    ao += dyn.dims[l]; dof += dyn.dims[l + 1];
-  }
+  a.rows = B * T; a.T = T; a.n = n; a.m = m; a.dyn = dyn; a.lay = lay;
   a.X = X; a.U = U; a.dX = dX; a.H = H; a.w = w; a.lam = lam; a.acts = acts; a.dels = dels;
   const size_t lds = 32 * GMPC_DG_LDA * sizeof(float) + (size_t)(dyn.L > 1 ? dyn.L - 1 : 1) * GMPC_DG_ROWS * 256;
   hipLaunchKernelGGL(k_dyn_rows, dim3((a.rows + GMPC_DG_ROWS - 1) / GMPC_DG_ROWS), dim3(GMPC_DG_THREADS), lds, s, a);

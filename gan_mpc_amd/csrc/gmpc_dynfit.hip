@@ -21,7 +21,7 @@ struct DynFitArgs {
   float* pred;         // [B][S][n]
   float* acts;         // [B*S][stride]: a_0 | a_1 | ... | a_{L-1}   (layer inputs)
   float* dels;         // [B*S][stride]: d_1 | ... | d_L             (layer output deltas)
-  int stride;
+  MlpRows rows;        // a_l starts at aoff[l], d_{l+1} (the delta at the output of layer l) at doff[l]
   float* loss;         // [B]
   int W;               // LDS activations per buffer (>= every layer width and n + m)
 };
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
   float* disc = reinterpret_cast<float*>(gsv + a.W);       // [S]
   float* red = disc + a.S;                                 // [4 * 4] loss partials per wave
   const int tid = threadIdx.x;
-  const int n = a.n, m = a.m, S = a.S, L = a.dyn.L, nm = n + m;
+  const int n = a.n, m = a.m, S = a.S, L = a.dyn.L, nm = n + m, stride = a.rows.stride;
   const int s0 = blockIdx.x * SB;
   float* xinf = reinterpret_cast<float*>(xin);
   if (tid == 0) {
@@ -62,12 +62,11 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
       const int s = min(s0 + sb, a.B - 1);
       const float v = i < n ? xinf[i * SB + sb] : a.useq[((size_t)s * S + t) * m + (i - n)];
       af[i * SB + sb] = v;
-      if (s0 + sb < a.B) a.acts[((size_t)s * S + t) * a.stride + i] = v;
+      if (s0 + sb < a.B) a.acts[((size_t)s * S + t) * stride + i] = v;
     }
     __syncthreads();
     float4* cur = bufA;
     float4* nxt = bufB;
-    int fo = nm;                 // offset of a_{l+1} in the acts row
     for (int l = 0; l < L; ++l) {
       const int K = a.dyn.dims[l], N = a.dyn.dims[l + 1];
       for (int j = tid; j < N; j += GMPC_THREADS) {
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
 #pragma unroll
           for (int cc = 0; cc < 4; ++cc)
             if (s0 + cc < a.B)
-              a.acts[((size_t)(s0 + cc) * S + t) * a.stride + fo + j] = f4get(v, cc);
+              a.acts[((size_t)(s0 + cc) * S + t) * stride + a.rows.aoff[l + 1] + j] = f4get(v, cc);
         } else {
           const float4 x = xin[j];
           v.x += x.x; v.y += x.y; v.z += x.z; v.w += x.w;
@@ -102,7 +101,6 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
         }
       }
       __syncthreads();
-      fo += N;
       float4* tmp = cur; cur = nxt; nxt = tmp;
     }
   }
@@ -117,10 +115,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
   if (tid < SB && s0 + tid < a.B)
     a.loss[s0 + tid] = ((red[tid] + red[4 + tid]) + red[8 + tid]) + red[12 + tid];
   // ---------------------------------------------------------------- BPTT sweep
-  // row layouts: a_l starts at aoff(l), d_{l+1} (the delta at the output of layer l) at doff(l)
-  auto aoff = [&](int l) { int o = l == 0 ? 0 : nm; for (int i = 1; i < l; ++i) o += a.dyn.dims[i]; return o; };
-  auto doff = [&](int l) { int o = 0; for (int i = 1; i <= l; ++i) o += a.dyn.dims[i]; return o; };
-  const int doff_last = doff(L - 1);
+  const int doff_last = a.rows.doff[L - 1];
   for (int t = S - 1; t >= 0; --t) {
     for (int j = tid; j < n; j += GMPC_THREADS) {
       float g[4];
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
         const int s = min(s0 + cc, a.B - 1);
         const size_t o = ((size_t)s * S + t) * n + j;
         g[cc] = w2 * (a.pred[o] - a.yseq[o]) + f4get(lm, cc);
-        if (s0 + cc < a.B) a.dels[((size_t)s * S + t) * a.stride + doff_last + j] = g[cc];
+        if (s0 + cc < a.B) a.dels[((size_t)s * S + t) * stride + doff_last + j] = g[cc];
       }
       const float4 gsave = make_float4(g[0], g[1], g[2], g[3]);
       gsv[j] = gsave;
@@ -142,7 +137,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
     float4* nxt = bufB;
     for (int l = L - 1; l >= 1; --l) {
       const int K = a.dyn.dims[l + 1], N = a.dyn.dims[l];      // d_l = relu'(a_l) . (W_l d_{l+1})
-      const int ao = aoff(l), dof = doff(l - 1);
+      const int ao = a.rows.aoff[l], dof = a.rows.doff[l - 1];
       for (int j = tid; j < N; j += GMPC_THREADS) {
         float4 acc[R4] = {make_float4(0.f, 0.f, 0.f, 0.f)};
         dense_rows<R4>(a.dyn.WT[l], K, N, j, cur, acc);
@@ -151,9 +146,9 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
         for (int cc = 0; cc < 4; ++cc) {
           const int s = min(s0 + cc, a.B - 1);
           const size_t row = (size_t)s * S + t;
-          const float al = a.acts[row * a.stride + ao + j];
+          const float al = a.acts[row * stride + ao + j];
           d[cc] = al > 0.f ? f4get(acc[0], cc) : 0.f;
-          if (s0 + cc < a.B) a.dels[row * a.stride + dof + j] = d[cc];
+          if (s0 + cc < a.B) a.dels[row * stride + dof + j] = d[cc];
         }
         nxt[j] = make_float4(d[0], d[1], d[2], d[3]);
       }
@@ -173,15 +168,9 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynfit(DynFitArgs a) {
   }
 }
 
-size_t gmpc_dynfit_stride(const gmpc_shape* s) {
-  size_t in = 0, out = 0;
-  for (int l = 0; l < s->dyn_layers; ++l) { in += s->dyn_dims[l]; out += s->dyn_dims[l + 1]; }
-  return in > out ? in : out;
-}
-
 int gmpc_launch_dynfit(int B, int S, int n, int m, const MlpDesc& dyn, const float* xseq,
                        const float* useq, const float* yseq, float gamma, int teacher_forcing,
-                       float* pred, float* acts, float* dels, int stride, float* loss, hipStream_t s) {
+                       float* pred, float* acts, float* dels, const MlpRows& rows, float* loss, hipStream_t s) {
   int W = GMPC_THREADS;
   for (int l = 0; l <= dyn.L; ++l) W = dyn.dims[l] > W ? dyn.dims[l] : W;
   if (W > 1088) return -1;
@@ -189,7 +178,7 @@ int gmpc_launch_dynfit(int B, int S, int n, int m, const MlpDesc& dyn, const flo
   a.W = W;
   a.B = B; a.S = S; a.n = n; a.m = m; a.dyn = dyn;
   a.xseq = xseq; a.useq = useq; a.yseq = yseq; a.gamma = gamma; a.teacher_forcing = teacher_forcing;
-  a.pred = pred; a.acts = acts; a.dels = dels; a.stride = stride; a.loss = loss;
+  a.pred = pred; a.acts = acts; a.dels = dels; a.rows = rows; a.loss = loss;
   const size_t lds = 5 * (size_t)W * sizeof(float4) + ((size_t)S + 16) * sizeof(float);
   static bool attr = false;
   if (!attr) {

@@ -524,7 +524,8 @@ struct DynlFitArgs {
   float gamma;
   int teacher_forcing;
   float* pred;           // [B][S][nx]
-  float* acts; float* dels; int stride;
+  float* acts; float* dels;
+  MlpRows tail;          // the tail's columns behind [x_in, u | h_prev] / dz in a row, and the whole row's stride
   float* save;           // [B*S][6F]
   float* loss;           // [B]
   int width;
@@ -534,6 +535,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_df[];
   const DynlDesc& d = a.d;
   const int nx = d.nx, F = d.F, m = d.m, G4 = 4 * F, S = a.S, W = a.width, L = d.tail.L, kin = nx + m;
+  const int stride = a.tail.stride, abase = kin + F, dbase = G4;   // where the tail's a_0 / d_1 start
   float* xin = reinterpret_cast<float*>(smem_df);   // nx
   float* uv = xin + nx;                             // m
   float* cs = uv + m;                               // F  c
@@ -559,7 +561,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
   // per-row offsets: acts [x_in,u | h_prev | a_0 | a_1 ...], dels [dz | d_1 | ... | d_L]
   for (int t = 0; t < S; ++t) {
     const size_t row = (size_t)b * S + t;
-    float* arow = a.acts + row * a.stride;
+    float* arow = a.acts + row * stride;
     if (a.teacher_forcing && t > 0) {
       for (int i = tid; i < nx; i += GMPC_THREADS) xin[i] = a.xseq[row * nx + i];
     }
@@ -574,13 +576,11 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
     float* in = hn;
     float* o0 = act0;
     float* o1 = act1;
-    int ao = kin + F;
     for (int l = 0; l < L; ++l) {
-      const int K = d.tail.dims[l], N = d.tail.dims[l + 1];
+      const int K = d.tail.dims[l], N = d.tail.dims[l + 1], ao = abase + a.tail.aoff[l];
       for (int k = tid; k < K; k += GMPC_THREADS) arow[ao + k] = in[k];
       dense_layer(d.tail.W[l], d.tail.b[l], K, N, in, o0, l + 1 < L);
       __syncthreads();
-      ao += K;
       in = o0;
       float* sw = o0; o0 = o1; o1 = sw;
     }
@@ -601,12 +601,11 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
   for (int i = tid; i < nx; i += GMPC_THREADS) lam[i] = 0.f;
   for (int j = tid; j < F; j += GMPC_THREADS) { dcv[j] = 0.f; dhv[j] = 0.f; }
   __syncthreads();
-  int doff_last = G4;
-  for (int l = 1; l < L; ++l) doff_last += d.tail.dims[l];
+  const int doff_last = dbase + a.tail.doff[L - 1];
   for (int t = S - 1; t >= 0; --t) {
     const size_t row = (size_t)b * S + t;
-    const float* arow = a.acts + row * a.stride;
-    float* drow = a.dels + row * a.stride;
+    const float* arow = a.acts + row * stride;
+    float* drow = a.dels + row * stride;
     const float* sv = a.save + row * 6 * F;
     // gout = 2 g^t (pred - y) + lam  -> delta at the tail's output (d_L) ; act0 holds the current delta
     for (int i = tid; i < nx; i += GMPC_THREADS) {
@@ -618,11 +617,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
     __syncthreads();
     float* cur = act0;
     float* nxt = act1;
-    int ao = kin + F, dof = doff_last;
-    for (int l = 0; l < L; ++l) ao += d.tail.dims[l];
     for (int l = L - 1; l >= 0; --l) {
-      const int K = d.tail.dims[l], N = d.tail.dims[l + 1];
-      ao -= K;
+      const int K = d.tail.dims[l], N = d.tail.dims[l + 1], ao = abase + a.tail.aoff[l];
       // delta at layer l's input: W_l cur, masked by relu'(a_l) for l > 0 (a_0 = h' has no relu)
       for (int k = tid; k < K; k += GMPC_THREADS) {
         float acc = 0.f;
@@ -633,7 +629,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
       }
       __syncthreads();
       if (l > 0) {
-        dof -= K;
+        const int dof = dbase + a.tail.doff[l - 1];
         for (int k = tid; k < K; k += GMPC_THREADS) drow[dof + k] = nxt[k];
       }
       float* sw = cur; cur = nxt; nxt = sw;
@@ -672,17 +668,20 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_dynl_fit(DynlFitArgs a) {
 }
 
 size_t gmpc_dynl_fit_stride(const DynlDesc& d) {
-  size_t in = (size_t)d.nx + d.m + d.F, out = 4 * (size_t)d.F;
-  for (int l = 0; l < d.tail.L; ++l) { in += d.tail.dims[l]; out += d.tail.dims[l + 1]; }
+  // [x_in, u | h_prev] / dz in front of the tail's rows
+  const int L = d.tail.L;
+  const MlpRows r = mlp_rows(L, d.tail.dims);
+  const size_t in = (size_t)d.nx + d.m + d.F + r.aoff[L - 1] + d.tail.dims[L - 1];
+  const size_t out = 4 * (size_t)d.F + r.doff[L - 1] + d.tail.dims[L];
   return in > out ? in : out;
 }
 
 void gmpc_launch_dynl_fit(int B, int S, const DynlDesc& d, const float* xseq, const float* useq, const float* yseq,
-                          float gamma, int teacher_forcing, float* pred, float* acts, float* dels, int stride,
-                          float* save, float* loss, hipStream_t s) {
+                          float gamma, int teacher_forcing, float* pred, float* acts, float* dels,
+                          const MlpRows& tail, float* save, float* loss, hipStream_t s) {
   DynlFitArgs a;
   a.B = B; a.S = S; a.d = d; a.xseq = xseq; a.useq = useq; a.yseq = yseq; a.gamma = gamma;
-  a.teacher_forcing = teacher_forcing; a.pred = pred; a.acts = acts; a.dels = dels; a.stride = stride;
+  a.teacher_forcing = teacher_forcing; a.pred = pred; a.acts = acts; a.dels = dels; a.tail = tail;
   a.save = save; a.loss = loss;
   a.width = dynl_width(d, nullptr);
   const size_t lds = ((size_t)2 * d.nx + d.m + 7 * (size_t)d.F + 8 * (size_t)d.F + 2 * (size_t)a.width + S + 8) *

@@ -18,18 +18,19 @@
 __global__ __launch_bounds__(GMPC_EX_THREADS) void k_expert_seq(ExpertArgs a) {
   constexpr int SB = 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const ExpertNet& net = a.net;
   float4* act = reinterpret_cast<float4*>(smem);        // [n + F]: x | h   (LSTM input image)
-  float4* gbuf = act + (a.n + a.F);                     // [512] gates
-  const int hw = a.hw;                                  // activations per head (>= every head width)
+  float4* gbuf = act + (net.n + net.F);                   // [512] gates
+  const int hw = net.hw;                                 // activations per head (>= every head width)
   float4* hA = gbuf + GMPC_EX_THREADS;                  // [2 hw] head activations (x half | u half)
   float4* hB = hA + 2 * hw;                             // [2 hw]
   const int tid = threadIdx.x;
-  const int n = a.n, m = a.m, F = a.F, G4 = 4 * F;
+  const int n = net.n, m = net.m, F = net.F, G4 = 4 * F;
   const int s0 = blockIdx.x * SB;
   float* actf = reinterpret_cast<float*>(act);
   float* gbf = reinterpret_cast<float*>(gbuf);
   const int half = tid >> 8, hj = tid & 255;            // head: 0 = state, 1 = action; neuron index
-  const MlpDesc& hd = half == 0 ? a.hx : a.hu;
+  const MlpDesc& hd = half == 0 ? net.hx : net.hu;
   float c = 0.f;                                        // cell state of (unit tid % F, sequence tid / F)
   for (int e = tid; e < F * SB; e += blockDim.x) actf[n * SB + e] = 0.f;     // h = 0
   const int steps = a.hist + a.T;
@@ -49,9 +50,9 @@ __global__ __launch_bounds__(GMPC_EX_THREADS) void k_expert_seq(ExpertArgs a) {
     // ---- y: LSTM cell or first dense layer
     if (F > 0) {
       if (tid < G4) {
-        const float bj = a.bcat[tid];
+        const float bj = net.bcat[tid];
         float4 acc[1] = {make_float4(bj, bj, bj, bj)};
-        dense_rows<1>(a.Wcat, n + F, G4, tid, act, acc);
+        dense_rows<1>(net.Wcat, n + F, G4, tid, act, acc);
         float4 v = acc[0];
         if (tid >= 2 * F && tid < 3 * F) { v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w); }
         else { v.x = sigmoidf_(v.x); v.y = sigmoidf_(v.y); v.z = sigmoidf_(v.z); v.w = sigmoidf_(v.w); }
@@ -70,11 +71,11 @@ __global__ __launch_bounds__(GMPC_EX_THREADS) void k_expert_seq(ExpertArgs a) {
       // both heads read y = h
       if (hj < F) hA[half * hw + hj] = act[n + hj];
     } else {
-      const int H0 = a.hx.dims[0];
+      const int H0 = net.Y;
       if (tid < H0) {
-        const float bj = a.bcat[tid];
+        const float bj = net.bcat[tid];
         float4 acc[1] = {make_float4(bj, bj, bj, bj)};
-        dense_rows<1>(a.Wcat, n, H0, tid, act, acc);
+        dense_rows<1>(net.Wcat, n, H0, tid, act, acc);
         const float4 v = make_float4(fmaxf(acc[0].x, 0.f), fmaxf(acc[0].y, 0.f), fmaxf(acc[0].z, 0.f),
                                      fmaxf(acc[0].w, 0.f));
         hA[tid] = v;
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(GMPC_EX_THREADS) void k_expert_seq(ExpertArgs a) {
     // ---- heads (same depth): state head on threads 0..255, action head on 256..511
     float4* in = hA;
     float4* out = hB;
-    const int L = a.hx.L;
+    const int L = net.hx.L;
     for (int l = 0; l < L; ++l) {
       const int K = hd.dims[l], N = hd.dims[l + 1];
       for (int j = hj; j < N; j += 256) {
@@ -129,17 +130,13 @@ __global__ __launch_bounds__(GMPC_EX_THREADS) void k_expert_seq(ExpertArgs a) {
 
 int gmpc_launch_expert(const ExpertArgs& a0, hipStream_t s) {
   ExpertArgs a = a0;
-  if (a.n > 1024 || a.m > 1024 || 4 * a.F > GMPC_EX_THREADS) return -1;
-  if (a.hx.L != a.hu.L || a.hx.L < 1) return -1;
-  if (a.F == 0 && a.hx.dims[0] > GMPC_EX_THREADS) return -1;      // MLP variant: one first-layer unit per thread
-  int hw = 256;
-  for (int l = 0; l <= a.hx.L; ++l) {
-    if (a.hx.dims[l] > 1024 || a.hu.dims[l] > 1024) return -1;
-    hw = a.hx.dims[l] > hw ? a.hx.dims[l] : hw;
-    hw = a.hu.dims[l] > hw ? a.hu.dims[l] : hw;
-  }
-  a.hw = hw;
-  const size_t lds = ((size_t)(a.n + a.F) + GMPC_EX_THREADS + 4 * (size_t)hw) * sizeof(float4);
+  ExpertNet& e = a.net;
+  if (e.n > 1024 || e.m > 1024 || 4 * e.F > GMPC_EX_THREADS) return -1;
+  if (e.hx.L != e.hu.L || e.hx.L < 1) return -1;
+  if (e.F == 0 && e.Y > GMPC_EX_THREADS) return -1;      // MLP variant: one first-layer unit per thread
+  if (e.hw > 1024) return -1;
+  if (e.hw < 256) e.hw = 256;
+  const size_t lds = ((size_t)(e.n + e.F) + GMPC_EX_THREADS + 4 * (size_t)e.hw) * sizeof(float4);
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_expert_seq),

@@ -10,8 +10,8 @@
 // path (residual + heads) reaches earlier steps only when teacher forcing is off.
 //
 // k_expert_fit: one 256-thread workgroup per sequence runs the S-step forward and then BPTT in reverse
-// time.  It emits, per row r = b*S + t, the row operands of the weight-gradient GEMMs into the ctx-owned
-// workspace:
+// time.  It emits, per row r = b*S + t, the row operands of the weight-gradient GEMMs into the context's call
+// workspace, at the columns of ExpertNet (bind_expert, gmpc_ctx.h):
 //   acts row: [x_in (n) | h_prev (F, LSTM only) | y (Y) | head_x inputs a_1..a_{L-1} | head_u inputs ...]
 //   dels row: [dz (4F) or d y_pre (Y) | head_x output deltas d_1..d_L | head_u output deltas d_1..d_L]
 //   save row: [activated gates (4F) | c_prev (F) | tanh(c') (F)  (LSTM only) | next_x (n) | u (m)]
@@ -31,7 +31,8 @@ __device__ __forceinline__ float efit_block_sum(float v, float* red) {
 
 __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_ef[];
-  const int n = a.n, m = a.m, F = a.F, Y = a.Y, G4 = 4 * F, S = a.S, hw = a.hw, L = a.hx.L;
+  const ExpertNet& net = a.net;
+  const int n = net.n, m = net.m, F = net.F, Y = net.Y, G4 = 4 * F, S = a.S, hw = net.hw, L = net.hx.L;
   const int G = F > 0 ? G4 : Y;           // width of the first layer's output delta
   float* xin = reinterpret_cast<float*>(smem_ef);   // n
   float* lam = xin + n;                             // n   d loss / d next_x through the next input
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
   float lsum = 0.f, disc = 1.f;
   for (int t = 0; t < S; ++t) {
     const size_t row = (size_t)b * S + t;
-    float* arow = a.acts + row * a.stride;
+    float* arow = a.acts + row * net.stride;
     float* sv = a.save + row * a.sstride;
     if (t == 0 || a.teacher_forcing)
       for (int i = tid; i < n; i += GMPC_THREADS) xin[i] = a.xseq[row * n + i];
@@ -63,9 +64,9 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
     // ---- y: LSTM cell (gates i, f, g, o) or the first dense layer + relu
     if (F > 0) {
       for (int j = tid; j < G4; j += GMPC_THREADS) {
-        float acc = a.bcat[j];
-        for (int k = 0; k < n; ++k) acc = fmaf(xin[k], a.Wcat[(size_t)k * G4 + j], acc);
-        for (int k = 0; k < F; ++k) acc = fmaf(hs[k], a.Wcat[(size_t)(n + k) * G4 + j], acc);
+        float acc = net.bcat[j];
+        for (int k = 0; k < n; ++k) acc = fmaf(xin[k], net.Wcat[(size_t)k * G4 + j], acc);
+        for (int k = 0; k < F; ++k) acc = fmaf(hs[k], net.Wcat[(size_t)(n + k) * G4 + j], acc);
         zg[j] = (j >= 2 * F && j < 3 * F) ? tanhf(acc) : sigmoidf_(acc);
       }
       __syncthreads();
@@ -84,8 +85,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
       }
     } else {
       for (int j = tid; j < Y; j += GMPC_THREADS) {
-        float acc = a.bcat[j];
-        for (int k = 0; k < n; ++k) acc = fmaf(xin[k], a.Wcat[(size_t)k * Y + j], acc);
+        float acc = net.bcat[j];
+        for (int k = 0; k < n; ++k) acc = fmaf(xin[k], net.Wcat[(size_t)k * Y + j], acc);
         const float y = fmaxf(acc, 0.f);
         yv[j] = y;
         if (a.grad) arow[ay + j] = y;
@@ -98,18 +99,18 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
     float* out = hA;
     float* other = hB;
     for (int l = 0; l < L; ++l) {
-      const int Kx = a.hx.dims[l], Nx = a.hx.dims[l + 1], Ku = a.hu.dims[l], Nu = a.hu.dims[l + 1];
+      const int Kx = net.hx.dims[l], Nx = net.hx.dims[l + 1], Ku = net.hu.dims[l], Nu = net.hu.dims[l + 1];
       for (int e = tid; e < Nx + Nu; e += GMPC_THREADS) {
         const bool isx = e < Nx;
         const int j = isx ? e : e - Nx;
         const int K = isx ? Kx : Ku, N = isx ? Nx : Nu;
-        const float* W = isx ? a.hx.W[l] : a.hu.W[l];
+        const float* W = isx ? net.hx.W[l] : net.hu.W[l];
         const float* in = isx ? inx : inu;
-        float acc = (isx ? a.hx.b[l] : a.hu.b[l])[j];
+        float acc = (isx ? net.hx.b[l] : net.hu.b[l])[j];
         for (int k = 0; k < K; ++k) acc = fmaf(in[k], W[(size_t)k * N + j], acc);
         if (l < L - 1) {
           acc = fmaxf(acc, 0.f);
-          if (a.grad) arow[(isx ? a.ax[l + 1] : a.au[l + 1]) + j] = acc;
+          if (a.grad) arow[(isx ? net.ax[l + 1] : net.au[l + 1]) + j] = acc;
         }
         out[(isx ? 0 : hw) + j] = acc;
       }
@@ -145,8 +146,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
   __syncthreads();
   for (int t = S - 1; t >= 0; --t) {
     const size_t row = (size_t)b * S + t;
-    const float* arow = a.acts + row * a.stride;
-    float* drow = a.dels + row * a.stride;
+    const float* arow = a.acts + row * net.stride;
+    float* drow = a.dels + row * net.stride;
     const float* sv = a.save + row * a.sstride;
     float dt = 1.f;
     for (int k = 0; k < t; ++k) dt *= a.gamma;    // the forward's discount, bit for bit
@@ -157,41 +158,41 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
         const float g = 2.f * dt * (sv[so + e] - a.yseq[row * n + e]) + lam[e];
         lam[e] = g;
         hA[e] = g;
-        drow[a.dx[L - 1] + e] = g;
+        drow[net.dx[L - 1] + e] = g;
       } else {
         const int j = e - n;
         const float u = sv[so + e];
         const float g = 2.f * dt * (u - a.useq[row * m + j]) * (1.f - u * u);
         hA[hw + j] = g;
-        drow[a.du[L - 1] + j] = g;
+        drow[net.du[L - 1] + j] = g;
       }
     }
     __syncthreads();
     float* cur = hA;
     float* nxt = hB;
     for (int l = L - 1; l >= 1; --l) {
-      const int Kx = a.hx.dims[l], Nx = a.hx.dims[l + 1], Ku = a.hu.dims[l], Nu = a.hu.dims[l + 1];
+      const int Kx = net.hx.dims[l], Nx = net.hx.dims[l + 1], Ku = net.hu.dims[l], Nu = net.hu.dims[l + 1];
       for (int e = tid; e < Kx + Ku; e += GMPC_THREADS) {
         const bool isx = e < Kx;
         const int k = isx ? e : e - Kx;
         const int N = isx ? Nx : Nu;
-        const float* w = (isx ? a.hx.W[l] : a.hu.W[l]) + (size_t)k * N;
+        const float* w = (isx ? net.hx.W[l] : net.hu.W[l]) + (size_t)k * N;
         const float* d = cur + (isx ? 0 : hw);
         float acc = 0.f;
         for (int j = 0; j < N; ++j) acc = fmaf(w[j], d[j], acc);
-        acc = arow[(isx ? a.ax[l] : a.au[l]) + k] > 0.f ? acc : 0.f;    // relu'(a_l)
+        acc = arow[(isx ? net.ax[l] : net.au[l]) + k] > 0.f ? acc : 0.f;    // relu'(a_l)
         nxt[(isx ? 0 : hw) + k] = acc;
-        drow[(isx ? a.dx[l - 1] : a.du[l - 1]) + k] = acc;
+        drow[(isx ? net.dx[l - 1] : net.du[l - 1]) + k] = acc;
       }
       __syncthreads();
       float* sw = cur; cur = nxt; nxt = sw;
     }
     // d loss / d y: both heads' first layers
     {
-      const int Nx = a.hx.dims[1], Nu = a.hu.dims[1];
+      const int Nx = net.hx.dims[1], Nu = net.hu.dims[1];
       for (int k = tid; k < Y; k += GMPC_THREADS) {
-        const float* wx = a.hx.W[0] + (size_t)k * Nx;
-        const float* wu = a.hu.W[0] + (size_t)k * Nu;
+        const float* wx = net.hx.W[0] + (size_t)k * Nx;
+        const float* wu = net.hu.W[0] + (size_t)k * Nu;
         float accx = 0.f, accu = 0.f;
         for (int j = 0; j < Nx; ++j) accx = fmaf(wx[j], cur[j], accx);
         for (int j = 0; j < Nu; ++j) accu = fmaf(wu[j], cur[hw + j], accu);
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
       }
       __syncthreads();
       for (int k = tid; k < F; k += GMPC_THREADS) {
-        const float* w = a.Wcat + (size_t)(n + k) * G4;
+        const float* w = net.Wcat + (size_t)(n + k) * G4;
         float acc = 0.f;
         for (int j = 0; j < G4; ++j) acc = fmaf(w[j], zg[j], acc);
         dhv[k] = acc;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
     for (int i = tid; i < n; i += GMPC_THREADS) {
       float acc = 0.f;
       if (!a.teacher_forcing && t > 0) {
-        const float* w = a.Wcat + (size_t)i * G;
+        const float* w = net.Wcat + (size_t)i * G;
         for (int j = 0; j < G; ++j) acc = fmaf(w[j], zg[j], acc);
         acc += lam[i];
       }
@@ -241,32 +242,9 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_expert_fit(ExpertFitArgs a) {
   }
 }
 
-int gmpc_expert_fit_layout(ExpertFitArgs& a) {
-  const int L = a.hx.L;
-  int off = a.n + a.F + a.Y;              // head inputs a_1.. follow y
-  a.ax[0] = a.au[0] = a.n + a.F;
-  for (int l = 1; l < L; ++l) { a.ax[l] = off; off += a.hx.dims[l]; }
-  for (int l = 1; l < L; ++l) { a.au[l] = off; off += a.hu.dims[l]; }
-  const int in_w = off;
-  off = a.F > 0 ? 4 * a.F : a.Y;
-  for (int l = 0; l < L; ++l) { a.dx[l] = off; off += a.hx.dims[l + 1]; }
-  for (int l = 0; l < L; ++l) { a.du[l] = off; off += a.hu.dims[l + 1]; }
-  a.stride = in_w > off ? in_w : off;
-  a.sstride = (a.F > 0 ? 6 * a.F : 0) + a.n + a.m;
-  int hw = 1;
-  for (int l = 0; l <= L; ++l) {
-    hw = a.hx.dims[l] > hw ? a.hx.dims[l] : hw;
-    hw = a.hu.dims[l] > hw ? a.hu.dims[l] : hw;
-  }
-  a.hw = hw;
-  return a.stride;
-}
-
-size_t gmpc_expert_fit_lds(const ExpertFitArgs& a) {
-  const int G = a.F > 0 ? 4 * a.F : a.Y;
-  return ((size_t)2 * a.n + 4 * (size_t)a.F + G + a.Y + 4 * (size_t)a.hw) * sizeof(float);
-}
-
 void gmpc_launch_expert_fit(const ExpertFitArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_expert_fit, dim3(a.B), dim3(GMPC_THREADS), gmpc_expert_fit_lds(a), s, a);
+  const ExpertNet& e = a.net;
+  const int G = e.F > 0 ? 4 * e.F : e.Y;
+  const size_t lds = ((size_t)2 * e.n + 4 * (size_t)e.F + G + e.Y + 4 * (size_t)e.hw) * sizeof(float);
+  hipLaunchKernelGGL(k_expert_fit, dim3(a.B), dim3(GMPC_THREADS), lds, s, a);
 }

@@ -15,10 +15,11 @@
 // k_expert_vjp: one 512-thread workgroup owns 4 windows as float4 components (k_expert_seq's form: one weight read
 // serves four windows), runs the forward and then the reverse sweep.  Every matrix-vector product of either sweep is
 // "thread j = output j" over a row-major operand, coalesced over j: the reverse sweep reads the transposed weight copies
-// that k_expert_transpose_all builds into the call's workspace (one launch: [Wx; Wh] or W_first, and every head layer).
+// that k_transpose_all (gmpc_optim.hip) builds into the call workspace (one launch: [Wx; Wh] or W_first, and every head
+// layer).
 // The kernel keeps per (workgroup, step) a float4 save row [activated gates (4F) | c_prev (F) | tanh c' (F) | u (m)] and
 // emits per (step, window) the row operands of the weight-gradient GEMMs in k_expert_fit's column layout
-// (gmpc_expert_fit_layout):
+// (ExpertNet, bind_expert):
 //   acts row: [x_in (n) | h_prev (F) | y (Y) | head_x inputs a_1..a_{L-1} | head_u inputs ...]   (the relu state too)
 //   dels row: [dz (4F) or d y_pre (Y) | head_x output deltas d_1..d_L | head_u output deltas d_1..d_L]
 // Rows are step-major, row = (st - st0) B + b with st0 = 0 (LSTM) or hist (MLP), so the rows with head deltas are the
@@ -28,27 +29,11 @@
 
 #define GMPC_EV_THREADS 512
 
-// every transpose of a call in one launch: blockIdx.z = matrix, 32 x 32 tiles through LDS
-__global__ __launch_bounds__(256) void k_expert_transpose_all(ExpertVjpMats d) {
-  __shared__ float tile[32][33];
-  const int mt = blockIdx.z;
-  const int R = d.R[mt], C = d.C[mt];
-  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-  if (r0 >= R || c0 >= C) return;
-  const float* in = d.in[mt];
-  float* out = d.out[mt];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8)
-    if (r0 + r < R && c0 + tx < C) tile[r][tx] = in[(size_t)(r0 + r) * C + c0 + tx];
-  __syncthreads();
-  for (int cc = ty; cc < 32; cc += 8)
-    if (c0 + cc < C && r0 + tx < R) out[(size_t)(c0 + cc) * R + r0 + tx] = tile[tx][cc];
-}
-
 __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a) {
   constexpr int SB = 4;
   extern __shared__ __attribute__((aligned(16))) char smem_ev[];
-  const int n = a.n, m = a.m, F = a.F, Y = a.Y, G4 = 4 * F, L = a.hx.L, hw = a.hw, B = a.B;
+  const ExpertNet& net = a.net;
+  const int n = net.n, m = net.m, F = net.F, Y = net.Y, G4 = 4 * F, L = net.hx.L, hw = net.hw, B = a.B;
   float4* act = reinterpret_cast<float4*>(smem_ev);     // [n + F] forward: x | h;  reverse: lam | dh
   float4* gbuf = act + (n + F);                         // [4F or Y] gates (forward), first-layer delta (reverse)
   float4* hA = gbuf + (F > 0 ? G4 : Y);                 // [2 hw] x half | u half
@@ -58,13 +43,13 @@ __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a)
   const int tid = threadIdx.x;
   const int s0 = blockIdx.x * SB;
   const int half = tid >> 8, hj = tid & 255;            // head: 0 = state, 1 = action; neuron index
-  const MlpDesc& hd = half == 0 ? a.hx : a.hu;
-  const int* aoff = half == 0 ? a.ax : a.au;
-  const int* doff = half == 0 ? a.dx : a.du;
+  const MlpDesc& hd = half == 0 ? net.hx : net.hu;
+  const int* aoff = half == 0 ? net.ax : net.au;
+  const int* doff = half == 0 ? net.dx : net.du;
   const int hist = a.hist, T = a.T, S = hist + T, st0 = a.st0;
   const int ay = n + F;                                 // acts offset of y
   const int su = F > 0 ? 6 * F : 0;                     // save offset of u
-  const size_t stride = a.stride;
+  const size_t stride = net.stride;
   // windows past B (the last workgroup) compute on window B - 1's data and write nothing
   int bw[SB];
   bool ok[SB];
@@ -98,9 +83,9 @@ __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a)
     for (int j = tid; j < n + F; j += GMPC_EV_THREADS) put(a.acts, st, j, act[j]);
     if (F > 0) {
       if (tid < G4) {
-        const float bj = a.bcat[tid];
+        const float bj = net.bcat[tid];
         float4 acc[1] = {make_float4(bj, bj, bj, bj)};
-        dense_rows<1>(a.Wcat, n + F, G4, tid, act, acc);
+        dense_rows<1>(net.Wcat, n + F, G4, tid, act, acc);
         float4 v = acc[0];
         if (tid >= 2 * F && tid < 3 * F) { v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w); }
         else { v.x = sigmoidf_(v.x); v.y = sigmoidf_(v.y); v.z = sigmoidf_(v.z); v.w = sigmoidf_(v.w); }
@@ -124,9 +109,9 @@ __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a)
       if (tid < F) put(a.acts, st, ay + tid, act[n + tid]);
     } else {
       if (tid < Y) {
-        const float bj = a.bcat[tid];
+        const float bj = net.bcat[tid];
         float4 acc[1] = {make_float4(bj, bj, bj, bj)};
-        dense_rows<1>(a.Wcat, n, Y, tid, act, acc);
+        dense_rows<1>(net.Wcat, n, Y, tid, act, acc);
         const float4 v = make_float4(fmaxf(acc[0].x, 0.f), fmaxf(acc[0].y, 0.f), fmaxf(acc[0].z, 0.f),
                                      fmaxf(acc[0].w, 0.f));
         hA[tid] = v;
@@ -199,7 +184,7 @@ __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a)
           const float4 v = make_float4(g.x + lm.x, g.y + lm.y, g.z + lm.z, g.w + lm.w);
           act[j] = v;          // own element
           hA[j] = v;
-          if (a.dels) put(a.dels, st, a.dx[L - 1] + j, v);
+          if (a.dels) put(a.dels, st, net.dx[L - 1] + j, v);
         }
       } else {
         for (int j = hj; j < m; j += 256) {
@@ -212,7 +197,7 @@ __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a)
           const float4 v = make_float4(g.x * (1.f - u.x * u.x), g.y * (1.f - u.y * u.y), g.z * (1.f - u.z * u.z),
                                        g.w * (1.f - u.w * u.w));
           hA[hw + j] = v;
-          if (a.dels) put(a.dels, st, a.du[L - 1] + j, v);
+          if (a.dels) put(a.dels, st, net.du[L - 1] + j, v);
         }
       }
       __syncthreads();
@@ -270,7 +255,7 @@ __global__ __launch_bounds__(GMPC_EV_THREADS) void k_expert_vjp(ExpertVjpArgs a)
     const int KG = F > 0 ? G4 : Y;
     for (int k = (need_x ? 0 : n) + tid; k < n + F; k += GMPC_EV_THREADS) {
       float4 acc[1] = {make_float4(0.f, 0.f, 0.f, 0.f)};
-      dense_rows<1>(a.WcatT, KG, n + F, k, gbuf, acc);
+      dense_rows<1>(net.WcatT, KG, n + F, k, gbuf, acc);
       float4 v = acc[0];
       if (k >= n) {
         act[k] = v;            // dh
@@ -299,13 +284,12 @@ size_t gmpc_expert_vjp_save_floats(const ExpertVjpArgs& a) {
   return (size_t)((a.B + 3) / 4) * (a.hist + a.T - a.st0) * a.sstride * 4;
 }
 
-int gmpc_launch_expert_vjp(const ExpertVjpArgs& a, const ExpertVjpMats& mats, hipStream_t s) {
-  if (a.n > 1024 || a.m > 1024 || 4 * a.F > GMPC_EV_THREADS) return -1;
-  if (a.hx.L != a.hu.L || a.hx.L < 1) return -1;
-  if (a.F == 0 && a.Y > GMPC_EV_THREADS) return -1;      // MLP variant: one first-layer unit per thread
-  for (int l = 0; l <= a.hx.L; ++l)
-    if (a.hx.dims[l] > a.hw || a.hu.dims[l] > a.hw) return -1;
-  const size_t lds = ((size_t)(a.n + a.F) + (a.F > 0 ? 4 * a.F : a.Y) + 4 * (size_t)a.hw) * sizeof(float4);
+int gmpc_launch_expert_vjp(const ExpertVjpArgs& a, hipStream_t s) {
+  const ExpertNet& e = a.net;
+  if (e.n > 1024 || e.m > 1024 || 4 * e.F > GMPC_EV_THREADS) return -1;
+  if (e.hx.L != e.hu.L || e.hx.L < 1) return -1;
+  if (e.F == 0 && e.Y > GMPC_EV_THREADS) return -1;      // MLP variant: one first-layer unit per thread
+  const size_t lds = ((size_t)(e.n + e.F) + (e.F > 0 ? 4 * e.F : e.Y) + 4 * (size_t)e.hw) * sizeof(float4);
   if (lds > 159 * 1024) return -1;
   static bool attr = false;
   if (!attr) {
@@ -314,12 +298,18 @@ int gmpc_launch_expert_vjp(const ExpertVjpArgs& a, const ExpertVjpMats& mats, hi
     (void)hipGetLastError();
     attr = true;
   }
-  int rmax = 1, cmax = 1;
-  for (int i = 0; i < mats.nm; ++i) {
-    rmax = mats.R[i] > rmax ? mats.R[i] : rmax;
-    cmax = mats.C[i] > cmax ? mats.C[i] : cmax;
+  // the transposed copies: [Wx; Wh] (or W_first) and every head layer, each at the matrix's own offset
+  TransposeList mats{};
+  auto add_mat = [&](int R, int C, const float* in, const float* out) {
+    mats.R[mats.nm] = R; mats.C[mats.nm] = C; mats.in[mats.nm] = in; mats.out[mats.nm] = const_cast<float*>(out);
+    ++mats.nm;
+  };
+  add_mat(e.n + e.F, e.F > 0 ? 4 * e.F : e.Y, e.Wcat, e.WcatT);
+  for (int l = 0; l < e.hx.L; ++l) {
+    add_mat(e.hx.dims[l], e.hx.dims[l + 1], e.hx.W[l], e.hx.WT[l]);
+    add_mat(e.hu.dims[l], e.hu.dims[l + 1], e.hu.W[l], e.hu.WT[l]);
   }
-  hipLaunchKernelGGL(k_expert_transpose_all, dim3((cmax + 31) / 32, (rmax + 31) / 32, mats.nm), dim3(256), 0, s, mats);
+  gmpc_launch_transpose_all(mats, s);
   hipLaunchKernelGGL(k_expert_vjp, dim3((a.B + 3) / 4), dim3(GMPC_EV_THREADS), lds, s, a);
   return 0;
 }

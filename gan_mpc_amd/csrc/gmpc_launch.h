@@ -112,6 +112,8 @@ void gmpc_launch_lstm_bwd(int Bc, const CriticDesc& cd, const float* gates, cons
 
 // gmpc_optim.hip: optimiser and utility kernels ----------------------------------------------------------------------
 void gmpc_launch_transpose(int R, int C, const float* in, float* out, hipStream_t s);   // in [R][C] -> out [C][R]
+void gmpc_launch_transpose_all(const TransposeList& mats, hipStream_t s);   // a list of them in one launch
+void gmpc_launch_mlp_transpose_all(const MlpDesc& d, hipStream_t s);        // every W[l] -> WT[l] in one launch
 void gmpc_launch_sum(int count, const float* v, float* out, int square, hipStream_t s);
 void gmpc_launch_adam(long count, float* p, const float* g, float* m, float* v, float scale, int step, double lr,
                       double max_norm, double b1, double b2, double eps, float* scratch /* >= 257 */, hipStream_t s);
@@ -131,10 +133,10 @@ void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const fl
 bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
                             float* colsum, int cs_rows, float* part, long part_floats, hipStream_t s);
 // One MLP's rows summed into its packed gradient g = W_0 | b_0 | W_1 | b_1 | ... (the layout of a parameter vector):
-// layer l's inputs are columns sum(dims[0..l-1]).. of `acts`, its deltas columns sum(dims[1..l]).. of `dels`, both
-// [rows + GMPC_WGRAD_PAD][stride]; the biases sum the first cs_rows rows.  Returns g behind the last layer.
+// `acts` and `dels` are [rows + GMPC_WGRAD_PAD][r.stride] in the layout of `r` (MlpRows); the biases sum the first
+// cs_rows rows.  Returns g behind the last layer.
 float* gmpc_launch_wgrad_mlp(int rows, int cs_rows, int L, const int* dims, const float* acts, const float* dels,
-                             int stride, float* g, float* part, long part_floats, hipStream_t s);
+                             const MlpRows& r, float* g, float* part, long part_floats, hipStream_t s);
 // all problems in one launch (+ one reduction); false when one does not qualify (the caller issues them one by one)
 bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_floats, hipStream_t s);
 // colsum[N] = sum_{r < rows} B[r][:N] on its own (two launches; `part` holds the chunk sums)
@@ -149,10 +151,10 @@ bool gmpc_launch_lstm_fwd2(int Bc, const CriticDesc& cd, const float* xseq, floa
 bool gmpc_launch_lstm_bwd2(int Bc, const CriticDesc& cd, const float* xseq, const float* G, const float* Cst,
                            const float* Hst, const float* dhT, float* Wp, float* gWx, float* gWh, float* gb,
                            float* dxseq, hipStream_t s);
-void gmpc_launch_mlp_transpose_all(const MlpDesc& d, hipStream_t s);   // every W[l] -> WT[l] in one launch
 #define GMPC_HEAD2_LD 264     // leading dimension of plast: 256 products + dscore, padded to a multiple of 8
 void gmpc_launch_head2(int Bc, const CriticDesc& cd, int loss_kind, const float* hT, const float* label, float* score,
-                       float* loss, float* acts, float* dels, float* plast, float* dhT, int act_stride, hipStream_t s);
+                       float* loss, float* acts, float* dels, float* plast, float* dhT, const MlpRows& rows,
+                       hipStream_t s);
 
 // gmpc_bilevel.hip ----------------------------------------------------------------------------------------------------
 void gmpc_launch_l2loss(int B, int T, int n, int ng, const float* X, const float* desired, float* loss, float* lx,
@@ -161,7 +163,7 @@ void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* 
                       hipStream_t s);
 void gmpc_launch_costvjp(int B, int T, int n, int m, const MlpDesc& cm, const float* mpc_w, float sign, const float* X,
                          const float* U, const float* goal, int ng, const float* Hc, const float* dX, float* gmpc,
-                         float* cact, float* cdel, int stride, hipStream_t s);
+                         float* cact, float* cdel, const MlpRows& rows, hipStream_t s);
 void gmpc_launch_get_cost(int B, int n, int ng, int m, const MlpDesc& cm, const float* mpc_w, const float* x,
                           const float* u, const float* goal_row, int terminal, float* out, hipStream_t s);
 
@@ -178,30 +180,26 @@ void gmpc_launch_goal_grad(int B, int T, int n, int ng, const float* mpc_w, cons
 void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X, const float* goal,
                               const float* dX, const float* lx, const float* AB, const float* QT, const float* qT,
                               float* w, float* lam, hipStream_t s);
-// the row layout of gmpc_launch_dyn_rows: floats per row (the larger of the input and the output columns)
-int gmpc_dyn_rows_stride(const MlpDesc& d);
-// acts / dels: 2 B T rows of gmpc_dyn_rows_stride floats.  Widths up to 256; returns 1 otherwise.
+// acts / dels: 2 B T rows in the layout `lay` of the dynamics MLP.  Widths up to 256; returns 1 otherwise.
 int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const float* X, const float* U,
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
-                         hipStream_t s);
+                         const MlpRows& lay, hipStream_t s);
 
 // gmpc_rollout_vjp.hip ------------------------------------------------------------------------------------------------
-int gmpc_rvjp_cost_stride(const MlpDesc& c);   // floats per cost row (the larger of the summed input / output widths)
-// masks: [B][T][Lh][GMPC_MW] relu bits at (X_t, U_t).  Null outputs are skipped; cacts / cdels ([B][cost stride]) and
-// gm go together; dels: B T rows of dstride floats in gmpc_dyn_rows_stride's layout.
+// masks: [B][T][Lh][GMPC_MW] relu bits at (X_t, U_t).  Null outputs are skipped; cacts / cdels (B rows in the cost
+// MLP's layout cr) and gm go together; dels: B T rows in the dynamics MLP's layout dr.
 void gmpc_launch_rvjp_sweep(int B, int n, int m, int T, const MlpDesc& dyn, const MlpDesc& cost, const float* mpc_w,
                             const float* X, const float* U, const float* goal, const float* gX, const float* gc,
                             const uint32_t* masks, float* gx0, float* gU, float* ggoal, float* gm, float* cacts,
-                            float* cdels, float* dels, int dstride, hipStream_t s);
-// acts: B T rows of dstride floats (the layer inputs at gmpc_dyn_rows_stride's offsets); masks as k_masks writes them
+                            float* cdels, float* dels, const MlpRows& dr, const MlpRows& cr, hipStream_t s);
+// acts: B T rows in the layout dr (the layer inputs); masks as k_masks writes them
 void gmpc_launch_rvjp_acts(int B, int n, int m, int T, const MlpDesc& dyn, const float* X, const float* U, float* acts,
-                           int dstride, uint32_t* masks, hipStream_t s);
+                           const MlpRows& dr, uint32_t* masks, hipStream_t s);
 
 // gmpc_dynfit.hip: dynamics regression --------------------------------------------------------------------------------
-size_t gmpc_dynfit_stride(const gmpc_shape* s);   // floats per acts / dels row
 int gmpc_launch_dynfit(int B, int S, int n, int m, const MlpDesc& dyn, const float* xseq, const float* useq,
                        const float* yseq, float gamma, int teacher_forcing, float* pred, float* acts, float* dels,
-                       int stride, float* loss, hipStream_t s);
+                       const MlpRows& rows, float* loss, hipStream_t s);
 
 // gmpc_dynl.hip: LSTM dynamics variant --------------------------------------------------------------------------------
 void gmpc_launch_dynl_rollout(DynlTrajArgs a, hipStream_t s);
@@ -215,21 +213,20 @@ void gmpc_launch_add_phi(int B, int n, int m, const float* Phi, float* HG, float
 // the first nx of n columns of every row: src [rows][n] -> dst [rows][nx], and back (zero on the other columns)
 void gmpc_launch_cols_gather(long rows, int n, int nx, const float* src, float* dst, hipStream_t s);
 void gmpc_launch_cols_scatter(long rows, int n, int nx, const float* src, float* dst, hipStream_t s);
-size_t gmpc_dynl_fit_stride(const DynlDesc& d);   // floats per acts / dels row
+size_t gmpc_dynl_fit_stride(const DynlDesc& d);   // floats per acts / dels row: the LSTM columns, then the tail's
+// tail: the tail MLP's MlpRows, its stride set to gmpc_dynl_fit_stride
 void gmpc_launch_dynl_fit(int B, int S, const DynlDesc& d, const float* xseq, const float* useq, const float* yseq,
-                          float gamma, int teacher_forcing, float* pred, float* acts, float* dels, int stride,
+                          float gamma, int teacher_forcing, float* pred, float* acts, float* dels, const MlpRows& tail,
                           float* save, float* loss, hipStream_t s);
 
 // gmpc_expert.hip / gmpc_expert_fit.hip -------------------------------------------------------------------------------
 int gmpc_launch_expert(const ExpertArgs& a, hipStream_t s);   // non-zero on an unsupported shape
-// acts / dels row layout of one shape (see the header of gmpc_expert_fit.hip); returns the row stride
-int gmpc_expert_fit_layout(ExpertFitArgs& a);
 void gmpc_launch_expert_fit(const ExpertFitArgs& a, hipStream_t s);
 
-// gmpc_expert_vjp.hip: floats of the save rows of one call; the transposes and the sweep (non-zero on an unsupported
-// shape, before any launch)
+// gmpc_expert_vjp.hip: floats of the save rows of one call; the transposes of a.net and the sweep (non-zero on an
+// unsupported shape, before any launch)
 size_t gmpc_expert_vjp_save_floats(const ExpertVjpArgs& a);
-int gmpc_launch_expert_vjp(const ExpertVjpArgs& a, const ExpertVjpMats& mats, hipStream_t s);
+int gmpc_launch_expert_vjp(const ExpertVjpArgs& a, hipStream_t s);
 
 // gmpc_comm.hip: multi-GPU exchange -----------------------------------------------------------------------------------
 struct GmpcComm { void* comm = nullptr; int world = 1, rank = 0; };   // comm: the ncclComm_t, null in a world of one

@@ -1,5 +1,5 @@
 // Optimiser and utility kernels: fixed-order sums, global-norm clip + Adam (gan/runner.py:51-63), the Polyak blend
-// and the matrix transpose.
+// and the matrix transposes (one matrix, or a list of them in one launch).
 #include "gmpc_launch.h"
 
 // Single-block sum of `count` floats (fixed order: thread-strided partials, then tree in LDS).
@@ -80,11 +80,17 @@ __global__ void k_transpose(int R, int C, const float* in, float* out) {
   out[(size_t)c * R + r] = in[e];
 }
 
-// 32 x 32 tiles through LDS: both the read and the write are coalesced (large activations)
-__global__ __launch_bounds__(256) void k_transpose_tiled(int R, int C, const float* in, float* out) {
+// every transpose of a list in one launch: blockIdx.z = matrix, 32 x 32 tiles through LDS (both the read and the write
+// are coalesced)
+__global__ __launch_bounds__(256) void k_transpose_all(TransposeList d) {
   __shared__ float tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int mt = blockIdx.z;
+  const int R = d.R[mt], C = d.C[mt];
   const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+  if (r0 >= R || c0 >= C) return;
+  const float* in = d.in[mt];
+  float* out = d.out[mt];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int r = ty; r < 32; r += 8)
     if (r0 + r < R && c0 + tx < C) tile[r][tx] = in[(size_t)(r0 + r) * C + c0 + tx];
   __syncthreads();
@@ -117,11 +123,31 @@ void gmpc_launch_polyak(long count, const float* prev, const float* cur, double 
 }
 
 void gmpc_launch_transpose(int R, int C, const float* in, float* out, hipStream_t s) {
-  if ((long)R * C > (1L << 16)) {
-    hipLaunchKernelGGL(k_transpose_tiled, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, s, R, C, in,
-                       out);
+  if ((long)R * C > (1L << 16)) {     // large activations: the tiled form
+    TransposeList one{};
+    one.nm = 1; one.R[0] = R; one.C[0] = C; one.in[0] = in; one.out[0] = out;
+    gmpc_launch_transpose_all(one, s);
     return;
   }
   const int cnt = R * C;
   hipLaunchKernelGGL(k_transpose, dim3((cnt + 255) / 256), dim3(256), 0, s, R, C, in, out);
+}
+
+void gmpc_launch_transpose_all(const TransposeList& mats, hipStream_t s) {
+  int rmax = 1, cmax = 1;
+  for (int i = 0; i < mats.nm; ++i) {
+    rmax = mats.R[i] > rmax ? mats.R[i] : rmax;
+    cmax = mats.C[i] > cmax ? mats.C[i] : cmax;
+  }
+  hipLaunchKernelGGL(k_transpose_all, dim3((cmax + 31) / 32, (rmax + 31) / 32, mats.nm), dim3(256), 0, s, mats);
+}
+
+void gmpc_launch_mlp_transpose_all(const MlpDesc& d, hipStream_t s) {
+  TransposeList mats{};
+  mats.nm = d.L;
+  for (int l = 0; l < d.L; ++l) {
+    mats.R[l] = d.dims[l]; mats.C[l] = d.dims[l + 1];
+    mats.in[l] = d.W[l]; mats.out[l] = const_cast<float*>(d.WT[l]);
+  }
+  gmpc_launch_transpose_all(mats, s);
 }

@@ -30,12 +30,9 @@ struct RvjpArgs {
   const uint32_t* masks;                 // [B][T][Lh][GMPC_MW]
   float *gx0, *gU, *ggoal;               // [B][n], [B][T][m], [B][T+1][n]; each may be null
   float* gm;                             // [B][3] d/d mpc_w per trajectory, or null
-  float *cacts, *cdels;                  // [B][cstride] cost-layer inputs / deltas, or null
-  int cstride;
-  float *acts, *dels;                    // [B T][dstride] dynamics-layer inputs (k_rvjp_acts) / deltas, or null
-  int dstride;
-  int aoff[GMPC_MAX_LAYERS], doff[GMPC_MAX_LAYERS];     // column of a_l / e_l in a dynamics row
-  int caoff[GMPC_MAX_LAYERS], cdoff[GMPC_MAX_LAYERS];   // the same for the cost rows
+  float *cacts, *cdels;                  // [B][cr.stride] cost-layer inputs / deltas, or null
+  float *acts, *dels;                    // [B T][dr.stride] dynamics-layer inputs (k_rvjp_acts) / deltas, or null
+  MlpRows dr, cr;                        // column of a_l / e_l in a dynamics row / a cost row, and the row strides
   int aw;                                // float4 per LDS activation buffer
 };
 
@@ -105,12 +102,12 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_sweep(RvjpArgs a) {
   __syncthreads();
   if (gcon) {
     for (int l = 0; l < Lc; ++l) {
-      hidden_layer(a.cost.W[l], a.cost.b[l], a.cost.dims[l], a.cost.dims[l + 1], cin + a.caoff[l],
-                   cin + a.caoff[l + 1], nullptr, 0, 0u);
+      hidden_layer(a.cost.W[l], a.cost.b[l], a.cost.dims[l], a.cost.dims[l + 1], cin + a.cr.aoff[l],
+                   cin + a.cr.aoff[l + 1], nullptr, 0, 0u);
       __syncthreads();
     }
     const int fo = a.cost.dims[Lc + 1];
-    dense_small<1>(a.cost.W[Lc], a.cost.dims[Lc], fo, cin + a.caoff[Lc], part);
+    dense_small<1>(a.cost.W[Lc], a.cost.dims[Lc], fo, cin + a.cr.aoff[Lc], part);
     const float* pf = reinterpret_cast<const float*>(part);
     {
       const int c = wave;
@@ -135,15 +132,15 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_sweep(RvjpArgs a) {
       const int K = a.cost.dims[l + 1], N = a.cost.dims[l];
       if (a.cdels) {
         for (int j = tid; j < K; j += GMPC_THREADS)
-          rv_store4(a.cdels + a.cdoff[l] + j, a.cstride, wbits, bi, in[j]);
+          rv_store4(a.cdels + a.cr.doff[l] + j, a.cr.stride, wbits, bi, in[j]);
         for (int j = tid; j < N; j += GMPC_THREADS)
-          rv_store4(a.cacts + a.caoff[l] + j, a.cstride, wbits, bi, cin[a.caoff[l] + j]);
+          rv_store4(a.cacts + a.cr.aoff[l] + j, a.cr.stride, wbits, bi, cin[a.cr.aoff[l] + j]);
       }
       rv_product(a.cost.WT[l], K, N, in, out, part);
       __syncthreads();
       if (l > 0) {
         // relu mask of the layer input: a_l > 0 exactly where its pre-activation was
-        const float4* al4 = cin + a.caoff[l];
+        const float4* al4 = cin + a.cr.aoff[l];
         for (int j = tid; j < N; j += GMPC_THREADS) {
           float4 g = out[j];
           const float4 h = al4[j];
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_sweep(RvjpArgs a) {
 
   // ---- the steps, last first
   const size_t mst = (size_t)Lh * GMPC_MW;        // mask words per step
-  const size_t drow = (size_t)T * a.dstride;      // delta-row floats per trajectory
+  const size_t drow = (size_t)T * a.dr.stride;      // delta-row floats per trajectory
   for (int t = T - 1; t >= 0; --t) {
     // staging-cost norms of slot `wave` (read by the update below, behind at least one barrier)
     {
@@ -201,7 +198,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_sweep(RvjpArgs a) {
     // backward pass of e_{L-1} = v_{t+1} through the dynamics MLP
     if (a.dels)
       for (int i = tid; i < n; i += GMPC_THREADS)
-        rv_store4(a.dels + (size_t)t * a.dstride + a.doff[L - 1] + i, drow, wbits, bi, vcur[i]);
+        rv_store4(a.dels + (size_t)t * a.dr.stride + a.dr.doff[L - 1] + i, drow, wbits, bi, vcur[i]);
     const float4* in = vcur;
     float4* out = bufA;
     for (int l = L - 1; l >= 0; --l) {
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_sweep(RvjpArgs a) {
             if (((w >> (j & 31)) & 1u) == 0u) f4set(g, c, 0.f);
           }
           out[j] = g;
-          if (a.dels) rv_store4(a.dels + (size_t)t * a.dstride + a.doff[l - 1] + j, drow, wbits, bi, g);
+          if (a.dels) rv_store4(a.dels + (size_t)t * a.dr.stride + a.dr.doff[l - 1] + j, drow, wbits, bi, g);
         }
         __syncthreads();
       }
@@ -282,7 +279,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_acts(RvjpArgs a, uint32_t
       f4set(v, c, i < n ? a.X[((size_t)b * (T + 1) + t) * n + i] : a.U[(size_t)si[c] * m + (i - n)]);
     }
     actA[i] = v;
-    rv_store4(a.acts + a.aoff[0] + i, a.dstride, wbits, si, v);
+    rv_store4(a.acts + a.dr.aoff[0] + i, a.dr.stride, wbits, si, v);
   }
   __syncthreads();
   float4* in = actA;
@@ -291,21 +288,13 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_rvjp_acts(RvjpArgs a, uint32_t
     const int N = a.dyn.dims[l + 1];
     hidden_layer(a.dyn.W[l], a.dyn.b[l], a.dyn.dims[l], N, in, out, masks + ((size_t)s0 * Lh + l) * GMPC_MW,
                  (size_t)Lh * GMPC_MW, wbits);
-    if (tid < N) rv_store4(a.acts + a.aoff[l + 1] + tid, a.dstride, wbits, si, out[tid]);
+    if (tid < N) rv_store4(a.acts + a.dr.aoff[l + 1] + tid, a.dr.stride, wbits, si, out[tid]);
     __syncthreads();
     float4* tmp = in; in = out; out = tmp;
   }
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-static void rv_offsets(const MlpDesc& d, int* ao, int* dof) {
-  int x = 0, y = 0;
-  for (int l = 0; l < d.L; ++l) {
-    ao[l] = x; dof[l] = y;
-    x += d.dims[l]; y += d.dims[l + 1];
-  }
-}
-
 static int rv_width(int n, int m, const MlpDesc& d, const MlpDesc* d2) {
   int w = n + m;
   for (int l = 0; l <= d.L; ++l) w = d.dims[l] > w ? d.dims[l] : w;
@@ -313,28 +302,18 @@ static int rv_width(int n, int m, const MlpDesc& d, const MlpDesc* d2) {
   return (w + 3) & ~3;
 }
 
-int gmpc_rvjp_cost_stride(const MlpDesc& c) {
-  int in = 0, out = 0;
-  for (int l = 0; l < c.L; ++l) { in += c.dims[l]; out += c.dims[l + 1]; }
-  return in > out ? in : out;
-}
-
 void gmpc_launch_rvjp_sweep(int B, int n, int m, int T, const MlpDesc& dyn, const MlpDesc& cost, const float* mpc_w,
                             const float* X, const float* U, const float* goal, const float* gX, const float* gc,
                             const uint32_t* masks, float* gx0, float* gU, float* ggoal, float* gm, float* cacts,
-                            float* cdels, float* dels, int dstride, hipStream_t s) {
+                            float* cdels, float* dels, const MlpRows& dr, const MlpRows& cr, hipStream_t s) {
   RvjpArgs a;
   memset(&a, 0, sizeof(a));
   a.B = B; a.n = n; a.m = m; a.T = T; a.dyn = dyn; a.cost = cost; a.mpc_w = mpc_w;
   a.X = X; a.U = U; a.goal = goal; a.gX = gX; a.gc = gc; a.masks = masks;
   a.gx0 = gx0; a.gU = gU; a.ggoal = ggoal; a.gm = gm; a.cacts = cacts; a.cdels = cdels;
-  a.cstride = gmpc_rvjp_cost_stride(cost);
-  a.dels = dels; a.dstride = dstride;
-  rv_offsets(dyn, a.aoff, a.doff);
-  rv_offsets(cost, a.caoff, a.cdoff);
+  a.dels = dels; a.dr = dr; a.cr = cr;
   a.aw = rv_width(n, m, dyn, &cost);
-  int cw = 0;
-  for (int l = 0; l < cost.L; ++l) cw += cost.dims[l];
+  const int cw = cr.aoff[cost.L - 1] + cost.dims[cost.L - 1];   // the cost-layer inputs a_0 .. a_{Lc}
   // n <= 1024, m <= 64, widths <= 256: at most 100 KB
   const size_t lds = ((size_t)2 * a.aw + GMPC_THREADS + n + cw) * sizeof(float4);
   static bool attr = false;
@@ -348,11 +327,10 @@ void gmpc_launch_rvjp_sweep(int B, int n, int m, int T, const MlpDesc& dyn, cons
 }
 
 void gmpc_launch_rvjp_acts(int B, int n, int m, int T, const MlpDesc& dyn, const float* X, const float* U, float* acts,
-                           int dstride, uint32_t* masks, hipStream_t s) {
+                           const MlpRows& dr, uint32_t* masks, hipStream_t s) {
   RvjpArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = B; a.n = n; a.m = m; a.T = T; a.dyn = dyn; a.X = X; a.U = U; a.acts = acts; a.dstride = dstride;
-  rv_offsets(dyn, a.aoff, a.doff);
+  a.B = B; a.n = n; a.m = m; a.T = T; a.dyn = dyn; a.X = X; a.U = U; a.acts = acts; a.dr = dr;
   a.aw = rv_width(n, m, dyn, nullptr);
   const int NS = B * T;
   hipLaunchKernelGGL(k_rvjp_acts, dim3((NS + 3) / 4), dim3(GMPC_THREADS), 2 * (size_t)a.aw * sizeof(float4), s, a,

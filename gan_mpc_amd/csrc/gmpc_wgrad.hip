@@ -496,15 +496,12 @@ void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const fl
 }
 
 float* gmpc_launch_wgrad_mlp(int rows, int cs_rows, int L, const int* dims, const float* acts, const float* dels,
-                             int stride, float* g, float* part, long part_floats, hipStream_t s) {
-  int aoff = 0, doff = 0;
+                             const MlpRows& r, float* g, float* part, long part_floats, hipStream_t s) {
   for (int l = 0; l < L; ++l) {
     const int M = dims[l], N = dims[l + 1];
-    gmpc_launch_wgrad(rows, M, N, acts + aoff, stride, dels + doff, stride, g, g + (long)M * N, cs_rows, part, s,
-                      part_floats, true);
+    gmpc_launch_wgrad(rows, M, N, acts + r.aoff[l], r.stride, dels + r.doff[l], r.stride, g, g + (long)M * N, cs_rows,
+                      part, s, part_floats, true);
     g += (long)M * N + N;
-    aoff += M;
-    doff += N;
   }
   return g;
 }

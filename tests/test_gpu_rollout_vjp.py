@@ -6,7 +6,9 @@ GPU.
   2. cross-checks against verified kernels that work differently: gmpc_lqr_backward's grad / adjoints (Jacobians,
      Riccati sweep) for gX = 0, gc = 1, and gmpc_dynamics_loss_grad for the discounted-MSE cotangents;
   3. linearity in (gX, gc), determinism, NULL outputs;
-  4. the call is read-only between a solve, its bilevel calls and the inputs / dynamics calls;
+  4. the call is read-only between a solve, its bilevel calls and the inputs / dynamics calls, and the one call
+     workspace it shares with gmpc_expert_vjp, gmpc_expert_loss_grad and gmpc_bilevel_grad_dynamics carries nothing from
+     one call into the next;
   5. refusals;
   6. the torch layer."""
 
@@ -23,8 +25,9 @@ import test_gpu_input_grads as ig
 import test_gpu_mirror as mirror
 import test_gpu_parity as par
 from gan_mpc_amd import _lib
+from gan_mpc_amd import params as P
 from gan_mpc_amd._lib import GmpcError
-from gan_mpc_amd.engine import Engine
+from gan_mpc_amd.engine import Engine, make_expert_shape
 from gan_mpc_amd.norm import l2_policy
 from gan_mpc_amd.policy import differentiable as dl
 from test_rollout_vjp_host import reference
@@ -203,6 +206,70 @@ def test_read_only_between_solve_and_bilevel_calls(name):
     for key in KEYS:
         np.testing.assert_array_equal(vjp()[key], first[key], err_msg=key)
     del goal
+
+
+def test_call_workspace_is_shared_safely():
+    """gmpc_rollout_vjp, gmpc_expert_vjp, gmpc_expert_loss_grad and gmpc_bilevel_grad_dynamics fill one call workspace
+    of the context.  Each of them, for two expert variants and at B = 7 and B = 3, first on a fresh engine (nothing
+    else has touched the workspace), then interleaved in two orders on a single engine, where a later call finds the
+    buffers as an earlier, larger call with another row stride left them (dynamics rows 87 floats, cost rows 30,
+    LSTM expert rows 133, MLP expert rows 118): every output has the fresh engine's bytes."""
+    n, m, T, B, kw = SHAPES["tiny-ragged"]
+    pb = gu.problem(n, m, T, B, seed=11, **kw)
+    gu.set_config(f"call workspace tiny-ragged n={n} m={m} T={T} B={B}")
+    rng = np.random.default_rng(9)
+    experts = {}
+    for name, F, layers in (("lstm", 13, 2), ("mlp", 0, 3)):     # F 13, one hidden head layer of 37; Y 37
+        flat, F_, dx, du = P.pack_expert(orc.make_expert(rng, n, m, lstm_features=F, num_layers=layers,
+                                                         num_hidden_units=37))
+        experts[name] = (flat, make_expert_shape(F_, dx, du))
+    hist, S = 1, 3
+    rnd = lambda *shape: rng.standard_normal(shape).astype(np.float32)  # noqa: E731
+    first = gu.engine_for(pb, critic=False)
+    X = first.rollout_cost(*(first.to_dev(pb[k]) for k in ("x0", "U", "goal")))[0].cpu().numpy()
+    first.close()
+    data = dict(gX=rnd(B, T + 1, n), gc=rnd(B, T + 1), history=rnd(B, hist + 1, n), g_goal=rnd(B, T + 1, n),
+                g_U=rnd(B, T, m), xseq=rnd(B, S, n), useq=np.tanh(rnd(B, S, m)), yseq=rnd(B, S, n),
+                lx=rnd(B, T + 1, n), lu=rnd(B, T, m))
+
+    def run(eng, op, Bq):
+        d = lambda a: eng.to_dev(np.ascontiguousarray(a[:Bq]))  # noqa: E731
+        kind, _, variant = op.partition("/")
+        if kind == "rollout_vjp":
+            out = eng.rollout_vjp(d(X), d(pb["U"]), d(pb["goal"]), d(data["gX"]), d(data["gc"]))
+        elif kind == "expert_vjp":
+            flat, es = experts[variant]
+            out = eng.expert_vjp(d(data["history"]), eng.to_dev(flat), es, d(data["g_goal"]), d(data["g_U"]))
+        elif kind == "expert_loss_grad":
+            flat, es = experts[variant]
+            out = dict(zip(("loss", "grad"), eng.expert_loss_grad(d(data["xseq"]), d(data["useq"]), d(data["yseq"]),
+                                                                  eng.to_dev(flat), es, 0.9, False)))
+        else:
+            eng.ilqr_solve(d(pb["x0"]), d(pb["U"]), d(pb["goal"]), {"maxiter": 1})
+            lx = d(data["lx"])
+            out = dict(cot=eng.bilevel_grad_cotangent(Bq, lx, d(data["lu"]), sign=-1.0),
+                       dyn=eng.bilevel_grad_dynamics(Bq, lx))
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    ops = ("rollout_vjp", "expert_vjp/lstm", "expert_vjp/mlp", "expert_loss_grad/lstm", "expert_loss_grad/mlp",
+           "bilevel_grad_dynamics")
+    fresh = {}
+    for op, Bq in itertools.product(ops, (B, 3)):
+        eng = gu.engine_for(pb, critic=False)
+        fresh[op, Bq] = run(eng, op, Bq)
+        eng.close()
+        assert all(np.isfinite(v).all() and np.abs(v).max() > 0 for v in fresh[op, Bq].values()), (op, Bq)
+    big = [(op, B) for op in ops]
+    small = [(op, 3) for op in ops]
+    orders = (big + small[::2] + big[::-1] + small[1::2],
+              big[::-1] + small[::-1] + big[3:] + big[:3])
+    eng = gu.engine_for(pb, critic=False)
+    for i, order in enumerate(orders):
+        for step, (op, Bq) in enumerate(order):
+            got = run(eng, op, Bq)
+            for key, want in fresh[op, Bq].items():
+                np.testing.assert_array_equal(got[key], want, err_msg=f"order {i} step {step}: {op} B={Bq} {key}")
+    eng.close()
 
 
 def test_refusals():
