@@ -95,6 +95,7 @@ SIGNATURES = {
     "gmpc_critic_loss_grad": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "gmpc_critic_score_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "gmpc_critic_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gmpc_critic_dir_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_adam_clip_step": (C.c_int, [_P, C.c_long, _P, _P, _P, _P, C.c_float, C.c_int, C.c_double,
                                       C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "gmpc_bgemm_tn": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, C.c_float,

@@ -240,6 +240,98 @@ extern "C" int gmpc_critic_vjp(gmpc_ctx* c, int Bc, const float* xseq, const flo
   return 0;
 }
 
+// The second-order VJP of the scores (gmpc_critic_dir.hip): forward of (score, sdot = <d score / d x, v>), the tangent
+// head's reverse for the caller's delta g_dir on sdot, the dual BPTT sweep, and the weight gradients as GEMMs over the
+// rows the sweeps wrote.  Stateless as gmpc_critic_vjp; everything per call lives in the call workspace.
+extern "C" int gmpc_critic_dir_vjp(gmpc_ctx* c, int Bc, const float* xseq, const float* critic, const float* v_xseq,
+                                   const float* g_dir, float* score, float* sdot, float* grad_xseq,
+                                   float* grad_critic_sum, void* stream) {
+  if (!c) return fail(GMPC_EINVAL, "ctx is null");
+  if (c->sh.lstm_features <= 0)
+    return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: this ctx was created without a critic");
+  if (Bc < 1 || Bc > 2 * c->maxB)
+    return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: Bc=%d outside [1, 2*max_batch=%d]", Bc, 2 * c->maxB);
+  if (!xseq) return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: xseq is null");
+  if (!critic) return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: critic is null");
+  if (!v_xseq) return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: v_xseq is null");
+  if (!sdot) return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: sdot is null");
+  if ((grad_xseq || grad_critic_sum) && !g_dir)
+    return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: g_dir is null but a gradient output is not");
+  const gmpc_shape& sh = c->sh;
+  const int n = c->nx, F = sh.lstm_features, T1 = sh.T + 1, G4 = 4 * F, K = n + F;
+  if (K > GMPC_THREADS)
+    return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: unsupported shape: x_size + lstm_features = %d + %d > %d (the "
+                "wide-input route)", n, F, GMPC_THREADS);
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool want_w = grad_critic_sum != nullptr, want_grad = want_w || grad_xseq != nullptr;
+  const size_t R = (size_t)Bc * T1;
+  CriticDesc cd;
+  cd.n = n; cd.F = F; cd.T1 = T1;
+  if (!gmpc_dir_supported(cd))
+    return fail(GMPC_EINVAL, "gmpc_critic_dir_vjp: unsupported shape: x_size = %d, lstm_features = %d", n, F);
+  // the call's workspace first: an allocation failure leaves nothing in flight
+  CallWork& w = c->cw;
+  TRY(w.save.grow(c, gmpc_dir_save_floats(cd, Bc)));
+  if (want_w) {
+    TRY(w.acts.reserve(c, 2 * R, K, s));
+    TRY(w.dels.reserve(c, 2 * R, G4, s));
+  }
+  if (want_grad) {
+    TRY(w.acts2.reserve(c, Bc, c->hrows.stride, s));
+    TRY(w.dels2.reserve(c, Bc, c->hrows.stride, s));
+  }
+  if (want_grad) {
+    // the sweeps read [Wx; Wh]^T on every shape: bind_critic leaves it out where the register-weight kernels run
+    TRY(bind_critic(c, critic, cd, s));
+    if (c->lwp != nullptr && gmpc_lstm2_supported(cd)) gmpc_launch_transpose(K, G4, cd.Wcat, c->critT, s);
+  } else {
+    cd.Wcat = critic;
+    cd.WcatT = nullptr;
+    cd.b = critic + (long)K * G4;
+    bind_mlp(cd.head, sh.head_layers, sh.head_dims, cd.b + G4, nullptr);
+  }
+  DirSaves sv;
+  gmpc_dir_bind_saves(cd, Bc, w.save.p, &sv);
+  sv.A = want_w ? w.acts.p : nullptr;
+  {
+    ProfScope ps(c, PROF_LSTM_FWD, s);
+    gmpc_launch_dir_fwd(Bc, cd, xseq, v_xseq, sv, s);
+  }
+  {
+    ProfScope ps(c, PROF_HEAD, s);
+    gmpc_launch_dir_head(Bc, cd, sv, want_grad ? g_dir : nullptr, score, sdot, w.acts2.p, w.dels2.p, c->hrows, s);
+  }
+  if (want_grad) {
+    ProfScope ps(c, PROF_LSTM_BWD, s);
+    gmpc_launch_dir_bwd(Bc, cd, sv, want_w ? w.dels.p : nullptr, grad_xseq, s);
+  }
+  if (want_w) {
+    ProfScope ps(c, PROF_WGRAD, s);
+    // [gWx ; gWh] = A^T D over both halves of the rows, gb = the column sums of D's primal half
+    float* gb = grad_critic_sum + (long)K * G4;
+    const int rows = (int)(2 * R);
+    WgProb q{};
+    q.rows = rows; q.M = K; q.N = G4; q.lda = K; q.ldb = G4; q.cs_rows = (int)R;
+    q.A = w.acts.p; q.B = w.dels.p; q.C = grad_critic_sum; q.colsum = gb;
+    if (!(G4 % 256 == 0 && rows >= 64 && gmpc_launch_wgrad_batch(&q, 1, c->wpart, c->wpart_floats, s)))
+      gmpc_launch_wgrad(rows, K, G4, w.acts.p, K, w.dels.p, G4, grad_critic_sum, gb, (int)R, c->wpart, s,
+                        c->wpart_floats, true);
+    // head: dW_l = sum_b ad_l^T d_l; the biases enter the tangent through the masks only: exact zeros
+    float* gh = gb + G4;
+    HIP_TRY(hipMemsetAsync(gh, 0, mlp_count(sh.head_layers, sh.head_dims) * sizeof(float), s));
+    for (int l = 0; l < sh.head_layers; ++l) {
+      const int M = sh.head_dims[l], N = sh.head_dims[l + 1];
+      gmpc_launch_wgrad(Bc, M, N, w.acts2.p + c->hrows.aoff[l], c->hrows.stride, w.dels2.p + c->hrows.doff[l],
+                        c->hrows.stride, gh, nullptr, 0, c->wpart, s, c->wpart_floats, true);
+      gh += (long)M * N + N;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // upper-level loss only, at the solution held by the ctx (norm/cost_trainer.py:13-21 test loss)
 int upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired, const float* critic,
                       float* loss, bool want_lx, hipStream_t s) {

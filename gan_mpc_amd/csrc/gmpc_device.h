@@ -243,6 +243,15 @@ struct CriticDesc {
   MlpDesc head;              // dims[0] = F ... dims[L] = 1
 };
 
+// The saves of gmpc_critic_dir.hip's sweeps, [sequence][step] row-major (R = Bc T1 rows), and the head's hand-over
+struct DirSaves {
+  float* gates; float* zd;       // [R][4F] activated gates, tangent pre-activations
+  float* cs; float* cds;         // [R][F] c_t, its tangent
+  float* hT; float* hdT;         // [Bc][F] final state, its tangent
+  float* dhd;                    // [Bc][F] adjoint of hd_T from the tangent head
+  float* A;                      // [2 R][n + F] rows [x_t, h_{t-1}], then [v_t, hd_{t-1}]; null: not wanted
+};
+
 // one weight-gradient problem  C[M][N] = sum_r A[r][:M]^T B[r][:N],  colsum[N] = sum_{r<cs_rows} B[r]
 struct WgProb {
   int rows, M, N, lda, ldb, cs_rows;

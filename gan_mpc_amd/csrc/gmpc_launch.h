@@ -156,6 +156,20 @@ void gmpc_launch_head2(int Bc, const CriticDesc& cd, int loss_kind, const float*
                        float* loss, float* acts, float* dels, float* plast, float* dhT, const MlpRows& rows,
                        hipStream_t s);
 
+// gmpc_critic_dir.hip: the tangent critic and its reverse sweep (gmpc_critic_dir_vjp), n + F <= 256 ----------------------
+bool gmpc_dir_supported(const CriticDesc& cd);
+size_t gmpc_dir_save_floats(const CriticDesc& cd, int Bc);     // floats behind DirSaves (without A)
+void gmpc_dir_bind_saves(const CriticDesc& cd, int Bc, float* save, DirSaves* sv);
+// primal and tangent forward sweep of (xseq, vseq); fills sv (and sv.A where set)
+void gmpc_launch_dir_fwd(int Bc, const CriticDesc& cd, const float* xseq, const float* vseq, const DirSaves& sv,
+                         hipStream_t s);
+// score (optional), sdot; with g_dir the reverse of the tangent head: sv.dhd and the acts / dels rows (layout `rows`,
+// needs cd.head.WT)
+void gmpc_launch_dir_head(int Bc, const CriticDesc& cd, const DirSaves& sv, const float* g_dir, float* score, float* sdot,
+                          float* acts, float* dels, const MlpRows& rows, hipStream_t s);
+// dual BPTT (needs cd.WcatT); D [2 R][4F] = [z~ ; zd~] and dxseq are optional
+void gmpc_launch_dir_bwd(int Bc, const CriticDesc& cd, const DirSaves& sv, float* D, float* dxseq, hipStream_t s);
+
 // gmpc_bilevel.hip ----------------------------------------------------------------------------------------------------
 void gmpc_launch_l2loss(int B, int T, int n, int ng, const float* X, const float* desired, float* loss, float* lx,
                         hipStream_t s);

@@ -398,6 +398,29 @@ class Engine:
                                             _ptr(out["dx"]), _ptr(out["params"]), self._stream()))
         return out
 
+    def critic_dir_vjp(self, xseq, critic, v, g_dir=None, want_dx=True, want_params=True, grad_sum=None):
+        """The second-order VJP of the critic's scores (gmpc_critic_dir_vjp): sdot_b = <dscore_b/dxseq_b, v_b> for the
+        directions v (Bc, T+1, nx), and for g_dir = dL/dsdot (Bc,) its reverse sweep.  -> dict(score (Bc,), sdot (Bc,),
+        dx (Bc, T+1, nx) = g_b dsdot_b/dxseq_b, params [critic_count] = sum_b g_b dsdot_b/dtheta in critic_loss_grad's
+        layout, head biases exactly zero), None where not wanted.  Without g_dir the call is the forward only: dx and
+        params are None whatever want_dx / want_params say.  grad_sum: optional caller-owned [critic_count] view for
+        params.  Critics with nx + lstm_features <= 256.  Stateless, as critic_vjp."""
+        Bc = xseq.shape[0]
+        for name, t, shape in (("xseq", xseq, (Bc, self.T + 1, self.nx)), ("critic", critic, (self.critic_count,)),
+                               ("v", v, (Bc, self.T + 1, self.nx)), ("g_dir", g_dir, (Bc,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"critic_dir_vjp: {name} must be {shape}, got {tuple(t.shape)}")
+        want_dx, want_params = bool(want_dx and g_dir is not None), bool(want_params and g_dir is not None)
+        if grad_sum is not None and (not want_params or tuple(grad_sum.shape) != (self.critic_count,)):
+            raise _lib.GmpcError(f"critic_dir_vjp: grad_sum must be ({self.critic_count},) and goes with want_params and "
+                                 f"g_dir, got {tuple(grad_sum.shape)}, want_params={want_params}")
+        out = dict(score=self.new(Bc), sdot=self.new(Bc), dx=self.new(Bc, self.T + 1, self.nx) if want_dx else None,
+                   params=(self.new(self.critic_count) if grad_sum is None else grad_sum) if want_params else None)
+        _lib.check(self.lib.gmpc_critic_dir_vjp(self.ctx, Bc, _ptr(xseq), _ptr(critic), _ptr(v), _ptr(g_dir),
+                                                _ptr(out["score"]), _ptr(out["sdot"]), _ptr(out["dx"]),
+                                                _ptr(out["params"]), self._stream()))
+        return out
+
     def adam_clip_step(self, params, grad, m, v, step, lr, grad_scale=1.0, max_norm=100.0, b1=0.9,
                        b2=0.999, eps=1e-8):
         _lib.check(self.lib.gmpc_adam_clip_step(

@@ -11,7 +11,19 @@ loss written in torch on top of critic_layer (policy/differentiable.py), so any 
 The critic step differentiates sum_b critic_objective through critic_layer's backward (one gmpc_critic_vjp call) and
 joins the packed [loss | grad | count] all-reduce as JS_MPC does.  The generator step hands lx = d generator_objective /
 dX -- through critic_layer again -- to the bilevel gradient as a batched cotangent (BaseMPC.batch_cotangents), with no
-lu.  Plain torch.autograd only: no torch.func transform of the layer."""
+lu.  Plain torch.autograd only: no torch.func transform of the layer.
+
+gradient_penalty = dict(weight, target=1.0, at="mixed" | "true", seed=0) adds weight * mean_p (||dscore/dxhat_p||_2 -
+target)^2 to the critic's loss (critic_layer is differentiable twice in its sequences: one gmpc_critic_dir_vjp call):
+  at = "true"   xhat = the batch's true sequences (label > 0); with target 0 this is the R1 penalty up to its factor 1/2
+  at = "mixed"  xhat_k = eps_k true_k + (1 - eps_k) pred_k, the k-th true sequence with the k-th predicted one in batch
+                order, P = the smaller of the two counts (WGAN-GP at target 1); eps ~ U[0, 1) from the device generator
+                `penalty_generator`.
+Per rank the packed sums get weight (Bc / P) sum_p penalty_p with count Bc, so a single rank reports mean objective +
+weight * mean penalty; a shard without penalty points (P = 0) adds exact zeros and runs no kernel for it.  The generator
+step does not see the penalty."""
+
+import math
 
 import torch
 import torch.nn.functional as Fn
@@ -44,6 +56,42 @@ def get_objective(objective):
     return critic_obj, gen_obj
 
 
+def get_gradient_penalty(spec):
+    """The validated penalty spec dict(weight, target, at, seed) of GAN_MPC's `gradient_penalty` argument, or None."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError(f"gradient_penalty must be None or a dict(weight, target=1.0, at='mixed', seed=0), got {spec!r}")
+    unknown = sorted(set(spec) - {"weight", "target", "at", "seed"})
+    if unknown:
+        raise ValueError(f"gradient_penalty: unknown keys {unknown}; the keys are weight, target, at, seed")
+    if "weight" not in spec:
+        raise ValueError("gradient_penalty: weight is required")
+    out = dict(weight=spec["weight"], target=spec.get("target", 1.0), at=spec.get("at", "mixed"), seed=spec.get("seed", 0))
+    for key in ("weight", "target"):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"gradient_penalty: {key} must be a finite number >= 0, got {v!r}")
+        out[key] = float(v)
+    if out["at"] not in ("mixed", "true"):
+        raise ValueError(f"gradient_penalty: at must be 'mixed' or 'true', got {out['at']!r}")
+    if isinstance(out["seed"], bool) or not isinstance(out["seed"], int) or out["seed"] < 0:
+        raise ValueError(f"gradient_penalty: seed must be an integer >= 0, got {out['seed']!r}")
+    return out
+
+
+def gradient_penalty(policy, dparams, flat, xhat, target, eng=None):
+    """(P,) penalties (||dscore/dxhat_p||_2 - target)^2 of the policy's critic at the sequences xhat (P, T+1, x_size),
+    the norm over all (T+1) x_size entries; differentiable w.r.t. flat (dparams.flat or a leaf sharing its storage):
+    its backward is critic_layer's second derivative.  eng: the engine to run on (default: the policy's)."""
+    eng = policy._engine if eng is None else eng
+    xs = xhat.detach().to(torch.float32).contiguous().requires_grad_(True)
+    with torch.enable_grad():
+        score = diff.CriticFunction.apply(eng, dparams, flat, xs)
+        g, = torch.autograd.grad(score.sum(), xs, create_graph=True)
+        return (torch.linalg.vector_norm(g.reshape(g.shape[0], -1), dim=1) - target) ** 2
+
+
 def _per_sequence(val, count, what):
     if tuple(val.shape) != (count,):
         raise ValueError(f"{what} must return one loss per sequence, shape ({count},), got {tuple(val.shape)}")
@@ -51,10 +99,27 @@ def _per_sequence(val, count, what):
 
 
 class GAN_MPC(js_policy.JS_MPC):
-    def __init__(self, *args, objective="js", **kwargs):
+    def __init__(self, *args, objective="js", gradient_penalty=None, **kwargs):
         super().__init__(*args, **kwargs)
         self.objective = objective
         self.critic_objective, self.generator_objective = get_objective(objective)
+        self.gradient_penalty = get_gradient_penalty(gradient_penalty)
+        self.penalty_generator = None
+        if self.gradient_penalty is not None:
+            # eps of the mixed sequences: a device generator of its own, so that a caller can replay its state
+            self.penalty_generator = torch.Generator(device=self.device())
+            self.penalty_generator.manual_seed(self.gradient_penalty["seed"])
+
+    def penalty_points(self, xs, lab):
+        """The sequences the penalty is taken at, (P, T+1, x_size): see the module docstring."""
+        spec = self.gradient_penalty
+        true = xs[lab > 0]
+        if spec["at"] == "true":
+            return true
+        pred = xs[~(lab > 0)]
+        P = min(true.shape[0], pred.shape[0])
+        eps = torch.rand(P, generator=self.penalty_generator, device=xs.device, dtype=torch.float32)[:, None, None]
+        return eps * true[:P] + (1.0 - eps) * pred[:P]
 
     # ---- critic step ------------------------------------------------------------------------
     def _critic_sums(self, batch_xseq, batch_label, dparams, packed=None):
@@ -68,6 +133,11 @@ class GAN_MPC(js_policy.JS_MPC):
         with torch.enable_grad():
             score = diff.CriticFunction.apply(eng, dparams, flat, xs)
             loss = _per_sequence(self.critic_objective(score, lab.to(score.dtype)), Bc, "critic_objective").sum()
+            if self.gradient_penalty is not None:
+                xhat = self.penalty_points(xs.to(torch.float32), lab)
+                if xhat.shape[0] > 0:
+                    pen = gradient_penalty(self, dparams, flat, xhat, self.gradient_penalty["target"], eng=eng)
+                    loss = loss + (self.gradient_penalty["weight"] * Bc / xhat.shape[0]) * pen.sum()
         grad, = torch.autograd.grad(loss, flat, allow_unused=True)
         lo, cnt = dparams.range_of(("critic_params",))
         gs = torch.zeros(cnt, dtype=torch.float32, device=xs.device) if grad is None else grad[lo:lo + cnt]

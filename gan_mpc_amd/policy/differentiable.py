@@ -40,9 +40,15 @@ summed over the batch (zeros on every other range).  Any objective of the scores
 least squares, hinge, label smoothing, per-sequence weights -- so reaches the discriminator's parameters, and the
 generator loss runs through expert_layer -> ilqr_layer -> critic_layer -> loss in one backward(): neither its forward
 nor its backward touches a held iLQR solution or its bilevel tail.  xseq has x_size columns (with LSTM dynamics the
-caller slices X[..., :x_size]); it never rebuilds the policy's engine, so Bc <= 2 max_batch of the bound engine."""
+caller slices X[..., :x_size]); it never rebuilds the policy's engine, so Bc <= 2 max_batch of the bound engine.
+The layer is differentiable twice in xseq: torch.autograd.grad(score.sum(), xseq, create_graph=True) returns an input
+gradient with a graph behind it, whose backward is one call of gmpc_critic_dir_vjp -- what a
+gradient penalty on the critic needs (gan_policy.gradient_penalty).  The parameter gradient is not differentiable again
+(NotImplementedError), third derivatives are refused, and critics with x_size + lstm_features > 256 are refused by the
+second backward.  Without create_graph the layer runs the same calls as before."""
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from gan_mpc_amd._lib import GmpcError
 from gan_mpc_amd.engine import Engine
@@ -236,7 +242,7 @@ class CriticFunction(torch.autograd.Function):
         score, _ = eng.critic_score_vjp(xs, crit, want_dx=False)
         ctx.eng, ctx.crit = eng, crit
         ctx.range = dparams.range_of(("critic_params",))
-        ctx.flat_shape = flat.shape
+        ctx.flat, ctx.xseq = flat, xseq      # the graph's own inputs: a create_graph backward goes through them
         ctx.save_for_backward(xs)
         ctx.set_materialize_grads(False)
         return score
@@ -251,13 +257,54 @@ class CriticFunction(torch.autograd.Function):
             raise RuntimeError("critic_layer backward: the engine of the forward has been closed (the policy rebuilt "
                                "it for another shape or a larger batch)")
         xs, = ctx.saved_tensors
+        gflat, dx = CriticGradFunction.apply(eng, ctx.crit, ctx.range, xs, ctx.flat, ctx.xseq, g_score, want_params,
+                                             want_dx)
+        return None, None, gflat, dx
+
+
+class CriticGradFunction(torch.autograd.Function):
+    """CriticFunction's backward as a function of (flat, xseq, g_score) -> (gflat, dx): one gmpc_critic_vjp call.  Under
+    create_graph its own backward, for the cotangent v on dx, is one gmpc_critic_dir_vjp call with g_dir = g_score:
+    sdot for g_score, `params` into the critic range of flat, dx for xs."""
+
+    @staticmethod
+    def forward(ctx, eng, crit, rng, xs, flat, xseq, g_score, want_params, want_dx):
+        # (xs: the fp32 copy of xseq the layer's forward ran on; flat and xseq take part for the graph only)
+        lo, cnt = rng
+        gflat = torch.zeros(flat.shape, dtype=torch.float32, device=xs.device) if want_params else None
+        g32 = g_score.detach().to(torch.float32).contiguous()
+        out = eng.critic_vjp(xs, crit, g32, want_dx=want_dx, want_params=want_params,
+                             grad_sum=gflat[lo:lo + cnt] if want_params else None)
+        ctx.eng, ctx.crit, ctx.range, ctx.flat_shape = eng, crit, rng, flat.shape
+        ctx.save_for_backward(xs, g32)
+        ctx.set_materialize_grads(False)
+        return gflat, out["dx"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v_gflat, v_dx):
+        if v_gflat is not None:
+            raise NotImplementedError(
+                "critic_layer: a cotangent on the parameter gradient (d2 score / d theta2, d2 score / d theta dx "
+                "contracted on the theta side) is not implemented; only the input gradient dscore/dxseq is "
+                "differentiable again")
+        want_params, want_dx, want_g = ctx.needs_input_grad[4:7]
+        if v_dx is None or not (want_params or want_dx or want_g):
+            return (None,) * 9
+        eng = ctx.eng
+        if eng.ctx is None:
+            raise RuntimeError("critic_layer double backward: the engine of the forward has been closed (the policy "
+                               "rebuilt it for another shape or a larger batch)")
+        xs, g32 = ctx.saved_tensors
         gflat = None
         if want_params:
             lo, cnt = ctx.range
             gflat = torch.zeros(ctx.flat_shape, dtype=torch.float32, device=xs.device)
-        out = eng.critic_vjp(xs, ctx.crit, g_score.to(torch.float32).contiguous(), want_dx=want_dx,
-                             want_params=want_params, grad_sum=gflat[lo:lo + cnt] if want_params else None)
-        return None, None, gflat, out["dx"]
+        grads = want_params or want_dx
+        out = eng.critic_dir_vjp(xs, ctx.crit, v_dx.detach().to(torch.float32).contiguous(),
+                                 g_dir=g32 if grads else None, want_dx=want_dx, want_params=want_params,
+                                 grad_sum=gflat[lo:lo + cnt] if want_params else None)
+        return None, None, None, None, gflat, out["dx"], out["sdot"] if want_g else None, None, None
 
 
 def critic_layer(policy, params, xseq):

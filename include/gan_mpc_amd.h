@@ -19,9 +19,9 @@
  *    after a COMPLETED gmpc_ilqr_solve of the same batch size.  gmpc_set_params, gmpc_rollout_cost,
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
- *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp, gmpc_expert_vjp and
- *    gmpc_critic_vjp drop nothing: they may run between a solve and its bilevel calls, or between a bilevel call and
- *    gmpc_bilevel_grad_inputs / _dynamics.
+ *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp, gmpc_expert_vjp,
+ *    gmpc_critic_vjp and gmpc_critic_dir_vjp drop nothing: they may run between a solve and its bilevel calls, or
+ *    between a bilevel call and gmpc_bilevel_grad_inputs / _dynamics.
  *
  * Parameter layouts (flat fp32 vectors, flax Dense order: kernel (in,out) row-major, then bias):
  *   dyn    : for l in 0..dyn_layers-1:  W_l[dims[l]][dims[l+1]], b_l[dims[l+1]]
@@ -288,6 +288,29 @@ int gmpc_critic_score_vjp(gmpc_ctx* ctx, int Bc, const float* xseq, const float*
  * identical calls give identical bits.  Asynchronous; no allocation. */
 int gmpc_critic_vjp(gmpc_ctx* ctx, int Bc, const float* xseq, const float* critic, const float* g_score,
                     float* score, float* grad_xseq, float* grad_critic_sum, void* stream);
+
+/* The second-order VJP of the critic's scores: what a gradient penalty (WGAN-GP, R1) differentiates.  With
+ * g_b = d score_b / d xseq_b, any penalty P = sum_b p(g_b) has dP/dtheta = sum_b v_b . d g_b / d theta at v_b = dp/dg_b
+ * held constant, and v_b . g_b is the directional derivative sdot_b = <d score_b / d xseq_b, v_b>: the output of the
+ * tangent (forward-mode) critic run beside the primal one.  This call is the forward of (score, sdot) and one reverse
+ * sweep for a caller's delta g_dir = dL/dsdot [Bc]; no Hessian is formed.
+ *   xseq, v_xseq [Bc][T+1][x_size], critic the flat parameters (layout above), g_dir [Bc]
+ *   -> score [Bc] (may be NULL); sdot [Bc]; grad_xseq [Bc][T+1][x_size] = g_b * d sdot_b / d xseq_b per sequence;
+ *      grad_critic_sum [critic_count] = sum_b g_b * d sdot_b / d theta in gmpc_critic_loss_grad's layout,
+ *      SUMMED over the batch and overwritten; its head-bias ranges are written as zeros (the biases reach sdot
+ *      through the relu masks only, which are piecewise constant).  Either gradient may be NULL (its work is skipped);
+ *      with both NULL the call is the forward only and g_dir may be NULL too.
+ * Shapes: every critic with x_size + lstm_features <= 256 (one run-time-shape form, expf / tanhf activations, its own
+ * saves and its own [Wx; Wh] transpose: on the register-weight shapes `score` agrees with gmpc_critic_score_vjp to
+ * parity, not bit for bit).  The wide-input route (x_size + lstm_features > 256) fails with GMPC_EINVAL,
+ * "unsupported shape".  A NULL xseq, critic, v_xseq or sdot, a gradient output without g_dir, Bc outside [1, 2 max_batch] or a ctx
+ * created without a critic fail with GMPC_EINVAL before any launch.
+ * Stateless, deterministic (fixed reduction order, no atomics) and asynchronous as gmpc_critic_vjp: it drops neither a
+ * held solution nor a bilevel tail.  Per-call memory comes from the context's call workspace, which grows to the
+ * largest call seen (gmpc_create allocates nothing for it). */
+int gmpc_critic_dir_vjp(gmpc_ctx* ctx, int Bc, const float* xseq, const float* critic, const float* v_xseq,
+                        const float* g_dir, float* score, float* sdot, float* grad_xseq, float* grad_critic_sum,
+                        void* stream);
 
 /* a18: optax.chain(clip_by_global_norm(max_norm), adam(lr)) on one contiguous trainable range
  * (gan/runner.py:51-63).  grad is scaled by grad_scale first (1/B for a batch sum).
