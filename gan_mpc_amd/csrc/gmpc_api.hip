@@ -211,7 +211,12 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
   A_(adjs, B * (T + 1) * n);
   A_(obj, B); A_(alpha, B); A_(obj_step, B); A_(U_step, B);
   A_(iters, B); A_(cont, B);
-  if (!c->dynl && !c->big && s.T <= GMPC_FZ_MAX_T) A_(fzcand, B * GMPC_FZ_NC * ((T + 1) * n + T * m));
+  if (!c->dynl && !c->big && s.T <= GMPC_FZ_MAX_T) {
+    A_(fzcand, B * GMPC_FZ_NC * ((T + 1) * n + T * m));
+    A_(box_count, 2 * B);
+    A_(box_iters, B * T);
+    A_(box_clamped, B * T * m);
+  }
   // bilevel
   c->drows = mlp_rows(s.dyn_layers, s.dyn_dims);
   c->crows = mlp_rows(s.cost_layers, s.cost_dims);
@@ -510,7 +515,9 @@ extern "C" int gmpc_profile_read(gmpc_ctx* c, int slot, double* total_ms, int* c
 }
 
 // accessors used by the bilevel parity tests and the Python mirror (device pointers, valid until the
-// next solve): 0 X, 1 U, 2 H (A^-1 B), 3 dX, 4 Bvec, 5 AB, 6 K, 7 k
+// next solve): 0 X, 1 U, 2 H (A^-1 B), 3 dX, 4 Bvec, 5 AB, 6 K, 7 k; of gmpc_ilqr_solve_box (null on shapes it does not
+// cover): 15 [B][2] QPs that hit the iteration cap / QP iterations of the solve, 16 [B][T] QP iterations and 17
+// [B][T][m] clamped flags of the last backward pass
 extern "C" long gmpc_debug_buffer_count(gmpc_ctx* c, int which) {
   if (!c) return 0;
   const gmpc_shape& s = c->sh;
@@ -525,6 +532,9 @@ extern "C" long gmpc_debug_buffer_count(gmpc_ctx* c, int which) {
     case 12: return (long)GMPC_LS_ITEMS * B * (T + 1) * n;
     case 13: return (long)GMPC_LS_ITEMS * B * T * m;
     case 14: return 256;
+    case 15: return c->box_count ? 2 * B : 0;
+    case 16: return c->box_iters ? B * T : 0;
+    case 17: return c->box_clamped ? B * T * m : 0;
     default: return 0;
   }
 }
@@ -537,6 +547,7 @@ extern "C" const float* gmpc_debug_buffer(gmpc_ctx* c, int which) {
     case 14: return c->scratch + 768; case 12: return c->Xc; case 13: return c->Uc;
     case 8: return c->alpha; case 9: return c->obj_step; case 10: return c->U_step;
     case 11: return c->lx;
+    case 15: return c->box_count; case 16: return c->box_iters; case 17: return c->box_clamped;
     default: return nullptr;
   }
 }

@@ -264,23 +264,23 @@ extern "C" int gmpc_ilqr_solve(gmpc_ctx* c, int B, const float* x0, const float*
   return 0;
 }
 
-// The whole solve in one launch (gmpc_fused_solve.hip): same results and ctx state as gmpc_ilqr_solve on the shapes
-// it covers, nothing waited for on the host.
-extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const float* U_init,
-                                     const float* goal, const gmpc_ilqr_opts* opts, float* X, float* U,
-                                     float* obj, float* grad, float* adjoints, int* iterations,
-                                     void* stream) {
+// The whole solve in one launch (gmpc_fused_solve.hip), shared by gmpc_ilqr_solve_fused and gmpc_ilqr_solve_box
+// (`who` heads the refusals): coverage checks, the argument block, the launch.
+static int solve_one_launch(gmpc_ctx* c, int B, const float* x0, const float* U_init, const float* goal,
+                            const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad, float* adjoints,
+                            int* iterations, void* stream, const char* who, bool box, const float* u_lo,
+                            const float* u_hi) {
   TRY(check_call(c, B));
   if (!x0 || !U_init || !goal || !opts) return fail(GMPC_EINVAL, "null argument");
   if (opts->make_psd) return fail(GMPC_EINVAL, "make_psd=1 is not on the reference path");
   const gmpc_shape& sh = c->sh;
-  if (c->dynl) return fail(GMPC_EINVAL, "fused solve: MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
+  if (c->dynl) return fail(GMPC_EINVAL, "%s: MLP dynamics only (dyn_lstm_features = %d)", who, sh.dyn_lstm_features);
   if (c->big)
-    return fail(GMPC_EINVAL, "fused solve: n <= 64 and m <= 32 only (n=%d m=%d)", sh.n, sh.m);
-  if (sh.T > GMPC_FZ_MAX_T) return fail(GMPC_EINVAL, "fused solve: T <= %d only (T=%d)", GMPC_FZ_MAX_T, sh.T);
+    return fail(GMPC_EINVAL, "%s: n <= 64 and m <= 32 only (n=%d m=%d)", who, sh.n, sh.m);
+  if (sh.T > GMPC_FZ_MAX_T) return fail(GMPC_EINVAL, "%s: T <= %d only (T=%d)", who, GMPC_FZ_MAX_T, sh.T);
   const int k_max = gmpc_ls_halvings(opts->alpha_0, opts->alpha_min, GMPC_FZ_MAX_HALVINGS + 1);
   if (k_max > GMPC_FZ_MAX_HALVINGS)
-    return fail(GMPC_EINVAL, "fused solve: alpha_0 / alpha_min allow more than %d halvings", GMPC_FZ_MAX_HALVINGS);
+    return fail(GMPC_EINVAL, "%s: alpha_0 / alpha_min allow more than %d halvings", who, GMPC_FZ_MAX_HALVINGS);
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;
   c->gradB = 0;
@@ -294,10 +294,37 @@ extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const 
   a.obj = c->obj; a.alpha = c->alpha; a.obj_step = c->obj_step; a.U_step = c->U_step; a.iters = c->iters;
   a.cand = c->fzcand;
   a.oX = X; a.oU = U; a.oobj = obj; a.ograd = grad; a.oadj = adjoints; a.oiters = iterations;
-  gmpc_launch_ilqr_fused(a, B, s);
+  if (box) {
+    BoxSolveArgs x;
+    x.u_lo = u_lo; x.u_hi = u_hi;
+    x.count = c->box_count; x.iters = c->box_iters; x.clamped = c->box_clamped;
+    gmpc_launch_ilqr_box(a, x, B, s);
+  } else {
+    gmpc_launch_ilqr_fused(a, B, s);
+  }
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// Same results and ctx state as gmpc_ilqr_solve on the shapes it covers, nothing waited for on the host.
+extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const float* U_init,
+                                     const float* goal, const gmpc_ilqr_opts* opts, float* X, float* U,
+                                     float* obj, float* grad, float* adjoints, int* iterations,
+                                     void* stream) {
+  TRY(solve_one_launch(c, B, x0, U_init, goal, opts, X, U, obj, grad, adjoints, iterations, stream, "fused solve",
+                       false, nullptr, nullptr));
   c->solB = B;   // stream-ordered: a later call on the same stream sees the finished solve
   return 0;
+}
+
+// The control-limited solve.  It holds no solution for the bilevel tail (solB stays 0): the implicit
+// gradient through an active set is not implemented.
+extern "C" int gmpc_ilqr_solve_box(gmpc_ctx* c, int B, const float* x0, const float* U_init,
+                                   const float* goal, const gmpc_ilqr_opts* opts, float* X, float* U,
+                                   float* obj, float* grad, float* adjoints, int* iterations,
+                                   void* stream, const float* u_lo, const float* u_hi) {
+  return solve_one_launch(c, B, x0, U_init, goal, opts, X, U, obj, grad, adjoints, iterations, stream, "box solve",
+                          true, u_lo, u_hi);
 }
 
 // single model evaluations (the reference's model protocol, base.py:4-49) -----------------------

@@ -77,6 +77,9 @@ struct gmpc_ctx {
   int *iters, *cont;
   int* hcont = nullptr;                       // pinned ring of continuation flags (gmpc_ilqr_solve)
   float* fzcand = nullptr;                    // line-search candidates of gmpc_ilqr_solve_fused (shapes it covers)
+  // gmpc_ilqr_solve_box's QP reports (same shapes): [B][2] cap hits / QP iterations of the solve, [B][T] QP
+  // iterations and [B][T][m] clamped flags of the last backward pass
+  float *box_count = nullptr, *box_iters = nullptr, *box_clamped = nullptr;
   hipEvent_t poll_ev[GMPC_POLL_DEPTH] = {};
   int solB = 0;
   // batch size whose Bvec / H / dX (and Phi) a completed bilevel tail left for the held solution (0: none); every

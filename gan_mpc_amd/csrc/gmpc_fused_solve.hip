@@ -12,6 +12,11 @@
 //    tangent columns), [A_t | B_t] written to the ctx's AB; the terminal quadratisation the same way on the cost MLP.
 //  * Riccati sweep with the adjoint, the control gradient and the continuation test (the arithmetic of k_riccati's
 //    general form, Cholesky of G + 1e-8 I on one lane).
+//
+// The control-limited form (gmpc_ilqr_solve_box, template parameter BOX) is the same kernel with box
+// bounds lo <= u <= hi on the controls: the start and every candidate control are clamped, the gains of a step come
+// from a box QP (projected Newton on one lane, fz_box_qp) and the continuation test sees the projected gradient.
+// With no bound active every phase performs the arithmetic of the unconstrained form, operation for operation.
 #include "gmpc_fused_solve.h"
 
 #define FZ_THREADS GMPC_THREADS
@@ -20,11 +25,21 @@ static __host__ __device__ inline int fz_ric_floats(int n, int m) {
   const int nm = n + m;
   return n * nm + 3 * n * n + 3 * m * n + m * (n + 1) + 2 * m * m + 5 * n + 3 * m;
 }
+// QP workspace of the box form behind the Riccati carve-out: y, g, d, trial y (floats), free list, clamped flags, the
+// free count and the iteration count (ints)
+static __host__ __device__ inline int fz_box_floats(int m) { return 6 * m + 2; }
 static __host__ __device__ inline int fz_ls_floats(int n, int m) {
   return 2 * FZ_THREADS * GMPC_FZ_NC + GMPC_FZ_NC * (n + m);
 }
 static __host__ __device__ inline int fz_lin_floats(int n, int T) {
   return 2 * FZ_THREADS * GMPC_FZ_JR + (T + 1) * GMPC_FZ_LHM * GMPC_MW + 32 + 32 * n;
+}
+// the largest of the phases' carve-outs
+static __host__ __device__ inline int fz_phase_floats(int n, int m, int T, bool box) {
+  int f = fz_ric_floats(n, m) + (box ? fz_box_floats(m) : 0);
+  f = f > fz_ls_floats(n, m) ? f : fz_ls_floats(n, m);
+  f = f > fz_lin_floats(n, T) ? f : fz_lin_floats(n, T);
+  return f;
 }
 
 // sum of one value per thread, in thread order (deterministic); every thread gets the result
@@ -38,6 +53,9 @@ __device__ float fz_block_sum(float v, float* red) {
   return s;
 }
 
+// clamp to [lo, hi] that keeps a NaN (fmaxf / fminf would return the bound)
+__host__ __device__ __forceinline__ float fz_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 __device__ __forceinline__ bool fz_bit(const uint32_t* mb, int slot, int l, int c) {
   return (mb[(slot * GMPC_FZ_LHM + l) * GMPC_MW + (c >> 5)] >> (c & 31)) & 1u;
 }
@@ -46,7 +64,7 @@ __device__ __forceinline__ bool fz_bit(const uint32_t* mb, int slot, int l, int 
 // element k at k * R + r); returns the buffer holding the output [dims[L]][R].  mb != null: the relu bits of hidden
 // layer l of row r (< nrows) go to mask slot slot0 + r.
 template <int R4>
-__device__ float4* fz_forward(const MlpDesc& d, float4* bufA, float4* bufB, int nrows, uint32_t* mb, int slot0) {
+__device__ __forceinline__ float4* fz_forward(const MlpDesc& d, float4* bufA, float4* bufB, int nrows, uint32_t* mb, int slot0) {
   const int j = threadIdx.x, wave = j >> 6, lane = j & 63;
   float4* in = bufA;
   float4* out = bufB;
@@ -89,7 +107,7 @@ __device__ float4* fz_forward(const MlpDesc& d, float4* bufA, float4* bufB, int 
 // Reverse pass: row r (< nrows) is e_i^T d out / d in of the MLP d at the point whose relu bits are mask slot s,
 // with (i, s) = (rho % div, slot_base + rho / div), rho = rho0 + r.  Result in the returned buffer, [dims[0]][R].
 template <int R4>
-__device__ float4* fz_reverse(const MlpDesc& d, float4* bufA, float4* bufB, int nrows, int rho0, int div,
+__device__ __forceinline__ float4* fz_reverse(const MlpDesc& d, float4* bufA, float4* bufB, int nrows, int rho0, int div,
                               int slot_base, const uint32_t* mb) {
   constexpr int R = 4 * R4;
   const int c = threadIdx.x;
@@ -140,9 +158,10 @@ __device__ float4* fz_reverse(const MlpDesc& d, float4* bufA, float4* bufB, int 
 
 // Rollouts of nc rows.  NOMINAL: one row, u = U (the iterate's own rollout, X written to the ctx).  Otherwise row r
 // is the step size alpha_0 / 2^(kfirst + r) of trajax ddp_rollout: u = U_t + (alpha k_t + K_t (x - X_t)), trajectory
-// written to the candidate buffer.  Returns the objective of row r in thread r (r < nc).
-template <bool NOMINAL>
-__device__ float fz_rollout(const FusedSolveArgs& a, int b, int nc, int kfirst, float* sm) {
+// written to the candidate buffer.  BOX: that u clamped to [lo, hi] (bnd: lo[m] then hi[m]).  Returns the objective of
+// row r in thread r (r < nc).
+template <bool NOMINAL, bool BOX>
+__device__ __forceinline__ float fz_rollout(const FusedSolveArgs& a, int b, int nc, int kfirst, float* sm, const float* bnd) {
   constexpr int R4 = GMPC_FZ_NC / 4, R = GMPC_FZ_NC;
   const int n = a.n, m = a.m, T = a.T, tid = threadIdx.x;
   float4* bufA = reinterpret_cast<float4*>(sm);
@@ -182,6 +201,7 @@ __device__ float fz_rollout(const FusedSolveArgs& a, int b, int nc, int kfirst, 
           float v = 0.f;
           for (int j = 0; j < n; ++j) v = fmaf(Kr[j], xr[r * n + j] - Xb[(size_t)t * n + j], v);
           u = U0 + (alr * a.k[((size_t)b * T + t) * m + i] + v);
+          if constexpr (BOX) u = fz_clamp(u, bnd[i], bnd[m + i]);
           cb[r * cstride + (size_t)(T + 1) * n + (size_t)t * m + i] = u;
         }
       }
@@ -233,7 +253,7 @@ __device__ float fz_rollout(const FusedSolveArgs& a, int b, int nc, int kfirst, 
 }
 
 // Linearisation of the dynamics at every step of the iterate (AB) and the terminal quadratisation (QT, qT).
-__device__ void fz_linearize(const FusedSolveArgs& a, int b, float* sm) {
+__device__ __forceinline__ void fz_linearize(const FusedSolveArgs& a, int b, float* sm) {
   constexpr int R4 = GMPC_FZ_JR / 4, R = GMPC_FZ_JR;
   const int n = a.n, m = a.m, T = a.T, nm = n + m, tid = threadIdx.x;
   float4* bufA = reinterpret_cast<float4*>(sm);
@@ -306,9 +326,104 @@ __device__ void fz_linearize(const FusedSolveArgs& a, int b, float* sm) {
   __syncthreads();
 }
 
+// Box QP of one step of the control-limited backward pass, on ONE lane: min 1/2 y^T Gd y + h^T y subject to
+// lo - u <= y <= hi - u, Gd = G + delta I, by projected Newton from y = 0.  The clamped set is
+// c = {j : y_j at its lower bound and g_j > 0, or at its upper bound and g_j < 0}, g = h + Gd y; the step on the free
+// set is d_f = -Gd_ff^-1 g_f (Cholesky of Gd_ff, compact in Lc, the substitution order and the negation of
+// fz_riccati's gain solve); projected Armijo backtracking on yt = clamp(y + s d) with the decrease written as
+// g^T D + 1/2 D^T Gd D, D = yt - y; done when a full step leaves the clamped set unchanged.  Leaves y, the free list
+// fi[0 .. nf) the factor in Lc belongs to, nf in qi[2m] and the iteration count in qi[2m+1]; returns true when the
+// QP stopped at the iteration cap or without an acceptable step.  No comparison is true for a NaN, so NaN data
+// takes the full step of the unconstrained solve and ends after one iteration.
+__host__ __device__ __forceinline__ bool fz_box_qp(int m, const float* __restrict__ G, const float* __restrict__ hv,
+                                                const float* __restrict__ uv, const float* __restrict__ bnd,
+                                                float* __restrict__ Lc, float* __restrict__ qf, int* __restrict__ qi) {
+  const float delta = 1e-8f;
+  float* y = qf;
+  float* g = y + m;
+  float* d = g + m;
+  float* yt = d + m;
+  int* fi = qi;
+  int* cl = qi + m;
+  for (int j = 0; j < m; ++j) {
+    y[j] = 0.f;
+    g[j] = hv[j];
+    const float lb = bnd[j] - uv[j], ub = bnd[m + j] - uv[j];
+    cl[j] = (y[j] == lb && g[j] > 0.f) || (y[j] == ub && g[j] < 0.f);
+  }
+  int it = 0, nf = 0;
+  bool capped = true;
+  while (it < GMPC_BOX_QP_ITERS) {
+    nf = 0;
+    for (int j = 0; j < m; ++j)
+      if (!cl[j]) fi[nf++] = j;
+    for (int j = 0; j < nf; ++j) {
+      float sdiag = G[fi[j] * m + fi[j]] + delta;
+      for (int k = 0; k < j; ++k) sdiag -= Lc[j * m + k] * Lc[j * m + k];
+      const float dg = sqrtf(sdiag);
+      Lc[j * m + j] = dg;
+      for (int i = j + 1; i < nf; ++i) {
+        float v = G[fi[i] * m + fi[j]];
+        for (int k = 0; k < j; ++k) v -= Lc[i * m + k] * Lc[j * m + k];
+        Lc[i * m + j] = v / dg;
+      }
+    }
+    // d_f = -Gd_ff^-1 g_f (yt is the compact work vector), d_c = 0
+    for (int i = 0; i < nf; ++i) {
+      float v = g[fi[i]];
+      for (int k = 0; k < i; ++k) v -= Lc[i * m + k] * yt[k];
+      yt[i] = v / Lc[i * m + i];
+    }
+    for (int i = nf - 1; i >= 0; --i) {
+      float v = yt[i];
+      for (int k = i + 1; k < nf; ++k) v -= Lc[k * m + i] * yt[k];
+      yt[i] = v / Lc[i * m + i];
+    }
+    for (int j = 0; j < m; ++j) d[j] = 0.f;
+    for (int i = 0; i < nf; ++i) d[fi[i]] = -yt[i];
+    // projected Armijo backtracking
+    float s = 1.f;
+    bool found = false;
+    for (int ls = 0; ls < GMPC_BOX_QP_HALVINGS; ++ls) {
+      float gd = 0.f, quad = 0.f;
+      for (int j = 0; j < m; ++j) yt[j] = fz_clamp(y[j] + s * d[j], bnd[j] - uv[j], bnd[m + j] - uv[j]);
+      for (int i = 0; i < m; ++i) {
+        const float di = yt[i] - y[i];
+        float v = 0.f;
+        for (int j = 0; j < m; ++j) v = fmaf(G[i * m + j] + (i == j ? delta : 0.f), yt[j] - y[j], v);
+        gd = fmaf(g[i], di, gd);
+        quad = fmaf(di, v, quad);
+      }
+      if (!(gd + 0.5f * quad > GMPC_BOX_ARMIJO * gd)) { found = true; break; }
+      s *= 0.5f;
+    }
+    if (!found) break;
+    ++it;
+    bool changed = false;
+    for (int j = 0; j < m; ++j) y[j] = yt[j];
+    for (int i = 0; i < m; ++i) {
+      float v = 0.f;
+      for (int j = 0; j < m; ++j) v = fmaf(G[i * m + j] + (i == j ? delta : 0.f), y[j], v);
+      g[i] = hv[i] + v;
+      const float lb = bnd[i] - uv[i], ub = bnd[m + i] - uv[i];
+      const int c = (y[i] == lb && g[i] > 0.f) || (y[i] == ub && g[i] < 0.f);
+      changed |= c != cl[i];
+      cl[i] = c;
+    }
+    if (s == 1.f && !changed) { capped = false; break; }
+  }
+  qi[2 * m] = nf;
+  qi[2 * m + 1] = it;
+  return capped;
+}
+
 // Riccati sweep (trajax tvlqr / lqr_step, c = 0, M = 0) with the adjoint recursion and the control gradient, then the
-// continuation test of ilqr_base.  Returns the continuation flag (every thread).
-__device__ bool fz_riccati(const FusedSolveArgs& a, int b, float* sm, float* red) {
+// continuation test of ilqr_base.  Returns the continuation flag (every thread).  BOX: the gains of a step are those
+// of its box QP (k = y, the free rows of K = -Gd_ff^-1 H_f, the clamped rows 0.0), the value update is the same
+// general form, and the continuation test's gradient norm leaves out the components a bound holds back.
+template <bool BOX>
+__device__ __forceinline__ bool fz_riccati(const FusedSolveArgs& a, const BoxSolveArgs& x, int b, float* sm, float* red,
+                                           const float* bnd) {
   const int n = a.n, m = a.m, T = a.T, nm = n + m, lane = threadIdx.x;
   constexpr int NTH = FZ_THREADS;
   float* ABs = sm;                 // n x nm
@@ -329,6 +444,8 @@ __device__ bool fz_riccati(const FusedSolveArgs& a, int b, float* sm, float* red
   float* uv = tv + n;              // m
   float* rv = uv + m;              // m
   float* hv = rv + m;              // m
+  float* qf = hv + m;              // BOX: fz_box_qp's floats (4 m), then its ints (2 m + 2)
+  int* qi = reinterpret_cast<int*>(qf + 4 * m);
   const float w0 = sigmoidf_(a.mpc_w[0]), w1 = sigmoidf_(a.mpc_w[1]);
   const float al = GMPC_ALPHA;
   const float delta = 1e-8f;
@@ -361,7 +478,12 @@ __device__ bool fz_riccati(const FusedSolveArgs& a, int b, float* sm, float* red
       float g = 0.f;
       for (int i = 0; i < n; ++i) g = fmaf(ABs[i * nm + n + j], lam[i], g);
       g = rv[j] + g;
-      gn2 = fmaf(g, g, gn2);
+      if constexpr (BOX) {
+        const bool held = (uv[j] == bnd[j] && g > 0.f) || (uv[j] == bnd[m + j] && g < 0.f);
+        if (!held) gn2 = fmaf(g, g, gn2);
+      } else {
+        gn2 = fmaf(g, g, gn2);
+      }
       a.grad[bt * m + j] = g;
     }
     for (int c = lane; c < n; c += NTH) {
@@ -420,32 +542,64 @@ __device__ bool fz_riccati(const FusedSolveArgs& a, int b, float* sm, float* red
     }
     __syncthreads();
     // Cholesky of G + delta I (NaN on a non-positive pivot, like jax cho_factor), then [K k] = -(G + delta I)^-1 [H h]
-    if (lane == 0) {
-      for (int j = 0; j < m; ++j) {
-        float sdiag = G[j * m + j] + delta;
-        for (int k = 0; k < j; ++k) sdiag -= Lc[j * m + k] * Lc[j * m + k];
-        const float d = sqrtf(sdiag);
-        Lc[j * m + j] = d;
-        for (int i = j + 1; i < m; ++i) {
-          float v = G[i * m + j];
-          for (int k = 0; k < j; ++k) v -= Lc[i * m + k] * Lc[j * m + k];
-          Lc[i * m + j] = v / d;
+    if constexpr (BOX) {
+      if (lane == 0) {
+        const bool capped = fz_box_qp(m, G, hv, uv, bnd, Lc, qf, qi);
+        x.count[2 * b] += capped ? 1.f : 0.f;
+        x.count[2 * b + 1] += (float)qi[2 * m + 1];
+        x.iters[bt] = (float)qi[2 * m + 1];
+      }
+      __syncthreads();
+      const int nf = qi[2 * m];
+      const int* fi = qi;
+      for (int c = lane; c < n; c += NTH) {
+        for (int i = 0; i < m; ++i) Kk[i * (n + 1) + c] = 0.f;
+        for (int i = 0; i < nf; ++i) {
+          float v = Hm[fi[i] * n + c];
+          for (int k = 0; k < i; ++k) v -= Lc[i * m + k] * Kk[fi[k] * (n + 1) + c];
+          Kk[fi[i] * (n + 1) + c] = v / Lc[i * m + i];
+        }
+        for (int i = nf - 1; i >= 0; --i) {
+          float v = Kk[fi[i] * (n + 1) + c];
+          for (int k = i + 1; k < nf; ++k) v -= Lc[k * m + i] * Kk[fi[k] * (n + 1) + c];
+          Kk[fi[i] * (n + 1) + c] = v / Lc[i * m + i];
+        }
+        for (int i = 0; i < nf; ++i) Kk[fi[i] * (n + 1) + c] = -Kk[fi[i] * (n + 1) + c];
+      }
+      for (int j = lane; j < m; j += NTH) {
+        Kk[j * (n + 1) + n] = qf[j];
+        x.clamped[bt * m + j] = 1.f;
+      }
+      __syncthreads();
+      for (int i = lane; i < nf; i += NTH) x.clamped[bt * m + fi[i]] = 0.f;
+    } else {
+      if (lane == 0) {
+        for (int j = 0; j < m; ++j) {
+          float sdiag = G[j * m + j] + delta;
+          for (int k = 0; k < j; ++k) sdiag -= Lc[j * m + k] * Lc[j * m + k];
+          const float d = sqrtf(sdiag);
+          Lc[j * m + j] = d;
+          for (int i = j + 1; i < m; ++i) {
+            float v = G[i * m + j];
+            for (int k = 0; k < j; ++k) v -= Lc[i * m + k] * Lc[j * m + k];
+            Lc[i * m + j] = v / d;
+          }
         }
       }
-    }
-    __syncthreads();
-    for (int c = lane; c <= n; c += NTH) {
-      for (int i = 0; i < m; ++i) {
-        float v = c < n ? Hm[i * n + c] : hv[i];
-        for (int k = 0; k < i; ++k) v -= Lc[i * m + k] * Kk[k * (n + 1) + c];
-        Kk[i * (n + 1) + c] = v / Lc[i * m + i];
+      __syncthreads();
+      for (int c = lane; c <= n; c += NTH) {
+        for (int i = 0; i < m; ++i) {
+          float v = c < n ? Hm[i * n + c] : hv[i];
+          for (int k = 0; k < i; ++k) v -= Lc[i * m + k] * Kk[k * (n + 1) + c];
+          Kk[i * (n + 1) + c] = v / Lc[i * m + i];
+        }
+        for (int i = m - 1; i >= 0; --i) {
+          float v = Kk[i * (n + 1) + c];
+          for (int k = i + 1; k < m; ++k) v -= Lc[k * m + i] * Kk[k * (n + 1) + c];
+          Kk[i * (n + 1) + c] = v / Lc[i * m + i];
+        }
+        for (int i = 0; i < m; ++i) Kk[i * (n + 1) + c] = -Kk[i * (n + 1) + c];
       }
-      for (int i = m - 1; i >= 0; --i) {
-        float v = Kk[i * (n + 1) + c];
-        for (int k = i + 1; k < m; ++k) v -= Lc[k * m + i] * Kk[k * (n + 1) + c];
-        Kk[i * (n + 1) + c] = v / Lc[i * m + i];
-      }
-      for (int i = 0; i < m; ++i) Kk[i * (n + 1) + c] = -Kk[i * (n + 1) + c];
     }
     __syncthreads();
     for (int e = lane; e < m * n; e += NTH) {
@@ -508,15 +662,35 @@ __device__ bool fz_riccati(const FusedSolveArgs& a, int b, float* sm, float* red
   return go;
 }
 
-__global__ __launch_bounds__(FZ_THREADS) void k_ilqr_fused(FusedSolveArgs a) {
+template <bool BOX>
+__device__ __forceinline__ void fz_solve(const FusedSolveArgs& a, const BoxSolveArgs& x) {
   extern __shared__ float4 fz_smem[];
   float* sm = reinterpret_cast<float*>(fz_smem);
   __shared__ float red[FZ_THREADS];
   __shared__ float s_on[GMPC_FZ_NC];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = a.n, m = a.m, T = a.T;
+  // BOX: the bounds, lo[m] then hi[m], behind the phases' carve-outs (a null pointer: unbounded on that side)
+  const float* bnd = nullptr;
+  if constexpr (BOX) {
+    float* bw = sm + fz_phase_floats(n, m, T, true);
+    for (int j = tid; j < m; j += FZ_THREADS) {
+      bw[j] = x.u_lo ? x.u_lo[j] : -INFINITY;
+      bw[m + j] = x.u_hi ? x.u_hi[j] : INFINITY;
+    }
+    if (tid == 0) {
+      x.count[2 * b] = 0.f;
+      x.count[2 * b + 1] = 0.f;
+    }
+    __syncthreads();
+    bnd = bw;
+  }
   // start: the ctx's copies of U_init / goal, the loop state of ilqr_base
-  for (int e = tid; e < T * m; e += FZ_THREADS) a.U[(size_t)b * T * m + e] = a.U_init[(size_t)b * T * m + e];
+  for (int e = tid; e < T * m; e += FZ_THREADS) {
+    float u = a.U_init[(size_t)b * T * m + e];
+    if constexpr (BOX) u = fz_clamp(u, bnd[e % m], bnd[m + e % m]);
+    a.U[(size_t)b * T * m + e] = u;
+  }
   for (int e = tid; e < (T + 1) * n; e += FZ_THREADS)
     a.goal[(size_t)b * (T + 1) * n + e] = a.goal_in[(size_t)b * (T + 1) * n + e];
   if (tid == 0) {
@@ -527,12 +701,12 @@ __global__ __launch_bounds__(FZ_THREADS) void k_ilqr_fused(FusedSolveArgs a) {
   }
   __syncthreads();
   {
-    const float o = fz_rollout<true>(a, b, 1, 0, sm);
+    const float o = fz_rollout<true, BOX>(a, b, 1, 0, sm, bnd);
     if (tid == 0) a.obj[b] = o;
   }
   __syncthreads();
   fz_linearize(a, b, sm);
-  bool go = fz_riccati(a, b, sm, red);
+  bool go = fz_riccati<BOX>(a, x, b, sm, red, bnd);
   const size_t cstride = (size_t)(T + 1) * n + (size_t)T * m;
   for (int it = 0; it < a.opts.maxiter && go; ++it) {
     // line_search_ddp: halvings k = 0 .. k_max-1, GMPC_FZ_NC at a time, the first decrease in halving order wins
@@ -542,7 +716,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_ilqr_fused(FusedSolveArgs a) {
     float on_acc = 0.f;
     for (int k0 = 0; k0 < a.k_max && acc < 0; k0 += GMPC_FZ_NC) {
       const int nc = min(GMPC_FZ_NC, a.k_max - k0);
-      const float o = fz_rollout<false>(a, b, nc, k0, sm);
+      const float o = fz_rollout<false, BOX>(a, b, nc, k0, sm, bnd);
       if (tid < nc) s_on[tid] = o;
       __syncthreads();
       for (int j = 0; j < nc; ++j) {
@@ -578,7 +752,7 @@ __global__ __launch_bounds__(FZ_THREADS) void k_ilqr_fused(FusedSolveArgs a) {
     if (tid == 0) a.iters[b] += 1;
     __syncthreads();
     fz_linearize(a, b, sm);
-    go = fz_riccati(a, b, sm, red);
+    go = fz_riccati<BOX>(a, x, b, sm, red, bnd);
   }
   // caller outputs
   if (a.oX) for (int e = tid; e < (T + 1) * n; e += FZ_THREADS) a.oX[(size_t)b * (T + 1) * n + e] = a.X[(size_t)b * (T + 1) * n + e];
@@ -592,11 +766,11 @@ __global__ __launch_bounds__(FZ_THREADS) void k_ilqr_fused(FusedSolveArgs a) {
   }
 }
 
-size_t gmpc_fused_lds_bytes(int n, int m, int T) {
-  int f = fz_ric_floats(n, m);
-  f = max(f, fz_ls_floats(n, m));
-  f = max(f, fz_lin_floats(n, T));
-  return (size_t)f * sizeof(float);
+__global__ __launch_bounds__(FZ_THREADS) void k_ilqr_fused(FusedSolveArgs a) { fz_solve<false>(a, BoxSolveArgs{}); }
+__global__ __launch_bounds__(FZ_THREADS) void k_ilqr_box(FusedSolveArgs a, BoxSolveArgs x) { fz_solve<true>(a, x); }
+
+size_t gmpc_fused_lds_bytes(int n, int m, int T, bool box) {
+  return (size_t)(fz_phase_floats(n, m, T, box) + (box ? 2 * m : 0)) * sizeof(float);
 }
 
 void gmpc_launch_ilqr_fused(const FusedSolveArgs& a, int B, hipStream_t s) {
@@ -608,4 +782,38 @@ void gmpc_launch_ilqr_fused(const FusedSolveArgs& a, int B, hipStream_t s) {
     attr = true;
   }
   hipLaunchKernelGGL(k_ilqr_fused, dim3(B), dim3(FZ_THREADS), lds, s, a);
+}
+
+// fz_box_qp on the host, for the CPU tests: the routine the kernel runs on one lane, compiled for the host from the same
+// source, on one QP in host memory.
+extern "C" int gmpc_box_qp_host(int m, const float* G, const float* h, const float* u, const float* u_lo,
+                                const float* u_hi, float* y, int* clamped, int* iterations) {
+  if (m < 1 || m > GMPC_BOX_MAX_M || !G || !h || !u || !u_lo || !u_hi || !y || !clamped || !iterations)
+    return GMPC_EINVAL;
+  float bnd[2 * GMPC_BOX_MAX_M], Lc[GMPC_BOX_MAX_M * GMPC_BOX_MAX_M], qf[4 * GMPC_BOX_MAX_M];
+  int qi[2 * GMPC_BOX_MAX_M + 2];
+  for (int j = 0; j < m; ++j) {
+    bnd[j] = u_lo[j];
+    bnd[m + j] = u_hi[j];
+  }
+  const bool capped = fz_box_qp(m, G, h, u, bnd, Lc, qf, qi);
+  for (int j = 0; j < m; ++j) {
+    y[j] = qf[j];
+    clamped[j] = 1;
+  }
+  for (int i = 0; i < qi[2 * m]; ++i) clamped[qi[i]] = 0;
+  iterations[0] = qi[2 * m + 1];
+  iterations[1] = capped ? 1 : 0;
+  return 0;
+}
+
+void gmpc_launch_ilqr_box(const FusedSolveArgs& a, const BoxSolveArgs& x, int B, hipStream_t s) {
+  const size_t lds = gmpc_fused_lds_bytes(a.n, a.m, a.T, true);
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ilqr_box),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+    attr = true;
+  }
+  hipLaunchKernelGGL(k_ilqr_box, dim3(B), dim3(FZ_THREADS), lds, s, a, x);
 }

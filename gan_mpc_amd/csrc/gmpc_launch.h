@@ -1,6 +1,6 @@
 // Every host function that is defined in one .hip file and called from another, by defining file; that file includes
 // this header too, so each definition is checked against what its callers see.  Default arguments live here only.
-// (gmpc_fused_solve.h keeps the one-launch solve's argument block and limits beside its two prototypes.)
+// (gmpc_fused_solve.h keeps the one-launch solves' argument blocks and limits beside their prototypes.)
 #pragma once
 #include "gmpc_device.h"     // (and with it the device helpers: a kernel file needs this include only)
 

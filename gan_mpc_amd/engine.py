@@ -206,7 +206,37 @@ class Engine:
         returns the same dict as ilqr_solve without synchronising the stream."""
         return self._solve(self.lib.gmpc_ilqr_solve_fused, x0, U, goal, kwargs)
 
-    def _solve(self, fn, x0, U, goal, kwargs):
+    def ilqr_solve_box(self, x0, U, goal, u_lo, u_hi, kwargs=None):
+        """The one-launch solve under box bounds u_lo <= u_t <= u_hi on the controls (gmpc_ilqr_solve_box: the shapes
+        of ilqr_solve_fused).  u_lo, u_hi: None (unbounded on that side), a scalar or m values, -inf / +inf allowed;
+        checked on the host before any launch (their device copies are uploaded when the values change).  Returns the same dict as ilqr_solve; the ctx holds no solution for
+        bilevel_grad* / upper_loss afterwards."""
+        lo, hi = self._bound_vector("u_lo", u_lo), self._bound_vector("u_hi", u_hi)
+        if lo is not None and hi is not None and not bool(np.all(lo <= hi)):
+            raise _lib.GmpcError("u_lo must be <= u_hi")
+        # the device copies are kept: a policy solves with the same bounds at every control step
+        key = (None if lo is None else lo.tobytes(), None if hi is None else hi.tobytes())
+        cache = self.__dict__.setdefault("_box_bounds", {})
+        if key not in cache:
+            if len(cache) >= 8:
+                cache.clear()
+            cache[key] = (None if lo is None else self.to_dev(lo), None if hi is None else self.to_dev(hi))
+        lo_d, hi_d = cache[key]
+        return self._solve(self.lib.gmpc_ilqr_solve_box, x0, U, goal, kwargs, tail=(_ptr(lo_d), _ptr(hi_d)))
+
+    def _bound_vector(self, name, b):
+        """None, a scalar or m values -> None or a host fp32 vector [m] without NaN."""
+        if b is None:
+            return None
+        v = b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)
+        v = np.array(np.broadcast_to(v.astype(np.float32), (self.m,)) if v.ndim == 0 else v.astype(np.float32))
+        if v.shape != (self.m,):
+            raise _lib.GmpcError(f"{name} must be a scalar or {self.m} values, got shape {v.shape}")
+        if np.isnan(v).any():
+            raise _lib.GmpcError(f"{name} has a NaN entry: u_lo must be <= u_hi")
+        return v
+
+    def _solve(self, fn, x0, U, goal, kwargs, tail=()):
         B = x0.shape[0]
         self.solve_count += 1     # before the call: a failed solve drops the held solution as well
         n, m, T = self.n, self.m, self.T
@@ -217,7 +247,7 @@ class Engine:
         _lib.check(fn(
             self.ctx, B, _ptr(x0), _ptr(U), _ptr(goal), C.byref(opts), _ptr(out["X"]), _ptr(out["U"]),
             _ptr(out["obj"]), _ptr(out["grad"]), _ptr(out["adjoints"]), _ptr(out["iterations"]),
-            self._stream()))
+            self._stream(), *tail))
         return out
 
     def bilevel_grad(self, B, loss_kind, desired=None, critic=None, sign=1.0, grad_sum=None):

@@ -44,16 +44,23 @@ class LqrBlock:
 
 
 class EvalMPC:
-    SOLVERS = ("rounds", "fused")
+    SOLVERS = ("rounds", "fused", "box")
 
     def __init__(self, config, cost_model, dynamics_model, expert_model,
-                 trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds"):
+                 trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
-        short-horizon / batch-1 MPC action)."""
+        short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
+        limited to control_bounds = (lo, hi), each None, a scalar or one value per control (no bilevel gradient)."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
+        if (solver == "box") != (control_bounds is not None):
+            raise ValueError('control_bounds=(lo, hi) and solver="box" go together: got '
+                             f"solver={solver!r}, control_bounds={control_bounds!r}")
+        if control_bounds is not None and len(control_bounds) != 2:
+            raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
+        self.control_bounds = None if control_bounds is None else tuple(control_bounds)
         self.config = config
         self.cost_model = cost_model
         self.dynamics_model = dynamics_model

@@ -5,13 +5,24 @@ evaluations and their derivatives are fused HIP kernels behind the C ABI, so the
 replaced by the policy object that owns the engine and the bound parameters.  Everything is batched
 over the leading axis (the reference's jax.vmap axis)."""
 
+import functools
+
 import torch
 
 
 def _solver(policy, eng):
-    """The engine entry point of the policy's solver: "rounds" (gmpc_ilqr_solve, host-driven iterations) or
-    "fused" (gmpc_ilqr_solve_fused, the whole solve in one launch)."""
-    return eng.ilqr_solve_fused if getattr(policy, "solver", "rounds") == "fused" else eng.ilqr_solve
+    """The engine entry point of the policy's solver: "rounds" (gmpc_ilqr_solve, host-driven iterations), "fused"
+    (gmpc_ilqr_solve_fused, the whole solve in one launch) or "box" (gmpc_ilqr_solve_box, the one-launch solve under
+    the policy's control_bounds)."""
+    solver = getattr(policy, "solver", "rounds")
+    if solver == "box":
+        lo, hi = policy.control_bounds
+        return functools.partial(_box_solve, eng, lo, hi)
+    return eng.ilqr_solve_fused if solver == "fused" else eng.ilqr_solve
+
+
+def _box_solve(eng, lo, hi, x0, U, goal, kwargs=None):
+    return eng.ilqr_solve_box(x0, U, goal, lo, hi, kwargs)
 
 
 def ilqr_solve(policy, dparams, x0, U, goal, trajax_ilqr_kwargs=None):

@@ -179,6 +179,34 @@ int gmpc_ilqr_solve_fused(gmpc_ctx* ctx, int B, const float* x0, const float* U_
                           const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad,
                           float* adjoints, int* iterations, void* stream);
 
+/* Control-limited iLQR in one kernel launch: gmpc_ilqr_solve_fused under box bounds u_lo <= u_t <= u_hi on the
+ * controls (control-limited DDP, Tassa, Mansard and Todorov 2014).  u_lo, u_hi: device pointers, [m] each,
+ * shared by all trajectories and steps; either may be NULL (unbounded on that side), entries may be -inf / +inf.  The
+ * caller guarantees u_lo <= u_hi and no NaN entry (the pointers are device memory: not checked here).
+ *   The start is clamped, every candidate rollout applies u = clamp(U_t + (alpha k_t + K_t (x - X_t))), and the gains of
+ *   a step are those of the box QP  min 1/2 y^T G y + h^T y,  u_lo - u_t <= y <= u_hi - u_t  (projected Newton, at most
+ *   40 iterations): k_t = y, the rows of K_t of clamped controls are exactly 0.  The continuation test uses the norm of
+ *   the projected gradient; `grad` is the full gradient (its entries at clamped controls are the bounds' multipliers).
+ *   With no bound active every result is bit for bit that of gmpc_ilqr_solve_fused.
+ * Arguments, results, coverage and asynchrony as gmpc_ilqr_solve_fused; refusals start with "box solve: ...".
+ * ctx state left behind: X, U, goals, obj, grad, adjoints, [A|B], K / k, alpha / obj_step / U_step as after the fused
+ * solve, and gmpc_debug_buffer 15 ([B][2]: QPs of the solve that stopped at the iteration cap, QP iterations of the
+ * solve), 16 ([B][T]: QP iterations per step of the last backward pass), 17 ([B][T][m]: 1.0 where a control is in the
+ * final clamped set of that pass).
+ * NO solution is held for the bilevel tail: gmpc_bilevel_grad*, gmpc_upper_loss after this call fail with "must
+ * precede".  The implicit gradient through an active set is not implemented. */
+int gmpc_ilqr_solve_box(gmpc_ctx* ctx, int B, const float* x0, const float* U_init, const float* goal,
+                        const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad,
+                        float* adjoints, int* iterations, void* stream, const float* u_lo, const float* u_hi);
+
+/* Test hook, host memory only, no ctx and no device: ONE box QP of gmpc_ilqr_solve_box's backward pass, solved on the
+ * host by the routine the kernel runs on one lane (the same source compiled for the host).  G [m][m] symmetric WITHOUT
+ * the 1e-8 regulariser (the routine adds it), h, u, u_lo, u_hi [m]; m <= 32.  -> y [m] (the minimiser of
+ * 1/2 y^T (G + 1e-8 I) y + h^T y on u_lo - u <= y <= u_hi - u), clamped [m] (1 / 0: the final clamped set),
+ * iterations [2]: the QP iterations and 1 where it stopped at a cap.  Returns 0, or GMPC_EINVAL. */
+int gmpc_box_qp_host(int m, const float* G, const float* h, const float* u, const float* u_lo,
+                     const float* u_hi, float* y, int* clamped, int* iterations);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
