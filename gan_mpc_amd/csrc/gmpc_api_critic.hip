@@ -61,11 +61,7 @@ static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const
   CriticDesc cr = cd;
   auto gemm1 = [&](int M, int N, int K, const float* X, int ldx, const float* Y, int ldy, float* Cp,
                    int ldc) {
-    BgemmArgs g;
-    g.batch = 1; g.M = M; g.N = N; g.K = K;
-    g.X = X; g.sx = 0; g.ldx = ldx; g.Y = Y; g.sy = 0; g.ldy = ldy; g.C = Cp; g.sc = 0; g.ldc = ldc;
-    g.alpha = 1.f; g.beta = 0.f; g.active = nullptr;
-    gmpc_launch_bgemm_tn(g, s);
+    gmpc_launch_bgemm_tn(bgemm_args(1, M, N, K, X, 0, ldx, Y, 0, ldy, Cp, 0, ldc, nullptr), s);
   };
   if (widein) {
     cr.n = 0;
@@ -397,7 +393,7 @@ extern "C" int gmpc_adam_clip_step(gmpc_ctx* c, long count, float* params, const
   return 0;
 }
 
-// Batched TN GEMM used by the large-state Riccati path, exported for its unit test:
+// Batched TN GEMM (gmpc_bgemm.hip) used by the large-state Riccati path, exported for its unit test:
 // C[b] = alpha * X[b]^T Y[b] + beta * C[b] with X[b] K x M, Y[b] K x N, C[b] M x N, all row-major
 // and densely packed per batch element.  Y must be followed by >= 8 readable rows.
 extern "C" int gmpc_bgemm_tn(gmpc_ctx* c, int batch, int M, int N, int K, const float* X, const float* Y,
@@ -405,13 +401,9 @@ extern "C" int gmpc_bgemm_tn(gmpc_ctx* c, int batch, int M, int N, int K, const 
   if (!c || !X || !Y || !C || batch < 1 || M < 1 || N < 1 || K < 1) return fail(GMPC_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(c->device));
   (void)hipGetLastError();   // clean slate (see check_call)
-  BgemmArgs a;
-  a.batch = batch; a.M = M; a.N = N; a.K = K;
-  a.X = X; a.sx = (long)K * M; a.ldx = M;
-  a.Y = Y; a.sy = (long)K * N; a.ldy = N;
-  a.C = C; a.sc = (long)M * N; a.ldc = N;
-  a.alpha = alpha; a.beta = beta; a.active = nullptr;
-  gmpc_launch_bgemm_tn(a, static_cast<hipStream_t>(stream));
+  gmpc_launch_bgemm_tn(bgemm_args(batch, M, N, K, X, (long)K * M, M, Y, (long)K * N, N, C, (long)M * N, N, nullptr,
+                                  alpha, beta),
+                       static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -321,7 +321,7 @@ struct TransposeList {
   float* out[2 * GMPC_MAX_LAYERS + 1];
 };
 
-// batched "TN" GEMM of the large-state path (gmpc_large.hip)
+// batched "TN" GEMM (gmpc_bgemm.hip: the contract is in its header comment)
 struct BgemmArgs {
   int batch, M, N, K;
   const float* X; long sx; int ldx;     // X[b]: K x M row-major (leading dim ldx), batch stride sx
@@ -342,8 +342,43 @@ struct BgemmArgs {
   const float* E = nullptr; long se = 0; int lde = 0; int En = 0;   // C[row][col] += E[b][row][col], col < En
   const uint32_t* rowmask = nullptr; long srm = 0;                  // [b] bit words: row r of C is zeroed when bit r is clear
 };
+// the plain product C = X^T Y (alpha = 1, beta = 0, no options); callers set the extras on the result
+inline BgemmArgs bgemm_args(int batch, int M, int N, int K, const float* X, long sx, int ldx, const float* Y, long sy,
+                            int ldy, float* C, long sc, int ldc, const int* active, float alpha = 1.f,
+                            float beta = 0.f) {
+  BgemmArgs g;
+  g.batch = batch; g.M = M; g.N = N; g.K = K;
+  g.X = X; g.sx = sx; g.ldx = ldx; g.Y = Y; g.sy = sy; g.ldy = ldy; g.C = C; g.sc = sc; g.ldc = ldc;
+  g.alpha = alpha; g.beta = beta; g.active = active;
+  return g;
+}
 
-// workspace of the large-state backward pass (gmpc_large.hip)
+// per-trajectory pieces of one step of the large-state backward pass (k_big_step, gmpc_big_step.hip)
+struct BigStepArgs {
+  int B, n, m, T, t;
+  int mode;              // 0: iLQR step (trajax lqr_step, Cholesky of G + 1e-8 I)
+                         // 1: bilevel Hessian solve (oracle hessian_solve: no regulariser, LU with
+                         //    partial pivoting, linear term -Bvec_t, loss adjoint mu in `lam`)
+  const float* lx;       // mode 1: [B][T+1][n] d loss / d X
+  const float* lu;       // mode 1: [B][T][m]   d loss / d U, or null (a loss of X only: no term at all)
+  float* Bvec;           // mode 1: [B][T][m]   out: B_t^T mu_{t+1}
+  const float* X; const float* U; const float* goal; const float* mpc_w;
+  int ng;                // columns of `goal` (0: n)
+  const float* ABt;      // [B][n][n+m]   Jacobians of step t (dense form)
+  const float* Vt;       // low-rank form (non-null): [B][h][n+m] with A = I + WL^T Vx^T, B = WL^T Vu^T
+  const float* WL;       //   the output layer's kernel [h][n] (shared)
+  int h;
+  const float* HG;       // [B][m][n+m]   [B^T P A | B^T P B]
+  float* KV;             // [B][2m][n]    out: rows 0..m-1 = K_t, rows m..2m-1 = V = H + G K / 2
+  float* VK;             // [B][2m][n]    out: rows 0..m-1 = V,   rows m..2m-1 = K_t
+  float* pvec; float* lam;   // [B][n]    value vector / adjoint, updated in place
+  float* sbuf;           // [B]           out: sqrt(|x-g|^2 + alpha^2) of this step (for Q_t)
+  float* gn2;            // [B]           running sum of squared control gradients
+  const int* active;
+  float* K; float* k; float* grad; float* adj;   // [B][T][m][n], [B][T][m], [B][T][m], [B][T+1][n]
+  int solve_valu;        // mode 0: the gain solve on the vector pipe (the form before big_solve_mfma; GMPC_BIG_SOLVE=valu)
+};
+
 // LSTM dynamics variant (gmpc_dynl.hip)
 struct DynlDesc {
   int nx, F, m;          // x size, cell features, controls; state size N = nx + 2F
@@ -374,6 +409,7 @@ struct DynlTrajArgs {
   int width;             // LDS activation width: max(N, tail / cost widths)
 };
 
+// workspace of the large-state backward pass (gmpc_large.hip)
 struct BigWork {
   int ng = 0;            // columns of `goal` (0: n)
   int n, m, T;

@@ -87,8 +87,14 @@ void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pa
 size_t gmpc_linsparse_floats(int L, const int* dims, int n, int m);
 void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* out, hipStream_t s);
 
-// gmpc_large.hip: the step-major pipeline (n > 64 or m > 32) ---------------------------------------------------------
+// gmpc_bgemm.hip: the batched "TN" GEMM family ----------------------------------------------------------------------
 void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s);
+
+// gmpc_big_step.hip: k_big_step for the a.B trajectories of step a.t --------------------------------------------------
+// non-zero (nothing launched) when the step's LDS does not fit one workgroup per CU
+int gmpc_launch_big_step(const BigStepArgs& a, hipStream_t s);
+
+// gmpc_large.hip: the step-major pipeline (n > 64 or m > 32) ---------------------------------------------------------
 // one backward pass, non-zero when no Jacobian kernel covers the shape; lx / Bvec (lu optional): the bilevel tail's
 int gmpc_big_backward(const BigWork& w, int B, const MlpDesc& dyn, const LinPad& lp, const uint32_t* masks,
                       const float* X, const float* U, const float* goal, const float* mpc_w, const float* QT,
