@@ -57,6 +57,29 @@ class Leaf(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class BgemmDesc(C.Structure):
+    """gmpc_bgemm_desc: every argument of the batched TN GEMM family (gmpc_bgemm_tn_ex / gmpc_bgemm_route)."""
+    _fields_ = [
+        ("batch", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+        ("X", _P), ("sx", C.c_long), ("ldx", C.c_int),
+        ("Y", _P), ("sy", C.c_long), ("ldy", C.c_int),
+        ("C", _P), ("sc", C.c_long), ("ldc", C.c_int),
+        ("alpha", C.c_float), ("beta", C.c_float),
+        ("active", _P),
+        ("X2", _P), ("sx2", C.c_long), ("ldx2", C.c_int),
+        ("Y2", _P), ("sy2", C.c_long), ("ldy2", C.c_int),
+        ("K2", C.c_int),
+        ("X3", _P), ("sx3", C.c_long), ("ldx3", C.c_int),
+        ("Y3", _P), ("sy3", C.c_long), ("ldy3", C.c_int),
+        ("K3", C.c_int),
+        ("upper_only", C.c_int),
+        ("E", _P), ("se", C.c_long), ("lde", C.c_int), ("En", C.c_int),
+        ("rowmask", _P), ("srm", C.c_long),
+    ]
+
+
 # name -> (restype, argtypes); exactly the entry points declared in include/gan_mpc_amd.h
 SIGNATURES = {
     "gmpc_last_error": (C.c_char_p, []),
@@ -103,6 +126,8 @@ SIGNATURES = {
                                       C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "gmpc_bgemm_tn": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, C.c_float,
                                 _P]),
+    "gmpc_bgemm_tn_ex": (C.c_int, [_P, C.POINTER(BgemmDesc), _P]),
+    "gmpc_bgemm_route": (C.c_int, [C.POINTER(BgemmDesc), C.POINTER(C.c_int)]),
     "gmpc_linesearch_candidates": (C.c_long, [_P]),
     "gmpc_linesearch_stats": (C.c_int, [_P, C.POINTER(C.c_long), C.c_int]),
     "gmpc_profile_enable": (C.c_int, [_P, C.c_int]),

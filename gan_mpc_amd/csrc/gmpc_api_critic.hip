@@ -408,6 +408,46 @@ extern "C" int gmpc_bgemm_tn(gmpc_ctx* c, int batch, int M, int N, int K, const 
   return 0;
 }
 
+// The same product with every field of BgemmArgs in the caller's hands (strides, leading dimensions, `active`, the
+// further K-segments, the epilogue extras, `upper_only`): the entry point of tests/bgemm_cases.py.
+static bool bgemm_desc_ok(const gmpc_bgemm_desc* d) {
+  if (!d || !d->X || !d->Y || !d->C || d->batch < 1 || d->M < 1 || d->N < 1 || d->K < 1) return false;
+  if (d->ldx < d->M || d->ldy < d->N || d->ldc < d->N || d->sx < 0 || d->sy < 0 || d->sc < 0) return false;
+  if (d->K2 < 0 || (d->K2 > 0 && (!d->X2 || !d->Y2 || d->ldx2 < d->M || d->ldy2 < d->N))) return false;
+  if (d->K3 < 0 || (d->K3 > 0 && (!d->X3 || !d->Y3 || d->ldx3 < d->M || d->ldy3 < d->N))) return false;
+  if (d->E && (d->En < 0 || d->En > d->N || d->lde < d->En)) return false;
+  if (d->upper_only && d->M != d->N) return false;
+  return true;
+}
+static BgemmArgs bgemm_desc_args(const gmpc_bgemm_desc* d) {
+  BgemmArgs g = bgemm_args(d->batch, d->M, d->N, d->K, d->X, d->sx, d->ldx, d->Y, d->sy, d->ldy, d->C, d->sc, d->ldc,
+                           d->active, d->alpha, d->beta);
+  g.X2 = d->X2; g.sx2 = d->sx2; g.ldx2 = d->ldx2; g.Y2 = d->Y2; g.sy2 = d->sy2; g.ldy2 = d->ldy2; g.K2 = d->K2;
+  g.X3 = d->X3; g.sx3 = d->sx3; g.ldx3 = d->ldx3; g.Y3 = d->Y3; g.sy3 = d->sy3; g.ldy3 = d->ldy3; g.K3 = d->K3;
+  g.upper_only = d->upper_only ? 1 : 0;
+  g.E = d->E; g.se = d->se; g.lde = d->lde; g.En = d->En;
+  g.rowmask = d->rowmask; g.srm = d->srm;
+  return g;
+}
+
+extern "C" int gmpc_bgemm_tn_ex(gmpc_ctx* c, const gmpc_bgemm_desc* d, void* stream) {
+  if (!c || !bgemm_desc_ok(d)) return fail(GMPC_EINVAL, "bad argument");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  gmpc_launch_bgemm_tn(bgemm_desc_args(d), static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The kernel form gmpc_bgemm_tn_ex would launch for `d`; host only, the pointers are compared with NULL and never
+// followed.
+extern "C" int gmpc_bgemm_route(const gmpc_bgemm_desc* d, int* route4) {
+  if (!bgemm_desc_ok(d) || !route4) return fail(GMPC_EINVAL, "bad argument");
+  const BgemmRoute r = gmpc_bgemm_route_of(bgemm_desc_args(d));
+  route4[0] = r.family; route4[1] = r.p[0]; route4[2] = r.p[1]; route4[3] = r.p[2];
+  return 0;
+}
+
 // multi-GPU exchange -----------------------------------------------------------------------------
 extern "C" int gmpc_comm_unique_id(char* id128) {
   if (!id128) return fail(GMPC_EINVAL, "null argument");

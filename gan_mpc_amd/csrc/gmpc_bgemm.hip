@@ -5,19 +5,25 @@
 // BgemmArgs (gmpc_device.h; bgemm_args fills the plain product).  What the callers rely on:
 //   - TN form only: X[b] is K x M, Y[b] is K x N, C[b] is M x N; a batch stride of 0 shares an operand; batch elements
 //     whose `active` entry is 0 are left untouched.
-//   - pad rows and columns of Y: the one-wave strips (k_bgemm_tn) read Y up to 6 rows past K and up to 32*NTW-1 columns
-//     past N (values discarded / multiplied by zero), so Y is followed by 8 readable rows.  The streaming kernel
-//     (k_bthin) and the LDS-staged one (k_bgemm_tn_lds) clamp / zero-fill at the edges: never outside the matrix.
-//   - options that exist in the LDS-staged kernel only -- setting one of them routes the product there whatever its
-//     shape: the epilogue addend E, `rowmask`, the further K-segments K2 / K3 and `upper_only`.
+//   - pad rows and columns of Y: the one-wave strips (k_bgemm_tn) read Y up to 4 rows past K and up to 32*NTW-1 columns
+//     past N (values discarded, never multiplied: a NaN there is harmless), so Y[b] + K * ldy is followed by
+//     max(8 * ldy, 4 * ldy + 32 * NTW) readable floats: 8 rows, which cover it whenever 4 * ldy >= 32 * NTW.  The
+//     streaming kernel (k_bthin) and the LDS-staged one (k_bgemm_tn_lds) clamp / zero-fill at the edges: never
+//     outside the matrix.
+//   - options that exist in the LDS-staged kernel only: the epilogue addend E, `rowmask` and the further K-segments
+//     K2 / K3 -- setting one of them routes the product there whatever its shape -- and `upper_only`, which does NOT
+//     route by itself: the streaming kernel is ruled out, but a shape that the strips take (M <= 32 or N <= 64, no
+//     other option) gets the full product from them, which is a valid answer.
+//   - gmpc_bgemm_route_of is the dispatcher's decision without its launch; gmpc_bgemm_tn_ex / gmpc_bgemm_route
+//     (gmpc_api_critic.hip) export the full BgemmArgs and the decision for tests/bgemm_cases.py.
 #include <type_traits>
 
 #include "gmpc_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // C[b] = alpha * sum_{k<K} X[b][k][0:M]^T (x) Y[b][k][0:N]  (+ beta * C[b]);  one wave per
-// 32 x 32*NTW strip of one batch element.  Y is read up to 6 rows past K and up to 32*NTW-1 columns
-// past N (values discarded / multiplied by zero): the caller pads its buffers.
+// 32 x 32*NTW strip of one batch element.  Y is read up to 4 rows past K and up to 32*NTW-1 columns
+// past N (values discarded, never multiplied): the caller pads its buffers.
 // ------------------------------------------------------------------------------------------------
 template <int NTW>
 __global__ __launch_bounds__(GMPC_THREADS) void k_bgemm_tn(BgemmArgs a) {
@@ -513,9 +519,10 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_bgemm_tn_lds(BgemmArgs a) {
 #ifndef GMPC_BG_KC
 #define GMPC_BG_KC 8
 #endif
-template <int WMT, int WNT>
+// The 16-byte staging form and its stage depth follow from the block width and the shape (gmpc_bgemm_route_of below).
+template <int WNT, int KC, bool VEC>
 static void launch_lds(const BgemmArgs& a0, hipStream_t s) {
-  constexpr int BM = 64 * WMT, BN = 64 * WNT;
+  constexpr int BM = 128, BN = 64 * WNT;
   BgemmArgs a = a0;
   const int mbk = (a.M + BM - 1) / BM, nbk = (a.N + BN - 1) / BN;
   long lb = (long)mbk * nbk;
@@ -526,19 +533,12 @@ static void launch_lds(const BgemmArgs& a0, hipStream_t s) {
   }
   const long total = (long)a.batch * lb;
   const long per = (total + 7) / 8;
-  // 16-byte staging needs columns in groups of four (M, N multiples of 4); the ROWS need not start on 16 bytes:
-  // buffer_load_dwordx4 takes any 4-byte-aligned address (ld = n + m = 393 at C4)
-  // (192-wide blocks stage 16 bytes per thread with 16-row stages only: 8 rows x 192 columns are 1.5 loads per thread)
-  const bool vec = (a.M & 3) == 0 && (a.N & 3) == 0;
-  if (vec)
-    hipLaunchKernelGGL((k_bgemm_tn_lds<WMT, WNT, WNT == 2 ? GMPC_BG_KC_VEC22 : GMPC_BG_KC_VEC, true>), dim3((unsigned)(per * 8)),
-                       dim3(GMPC_THREADS), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_bgemm_tn_lds<WMT, WNT, GMPC_BG_KC>), dim3((unsigned)(per * 8)), dim3(GMPC_THREADS), 0,
-                       s, a);
+  hipLaunchKernelGGL((k_bgemm_tn_lds<2, WNT, KC, VEC>), dim3((unsigned)(per * 8)), dim3(GMPC_THREADS), 0, s, a);
 }
 
-void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s) {
+// The dispatcher's decision, apart from its launch (host only, no GPU work: gmpc_bgemm_route exports it so that a test
+// can tell which instantiation a shape reaches).
+BgemmRoute gmpc_bgemm_route_of(const BgemmArgs& a) {
   // a thin product whose wide operand is worth streaming (k_bthin)
   {
     const bool widex = a.N <= 64 && a.M >= 128, widey = a.M <= 64 && a.N >= 128;
@@ -553,17 +553,10 @@ void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s) {
       // (two strips x four tiles are 268 registers, one wave per SIMD: 0.387 ms against 0.360 with two tiles for
       // the [64 x 1088] x K = 200 products of C5)
       const int ntj = (waves4 < 4096 || ns == 2) ? 2 : 4;
-      const long total = (long)a.batch * ((Wd + 32 * ntj - 1) / (32 * ntj)) * ((Th + 32 * ns - 1) / (32 * ns));
-      const dim3 grid((unsigned)((total + 3) / 4)), blk(GMPC_THREADS);
-#define BT_LAUNCH(WX, NJ, S) hipLaunchKernelGGL((k_bthin<WX, NJ, BT_RD, S>), grid, blk, 0, s, a)
-      if (ns == 2)       { if (widex) BT_LAUNCH(true, 2, 2); else BT_LAUNCH(false, 2, 2); }
-      else if (ntj == 2) { if (widex) BT_LAUNCH(true, 2, 1); else BT_LAUNCH(false, 2, 1); }
-      else               { if (widex) BT_LAUNCH(true, 4, 1); else BT_LAUNCH(false, 4, 1); }
-#undef BT_LAUNCH
-      return;
+      return BgemmRoute{BGEMM_THIN, {widex ? 1 : 0, ntj, ns}};
     }
   }
-  // (the epilogue extras and the second K-segment exist in the LDS-staged kernel only)
+  // (the epilogue extras and the further K-segments exist in the LDS-staged kernel only)
   if ((a.M > 32 && a.N > 64) || a.E != nullptr || a.rowmask != nullptr || a.K2 > 0 || a.K3 > 0) {
     // column blocks of 128 / 192 / 256: the one that pads N least (ties: the widest)
     // (upper-only outputs: the area of the blocks that are not skipped -- narrow blocks follow the diagonal)
@@ -580,17 +573,50 @@ void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s) {
       }
       if (waste < 0 || padded <= waste) { waste = padded; best = w; }
     }
-    switch (best) {
-      case 2: launch_lds<2, 2>(a, s); break;
-      case 3: launch_lds<2, 3>(a, s); break;
-      default: launch_lds<2, 4>(a, s); break;
-    }
-    return;
+    // 16-byte staging needs columns in groups of four (M, N multiples of 4); the ROWS need not start on 16 bytes:
+    // buffer_load_dwordx4 takes any 4-byte-aligned address (ld = n + m = 393 at C4)
+    // (192-wide blocks stage 16 bytes per thread with 16-row stages only: 8 rows x 192 columns are 1.5 loads per thread)
+    const bool vec = (a.M & 3) == 0 && (a.N & 3) == 0;
+    return BgemmRoute{BGEMM_LDS, {best, vec ? (best == 2 ? GMPC_BG_KC_VEC22 : GMPC_BG_KC_VEC) : GMPC_BG_KC, vec ? 1 : 0}};
   }
-  // a thin product: one wave per strip (the second K-segment is not supported here)
+  // a thin product: one wave per strip (the further K-segments are not supported here)
   const int tiles = (a.N + 31) / 32;
   const int ntw = tiles >= 8 && tiles % 8 == 0 ? 8 : tiles >= 6 && tiles % 6 == 0 ? 6
                   : tiles >= 4 ? 4 : tiles >= 2 ? 2 : 1;
+  return BgemmRoute{BGEMM_STRIPS, {ntw, 0, 0}};
+}
+
+void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s) {
+  const BgemmRoute r = gmpc_bgemm_route_of(a);
+  if (r.family == BGEMM_THIN) {
+    const bool widex = r.p[0] != 0;
+    const int ntj = r.p[1], ns = r.p[2];
+    const int Wd = widex ? a.M : a.N, Th = widex ? a.N : a.M;
+    const long total = (long)a.batch * ((Wd + 32 * ntj - 1) / (32 * ntj)) * ((Th + 32 * ns - 1) / (32 * ns));
+    const dim3 grid((unsigned)((total + 3) / 4)), blk(GMPC_THREADS);
+#define BT_LAUNCH(WX, NJ, S) hipLaunchKernelGGL((k_bthin<WX, NJ, BT_RD, S>), grid, blk, 0, s, a)
+    if (ns == 2)       { if (widex) BT_LAUNCH(true, 2, 2); else BT_LAUNCH(false, 2, 2); }
+    else if (ntj == 2) { if (widex) BT_LAUNCH(true, 2, 1); else BT_LAUNCH(false, 2, 1); }
+    else               { if (widex) BT_LAUNCH(true, 4, 1); else BT_LAUNCH(false, 4, 1); }
+#undef BT_LAUNCH
+    return;
+  }
+  if (r.family == BGEMM_LDS) {
+    const bool vec = r.p[2] != 0;
+    switch (r.p[0]) {
+      case 2:
+        if (vec) launch_lds<2, GMPC_BG_KC_VEC22, true>(a, s); else launch_lds<2, GMPC_BG_KC, false>(a, s);
+        break;
+      case 3:
+        if (vec) launch_lds<3, GMPC_BG_KC_VEC, true>(a, s); else launch_lds<3, GMPC_BG_KC, false>(a, s);
+        break;
+      default:
+        if (vec) launch_lds<4, GMPC_BG_KC_VEC, true>(a, s); else launch_lds<4, GMPC_BG_KC, false>(a, s);
+        break;
+    }
+    return;
+  }
+  const int ntw = r.p[0];
   const int mstrips = (a.M + 31) / 32, ngroups = (a.N + 32 * ntw - 1) / (32 * ntw);
   const long total = (long)a.batch * mstrips * ngroups;
   const dim3 grid((unsigned)((total + 3) / 4)), blk(GMPC_THREADS);

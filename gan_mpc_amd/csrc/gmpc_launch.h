@@ -89,6 +89,10 @@ void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* 
 
 // gmpc_bgemm.hip: the batched "TN" GEMM family ----------------------------------------------------------------------
 void gmpc_launch_bgemm_tn(const BgemmArgs& a, hipStream_t s);
+// the kernel form the dispatcher picks: strips p = {NTW}, thin p = {WIDE_X, NTJ, NS}, lds p = {WNT, KC, VEC}
+enum { BGEMM_STRIPS = 0, BGEMM_THIN = 1, BGEMM_LDS = 2 };
+struct BgemmRoute { int family; int p[3]; };
+BgemmRoute gmpc_bgemm_route_of(const BgemmArgs& a);
 
 // gmpc_big_step.hip: k_big_step for the a.B trajectories of step a.t --------------------------------------------------
 // non-zero (nothing launched) when the step's LDS does not fit one workgroup per CU

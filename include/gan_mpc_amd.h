@@ -441,9 +441,39 @@ int gmpc_dynamics_loss_grad(gmpc_ctx* ctx, int B, int S, const float* xseq, cons
 /* Building block of the large-state (n > 64) Riccati path, exported for its unit test: batched
  * C[b] = alpha * X[b]^T Y[b] + beta * C[b] on the fp32 matrix cores; X[b] is K x M, Y[b] K x N,
  * C[b] M x N, row-major, densely packed per batch element; Y must be followed by >= 8 readable rows
- * of N floats. */
+ * of N floats (N < 64: by max(8 N, 4 N + 256) floats, see gmpc_bgemm_desc). */
 int gmpc_bgemm_tn(gmpc_ctx* ctx, int batch, int M, int N, int K, const float* X, const float* Y,
                   float* C, float alpha, float beta, void* stream);
+
+/* The same family with every argument the large-state pass sets, for the unit tests (tests/bgemm_cases.py):
+ *   C[b] = alpha * (X[b]^T Y[b] + X2[b]^T Y2[b] + X3[b]^T Y3[b]) + beta * C[b] + E[b][:, 0:En],
+ * then the rows of C[b] whose bit in rowmask[b] is clear (bit r & 31 of word r >> 5, srm words per batch element) are
+ * set to 0.  X*[b] is K* x M, Y*[b] K* x N with leading dimensions ld* >= the width and batch strides s* (in floats;
+ * 0 shares an operand); K2 = 0 / K3 = 0, E = NULL, rowmask = NULL switch a part off.  Batch elements whose `active`
+ * entry is 0 are left untouched (active = NULL: all of them).  upper_only (M = N, a symmetric result): entries below
+ * the diagonal may be left unwritten.  Y[b] + K * ldy must be followed by max(8 * ldy, 4 * ldy + 256) readable floats. */
+typedef struct gmpc_bgemm_desc {
+  int batch, M, N, K;
+  const float* X; long sx; int ldx;
+  const float* Y; long sy; int ldy;
+  float* C; long sc; int ldc;
+  float alpha, beta;
+  const int* active;
+  const float* X2; long sx2; int ldx2;
+  const float* Y2; long sy2; int ldy2;
+  int K2;
+  const float* X3; long sx3; int ldx3;
+  const float* Y3; long sy3; int ldy3;
+  int K3;
+  int upper_only;
+  const float* E; long se; int lde; int En;
+  const unsigned* rowmask; long srm;
+} gmpc_bgemm_desc;
+int gmpc_bgemm_tn_ex(gmpc_ctx* ctx, const gmpc_bgemm_desc* d, void* stream);
+/* The kernel form gmpc_bgemm_tn_ex launches for `d`, without GPU work (the pointers are only compared with NULL):
+ * route4 = {0, NTW, 0, 0} one-wave strips k_bgemm_tn<NTW>; {1, WIDE_X, NTJ, NS} streaming k_bthin;
+ * {2, WNT, KC, VEC} LDS-staged k_bgemm_tn_lds<2, WNT, KC, VEC>. */
+int gmpc_bgemm_route(const gmpc_bgemm_desc* d, int* route4);
 
 /* Number of candidate rollouts (trajectory, step size) the line searches of the last gmpc_ilqr_solve
  * evaluated -- the work count behind bench.py's secondary roofline.  Synchronises the whole device
