@@ -104,6 +104,8 @@ SIGNATURES = {
                                         _P, _P]),
     "gmpc_ilqr_solve_box": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(IlqrOpts), _P, _P, _P, _P, _P,
                                       _P, _P, _P, _P]),
+    "gmpc_ilqr_solve_box_held": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(IlqrOpts), _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P]),
     "gmpc_box_qp_host": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_bilevel_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),

@@ -216,6 +216,7 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
     A_(box_count, 2 * B);
     A_(box_iters, B * T);
     A_(box_clamped, B * T * m);
+    A_(box_mask, B * T);
   }
   // bilevel
   c->drows = mlp_rows(s.dyn_layers, s.dyn_dims);
@@ -517,7 +518,8 @@ extern "C" int gmpc_profile_read(gmpc_ctx* c, int slot, double* total_ms, int* c
 // accessors used by the bilevel parity tests and the Python mirror (device pointers, valid until the
 // next solve): 0 X, 1 U, 2 H (A^-1 B), 3 dX, 4 Bvec, 5 AB, 6 K, 7 k; of gmpc_ilqr_solve_box (null on shapes it does not
 // cover): 15 [B][2] QPs that hit the iteration cap / QP iterations of the solve, 16 [B][T] QP iterations and 17
-// [B][T][m] clamped flags of the last backward pass
+// [B][T][m] clamped flags of the last backward pass; of gmpc_ilqr_solve_box_held: 18 [B][T] 32-bit words (read them as
+// such), bit j = control j is in the clamped set the bilevel tail differentiates through
 extern "C" long gmpc_debug_buffer_count(gmpc_ctx* c, int which) {
   if (!c) return 0;
   const gmpc_shape& s = c->sh;
@@ -535,6 +537,7 @@ extern "C" long gmpc_debug_buffer_count(gmpc_ctx* c, int which) {
     case 15: return c->box_count ? 2 * B : 0;
     case 16: return c->box_iters ? B * T : 0;
     case 17: return c->box_clamped ? B * T * m : 0;
+    case 18: return c->box_mask ? B * T : 0;
     default: return 0;
   }
 }
@@ -548,6 +551,7 @@ extern "C" const float* gmpc_debug_buffer(gmpc_ctx* c, int which) {
     case 8: return c->alpha; case 9: return c->obj_step; case 10: return c->U_step;
     case 11: return c->lx;
     case 15: return c->box_count; case 16: return c->box_iters; case 17: return c->box_clamped;
+    case 18: return reinterpret_cast<const float*>(c->box_mask);
     default: return nullptr;
   }
 }

@@ -26,6 +26,7 @@ static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const fl
     r.B = B; r.n = n; r.ng = c->nx; r.m = m; r.T = T; r.mode = 1;
     r.X = c->Xs; r.U = c->Us; r.goal = c->goals; r.mpc_w = c->mpc_w; r.AB = c->AB; r.QT = c->QT;
     r.qT = c->qT; r.K = c->Ks; r.k = c->ks; r.Bvec = c->Bvec; r.Hout = c->Hout; r.dX = c->dX;
+    r.clamped = c->solBox ? c->box_mask : nullptr;     // a held box solve: the solve on each step's free rows
     if (!c->dynl && gmpc_riccati_w2h_shape(r)) {
       // two waves per trajectory, products on the matrix pipe, the loss adjoint (a8) in the same sweep
       ProfScope ps(c, PROF_RICCATI, s);      // (bench.py: secondary.bilevel.kernel_ms)

@@ -182,6 +182,7 @@ extern "C" int gmpc_ilqr_solve(gmpc_ctx* c, int B, const float* x0, const float*
   if (opts->make_psd) return fail(GMPC_EINVAL, "make_psd=1 is not on the reference path");
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;   // restored only when the solve has completed (an early error return leaves none)
+  c->solBox = false;
   c->gradB = 0;
   const gmpc_shape& sh = c->sh;
   const size_t n = sh.n, m = sh.m, T = sh.T;
@@ -283,6 +284,7 @@ static int solve_one_launch(gmpc_ctx* c, int B, const float* x0, const float* U_
     return fail(GMPC_EINVAL, "%s: alpha_0 / alpha_min allow more than %d halvings", who, GMPC_FZ_MAX_HALVINGS);
   hipStream_t s = static_cast<hipStream_t>(stream);
   c->solB = 0;
+  c->solBox = false;
   c->gradB = 0;
   FusedSolveArgs a;
   memset(&a, 0, sizeof(a));
@@ -317,14 +319,31 @@ extern "C" int gmpc_ilqr_solve_fused(gmpc_ctx* c, int B, const float* x0, const 
   return 0;
 }
 
-// The control-limited solve.  It holds no solution for the bilevel tail (solB stays 0): the implicit
-// gradient through an active set is not implemented.
+// The control-limited solve.  It holds no solution for the bilevel tail (solB stays 0): the MPC action
+// path does not pay for the clamped-set launch; gmpc_ilqr_solve_box_held is the variant the tail may follow.
 extern "C" int gmpc_ilqr_solve_box(gmpc_ctx* c, int B, const float* x0, const float* U_init,
                                    const float* goal, const gmpc_ilqr_opts* opts, float* X, float* U,
                                    float* obj, float* grad, float* adjoints, int* iterations,
                                    void* stream, const float* u_lo, const float* u_hi) {
   return solve_one_launch(c, B, x0, U_init, goal, opts, X, U, obj, grad, adjoints, iterations, stream, "box solve",
                           true, u_lo, u_hi);
+}
+
+// The control-limited solve, held for the bilevel tail: the same launch, then the clamped set of the
+// solution -- from the ctx's U and full gradient and the caller's bounds -- as one word per step; the tail's Hessian
+// solve runs on each step's free rows.
+extern "C" int gmpc_ilqr_solve_box_held(gmpc_ctx* c, int B, const float* x0, const float* U_init,
+                                        const float* goal, const gmpc_ilqr_opts* opts, float* X, float* U,
+                                        float* obj, float* grad, float* adjoints, int* iterations,
+                                        void* stream, const float* u_lo, const float* u_hi) {
+  TRY(solve_one_launch(c, B, x0, U_init, goal, opts, X, U, obj, grad, adjoints, iterations, stream, "box solve",
+                       true, u_lo, u_hi));
+  gmpc_launch_box_clamped(B, c->sh.T, c->sh.m, c->Us, c->grads, u_lo, u_hi, c->box_mask,
+                          static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  c->solB = B;   // stream-ordered, as after the fused solve
+  c->solBox = true;
+  return 0;
 }
 
 // single model evaluations (the reference's model protocol, base.py:4-49) -----------------------

@@ -229,6 +229,10 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_terminal(int B, int T, int n, 
 // mode 0 : iLQR step (trajax lqr_step with delta = 1e-8, Cholesky; q_t, r_t from the cost)
 // mode 1 : bilevel Hessian solve (no regulariser; linear term r~_t = -Bvec_t, q~ = 0); then a forward
 //          tangent roll writes H_t = dU_t and dX_t  (oracle hessian_solve).
+//          BOX (a held box solve): a.clamped holds one word per step, bit j = control j sits on a
+//          bound; the system is solved on the step's free rows and the clamped rows of K_t, k_t are 0 -- row and
+//          column j of the elimination's copy of G become the unit vector, row j of its copy of [H | h] is zeroed,
+//          then the same elimination runs (an empty word changes nothing).  S and p are in the general-gain form.
 // ------------------------------------------------------------------------------------------------
 
 #ifndef GMPC_RIC_THREADS
@@ -239,7 +243,7 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_terminal(int B, int T, int n, 
 #endif
 // N_, M_ > 0: state / action sizes known at compile time (inner products fully unrolled, so their
 // LDS reads issue back to back instead of one dependent round trip per k); 0: run-time sizes.
-template <int N_, int M_>
+template <int N_, int M_, bool BOX = false>
 __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(RiccatiArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int n = N_ > 0 ? N_ : a.n, m = M_ > 0 ? M_ : a.m, T = a.T, nm = n + m;
@@ -314,6 +318,8 @@ __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(Ric
   for (int t = T - 1; t >= 0; --t) {
     const size_t bt = (size_t)b * T + t;
     const float* phi = (a.mode == 1 && a.Phi != nullptr) ? a.Phi + bt * nm * nm : nullptr;
+    uint32_t cw = 0u;                                // the step's clamped controls
+    if (BOX) cw = a.clamped[bt];
     if (N_ > 0) {
       if (t > 0) prefetch(t - 1);
     } else {
@@ -492,6 +498,14 @@ __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(Ric
         for (int i = 0; i < m; ++i) {
           for (int c = 0; c < n; ++c) Kk[i * (n + 1) + c] = Hm[i * n + c];
           Kk[i * (n + 1) + n] = hv[i];
+        }
+        if (BOX) {
+          for (int j = 0; j < m; ++j) {
+            if (!((cw >> j) & 1u)) continue;
+            for (int c = 0; c < m; ++c) { Lc[j * m + c] = 0.f; Lc[c * m + j] = 0.f; }
+            Lc[j * m + j] = 1.f;
+            for (int c = 0; c <= n; ++c) Kk[j * (n + 1) + c] = 0.f;
+          }
         }
         for (int j = 0; j < m; ++j) {
           int piv = j;
@@ -688,6 +702,12 @@ void gmpc_launch_riccati(const RiccatiArgs& a, hipStream_t s) {
   }
   const size_t lds = gmpc_riccati_lds_bytes(a.n, a.m);
   const dim3 g(a.B), b(GMPC_RIC_THREADS);
+  if (a.clamped != nullptr) {            // a held box solve (mode 1): the masked solve
+    if (a.n == 17 && a.m == 6) hipLaunchKernelGGL((k_riccati<17, 6, true>), g, b, lds, s, a);
+    else if (a.n == 3 && a.m == 1) hipLaunchKernelGGL((k_riccati<3, 1, true>), g, b, lds, s, a);
+    else hipLaunchKernelGGL((k_riccati<0, 0, true>), g, b, lds, s, a);
+    return;
+  }
   if (a.n == 17 && a.m == 6) hipLaunchKernelGGL((k_riccati<17, 6>), g, b, lds, s, a);
   else if (a.n == 3 && a.m == 1) hipLaunchKernelGGL((k_riccati<3, 1>), g, b, lds, s, a);
   else hipLaunchKernelGGL((k_riccati<0, 0>), g, b, lds, s, a);

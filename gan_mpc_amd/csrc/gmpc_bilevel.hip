@@ -187,6 +187,30 @@ void gmpc_launch_l2loss(int B, int T, int n, int ng, const float* X, const float
                         float* lx, hipStream_t s) {
   hipLaunchKernelGGL(k_l2loss, dim3(B), dim3(GMPC_THREADS), 0, s, B, T, n, ng, X, desired, loss, lx);
 }
+// The clamped set of a held box solve: one word per step (b, t), bit j = control j sits on a bound that
+// the solve's full gradient pushes it against -- (U == lo and grad > 0) or (U == hi and grad < 0), exact comparisons (a
+// NaN compares false: the entry is free).  It is the set the box solve's continuation test leaves out of its
+// projected-gradient norm.  u_lo / u_hi [m] or null (unbounded on that side); m <= 32.
+__global__ __launch_bounds__(256) void k_box_clamped(int steps, int m, const float* U, const float* grad,
+                                                     const float* u_lo, const float* u_hi, uint32_t* clamped) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= steps) return;
+  uint32_t w = 0u;
+  for (int j = 0; j < m; ++j) {
+    const float u = U[(size_t)s * m + j], g = grad[(size_t)s * m + j];
+    const bool lo = u_lo != nullptr && u == u_lo[j] && g > 0.f;
+    const bool hi = u_hi != nullptr && u == u_hi[j] && g < 0.f;
+    if (lo || hi) w |= 1u << j;
+  }
+  clamped[s] = w;
+}
+void gmpc_launch_box_clamped(int B, int T, int m, const float* U, const float* grad, const float* u_lo,
+                             const float* u_hi, uint32_t* clamped, hipStream_t s) {
+  const int steps = B * T;
+  hipLaunchKernelGGL(k_box_clamped, dim3((steps + 255) / 256), dim3(256), 0, s, steps, m, U, grad, u_lo, u_hi,
+                     clamped);
+}
+
 void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* lx, const float* lu, float* Bvec,
                       hipStream_t s) {
   const size_t lds = ((size_t)n * (n + m) + 2 * n) * sizeof(float);

@@ -80,8 +80,12 @@ struct gmpc_ctx {
   // gmpc_ilqr_solve_box's QP reports (same shapes): [B][2] cap hits / QP iterations of the solve, [B][T] QP
   // iterations and [B][T][m] clamped flags of the last backward pass
   float *box_count = nullptr, *box_iters = nullptr, *box_clamped = nullptr;
+  // gmpc_ilqr_solve_box_held: [B][T] words, bit j = control j of the step is clamped at the held solution
+  uint32_t* box_mask = nullptr;
   hipEvent_t poll_ev[GMPC_POLL_DEPTH] = {};
   int solB = 0;
+  // the held solution is a box solve's: the bilevel tail differentiates through the active set in box_mask
+  bool solBox = false;
   // batch size whose Bvec / H / dX (and Phi) a completed bilevel tail left for the held solution (0: none); every
   // change of the held solution clears it
   int gradB = 0;

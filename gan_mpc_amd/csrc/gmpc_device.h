@@ -233,6 +233,9 @@ struct RiccatiArgs {
   const float* Phi;    // [B][T][n+m][n+m] or null: lam_{t+1} . d^2 f / d(x,u)^2 (smooth dynamics, gmpc_dynl.hip)
   float* Hout;         // [B][T][m]
   float* dX;           // [B][T+1][n]
+  // [B][T] words or null, bit j: control j of the step is clamped at a bound (held box solve, m <= 32): the solve
+  // runs on the step's free rows, the clamped rows of K_t and k_t are 0 (the BOX instantiations only)
+  const uint32_t* clamped;
 };
 
 struct CriticDesc {

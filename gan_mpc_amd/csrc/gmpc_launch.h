@@ -185,6 +185,9 @@ void gmpc_launch_l2loss(int B, int T, int n, int ng, const float* X, const float
                         hipStream_t s);
 void gmpc_launch_bvec(int B, int T, int n, int m, const float* AB, const float* lx, const float* lu, float* Bvec,
                       hipStream_t s);
+// the clamped set of a held box solve, [B][T] words (bit j: control j); u_lo / u_hi [m] or null; m <= 32
+void gmpc_launch_box_clamped(int B, int T, int m, const float* U, const float* grad, const float* u_lo,
+                             const float* u_hi, uint32_t* clamped, hipStream_t s);
 void gmpc_launch_costvjp(int B, int T, int n, int m, const MlpDesc& cm, const float* mpc_w, float sign, const float* X,
                          const float* U, const float* goal, int ng, const float* Hc, const float* dX, float* gmpc,
                          float* cact, float* cdel, const MlpRows& rows, hipStream_t s);

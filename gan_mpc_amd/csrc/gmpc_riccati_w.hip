@@ -354,11 +354,16 @@ __global__ __launch_bounds__(128) void k_riccati_w2(RiccatiArgs a) {
 //     (gmpc_bilevel_grad_cotangent); lu_t is prefetched one step ahead with lx_t.  Without LU the term is absent,
 //     not zero (adding 0 would turn a -0 of B^T mu into +0);
 //   * after the sweep, the forward tangent roll dU_t = k_t + K_t dX_t, dX_{t+1} = A_t dX_t + B_t dU_t on wave 0, the
-//     next step's operands requested one step ahead.
+//     next step's operands requested one step ahead;
+//   * BOX (a held box solve): a.clamped holds one word per step, bit j = control j sits on a bound.  The
+//     system is solved on the step's free rows and the clamped rows of K_t, k_t are 0: row and column j of G become the
+//     unit vector where G is symmetrised into LDS and row j of every right-hand-side column is zeroed where it is
+//     loaded, then the same elimination runs (an empty word changes nothing).  The helper fetches the word with the
+//     step's other operands.  Nothing else changes: S and p are already in the general-gain form.
 // Reference: policy/optimizers.py:61-71, 86-105 (dense hessian + solve), restated as the structured solve of
 // oracle/gan_mpc_oracle.py:hessian_solve.
 // ------------------------------------------------------------------------------------------------
-template <int N_, int M_, bool LU>
+template <int N_, int M_, bool LU, bool BOX = false>
 __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float* lx, const float* lu,
                                                      float* bvec_out) {
   constexpr int n = N_, m = M_, nm = n + m, LD = 32;
@@ -371,6 +376,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
   __shared__ float Gr[m * m], Gp[m * m], G[m * m], Lc[m * m];
   __shared__ int pivs[8];
   __shared__ float dvb[2][LD], uvb[2][8], rvb[2][8], scal[2][4];   // helper -> chain, buffer t & 1
+  __shared__ uint32_t mskb[2];                                     // BOX: the step's clamped word, buffer t & 1
   __shared__ float pv[LD], lam[LD], Ap[LD], hv[8];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int b = blockIdx.x, T = a.T;
@@ -388,6 +394,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
     constexpr int PFN = (n * nm + 63) / 64;
     float pf_ab[PFN];
     float pf_d = 0.f, pf_u = 0.f, pf_lx = 0.f, pf_lu = 0.f;
+    uint32_t pf_msk = 0u;
     auto prefetch = [&](int tp) {
       const size_t btp = (size_t)b * T + tp;
 #pragma unroll
@@ -402,6 +409,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
       }
       if (lane < m) pf_u = a.U[btp * m + lane];
       if (LU && lane >= n && lane < nm) pf_lu = lu[btp * m + lane - n];
+      if (BOX && lane == 0) pf_msk = a.clamped[btp];
     };
     // everything of step tp that needs neither P nor p: operands into buffer tp & 1, scalars, the loss adjoint
     auto prepare = [&](int tp) {
@@ -414,6 +422,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
       }
       if (lane < n) dvb[bf][lane] = pf_d;
       if (lane < m) uvb[bf][lane] = pf_u;
+      if (BOX && lane == 0) mskb[bf] = pf_msk;
       const float lxt = pf_lx, lut = pf_lu;
       RW_SYNC();
       if (tp > 0) prefetch(tp - 1);
@@ -476,6 +485,7 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
     const size_t bt = (size_t)b * T + t;
     const int bf = t & 1;
     RW2_BARRIER();                                   // S_t: [A | B]_t, x - g, u, scalars are in buffer bf
+    const uint32_t cw = BOX ? mskb[bf] : 0u;         // the step's clamped controls
     const float* X_ = Xs[bf];
     const float* dv = dvb[bf];
     const float* uv = uvb[bf];
@@ -519,7 +529,9 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
     RW_SYNC();
     if (lane < m * m) {
       const int i = lane / m, j = lane - i * m;
-      G[lane] = (Gp[lane] + Gp[j * m + i]) * 0.5f;
+      float g = (Gp[lane] + Gp[j * m + i]) * 0.5f;
+      if (BOX && (((cw >> i) | (cw >> j)) & 1u)) g = i == j ? 1.f : 0.f;
+      G[lane] = g;
     }
     RW_SYNC();
     if (lane == 0) {
@@ -571,7 +583,10 @@ __global__ __launch_bounds__(128) void k_riccati_w2h(RiccatiArgs a, const float*
 #pragma unroll
         for (int j = 0; j < m; ++j) Lr[i][j] = Lc[i * m + j];
 #pragma unroll
-      for (int i = 0; i < m; ++i) y[i] = c < n ? Hm[i * LD + c] : hv[i];
+      for (int i = 0; i < m; ++i) {
+        y[i] = c < n ? Hm[i * LD + c] : hv[i];
+        if (BOX && ((cw >> i) & 1u)) y[i] = 0.f;
+      }
 #pragma unroll
       for (int j = 0; j < m; ++j) {
         const int piv = pivs[j];
@@ -714,7 +729,11 @@ bool gmpc_riccati_w2h_shape(const RiccatiArgs& a) {
 }
 void gmpc_launch_riccati_w2h(const RiccatiArgs& a, const float* lx, const float* lu, float* bvec_out,
                              hipStream_t s) {
-  if (lu != nullptr)
+  if (a.clamped != nullptr && lu != nullptr)         // a held box solve: the masked solve
+    hipLaunchKernelGGL((k_riccati_w2h<17, 6, true, true>), dim3(a.B), dim3(128), 0, s, a, lx, lu, bvec_out);
+  else if (a.clamped != nullptr)
+    hipLaunchKernelGGL((k_riccati_w2h<17, 6, false, true>), dim3(a.B), dim3(128), 0, s, a, lx, lu, bvec_out);
+  else if (lu != nullptr)
     hipLaunchKernelGGL((k_riccati_w2h<17, 6, true>), dim3(a.B), dim3(128), 0, s, a, lx, lu, bvec_out);
   else
     hipLaunchKernelGGL((k_riccati_w2h<17, 6, false>), dim3(a.B), dim3(128), 0, s, a, lx, lu, bvec_out);

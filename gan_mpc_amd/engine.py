@@ -209,8 +209,19 @@ class Engine:
     def ilqr_solve_box(self, x0, U, goal, u_lo, u_hi, kwargs=None):
         """The one-launch solve under box bounds u_lo <= u_t <= u_hi on the controls (gmpc_ilqr_solve_box: the shapes
         of ilqr_solve_fused).  u_lo, u_hi: None (unbounded on that side), a scalar or m values, -inf / +inf allowed;
-        checked on the host before any launch (their device copies are uploaded when the values change).  Returns the same dict as ilqr_solve; the ctx holds no solution for
-        bilevel_grad* / upper_loss afterwards."""
+        checked on the host before any launch (their device copies are uploaded when the values change).  Returns the
+        same dict as ilqr_solve; the ctx holds no solution for bilevel_grad* / upper_loss afterwards
+        (ilqr_solve_box_held's does)."""
+        return self._solve_box("gmpc_ilqr_solve_box", x0, U, goal, u_lo, u_hi, kwargs)
+
+    def ilqr_solve_box_held(self, x0, U, goal, u_lo, u_hi, kwargs=None):
+        """ilqr_solve_box with the solution held for the bilevel tail (gmpc_ilqr_solve_box_held): the same launch, the
+        same bound handling and cache, then the clamped set of the solution (debug buffer 18).  bilevel_grad,
+        bilevel_grad_cotangent, bilevel_grad_inputs, bilevel_grad_dynamics and upper_loss may follow: they
+        differentiate through the active set held fixed."""
+        return self._solve_box("gmpc_ilqr_solve_box_held", x0, U, goal, u_lo, u_hi, kwargs)
+
+    def _solve_box(self, name, x0, U, goal, u_lo, u_hi, kwargs):
         lo, hi = self._bound_vector("u_lo", u_lo), self._bound_vector("u_hi", u_hi)
         if lo is not None and hi is not None and not bool(np.all(lo <= hi)):
             raise _lib.GmpcError("u_lo must be <= u_hi")
@@ -222,7 +233,7 @@ class Engine:
                 cache.clear()
             cache[key] = (None if lo is None else self.to_dev(lo), None if hi is None else self.to_dev(hi))
         lo_d, hi_d = cache[key]
-        return self._solve(self.lib.gmpc_ilqr_solve_box, x0, U, goal, kwargs, tail=(_ptr(lo_d), _ptr(hi_d)))
+        return self._solve(getattr(self.lib, name), x0, U, goal, kwargs, tail=(_ptr(lo_d), _ptr(hi_d)))
 
     def _bound_vector(self, name, b):
         """None, a scalar or m values -> None or a host fp32 vector [m] without NaN."""

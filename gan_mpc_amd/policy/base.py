@@ -66,7 +66,7 @@ class BaseMPC(eval_policy.EvalMPC):
         B = len(history_X)
         packed = parallel.new_packed(1, self.device(), B)
         if B > 0:            # an empty shard still joins the exchange, with count 0
-            dparams, sol = self._solve(dparams, history_X)
+            dparams, sol = self._solve(dparams, history_X, hold=True)
             eng = self._engine
             if self._batched_loss():
                 loss, _, _ = self.batch_cotangents(sol["X"], sol["U"], dparams, (desired,), want_grad=False)

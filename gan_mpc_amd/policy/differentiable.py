@@ -72,7 +72,8 @@ class ILQRFunction(torch.autograd.Function):
             raise GmpcError(f"ilqr_layer: dL/dx0 is not available on the step-major pipeline (n={eng.n} > 64 or "
                             f"m={eng.m} > 32); pass x0 without requires_grad (goal gradients work)")
         f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
-        sol = opt._solver(policy, eng)(f32(x0), f32(init_U), f32(goal), kwargs or policy.trajax_ilqr_kwargs)
+        solve = opt._solver(policy, eng, hold=True)       # a "box" policy: the solve the tail may follow
+        sol = solve(f32(x0), f32(init_U), f32(goal), kwargs or policy.trajax_ilqr_kwargs)
         ctx.eng, ctx.solve_count, ctx.B = eng, eng.solve_count, B
         ctx.theta = dparams.range_of(_THETA_KEYS)
         ctx.dyn = dparams.range_of(("dynamics_params",)) if dynamics_grad else None
@@ -110,9 +111,10 @@ class ILQRFunction(torch.autograd.Function):
 
 
 def ilqr_layer(policy, params, x0, goal, init_U, trajax_ilqr_kwargs=None, dynamics_grad=False):
-    """(X (B, T+1, n), U (B, T, m)) of the policy's iLQR solve (its `solver`, "rounds" or "fused"), differentiable
-    w.r.t. x0, goal and the mpc_weights / cost_params ranges of params.flat, and with dynamics_grad=True its
-    dynamics_params range (see the module docstring).  params: the policy's DeviceParams (a parameter tree is
+    """(X (B, T+1, n), U (B, T, m)) of the policy's iLQR solve (its `solver`: "rounds", "fused", or "box" -- then
+    through the solution's active set held fixed), differentiable w.r.t. x0, goal and the
+    mpc_weights / cost_params ranges of params.flat, and with dynamics_grad=True its dynamics_params range (see the
+    module docstring).  params: the policy's DeviceParams (a parameter tree is
     converted, and then is not differentiable); x0, goal, init_U: device tensors."""
     dparams = policy.to_device_params(params)
     return ILQRFunction.apply(policy, dparams, trajax_ilqr_kwargs, dparams.flat, x0, goal, init_U,

@@ -51,7 +51,9 @@ class EvalMPC:
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
-        limited to control_bounds = (lo, hi), each None, a scalar or one value per control (no bilevel gradient)."""
+        limited to control_bounds = (lo, hi), each None, a scalar or one value per control; the training calls
+        (loss_and_grad, batch_loss, ilqr_layer) use gmpc_ilqr_solve_box_held and differentiate through the solution's
+        active set held fixed, the action path (get_optimal_values / get_optimal_action) the plain one."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
         if (solver == "box") != (control_bounds is not None):
@@ -157,7 +159,8 @@ class EvalMPC:
             return self.expert_model.get_goal_states_init_actions(history_X, expert_params, engine=eng)
         return self.expert_model.get_goal_states_init_actions(history_X, expert_params)
 
-    def _solve(self, params, history_X, history_U=None):
+    def _solve(self, params, history_X, history_U=None, hold=False):
+        """hold: a "box" policy's solution is held for upper_loss / the bilevel tail (optimizers.ilqr_solve)."""
         dparams = self.to_device_params(params)
         hx = np.asarray(history_X, np.float32)
         goal, init_U = self.get_goal_states_init_actions(hx, dparams)
@@ -169,7 +172,7 @@ class EvalMPC:
         if eng.n > eng.nx:
             carry = self.get_dynamics_carry(hx, history_U, dparams)
             x0 = torch.cat([x0, d(carry)], dim=1).contiguous()
-        sol = opt.ilqr_solve(self, dparams, x0, d(init_U), d(goal))
+        sol = opt.ilqr_solve(self, dparams, x0, d(init_U), d(goal), hold=hold)
         return dparams, sol
 
     def get_optimal_values(self, params, history_x, history_u=None):

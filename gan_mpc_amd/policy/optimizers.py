@@ -10,14 +10,15 @@ import functools
 import torch
 
 
-def _solver(policy, eng):
+def _solver(policy, eng, hold=False):
     """The engine entry point of the policy's solver: "rounds" (gmpc_ilqr_solve, host-driven iterations), "fused"
-    (gmpc_ilqr_solve_fused, the whole solve in one launch) or "box" (gmpc_ilqr_solve_box, the one-launch solve under
-    the policy's control_bounds)."""
+    (gmpc_ilqr_solve_fused, the whole solve in one launch) or "box" (the one-launch solve under the policy's
+    control_bounds: gmpc_ilqr_solve_box, or with hold=True gmpc_ilqr_solve_box_held, whose solution the bilevel tail
+    may follow).  "rounds" and "fused" always hold their solution."""
     solver = getattr(policy, "solver", "rounds")
     if solver == "box":
         lo, hi = policy.control_bounds
-        return functools.partial(_box_solve, eng, lo, hi)
+        return functools.partial(_box_solve_held if hold else _box_solve, eng, lo, hi)
     return eng.ilqr_solve_fused if solver == "fused" else eng.ilqr_solve
 
 
@@ -25,11 +26,16 @@ def _box_solve(eng, lo, hi, x0, U, goal, kwargs=None):
     return eng.ilqr_solve_box(x0, U, goal, lo, hi, kwargs)
 
 
-def ilqr_solve(policy, dparams, x0, U, goal, trajax_ilqr_kwargs=None):
+def _box_solve_held(eng, lo, hi, x0, U, goal, kwargs=None):
+    return eng.ilqr_solve_box_held(x0, U, goal, lo, hi, kwargs)
+
+
+def ilqr_solve(policy, dparams, x0, U, goal, trajax_ilqr_kwargs=None, hold=False):
     """reference policy/optimizers.py:10-21 -> trajax ilqr.  Device tensors in, dict of device
-    tensors out: X, U, obj, grad, adjoints, iterations (the `lqr` tuple stays in the ctx)."""
+    tensors out: X, U, obj, grad, adjoints, iterations (the `lqr` tuple stays in the ctx).  hold: a "box" policy's
+    solution is held for upper_loss / the bilevel tail (the other solvers always hold theirs)."""
     eng = policy.bind(dparams, x0.shape[0])
-    return _solver(policy, eng)(x0, U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
+    return _solver(policy, eng, hold=hold)(x0, U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
 
 
 def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=None,
@@ -37,7 +43,8 @@ def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=N
                          cotangents=None):
     """reference policy/optimizers.py:34-75, batched, WITHOUT the batch mean: returns
     (loss [B], low_level_grad [B,T,m], grad_sum [3 + cost_count] summed over the batch, itr [B]).
-    sign=+1 reproduces the reference as written.
+    sign=+1 reproduces the reference as written.  Under a "box" policy the gradient is the implicit
+    one through the solution's active set held fixed.
 
     loss_kind 0 (L2, against `desired`) and 1 (JS, the policy's critic) run on the kernels' own losses.  A
     callable is the reference's `loss(X, U, params, *loss_args)` of ONE trajectory: it is evaluated and
@@ -49,7 +56,7 @@ def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=N
     batch_cotangents); a None cotangent is passed on as NULL, not as zeros."""
     B = x0.shape[0]
     eng = policy.bind(dparams, B)
-    sol = _solver(policy, eng)(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
+    sol = _solver(policy, eng, hold=True)(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)
     if cotangents is not None or callable(loss_kind):
         if cotangents is not None:
             loss, lx, lu = cotangents(sol["X"], sol["U"])

@@ -194,10 +194,28 @@ int gmpc_ilqr_solve_fused(gmpc_ctx* ctx, int B, const float* x0, const float* U_
  * solve), 16 ([B][T]: QP iterations per step of the last backward pass), 17 ([B][T][m]: 1.0 where a control is in the
  * final clamped set of that pass).
  * NO solution is held for the bilevel tail: gmpc_bilevel_grad*, gmpc_upper_loss after this call fail with "must
- * precede".  The implicit gradient through an active set is not implemented. */
+ * precede" (the MPC action path does not pay for the clamped-set launch).  gmpc_ilqr_solve_box_held is the variant
+ * they may follow. */
 int gmpc_ilqr_solve_box(gmpc_ctx* ctx, int B, const float* x0, const float* U_init, const float* goal,
                         const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad,
                         float* adjoints, int* iterations, void* stream, const float* u_lo, const float* u_hi);
+
+/* gmpc_ilqr_solve_box with the solution held for the bilevel tail: signature, results, coverage and
+ * refusals are gmpc_ilqr_solve_box's (the same kernel launch), then one small kernel on the same stream builds the
+ * clamped set of the solution from the ctx's U and grad and the caller's u_lo / u_hi (NULL: unbounded on that side):
+ *   C = {(t, j) : (U_tj == lo_j and grad_tj > 0) or (U_tj == hi_j and grad_tj < 0)},  exact fp32 comparisons,
+ * the entries the solve's continuation test leaves out of its projected-gradient norm (a NaN compares false: free).
+ * It is kept as gmpc_debug_buffer 18: [B][T] 32-bit words, bit j = control j clamped (m <= 32 on this path).
+ * gmpc_bilevel_grad, gmpc_bilevel_grad_cotangent, gmpc_bilevel_grad_inputs, gmpc_bilevel_grad_dynamics and
+ * gmpc_upper_loss may follow with their usual arguments.  They differentiate through the active set held fixed: the
+ * clamped controls sit on bounds that depend on no parameter and the free gradient vanishes, so the implicit-function
+ * formula is unchanged with the masked solve H_C = 0, H_F = A_FF^-1 Bvec_F (A = d^2 J / dU^2) and dX the tangent roll
+ * of H.  Debug buffers 2 / 3 / 4 keep their meaning (2: the masked H).  With no bound active the tail's results are
+ * bit for bit those after gmpc_ilqr_solve_fused.  Gradients with respect to the bounds themselves are not computed.
+ * Any later solve, gmpc_set_params or call that drops a held solution drops this one. */
+int gmpc_ilqr_solve_box_held(gmpc_ctx* ctx, int B, const float* x0, const float* U_init, const float* goal,
+                             const gmpc_ilqr_opts* opts, float* X, float* U, float* obj, float* grad,
+                             float* adjoints, int* iterations, void* stream, const float* u_lo, const float* u_hi);
 
 /* Test hook, host memory only, no ctx and no device: ONE box QP of gmpc_ilqr_solve_box's backward pass, solved on the
  * host by the routine the kernel runs on one lane (the same source compiled for the host).  G [m][m] symmetric WITHOUT
@@ -221,7 +239,7 @@ int gmpc_bilevel_grad(gmpc_ctx* ctx, int B, int loss_kind, const float* desired,
  * callable, policy/optimizers.py:34-83, policy/base.py:84-85): the caller passes lx = dL/dX [B][T+1][n] (xc columns;
  * carry columns included for LSTM dynamics) and/or lu = dL/dU [B][T][m] (either may be NULL, not both); then
  * Bvec_t = lu_t + B_t^T mu_{t+1}.  -> grad_sum [3 + cost_count], the SUM over the batch, as gmpc_bilevel_grad.
- * Follows gmpc_ilqr_solve or gmpc_ilqr_solve_fused of the same B (else GMPC_EINVAL, "must precede"); leaves the
+ * Follows gmpc_ilqr_solve, gmpc_ilqr_solve_fused or gmpc_ilqr_solve_box_held of the same B (else GMPC_EINVAL, "must precede"); leaves the
  * same ctx state as gmpc_bilevel_grad (Bvec, H, dX: debug buffers 4 / 2 / 3).  lx and lu are only read; with
  * lx NULL the ctx's own lx buffer (debug buffer 11) is zeroed and used.  With lu NULL and the lx that
  * gmpc_bilevel_grad computes, the result is bit-identical to gmpc_bilevel_grad's. */
