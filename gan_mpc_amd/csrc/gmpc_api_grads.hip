@@ -85,7 +85,16 @@ extern "C" int gmpc_bilevel_grad_cotangent(gmpc_ctx* c, int B, const float* lx, 
   return 0;
 }
 
-// dL/dx0 and dL/dgoal of the loss whose bilevel gradient the ctx has just computed (gmpc_input_grads.hip): the
+// The arguments that both calls of k_tail_adjoints share: the held solution and what the bilevel tail left
+static TailAdjArgs tail_adj_args(const gmpc_ctx* c, int B, const float* lx) {
+  TailAdjArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.T = c->sh.T; a.n = c->sh.n; a.ng = c->nx; a.m = c->sh.m;
+  a.mpc_w = c->mpc_w; a.X = c->Xs; a.goal = c->goals; a.dX = c->dX; a.lx = lx; a.AB = c->AB; a.QT = c->QT;
+  return a;
+}
+
+// dL/dx0 and dL/dgoal of the loss whose bilevel gradient the ctx has just computed (gmpc_tail_adjoints.hip): the
 // implicit-function gradient through the held solution, from the H, dX (and Phi) the bilevel tail left.  Read-only
 // for every other ctx buffer.
 extern "C" int gmpc_bilevel_grad_inputs(gmpc_ctx* c, int B, const float* lx, float* grad_x0, float* grad_goal,
@@ -102,8 +111,9 @@ extern "C" int gmpc_bilevel_grad_inputs(gmpc_ctx* c, int B, const float* lx, flo
   const gmpc_shape& sh = c->sh;
   if (!lx) lx = c->lx;
   if (grad_x0) {
-    if (gmpc_launch_input_grads(B, sh.T, sh.n, c->nx, sh.m, c->mpc_w, c->Xs, c->goals, c->dX, c->Hout, lx, c->AB,
-                                c->QT, c->dynl ? c->phi : nullptr, grad_x0, grad_goal, s) != 0)
+    TailAdjArgs a = tail_adj_args(c, B, lx);
+    a.H = c->Hout; a.Phi = c->dynl ? c->phi : nullptr; a.gx0 = grad_x0; a.ggoal = grad_goal;
+    if (gmpc_launch_tail_adjoints(a, false, s) != 0)
       return fail(GMPC_EINVAL, "grad_x0: shape n=%d m=%d not covered", sh.n, sh.m);
   } else {
     gmpc_launch_goal_grad(B, sh.T, sh.n, c->nx, c->mpc_w, c->Xs, c->goals, c->dX, grad_goal, s);
@@ -112,9 +122,10 @@ extern "C" int gmpc_bilevel_grad_inputs(gmpc_ctx* c, int B, const float* lx, flo
   return 0;
 }
 
-// dL/dtheta_dyn of the loss whose bilevel gradient the ctx has just computed (gmpc_dyn_grads.hip): the adjoint
-// sweeps give w = mu - nu and lam per step, the row kernel the layer inputs and deltas of 2 B T rows, and the weight
-// GEMMs sum them over the batch.  Read-only for every ctx buffer but the call workspace and the GEMMs' shared scratch.
+// dL/dtheta_dyn of the loss whose bilevel gradient the ctx has just computed: the adjoint sweeps
+// (gmpc_tail_adjoints.hip) give w = mu - nu and lam per step, the row kernel (gmpc_dyn_grads.hip) the layer inputs and
+// deltas of 2 B T rows, and the weight GEMMs sum them over the batch.  Read-only for every ctx buffer but the call
+// workspace and the GEMMs' shared scratch.
 extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, float* grad_dyn_sum, void* stream) {
   TRY(check_call(c, B));
   const gmpc_shape& sh = c->sh;
@@ -137,8 +148,9 @@ extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, f
   TRY(k.aux2.grow(c, steps * n));
   TRY(k.acts.reserve(c, rows, c->drows.stride, s));
   TRY(k.dels.reserve(c, rows, c->drows.stride, s));
-  gmpc_launch_dyn_adjoints(B, T, n, c->nx, m, c->mpc_w, c->Xs, c->goals, c->dX, lx, c->AB, c->QT, c->qT, k.aux.p,
-                           k.aux2.p, s);
+  TailAdjArgs a = tail_adj_args(c, B, lx);
+  a.qT = c->qT; a.w = k.aux.p; a.lam = k.aux2.p;
+  gmpc_launch_tail_adjoints(a, true, s);     // (n <= 64, m <= 32: checked above)
   if (gmpc_launch_dyn_rows(B, T, n, m, c->dyn, c->Xs, c->Us, c->dX, c->Hout, k.aux.p, k.aux2.p, k.acts.p, k.dels.p,
                            c->drows, s) != 0)
     return fail(GMPC_EINVAL, "dynamics gradient: layer widths above 256");

@@ -1,20 +1,15 @@
 // Gradient of an upper-level loss L(X*, U*) with respect to the relu-MLP dynamics' weights
-// (gmpc_bilevel_grad_dynamics), from the state a preceding gmpc_bilevel_grad(_cotangent) leaves in the ctx:
-// H = A^{-1} Bvec, its tangent roll dX, [A_t | B_t], QT and qT.  f(x, u) = x + MLP([x; u]):
+// (gmpc_bilevel_grad_dynamics).  f(x, u) = x + MLP([x; u]):
 //
 //   dL/dtheta = dL/dtheta|_U - d/dtheta [ H . grad_U J ]   (H held fixed)
 //             = sum_t  mu_{t+1} . f_theta - nu_{t+1} . f_theta - lam_{t+1} . d/dtheta (f_x dX_t + f_u H_t)
 //
-//   lam_T = qT,        lam_t = q_t + A_t^T lam_{t+1}        q_t = w1 d / s  (d = x_t[:ng] - g_t, s = sqrt(|d|^2 + a^2))
-//   mu_T  = lx_T,      mu_t  = lx_t + A_t^T mu_{t+1}
-//   nu_T  = QT dX_T,   nu_t  = Q_t dX_t + A_t^T nu_{t+1}      (the relu dynamics have no curvature: Phi = 0)
-//
-// Per step, with w = mu_{t+1} - nu_{t+1}: one MLP pass over the primal row a_0 = [x_t; u_t] and the tangent row
-// a'_0 = [dX_t; H_t] (the primal's relu masks, no bias), backward passes of w and lam_{t+1} through the same masks:
+// The adjoints come from k_tail_adjoints (gmpc_tail_adjoints.hip) as the planes w = mu_{t+1} - nu_{t+1} and lam_{t+1}.
+// Per step: one MLP pass over the primal row a_0 = [x_t; u_t] and the tangent row a'_0 = [dX_t; H_t] (the primal's
+// relu masks, no bias), backward passes of w and lam_{t+1} through the same masks:
 //   gW_l = sum_{b,t} a_{l-1}^T delta_l(w) - a'_{l-1}^T delta_l(lam),   gb_l = sum_{b,t} delta_l(w).
 // The residual x adds nothing to the parameter gradient.
 //
-//   k_dyn_adjoints  one workgroup per trajectory: the three backward sweeps -> w, lam planes [B][T][n]
 //   k_dyn_rows      16 steps per workgroup on v_mfma_f32_16x16x4_f32: the layer inputs [a; -a'] and deltas
 //                   [delta(w); delta(lam)] as 2 B T rows, whose column sums (k_wgrad*) are the weight gradient.
 #include "gmpc_launch.h"
@@ -22,105 +17,8 @@
 #include <cstring>
 
 #define GMPC_DG_THREADS 256
-#define GMPC_DG_CHUNK 8          // steps staged per chunk of the adjoint sweep (at most)
-#define GMPC_DG_CHUNK_FLOATS 14336   // LDS budget of the staged steps (56 KB)
 #define GMPC_DG_ROWS 16          // steps per workgroup of the row kernel (32 GEMM rows: primal + tangent)
 #define GMPC_DG_LDA 260          // LDS row stride of the row kernel's activations (widths <= 256, + 4)
-
-// ---- the three adjoint sweeps ---------------------------------------------------------------------------------
-// n <= 64, m <= 32 ([A_t | B_t] is kept).  Wave 0 runs mu, wave 1 nu, wave 2 lam; lane c owns state c and holds its
-// adjoint in a register (lanes >= n hold 0).  A_t^T v is an NMAX-term sum of LDS reads of column c of A_t times v_i
-// broadcast with v_readlane.  Steps come in chunks of K (<= GMPC_DG_CHUNK): every thread loads the chunk into LDS,
-// the waves run it backwards and park v_{t+1} in LDS, and the chunk's w / lam rows go out behind the barrier.
-template <int NMAX>
-__global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_adjoints(int T, int n, int ng, int m, int K,
-                                                                  const float* mpc_w,
-                                                                  const float* X, const float* goal, const float* dX,
-                                                                  const float* lx, const float* AB, const float* QT,
-                                                                  const float* qT, float* wout, float* lout) {
-  extern __shared__ __attribute__((aligned(16))) char smem_da[];
-  const int nm = n + m, fa = n * nm;
-  float* S = reinterpret_cast<float*>(smem_da);
-  float* ABs = S;                    // [K][n][nm]
-  float* LXs = ABs + K * fa;         // [K][n]
-  float* DXs = LXs + K * n;          // [K][n]
-  float* Xs = DXs + K * n;           // [K][n]
-  float* Gs = Xs + K * n;            // [K][ng]
-  float* Vs = Gs + K * ng;           // [3][K][64]: v_{t+1} of each sweep
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, b = blockIdx.x;
-  const int lc = lane < n ? lane : 0;
-  const float al = GMPC_ALPHA;
-  const float w1 = sigmoidf_(mpc_w[1]);
-  const size_t xrow = (size_t)b * (T + 1), urow = (size_t)b * T;
-
-  // ---- terminal values (dX_T through LDS for the QT product)
-  if (tid < n) Xs[tid] = dX[(xrow + T) * n + tid];
-  __syncthreads();
-  float v_adj = 0.f;
-  if (lane < n) {
-    if (wave == 0) {
-      v_adj = lx[(xrow + T) * n + lane];
-    } else if (wave == 1) {
-      const float* q = QT + ((size_t)b * n + lane) * n;
-      float v = 0.f;
-      for (int k = 0; k < n; ++k) v = fmaf(q[k], Xs[k], v);
-      v_adj = v;
-    } else if (wave == 2) {
-      v_adj = qT[(size_t)b * n + lane];
-    }
-  }
-  __syncthreads();
-
-  auto atv = [&](const float* A, float v) {
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < NMAX; ++i) acc = fmaf(A[(i < n ? i : n - 1) * nm + lc], __int_as_float(
-                                                  __builtin_amdgcn_readlane(__float_as_int(v), i)), acc);
-    return acc;
-  };
-  for (int tend = T; tend > 0; tend -= K) {
-    const int t0 = tend - K > 0 ? tend - K : 0, kc = tend - t0;
-    for (int e = tid; e < kc * fa; e += GMPC_DG_THREADS) ABs[e] = AB[(urow + t0) * fa + e];
-    for (int e = tid; e < kc * n; e += GMPC_DG_THREADS) {
-      LXs[e] = lx[(xrow + t0) * n + e];
-      DXs[e] = dX[(xrow + t0) * n + e];
-      Xs[e] = X[(xrow + t0) * n + e];
-    }
-    for (int e = tid; e < kc * ng; e += GMPC_DG_THREADS) Gs[e] = goal[(xrow + t0) * ng + e];
-    __syncthreads();
-    if (wave < 3) {
-      float* vs = Vs + wave * K * 64;
-      for (int k = kc - 1; k >= 0; --k) {
-        vs[k * 64 + lane] = v_adj;          // v_{t0 + k + 1}
-        float src = 0.f;                    // this sweep's source term at step t0 + k
-        if (wave == 0) {
-          src = LXs[k * n + lc];
-        } else {
-          // |d|^2 and d . dX over the goal columns: q_t = w1 d / s, Q_t dX_t = w1 (dX / s - d (d . dX) / s^3)
-          const float cd = lane < ng ? Xs[k * n + lane] - Gs[k * ng + lane] : 0.f;
-          const float dd = wave_sum(cd * cd);
-          const float is = 1.f / sqrtf(dd + al * al);
-          if (wave == 1) {
-            const float cdx = lane < n ? DXs[k * n + lane] : 0.f;
-            const float dxd = wave_sum(cd * cdx);
-            src = lane < ng ? w1 * (cdx * is - cd * dxd * (is * is * is)) : 0.f;
-          } else {
-            src = lane < ng ? w1 * cd * is : 0.f;
-          }
-        }
-        const float v = atv(ABs + k * fa, v_adj);
-        v_adj = lane < n ? src + v : 0.f;
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < kc * n; e += GMPC_DG_THREADS) {
-      const int k = e / n, i = e - k * n;
-      wout[(urow + t0) * n + e] = Vs[k * 64 + i] - Vs[(K + k) * 64 + i];
-      lout[(urow + t0) * n + e] = Vs[(2 * K + k) * 64 + i];
-    }
-    __syncthreads();
-  }
-}
 
 // ---- the row kernel -------------------------------------------------------------------------------------------
 // One 16 x 16 output tile per (wave, column tile) for each of the two row halves: rows 0..15 of the LDS operand are
@@ -297,24 +195,7 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_dyn_rows(DgRowArgs a) {
   }
 }
 
-// Host-side launchers ---------------------------------------------------------------------------
-void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X,
-                              const float* goal, const float* dX, const float* lx, const float* AB, const float* QT,
-                              const float* qT, float* w, float* lam, hipStream_t s) {
-  const int F = n * (n + m) + 3 * n + ng;
-  int K = GMPC_DG_CHUNK_FLOATS / F;
-  if (K > GMPC_DG_CHUNK) K = GMPC_DG_CHUNK;
-  if (K > T) K = T;
-  if (K < 1) K = 1;   // (n <= 64, m <= 32: F <= 6400)
-  const size_t lds = ((size_t)K * F + 3 * (size_t)K * 64) * sizeof(float);
-  if (n <= 32)
-    hipLaunchKernelGGL(k_dyn_adjoints<32>, dim3(B), dim3(GMPC_DG_THREADS), lds, s, T, n, ng, m, K, mpc_w, X, goal,
-                       dX, lx, AB, QT, qT, w, lam);
-  else
-    hipLaunchKernelGGL(k_dyn_adjoints<64>, dim3(B), dim3(GMPC_DG_THREADS), lds, s, T, n, ng, m, K, mpc_w, X, goal,
-                       dX, lx, AB, QT, qT, w, lam);
-}
-
+// Host-side launcher ----------------------------------------------------------------------------
 int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const float* X, const float* U,
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
                          const MlpRows& lay, hipStream_t s) {

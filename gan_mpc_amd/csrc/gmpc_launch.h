@@ -194,19 +194,26 @@ void gmpc_launch_costvjp(int B, int T, int n, int m, const MlpDesc& cm, const fl
 void gmpc_launch_get_cost(int B, int n, int ng, int m, const MlpDesc& cm, const float* mpc_w, const float* x,
                           const float* u, const float* goal_row, int terminal, float* out, hipStream_t s);
 
-// gmpc_input_grads.hip ------------------------------------------------------------------------------------------------
-// x0 (and, with ggoal, the goal) gradient: n <= 64, m <= 32 (the caller checks); 0 on success
-int gmpc_launch_input_grads(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X, const float* goal,
-                            const float* dX, const float* H, const float* lx, const float* AB, const float* QT,
-                            const float* Phi, float* gx0, float* ggoal, hipStream_t s);
+// gmpc_tail_adjoints.hip ----------------------------------------------------------------------------------------------
+// The adjoint sweeps over the held solution.  X, dX, lx [B][T+1][n], goal [B][T+1][ng], AB [B][T][n][n+m],
+// QT [B][n][n], mpc_w [3].
+struct TailAdjArgs {
+  int B, T, n, ng, m;
+  const float *mpc_w, *X, *goal, *dX, *lx, *AB, *QT;
+  // the inputs call: H [B][T][m]; Phi [B][T][n+m][n+m] or null (relu dynamics); gx0 [B][n]; ggoal [B][T+1][ng] or null
+  const float *H, *Phi;
+  float *gx0, *ggoal;
+  // the dynamics call: qT [B][n]; the planes w = mu_{t+1} - nu_{t+1} and lam_{t+1}, [B][T][n]
+  const float* qT;
+  float *w, *lam;
+};
+// planes false: the inputs call, true: the dynamics call; non-zero for n > 64 or m > 32 (no [A_t | B_t] is kept), or
+// when one step with Phi exceeds the LDS budget
+int gmpc_launch_tail_adjoints(const TailAdjArgs& a, bool planes, hipStream_t s);
 void gmpc_launch_goal_grad(int B, int T, int n, int ng, const float* mpc_w, const float* X, const float* goal,
                            const float* dX, float* ggoal, hipStream_t s);
 
 // gmpc_dyn_grads.hip --------------------------------------------------------------------------------------------------
-// the adjoint planes w, lam [B][T][n]; n <= 64, m <= 32 (the caller checks)
-void gmpc_launch_dyn_adjoints(int B, int T, int n, int ng, int m, const float* mpc_w, const float* X, const float* goal,
-                              const float* dX, const float* lx, const float* AB, const float* QT, const float* qT,
-                              float* w, float* lam, hipStream_t s);
 // acts / dels: 2 B T rows in the layout `lay` of the dynamics MLP.  Widths up to 256; returns 1 otherwise.
 int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const float* X, const float* U,
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,

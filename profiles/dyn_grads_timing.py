@@ -1,7 +1,7 @@
 """Cost of gmpc_bilevel_grad_dynamics (dL/dtheta_dyn through the iLQR solution) against the bilevel call it follows.
 
 Engine level, after one solve and one gmpc_bilevel_grad_cotangent: the cotangent call, the dynamics call (adjoint
-sweeps k_dyn_adjoints, row kernel k_dyn_rows, weight sums k_wgrad*) and the inputs call for comparison, alternating,
+sweeps k_tail_adjoints, row kernel k_dyn_rows, weight sums k_wgrad*) and the inputs call for comparison, alternating,
 device time per call from a synchronised host clock over `--calls` calls.  Shapes: C3 (n 17, m 6, T 50, B 1024) and the reference regime
 (cheetah n 17, m 6, T 5, B 128); dynamics 3 x 200 relu, cost 128-128-10.  Kernel-only times come from a separate
 `rocprofv3 --kernel-trace --stats` run of this script per shape (--shape), committed as

@@ -1,7 +1,7 @@
 """Cost of gmpc_bilevel_grad_inputs (dL/dx0 and dL/dgoal through the iLQR solution) against the bilevel call it follows.
 
 Engine level, after one solve and one gmpc_bilevel_grad_cotangent: the cotangent call, the inputs call with both
-outputs (the x0 sweep, k_input_grads) and with the goal only (k_goal_grad), alternating, device time per call from a
+outputs (the x0 sweep, k_tail_adjoints) and with the goal only (k_goal_grad), alternating, device time per call from a
 synchronised host clock over `--calls` calls.  Shapes: C3 (n 17, m 6, T 50, B 1024) and the reference regime
 (cheetah n 17, m 6, T 5, B 128); dynamics 3 x 200 relu, cost 128-128-10.  Kernel-only times come from a separate
 `rocprofv3 --kernel-trace --stats` run of this script per shape (--shape), committed as

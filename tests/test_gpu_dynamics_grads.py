@@ -76,6 +76,7 @@ CASES = {
     "rw-128/cot": ("rw-128", False, "cot"),
     "rw-64/l2": ("rw-64", False, "l2"),
     "wide/cot": ("wide", False, "cot"),
+    "wide-T20/cot": (ig.WIDE20, False, "cot"),
 }
 
 

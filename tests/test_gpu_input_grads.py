@@ -106,6 +106,9 @@ def _state(eng, B):
 PEND5 = ("pendulum-T5", 3, 1, 5, 7, {})
 PEND5_B1 = ("pendulum-T5-B1", 3, 1, 5, 1, {})
 CHEETAH5 = ("cheetah-T5", 17, 6, 5, 128, dict(out_scale=0.1))
+# n > 32 over several chunks of the adjoint sweep with a ragged last one (out_scale: at 1.0 the random dynamics reach
+# |x| ~ 3.5e3 over 20 steps)
+WIDE20 = ("wide-T20", 40, 9, 20, 4, dict(dyn_hidden=(256, 64), cost_hidden=(256, 100), cost_fout=32, out_scale=0.1))
 CASES = {
     "pendulum-B1/l2": (PEND5_B1, False, "l2"),
     "pendulum-B7/cot": (PEND5, False, "cot"),
@@ -120,6 +123,8 @@ CASES = {
     "dynl-small/l2": ("dynl-small", False, "l2"),
     "big-70/cot": ("big-70", False, "cot"),
     "m40-n24/l2": ("m40-n24", False, "l2"),
+    "wide/cot": ("wide", False, "cot"),
+    "wide-T20/cot": (WIDE20, False, "cot"),
 }
 
 
