@@ -30,7 +30,7 @@ static int bilevel_from_cotangents(gmpc_ctx* c, int B, const float* lx, const fl
     if (!c->dynl && gmpc_riccati_w2h_shape(r)) {
       // two waves per trajectory, products on the matrix pipe, the loss adjoint (a8) in the same sweep
       ProfScope ps(c, PROF_RICCATI, s);      // (bench.py: secondary.bilevel.kernel_ms)
-      gmpc_launch_riccati_w2h(r, lx, lu, c->Bvec, s);
+      gmpc_launch_riccati_w(r, lx, lu, c->Bvec, s);
     } else {
       gmpc_launch_bvec(B, T, n, m, c->AB, lx, lu, c->Bvec, s);
       if (c->dynl) {

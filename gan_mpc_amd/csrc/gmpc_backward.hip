@@ -5,6 +5,7 @@
 // trajax ilqr (reference call sites policy/optimizers.py:19,55) on dynamics/nn.py:27-34 and
 // cost/cost_model.py:20-42, cost/nn.py:23-29.
 #include "gmpc_launch.h"
+#include "gmpc_riccati_parts.h"
 
 // ------------------------------------------------------------------------------------------------
 // k_linearize: [A_t | B_t] = I + W_L^T D_{L-1} W_{L-1}^T ... D_1 W_1^T for SP samples (b,t) per pass.
@@ -271,7 +272,6 @@ __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(Ric
   float* tv = hv + m;                            // n scratch
 
   const float w0 = sigmoidf_(a.mpc_w[0]), w1 = sigmoidf_(a.mpc_w[1]);
-  const float al = GMPC_ALPHA;
   const float delta = a.mode == 0 ? 1e-8f : 0.f;
   // the staging cost sees xc[:ng] only (reference cost_model.py:24-25); ng < n when xc carries the LSTM
   // dynamics' (c, h) behind x
@@ -332,8 +332,7 @@ __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(Ric
     float dd = 0.f, uu = 0.f;
     _Pragma("unroll") for (int i = 0; i < n; ++i) dd = fmaf(dv[i], dv[i], dd);
     _Pragma("unroll") for (int j = 0; j < m; ++j) uu = fmaf(uv[j], uv[j], uu);
-    const float s = sqrtf(dd + al * al), su = sqrtf(uu + al * al);
-    const float is = 1.f / s, is3 = is * is * is, isu = 1.f / su, isu3 = isu * isu * isu;
+    const auto [is, is3, isu, isu3] = gmpc_ric_stage(dd, uu);
     // q_t, r_t ; adjoint / gradient (iLQR) ; linear terms
     for (int i = lane; i < n; i += NTH) qv[i] = w1 * dv[i] * is;
     for (int j = lane; j < m; j += NTH) rv[j] = w0 * uv[j] * isu;
@@ -461,35 +460,9 @@ __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(Ric
           for (int i = 0; i < MM; ++i) Kk[i * (n + 1) + c] = -y[i];
         }
       } else {
-      // Cholesky (NaN on a non-positive pivot, like jax cho_factor)
-        if (lane == 0) {
-          for (int j = 0; j < m; ++j) {
-            float sdiag = G[j * m + j] + delta;
-            for (int k = 0; k < j; ++k) sdiag -= Lc[j * m + k] * Lc[j * m + k];
-            const float d = sqrtf(sdiag);
-            Lc[j * m + j] = d;
-            for (int i = j + 1; i < m; ++i) {
-              float v = G[i * m + j];
-              for (int k = 0; k < j; ++k) v -= Lc[i * m + k] * Lc[j * m + k];
-              Lc[i * m + j] = v / d;
-            }
-          }
-        }
+        if (lane == 0) gmpc_chol_lds_factor(m, G, delta, Lc);
         __syncthreads();
-        for (int c = lane; c <= n; c += NTH) {
-          // column c of the right-hand side: H[:,c] for c<n, h for c==n
-          for (int i = 0; i < m; ++i) {
-            float v = c < n ? Hm[i * n + c] : hv[i];
-            for (int k = 0; k < i; ++k) v -= Lc[i * m + k] * Kk[k * (n + 1) + c];
-            Kk[i * (n + 1) + c] = v / Lc[i * m + i];
-          }
-          for (int i = m - 1; i >= 0; --i) {
-            float v = Kk[i * (n + 1) + c];
-            for (int k = i + 1; k < m; ++k) v -= Lc[k * m + i] * Kk[k * (n + 1) + c];
-            Kk[i * (n + 1) + c] = v / Lc[i * m + i];
-          }
-          for (int i = 0; i < m; ++i) Kk[i * (n + 1) + c] = -Kk[i * (n + 1) + c];
-        }
+        for (int c = lane; c <= n; c += NTH) gmpc_chol_lds_solve(n, m, Lc, Hm, hv, c, Kk);
       }
     } else {
       // Gaussian elimination with partial pivoting (jax.scipy.linalg.solve), serial on lane 0
@@ -595,16 +568,7 @@ __global__ __launch_bounds__(GMPC_RIC_THREADS, GMPC_RIC_MINW) void k_riccati(Ric
       if (lane == 0) {
         gn2 = 0.f; un2 = 0.f;
         for (int w = 0; w < NTH / 64; ++w) { gn2 += tv[w]; un2 += tv[NTH / 64 + w]; }
-        float gn = sqrtf(gn2);
-        if (isnan(gn)) gn = INFINITY;
-        const float aobj = fabsf(a.obj[b]) + 1.0f;
-        const float un = sqrtf(un2) + 1.0f;
-        const bool progressing = (a.obj_step[b] > a.opts.obj_step_threshold * aobj) &&
-                                 (a.U_step[b] > a.opts.inputs_step_threshold * un);
-        const bool potential = (gn > a.opts.grad_norm_threshold) &&
-                               (gn > a.opts.relative_grad_norm_threshold * aobj);
-        const bool go = (a.iters[b] < a.opts.maxiter) && progressing && potential &&
-                        (a.alpha[b] > a.opts.alpha_min);
+        const bool go = gmpc_ric_continue(gn2, un2, b, a.obj, a.obj_step, a.U_step, a.iters, a.alpha, a.opts);
         a.cont[b] = go ? 1 : 0;
       }
     }
@@ -697,7 +661,7 @@ int gmpc_launch_terminal(int B, int T, int n, const MlpDesc& cm, const float* mp
 
 void gmpc_launch_riccati(const RiccatiArgs& a, hipStream_t s) {
   if (gmpc_riccati_w_shape(a)) {          // two waves per trajectory, products on the matrix pipe
-    gmpc_launch_riccati_w(a, s);
+    gmpc_launch_riccati_w(a, nullptr, nullptr, nullptr, s);
     return;
   }
   const size_t lds = gmpc_riccati_lds_bytes(a.n, a.m);

@@ -18,6 +18,7 @@
 // from a box QP (projected Newton on one lane, fz_box_qp) and the continuation test sees the projected gradient.
 // With no bound active every phase performs the arithmetic of the unconstrained form, operation for operation.
 #include "gmpc_fused_solve.h"
+#include "gmpc_riccati_parts.h"
 
 #define FZ_THREADS GMPC_THREADS
 
@@ -447,7 +448,6 @@ __device__ __forceinline__ bool fz_riccati(const FusedSolveArgs& a, const BoxSol
   float* qf = hv + m;              // BOX: fz_box_qp's floats (4 m), then its ints (2 m + 2)
   int* qi = reinterpret_cast<int*>(qf + 4 * m);
   const float w0 = sigmoidf_(a.mpc_w[0]), w1 = sigmoidf_(a.mpc_w[1]);
-  const float al = GMPC_ALPHA;
   const float delta = 1e-8f;
   for (int e = lane; e < n * n; e += NTH) P[e] = a.QT[(size_t)b * n * n + e];
   for (int i = lane; i < n; i += NTH) {
@@ -468,8 +468,7 @@ __device__ __forceinline__ bool fz_riccati(const FusedSolveArgs& a, const BoxSol
     float dd = 0.f, uu = 0.f;
     for (int i = 0; i < n; ++i) dd = fmaf(dv[i], dv[i], dd);
     for (int j = 0; j < m; ++j) uu = fmaf(uv[j], uv[j], uu);
-    const float s = sqrtf(dd + al * al), su = sqrtf(uu + al * al);
-    const float is = 1.f / s, is3 = is * is * is, isu = 1.f / su, isu3 = isu * isu * isu;
+    const auto [is, is3, isu, isu3] = gmpc_ric_stage(dd, uu);
     for (int i = lane; i < n; i += NTH) qv[i] = w1 * dv[i] * is;
     for (int j = lane; j < m; j += NTH) rv[j] = w0 * uv[j] * isu;
     __syncthreads();
@@ -573,33 +572,9 @@ __device__ __forceinline__ bool fz_riccati(const FusedSolveArgs& a, const BoxSol
       __syncthreads();
       for (int i = lane; i < nf; i += NTH) x.clamped[bt * m + fi[i]] = 0.f;
     } else {
-      if (lane == 0) {
-        for (int j = 0; j < m; ++j) {
-          float sdiag = G[j * m + j] + delta;
-          for (int k = 0; k < j; ++k) sdiag -= Lc[j * m + k] * Lc[j * m + k];
-          const float d = sqrtf(sdiag);
-          Lc[j * m + j] = d;
-          for (int i = j + 1; i < m; ++i) {
-            float v = G[i * m + j];
-            for (int k = 0; k < j; ++k) v -= Lc[i * m + k] * Lc[j * m + k];
-            Lc[i * m + j] = v / d;
-          }
-        }
-      }
+      if (lane == 0) gmpc_chol_lds_factor(m, G, delta, Lc);
       __syncthreads();
-      for (int c = lane; c <= n; c += NTH) {
-        for (int i = 0; i < m; ++i) {
-          float v = c < n ? Hm[i * n + c] : hv[i];
-          for (int k = 0; k < i; ++k) v -= Lc[i * m + k] * Kk[k * (n + 1) + c];
-          Kk[i * (n + 1) + c] = v / Lc[i * m + i];
-        }
-        for (int i = m - 1; i >= 0; --i) {
-          float v = Kk[i * (n + 1) + c];
-          for (int k = i + 1; k < m; ++k) v -= Lc[k * m + i] * Kk[k * (n + 1) + c];
-          Kk[i * (n + 1) + c] = v / Lc[i * m + i];
-        }
-        for (int i = 0; i < m; ++i) Kk[i * (n + 1) + c] = -Kk[i * (n + 1) + c];
-      }
+      for (int c = lane; c <= n; c += NTH) gmpc_chol_lds_solve(n, m, Lc, Hm, hv, c, Kk);
     }
     __syncthreads();
     for (int e = lane; e < m * n; e += NTH) {
@@ -650,14 +625,7 @@ __device__ __forceinline__ bool fz_riccati(const FusedSolveArgs& a, const BoxSol
   }
   gn2 = fz_block_sum(gn2, red);
   un2 = fz_block_sum(un2, red);
-  float gn = sqrtf(gn2);
-  if (isnan(gn)) gn = INFINITY;
-  const float aobj = fabsf(a.obj[b]) + 1.0f;
-  const float un = sqrtf(un2) + 1.0f;
-  const bool progressing = (a.obj_step[b] > a.opts.obj_step_threshold * aobj) &&
-                           (a.U_step[b] > a.opts.inputs_step_threshold * un);
-  const bool potential = (gn > a.opts.grad_norm_threshold) && (gn > a.opts.relative_grad_norm_threshold * aobj);
-  const bool go = (a.iters[b] < a.opts.maxiter) && progressing && potential && (a.alpha[b] > a.opts.alpha_min);
+  const bool go = gmpc_ric_continue(gn2, un2, b, a.obj, a.obj_step, a.U_step, a.iters, a.alpha, a.opts);
   __syncthreads();
   return go;
 }

@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "gmpc_launch.h"
+#include "gmpc_riccati_parts.h"
 
 // P = Q_t + T1 on the upper triangle, mirrored into the lower one: tile (I, J) with I <= J (64 x 64) is read
 // row-wise once and written twice (the transposed copy through LDS), so every global access is
@@ -106,7 +107,7 @@ __global__ void k_big_init(int B, int n, int T, const float* QT, const float* qT
   if (e == 0) gn2[b] = 0.f;
 }
 
-// trajax continuation test (same rule as the tail of k_riccati)
+// trajax continuation test (gmpc_ric_continue, as at the tail of k_riccati)
 __global__ void k_big_cont(int B, int T, int m, const float* U, const float* gn2, const int* iters,
                            const float* obj, const float* alpha, const float* obj_step,
                            const float* U_step, gmpc_ilqr_opts opts, const int* active, int* cont) {
@@ -115,14 +116,7 @@ __global__ void k_big_cont(int B, int T, int m, const float* U, const float* gn2
   if (active != nullptr && active[b] == 0) return;
   float un2 = 0.f;
   for (int e = 0; e < T * m; ++e) { const float u = U[(size_t)b * T * m + e]; un2 = fmaf(u, u, un2); }
-  float gn = sqrtf(gn2[b]);
-  if (isnan(gn)) gn = INFINITY;
-  const float aobj = fabsf(obj[b]) + 1.0f;
-  const float un = sqrtf(un2) + 1.0f;
-  const bool progressing = (obj_step[b] > opts.obj_step_threshold * aobj) &&
-                           (U_step[b] > opts.inputs_step_threshold * un);
-  const bool potential = (gn > opts.grad_norm_threshold) && (gn > opts.relative_grad_norm_threshold * aobj);
-  cont[b] = ((iters[b] < opts.maxiter) && progressing && potential && (alpha[b] > opts.alpha_min)) ? 1 : 0;
+  cont[b] = gmpc_ric_continue(gn2[b], un2, b, obj, obj_step, U_step, iters, alpha, opts) ? 1 : 0;
 }
 
 // out[b][c][r] = in[b][r][c], 64 x 64 tiles through LDS

@@ -60,8 +60,8 @@ void gmpc_launch_riccati(const RiccatiArgs& a, hipStream_t s);
 // gmpc_riccati_w.hip: the two-wave sweep
 bool gmpc_riccati_w_shape(const RiccatiArgs& a);      // mode 0 only; GMPC_RICCATI=valu keeps k_riccati
 bool gmpc_riccati_w2h_shape(const RiccatiArgs& a);    // mode 1 with the loss adjoint folded in (MLP dynamics)
-void gmpc_launch_riccati_w(const RiccatiArgs& a, hipStream_t s);
-void gmpc_launch_riccati_w2h(const RiccatiArgs& a, const float* lx, const float* lu, float* bvec_out, hipStream_t s);
+// k_riccati_w2 in the mode of a.mode; lx, lu (optional), bvec_out: the Hessian solve's loss adjoint, mode 1 only
+void gmpc_launch_riccati_w(const RiccatiArgs& a, const float* lx, const float* lu, float* bvec_out, hipStream_t s);
 
 // Jacobian chains (gmpc_linearize_*.hip) -----------------------------------------------------------------------------
 // All of them: Jacobians of NSamp samples; sample s is sample s*samp_mul + samp_add of `masks`.  They return 0 on

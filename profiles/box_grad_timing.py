@@ -6,9 +6,9 @@ profiles/box_solve_timing.py: this problem's optimal controls are small, so most
 bound; the share in the final clamped set is printed).  ONE process, alternating calls:
 
   (a) "tail_box":   bilevel_grad_cotangent (lx and lu of an L2 + control loss) on an engine holding the box solution --
-                    k_riccati_w2h<17, 6, LU, BOX> with the clamped words, then the cost stage and the weight sums;
+                    k_riccati_w2<17, 6, HESS, LU, BOX> with the clamped words, then the cost stage and the weight sums;
   (b) "tail_fused": the same call on a second engine holding the fused solution of the same problem --
-                    k_riccati_w2h<17, 6, LU>, the code the masked form leaves untouched;
+                    k_riccati_w2<17, 6, HESS, LU>, the code the masked form leaves untouched;
   (c) "solve_held" against "solve_box": the solve followed by reading the first controls back; their difference is the
       launch of k_box_clamped.
 

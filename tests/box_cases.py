@@ -30,9 +30,12 @@ CASES = {
     "wide_m": (lambda: gu.problem(4, 32, 3, 2, seed=1, dyn_hidden=(32, 32), cost_hidden=(16,), cost_fout=4), 0.5),
     "wide_n": (lambda: gu.problem(64, 2, 3, 2, seed=5, dyn_hidden=(32, 32), cost_hidden=(16,), cost_fout=4), 0.5),
     "cheetah128": (lambda: gu.problem(17, 6, 5, 128, seed=5), 0.5),     # the whole-solve test only
+    # the tail test only: the two-wave Hessian solve with each of its two clamped-word buffers used once (the CPU run:
+    # 10 of step 0's 42 controls on a bound, none of step 1's -- swapping the buffers would move the set)
+    "cheetah_T2": (lambda: gu.problem(17, 6, 2, 7, seed=5), 0.5),
 }
 SHAPES = {"base": (5, 2, 8, 3), "m1": (3, 1, 5, 7), "cheetah": (17, 6, 5, 7), "wide_m": (4, 32, 3, 2),
-          "wide_n": (64, 2, 3, 2), "cheetah128": (17, 6, 5, 128)}
+          "wide_n": (64, 2, 3, 2), "cheetah128": (17, 6, 5, 128), "cheetah_T2": (17, 6, 2, 7)}
 TABLE = ("base", "m1", "cheetah", "wide_m", "wide_n")       # the case table of the GPU tests
 # min_agree of the one-iteration protocol (decided(name, 1)): what the CPU run shows -- 2 of 3, 4 of 7, 3 of 7, 0 of 2,
 # 2 of 2 trajectories -- rounded down; asserted by test_box_ilqr_host.test_gpu_inputs_are_fixed_here.  wide_m: with 32

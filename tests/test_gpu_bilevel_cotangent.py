@@ -2,7 +2,7 @@
 cotangents lx = dL/dX, lu = dL/dU -- on the GPU (reference policy/optimizers.py:34-83: `loss` is any callable, and
 jax.grad sees its dependence on U as well).
 
-The cases reach every Bvec producer: k_riccati_w2h (trained-like), k_bvec (tiny-ragged, trained-like under
+The cases reach every Bvec producer: k_riccati_w2 in its Hessian form (trained-like, w2-T*), k_bvec (tiny-ragged, trained-like under
 GMPC_RICCATI=valu, dynl-small with the curvature term), k_big_step mode 1 (big-70, m40-n24, lowrank-1h, dynl-big).
 
   1. with the lx gmpc_bilevel_grad computes and no lu: the same bits as gmpc_bilevel_grad (grad_sum, Bvec, H, dX);
@@ -125,12 +125,19 @@ def _check_at_iterate(pb, pb64, X, U, cot, loss, grad, Hd, dXd, Bvd, batch_mean=
     return s32, s64
 
 
+# The two-wave sweep's Hessian form (17 x 6 only) at the horizons where its double buffering (t & 1), the one-step-ahead
+# helper wave and the tangent roll can go wrong: nothing prepared inside the loop (T 1), each buffer used once (T 2),
+# an odd horizon that wraps the buffers (T 3).  name: T (B 4, the seed and out_scale of trained-like)
+SHORT = {"w2-T1": 1, "w2-T2": 2, "w2-T3": 3}
+
+
 def _solved(name, critic=False, fused=False):
     """A problem of test_gpu_parity's table solved on the GPU (3 iterations), the trajectories at a relu kink
     dropped, and the kept ones re-solved with maxiter 0 so that the ctx holds exactly them (test_bilevel_grad)."""
-    if name == "fused-17x6":
-        pb = gu.problem(17, 6, 10, 16, seed=11, out_scale=0.1)
-        gu.set_config("fused bilevel n=17 m=6 T=10 B=16")
+    if name == "fused-17x6" or name in SHORT:
+        T, B = (10, 16) if name == "fused-17x6" else (SHORT[name], 4)
+        pb = gu.problem(17, 6, T, B, seed=11, out_scale=0.1)
+        gu.set_config(f"{'fused' if name == 'fused-17x6' else 'short'} bilevel n=17 m=6 T={T} B={B}")
         pb64, eng = orc.cast_problem(pb, np.float64), gu.engine_for(pb, critic=critic)
     else:
         pb, pb64, eng = par._setup(name, critic=critic)
@@ -156,7 +163,7 @@ def _ctx_state(eng, B):
 
 
 BVEC_CASES = ["trained-like", "trained-like/valu", "tiny-ragged", "m40-n24", "dynl-small", "big-70", "lowrank-1h",
-              "dynl-big"]
+              "dynl-big"] + [c + form for c in SHORT for form in ("", "/valu")]
 
 
 def _case(case, monkeypatch):

@@ -164,7 +164,7 @@ def _check(name, pb, pb64, X, U, cl, cot_fn, loss, got):
 
 
 @pytest.mark.parametrize("loss", ["l2", "huber"])
-@pytest.mark.parametrize("case", list(bc.TABLE) + ["cheetah/valu"])
+@pytest.mark.parametrize("case", list(bc.TABLE) + ["cheetah/valu", "cheetah_T2"])
 def test_g2_tail_against_the_masked_reference_at_the_iterate(case, loss, monkeypatch):
     name = cot._case(case, monkeypatch)
     pb, pb64, eng, out, B, b = _held_at_the_iterate(name)

@@ -25,6 +25,10 @@ SHAPES = {
     "rw-wide-io": (22, 9, 70, 6, dict(out_scale=0.3)),
     "rw-ragged": (17, 6, 9, 7, {}),
     "rw-one-step": (17, 6, 1, 6, {}),          # horizon 1: the first step is the last one
+    # the two-wave Riccati sweep's double buffering (t & 1) and one-step-ahead helper wave: each buffer used once
+    # (T 2), an odd horizon that wraps the buffers (T 3); at T 1 nothing is prepared inside the loop
+    "rw-two-steps": (17, 6, 2, 3, {}),
+    "rw-three-steps": (17, 6, 3, 3, {}),
     # the 128- and 64-wide instantiations of the register-weight rollout / line search (round 3; the Jacobian chain
     # has its regs<4, 64> / regs<2, 32> forms for them): waves 2-3 / 1-3 of the workgroup hold no neuron
     "rw-128": (9, 3, 12, 10, dict(dyn_hidden=(128, 128, 128), cost_hidden=(32,), cost_fout=4, out_scale=0.3)),
@@ -358,11 +362,12 @@ def test_ilqr_converges_on_lq_problem():
     assert gu.rel_err(obj, c64) < 1e-5
 
 
-def test_riccati_two_wave_form_and_linearize_event(monkeypatch):
+@pytest.mark.parametrize("name", ["c2-cheetah", "rw-one-step", "rw-two-steps", "rw-three-steps"])
+def test_riccati_two_wave_form_and_linearize_event(name, monkeypatch):
     """k_riccati_w2 (the default at n=17, m=6) against k_riccati (GMPC_RICCATI=valu) on the same inputs -- each is
     held to the oracle by test_lqr_backward, this pins them to each other --, and gmpc_set_linearize_event: the
     caller's event is recorded inside the backward pass, a second stream that waits for it sees the Jacobians."""
-    pb, pb64, eng = _setup("c2-cheetah")
+    pb, pb64, eng = _setup(name)
     d = eng.to_dev
     Xd, _ = eng.rollout_cost(d(pb["x0"]), d(pb["U"]), d(pb["goal"]))
     ev = torch.cuda.Event()
