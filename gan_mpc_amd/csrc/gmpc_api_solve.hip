@@ -346,6 +346,72 @@ extern "C" int gmpc_ilqr_solve_box_held(gmpc_ctx* c, int B, const float* x0, con
   return 0;
 }
 
+// The cross-entropy method: 2 max_iter + 1 launches on the caller's stream, nothing waited for.
+// Stateless: it writes the caller's arrays and the call workspace only, so a held solution survives it.
+extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
+                              const float* u_hi, const gmpc_cem_opts* o, float* mean_io, float* std_io, float* X,
+                              float* obj, float* costs, int* elites, float* samples, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl) return fail(GMPC_EINVAL, "cem: MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
+  for (int l = 0; l <= sh.dyn_layers; ++l)
+    if (sh.dyn_dims[l] > 256) return fail(GMPC_EINVAL, "cem: dynamics width %d above 256", sh.dyn_dims[l]);
+  for (int l = 0; l <= sh.cost_layers; ++l)
+    if (sh.cost_dims[l] > 256) return fail(GMPC_EINVAL, "cem: cost width %d above 256", sh.cost_dims[l]);
+  if (sh.n + sh.m > 256) return fail(GMPC_EINVAL, "cem: n + m = %d above 256", sh.n + sh.m);
+  if (!o) return fail(GMPC_EINVAL, "cem: opts is null");
+  if (!x0 || !goal || !mean_io || !std_io) return fail(GMPC_EINVAL, "cem: x0, goal, mean_io and std_io must not be null");
+  if (o->num_samples < 1 || o->num_samples > 4096)
+    return fail(GMPC_EINVAL, "cem: num_samples = %d outside [1, 4096]", o->num_samples);
+  if (o->num_elites < 1 || o->num_elites > o->num_samples)
+    return fail(GMPC_EINVAL, "cem: num_elites = %d outside [1, num_samples = %d]", o->num_elites, o->num_samples);
+  if (o->max_iter < 0) return fail(GMPC_EINVAL, "cem: max_iter = %d is negative", o->max_iter);
+  if (!(o->sampling_smoothing >= 0.f && o->sampling_smoothing < 1.f))
+    return fail(GMPC_EINVAL, "cem: sampling_smoothing = %g outside [0, 1)", (double)o->sampling_smoothing);
+  if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
+    return fail(GMPC_EINVAL, "cem: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = o->num_samples;
+  float* cost_buf = costs;
+  if (!cost_buf && o->max_iter > 0) {
+    TRY(c->cw.aux.grow(c, (size_t)B * N));
+    cost_buf = c->cw.aux.p;
+  }
+  CemRollArgs r;
+  memset(&r, 0, sizeof(r));
+  r.B = B; r.N = N; r.T = sh.T; r.n = sh.n; r.m = sh.m;
+  r.dyn = c->dyn; r.cost = c->cost; r.mpc_w = c->mpc_w;
+  r.x0 = x0; r.goal = goal; r.mean = mean_io; r.sd = std_io; r.lo = u_lo; r.hi = u_hi;
+  r.rng.key0 = (uint32_t)(o->seed & 0xFFFFFFFFull); r.rng.key1 = (uint32_t)(o->seed >> 32);
+  r.rng.beta = o->sampling_smoothing;
+  r.rng.cbeta = sqrtf(1.f - r.rng.beta * r.rng.beta);
+  r.costs = cost_buf;
+  CemUpdArgs u;
+  memset(&u, 0, sizeof(u));
+  u.B = B; u.N = N; u.E = o->num_elites; u.T = sh.T; u.m = sh.m;
+  u.costs = cost_buf; u.lo = u_lo; u.hi = u_hi; u.mean = mean_io; u.sd = std_io;
+  u.gamma = o->evolution_smoothing;
+  for (int i = 0; i < o->max_iter; ++i) {
+    const bool last = i == o->max_iter - 1;
+    r.rng.it = (uint32_t)(o->iter_offset + i);
+    r.samples = last ? samples : nullptr;
+    u.rng = r.rng;
+    u.elites = last ? elites : nullptr;
+    if (gmpc_launch_cem_rollout(r, s) || gmpc_launch_cem_update(u, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
+  }
+  if (X || obj) {
+    // the final mean's own rollout: one row per problem, no noise, no clamp
+    if (!obj) {
+      TRY(c->cw.aux2.grow(c, (size_t)B));
+      obj = c->cw.aux2.p;
+    }
+    r.N = 1; r.mean_row = 1; r.samples = nullptr; r.costs = obj; r.X = X;
+    if (gmpc_launch_cem_rollout(r, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // single model evaluations (the reference's model protocol, base.py:4-49) -----------------------
 
 extern "C" int gmpc_get_cost(gmpc_ctx* c, int B, const float* x, const float* u, const float* goal_row,

@@ -219,6 +219,33 @@ int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const f
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
                          const MlpRows& lay, hipStream_t s);
 
+// gmpc_cem.hip: the cross-entropy method's two kernels --------------------------------------------------
+// The noise stream of one iteration: Philox4x32-10 under the key (key0, key1), counter (element group, sample,
+// problem, it); cbeta = sqrt(1 - beta^2) of the smoothing along time.
+struct CemRng { uint32_t key0, key1, it; float beta, cbeta; };
+// k_cem_rollout: N sample rows per problem in tiles of 32; mean / sd [B][T][m]; lo / hi [m] or null.  mean_row: the
+// rows are the mean itself (std 0, no bounds; N = 1, and X [B][T+1][n] may be set).  costs [B][N]; samples
+// [B][N][T][m] or null.
+struct CemRollArgs {
+  int B, N, T, n, m, mean_row;
+  MlpDesc dyn, cost;
+  const float *mpc_w, *x0, *goal, *mean, *sd, *lo, *hi;
+  CemRng rng;
+  float *costs, *X, *samples;
+};
+// k_cem_update: the E smallest of costs [B][N] by (cost, index), mean / sd updated in place; elites [B][E] or null
+struct CemUpdArgs {
+  int B, N, E, T, m;
+  const float *costs, *lo, *hi;
+  float *mean, *sd;
+  CemRng rng;
+  float gamma;
+  int* elites;
+};
+// widths up to 256 and n + m <= 256, N <= 4096: non-zero (nothing launched) otherwise
+int gmpc_launch_cem_rollout(const CemRollArgs& a, hipStream_t s);
+int gmpc_launch_cem_update(const CemUpdArgs& a, hipStream_t s);
+
 // gmpc_rollout_vjp.hip ------------------------------------------------------------------------------------------------
 // masks: [B][T][Lh][GMPC_MW] relu bits at (X_t, U_t).  Null outputs are skipped; cacts / cdels (B rows in the cost
 // MLP's layout cr) and gm go together; dels: B T rows in the dynamics MLP's layout dr.

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IlqrOpts, Shape
+from ._lib import CemOpts, IlqrOpts, Shape
 
 # trajax iLQR keywords exactly as the reference passes them (policy/eval.py:10-20)
 TRAJAX_iLQR_KWARGS = {
@@ -24,6 +24,16 @@ TRAJAX_iLQR_KWARGS = {
     "psd_delta": 0.0,
     "alpha_0": 1.0,
     "alpha_min": 0.00005,
+}
+
+# trajax cem keywords at their defaults (trajax optimizers.py `cem`: hyperparams)
+TRAJAX_CEM_KWARGS = {
+    "sampling_smoothing": 0.0,
+    "evolution_smoothing": 0.1,
+    "elite_portion": 0.1,
+    "max_iter": 10,
+    "num_samples": 400,
+    "seed": 0,
 }
 
 
@@ -74,6 +84,24 @@ def make_opts(kwargs=None):
     o.psd_delta = float(kw["psd_delta"])
     o.alpha_0 = float(kw["alpha_0"])
     o.alpha_min = float(kw["alpha_min"])
+    return o
+
+
+def make_cem_opts(kwargs=None, iter_offset=0):
+    """gmpc_cem_opts from trajax' keyword set: num_elites = int(num_samples * elite_portion), as trajax computes it."""
+    kw = dict(TRAJAX_CEM_KWARGS)
+    if kwargs:
+        unknown = set(kwargs) - set(kw)
+        if unknown:
+            raise _lib.GmpcError(f"cem: unknown keyword(s) {sorted(unknown)}")
+        kw.update(kwargs)
+    o = CemOpts()
+    o.max_iter, o.num_samples = int(kw["max_iter"]), int(kw["num_samples"])
+    o.num_elites = int(kw["num_samples"] * kw["elite_portion"])
+    o.iter_offset = int(iter_offset)
+    o.sampling_smoothing = float(kw["sampling_smoothing"])
+    o.evolution_smoothing = float(kw["evolution_smoothing"])
+    o.seed = int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF
     return o
 
 
@@ -222,6 +250,11 @@ class Engine:
         return self._solve_box("gmpc_ilqr_solve_box_held", x0, U, goal, u_lo, u_hi, kwargs)
 
     def _solve_box(self, name, x0, U, goal, u_lo, u_hi, kwargs):
+        _, _, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+        return self._solve(getattr(self.lib, name), x0, U, goal, kwargs, tail=(_ptr(lo_d), _ptr(hi_d)))
+
+    def _device_bounds(self, u_lo, u_hi):
+        """The checked host vectors of a pair of bounds and their cached device copies -> (lo, hi, lo_d, hi_d)."""
         lo, hi = self._bound_vector("u_lo", u_lo), self._bound_vector("u_hi", u_hi)
         if lo is not None and hi is not None and not bool(np.all(lo <= hi)):
             raise _lib.GmpcError("u_lo must be <= u_hi")
@@ -232,8 +265,49 @@ class Engine:
             if len(cache) >= 8:
                 cache.clear()
             cache[key] = (None if lo is None else self.to_dev(lo), None if hi is None else self.to_dev(hi))
-        lo_d, hi_d = cache[key]
-        return self._solve(getattr(self.lib, name), x0, U, goal, kwargs, tail=(_ptr(lo_d), _ptr(hi_d)))
+        return (lo, hi) + cache[key]
+
+    CEM_WANT = ("costs", "elites", "samples")
+
+    def cem_solve(self, x0, U_init, goal, u_lo, u_hi, kwargs=None, init_std=None, want=(), iter_offset=0):
+        """The cross-entropy method from the mean U_init under u_lo <= u <= u_hi (gmpc_cem_solve; trajax `cem`, keywords
+        TRAJAX_CEM_KWARGS).  u_lo, u_hi as for ilqr_solve_box.  init_std: None -- (u_hi - u_lo) / 2 per control, as
+        trajax does, which needs both bounds finite --, a scalar, m values or a (B, T, m) tensor.  -> dict(X, U (the
+        final mean, not clipped), obj, std) plus the last iteration's `want`ed debug outputs: "costs" (B, N), "elites"
+        (B, E) int32, "samples" (B, N, T, m).  iter_offset: the noise stream's first iteration (chained calls).
+        Stateless: a held iLQR solution stays valid; nothing is synchronised."""
+        B, n, m, T = x0.shape[0], self.n, self.m, self.T
+        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
+            if tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"cem: {name} must be {shape}, got {tuple(t.shape)}")
+        unknown = set(want) - set(self.CEM_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"cem: want has unknown entries {sorted(unknown)}; known: {self.CEM_WANT}")
+        opts = make_cem_opts(kwargs, iter_offset)
+        lo, hi = self._bound_vector("u_lo", u_lo), self._bound_vector("u_hi", u_hi)
+        if init_std is None and (lo is None or hi is None or not (np.isfinite(lo).all() and np.isfinite(hi).all())):
+            raise _lib.GmpcError("cem: without init_std both bounds must be finite (std = (u_hi - u_lo) / 2)")
+        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+        if init_std is None:
+            std = self.to_dev(np.broadcast_to((hi - lo) / np.float32(2), (B, T, m)))
+        elif torch.is_tensor(init_std) and tuple(init_std.shape) == (B, T, m):
+            std = self.to_dev(init_std).clone()
+        else:
+            v = self._bound_vector("init_std", init_std)
+            std = self.to_dev(np.broadcast_to(v, (B, T, m)))
+        N, E = opts.num_samples, opts.num_elites
+        out = dict(X=self.new(B, T + 1, n), U=U_init.clone(), obj=self.new(B), std=std)
+        if "costs" in want:
+            out["costs"] = self.new(B, N)
+        if "elites" in want:
+            out["elites"] = self.new(B, max(E, 0), dtype=torch.int32)
+        if "samples" in want:
+            out["samples"] = self.new(B, N, T, m)
+        _lib.check(self.lib.gmpc_cem_solve(
+            self.ctx, B, _ptr(x0), _ptr(goal), _ptr(lo_d), _ptr(hi_d), C.byref(opts), _ptr(out["U"]), _ptr(out["std"]),
+            _ptr(out["X"]), _ptr(out["obj"]), _ptr(out.get("costs")), _ptr(out.get("elites")), _ptr(out.get("samples")),
+            self._stream()))
+        return out
 
     def _bound_vector(self, name, b):
         """None, a scalar or m values -> None or a host fp32 vector [m] without NaN."""

@@ -17,10 +17,10 @@ class BaseMPC(eval_policy.EvalMPC):
 
     def __init__(self, config, cost_model, dynamics_model, expert_model, loss_vmap=(0,),
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, bilevel_sign=1.0, solver="rounds",
-                 control_bounds=None):
+                 control_bounds=None, cem_kwargs=None):
         super().__init__(config=config, cost_model=cost_model, dynamics_model=dynamics_model,
                          expert_model=expert_model, trajax_ilqr_kwargs=trajax_ilqr_kwargs,
-                         device=device, solver=solver, control_bounds=control_bounds)
+                         device=device, solver=solver, control_bounds=control_bounds, cem_kwargs=cem_kwargs)
         self.loss_vmap = loss_vmap
         # +1 reproduces the reference as written; -1 is the implicit-function gradient
         self.bilevel_sign = float(bilevel_sign)
@@ -62,6 +62,7 @@ class BaseMPC(eval_policy.EvalMPC):
 
     def batch_loss(self, dparams, history_X, desired):
         """mean over the (global) batch of loss(iLQR(x)) -- norm/cost_trainer.py:13-21."""
+        opt.refuse_cem(self, "batch_loss")
         custom = self._custom_loss()
         B = len(history_X)
         packed = parallel.new_packed(1, self.device(), B)
@@ -85,6 +86,7 @@ class BaseMPC(eval_policy.EvalMPC):
         returns (avg_loss, grads) where grads is a flat device vector over [mpc_weights | cost_params]
         (every other leaf's gradient is exactly zero in the reference), both averaged
         over the global batch."""
+        opt.refuse_cem(self, "loss_and_grad")
         custom = self._custom_loss()
         dparams = self.to_device_params(params)
         hx = np.asarray(history_X, np.float32)

@@ -115,7 +115,9 @@ def ilqr_layer(policy, params, x0, goal, init_U, trajax_ilqr_kwargs=None, dynami
     through the solution's active set held fixed), differentiable w.r.t. x0, goal and the
     mpc_weights / cost_params ranges of params.flat, and with dynamics_grad=True its dynamics_params range (see the
     module docstring).  params: the policy's DeviceParams (a parameter tree is
-    converted, and then is not differentiable); x0, goal, init_U: device tensors."""
+    converted, and then is not differentiable); x0, goal, init_U: device tensors.  A "cem" policy is refused
+    (NotImplementedError): the sampler has no derivative."""
+    opt.refuse_cem(policy, "ilqr_layer")
     dparams = policy.to_device_params(params)
     return ILQRFunction.apply(policy, dparams, trajax_ilqr_kwargs, dparams.flat, x0, goal, init_U,
                               bool(dynamics_grad))

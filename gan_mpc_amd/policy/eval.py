@@ -5,7 +5,7 @@ batch (B, hist+1, n)."""
 import numpy as np
 import torch
 
-from gan_mpc_amd.engine import TRAJAX_iLQR_KWARGS, Engine
+from gan_mpc_amd.engine import TRAJAX_CEM_KWARGS, TRAJAX_iLQR_KWARGS, Engine
 from gan_mpc_amd.policy import optimizers as opt
 from gan_mpc_amd.policy.device_params import DeviceParams
 
@@ -44,21 +44,27 @@ class LqrBlock:
 
 
 class EvalMPC:
-    SOLVERS = ("rounds", "fused", "box")
+    SOLVERS = ("rounds", "fused", "box", "cem")
 
     def __init__(self, config, cost_model, dynamics_model, expert_model,
-                 trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None):
+                 trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None,
+                 cem_kwargs=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
         limited to control_bounds = (lo, hi), each None, a scalar or one value per control; the training calls
         (loss_and_grad, batch_loss, ilqr_layer) use gmpc_ilqr_solve_box_held and differentiate through the solution's
-        active set held fixed, the action path (get_optimal_values / get_optimal_action) the plain one."""
+        active set held fixed (DESIGN §19), the action path (get_optimal_values / get_optimal_action) the plain one;
+        "cem" -- gmpc_cem_solve, the cross-entropy method under control_bounds with trajax' keywords cem_kwargs (DESIGN
+        §20: MLP dynamics, any horizon; the action path only -- the training calls raise NotImplementedError; the seed
+        advances by one per solve)."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
-        if (solver == "box") != (control_bounds is not None):
-            raise ValueError('control_bounds=(lo, hi) and solver="box" go together: got '
+        if (solver in ("box", "cem")) != (control_bounds is not None):
+            raise ValueError('control_bounds=(lo, hi) and solver="box" / "cem" go together: got '
                              f"solver={solver!r}, control_bounds={control_bounds!r}")
+        if cem_kwargs is not None and solver != "cem":
+            raise ValueError(f'cem_kwargs and solver="cem" go together: got solver={solver!r}')
         if control_bounds is not None and len(control_bounds) != 2:
             raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
@@ -68,6 +74,8 @@ class EvalMPC:
         self.dynamics_model = dynamics_model
         self.expert_model = expert_model
         self.trajax_ilqr_kwargs = dict(trajax_ilqr_kwargs)
+        self.cem_kwargs = dict(TRAJAX_CEM_KWARGS, **(cem_kwargs or {}))
+        self.cem_solves = 0       # solves issued by a "cem" policy: solve k runs under seed + k
         self.critic_model = getattr(self, "critic_model", None)
         self._device = device
         self._engine = None
@@ -186,6 +194,9 @@ class EvalMPC:
             hu = hu[None] if single else hu
         _, sol = self._solve(params, hx, hu)
         B = sol["X"].shape[0]
+        if self.solver == "cem":      # no gradient, adjoints or linearisation; every problem runs max_iter iterations
+            out = (sol["X"], sol["U"], sol["obj"], None, None, None, sol["iterations"])
+            return tuple(o if o is None else o[0] for o in out) if single else out
         lqr = LqrBlock(self._engine, B)
         out = (sol["X"], sol["U"], sol["obj"], sol["grad"], sol["adjoints"], lqr, sol["iterations"])
         if single:

@@ -14,12 +14,43 @@ def _solver(policy, eng, hold=False):
     """The engine entry point of the policy's solver: "rounds" (gmpc_ilqr_solve, host-driven iterations), "fused"
     (gmpc_ilqr_solve_fused, the whole solve in one launch) or "box" (the one-launch solve under the policy's
     control_bounds: gmpc_ilqr_solve_box, or with hold=True gmpc_ilqr_solve_box_held, whose solution the bilevel tail
-    may follow).  "rounds" and "fused" always hold their solution."""
+    may follow).  "rounds" and "fused" always hold their solution; "cem" (gmpc_cem_solve under the same bounds) holds none and refuses
+    hold=True."""
     solver = getattr(policy, "solver", "rounds")
+    if solver == "cem":
+        if hold:
+            refuse_cem(policy, "a solve held for the bilevel tail")
+        return functools.partial(_cem_solve, policy, eng)
     if solver == "box":
         lo, hi = policy.control_bounds
         return functools.partial(_box_solve_held if hold else _box_solve, eng, lo, hi)
     return eng.ilqr_solve_fused if solver == "fused" else eng.ilqr_solve
+
+
+def refuse_cem(policy, what):
+    """The training calls of a "cem" policy: the sampler has no derivative (raised before any device work)."""
+    if getattr(policy, "solver", "rounds") == "cem":
+        raise NotImplementedError(f'solver="cem" has no gradient through the sampler: {what} needs an iLQR solver '
+                                  '("rounds", "fused" or "box")')
+
+
+def _cem_solve(policy, eng, x0, U, goal, kwargs=None):
+    """The policy's CEM solve in the shape of an iLQR solve's dict (no grad / adjoints; iterations = max_iter); kwargs
+    (the iLQR keyword set of the caller) does not apply.  Solve k of the policy runs under seed + k.  The engine's
+    mean is trajax' -- not clipped: a start outside the bounds decays by evolution_smoothing per iteration only, and a
+    mean of controls on a bound may pass it by a rounding -- so the policy, whose controls go to an actuator, clamps
+    the start before the solve and U after it (X and obj are those of the mean: the same up to that rounding)."""
+    del kwargs
+    lo, hi = policy.control_bounds
+    kw = dict(policy.cem_kwargs)
+    kw["seed"] = int(kw["seed"]) + policy.cem_solves
+    policy.cem_solves += 1
+    _, _, lo_t, hi_t = eng._device_bounds(lo, hi)      # (the cached device copies the solve itself uses)
+    clamp = (lambda t: t) if lo_t is None and hi_t is None else (lambda t: torch.clamp(t, min=lo_t, max=hi_t))
+    sol = eng.cem_solve(x0, clamp(U), goal, lo, hi, kw)
+    sol["U"] = clamp(sol["U"])
+    sol["iterations"] = torch.full((x0.shape[0],), int(kw["max_iter"]), dtype=torch.int32, device=x0.device)
+    return sol
 
 
 def _box_solve(eng, lo, hi, x0, U, goal, kwargs=None):
@@ -54,6 +85,7 @@ def bilevel_optimization(policy, dparams, x0, init_U, goal, loss_kind, desired=N
     cotangents (loss_kind is then ignored): a callable (X, U) -> (loss [B], lx (B, T+1, n) or None, lu (B, T, m) or
     None) for the whole batch at once, for a loss that is not a vmap of per-trajectory torch code (BaseMPC.
     batch_cotangents); a None cotangent is passed on as NULL, not as zeros."""
+    refuse_cem(policy, "bilevel_optimization")
     B = x0.shape[0]
     eng = policy.bind(dparams, B)
     sol = _solver(policy, eng, hold=True)(x0, init_U, goal, trajax_ilqr_kwargs or policy.trajax_ilqr_kwargs)

@@ -20,7 +20,7 @@
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
  *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp, gmpc_expert_vjp,
- *    gmpc_critic_vjp and gmpc_critic_dir_vjp drop nothing: they may run between a solve and its bilevel calls, or
+ *    gmpc_critic_vjp, gmpc_critic_dir_vjp and gmpc_cem_solve drop nothing: they may run between a solve and its bilevel calls, or
  *    between a bilevel call and gmpc_bilevel_grad_inputs / _dynamics.
  *
  * Parameter layouts (flat fp32 vectors, flax Dense order: kernel (in,out) row-major, then bias):
@@ -224,6 +224,43 @@ int gmpc_ilqr_solve_box_held(gmpc_ctx* ctx, int B, const float* x0, const float*
  * iterations [2]: the QP iterations and 1 where it stopped at a cap.  Returns 0, or GMPC_EINVAL. */
 int gmpc_box_qp_host(int m, const float* G, const float* h, const float* u, const float* u_lo,
                      const float* u_hi, float* y, int* clamped, int* iterations);
+
+/* The cross-entropy method on the same cost and dynamics (trajax `cem`, the sampling solver beside `ilqr`; DESIGN
+ * §20): control limits by construction, at any horizon, no Jacobian and no Riccati sweep.  Per problem b and
+ * iteration it = iter_offset + i, i < max_iter:
+ *   z[s][t][j] standard normal from Philox4x32-10, key (seed low word, seed high word), counter (e >> 2, s, b, it)
+ *   and output word e & 3 for e = t m + j; words become u = ((r >> 9) 2 + 1) 2^-24 and Box-Muller pairs (u0, u1),
+ *   (u2, u3) give z = sqrt(-2 ln u0) (cos, sin)(2 pi u1);  smoothing along time zt_0 = z_0,
+ *   zt_t = beta zt_{t-1} + sqrt(1 - beta^2) z_t (beta = sampling_smoothing);
+ *   u = clamp(std_tj zt + mean_tj, lo_j, hi_j)  (a NaN stays a NaN);  cost_s = the objective of gmpc_rollout_cost under
+ *   the sample's controls (fp32 sum over t, terminal cost last);  the num_elites smallest by (cost, sample index), a
+ *   NaN cost counting as +inf, give new_mean = sum u / E and new_std = sqrt(sum (u - new_mean)^2 / E) in rank order;
+ *   mean <- gamma mean + (1 - gamma) new_mean, std likewise (gamma = evolution_smoothing).
+ * mean_io / std_io [B][T][m] hold the initial mean and std and receive the final ones (the mean is trajax' U: not
+ * clipped).  u_lo / u_hi: device [m] shared by all problems and steps, either may be NULL (unbounded on that side).
+ * X [B][T+1][n] and obj [B]: the rollout and objective of the final mean (either may be NULL).  costs [B][N],
+ * elites [B][E] (sample indices in rank order) and samples [B][N][T][m]: those of the last iteration, each may be NULL
+ * (nothing of size B N T m exists unless `samples` is passed).  One call with max_iter = K equals K chained calls with
+ * max_iter = 1 and iter_offset = 0 .. K-1, bit for bit; a sample's cost depends on neither N nor B.
+ * Coverage -- anything else fails with GMPC_EINVAL ("cem: ...") before any launch: MLP dynamics
+ * (dyn_lstm_features == 0); every dynamics and cost width <= 256 and n + m <= 256; any T; B <= max_batch;
+ * 1 <= num_elites <= num_samples <= 4096; max_iter >= 0; 0 <= sampling_smoothing < 1 (above 0 the sampler costs
+ * O(T) per control); 0 <= evolution_smoothing <= 1.
+ * 2 max_iter + 1 launches on `stream` (2 max_iter with X and obj both NULL), no host synchronisation, no atomics;
+ * deterministic.  Stateless like gmpc_rollout_vjp: it writes the caller's arrays and the call workspace only (B N
+ * floats when costs is NULL, allocated by the first call that needs more than the ctx holds), touches neither the
+ * ctx's trajectories and masks nor a held solution. */
+typedef struct gmpc_cem_opts {
+  int max_iter, num_samples, num_elites, iter_offset;
+  float sampling_smoothing, evolution_smoothing;
+  unsigned long long seed;
+} gmpc_cem_opts;
+int gmpc_cem_solve(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
+                   const float* u_lo, const float* u_hi,
+                   const gmpc_cem_opts* opts, float* mean_io, float* std_io,
+                   float* X, float* obj,
+                   float* costs, int* elites, float* samples,
+                   void* stream);
 
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
