@@ -97,7 +97,7 @@ static int backward_pass(gmpc_ctx* c, int B, const float* X, const float* U, con
       c->lin_kernel = "k_dynl_jac";
     } else if (!lin_dense && gmpc_launch_linearize_sparse(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks,
                                                           active, AB, 1, 0, s) == 0) {
-      c->lin_kernel = sh.n > 16 ? "k_linearize_sparse (rows 0..15) + k_linearize_regs (rows 16..n-1)"
+      c->lin_kernel = sh.n > 16 ? "k_linearize_sparse (rows 0..15 per sample, rows 16..n-1 per time group)"
                                 : "k_linearize_sparse";
     } else if (gmpc_launch_linearize_regs(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
                                           s) == 0) {

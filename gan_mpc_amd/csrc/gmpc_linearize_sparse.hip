@@ -8,8 +8,17 @@
 //
 // One wave per sample, rows 0..15 of its Jacobian on v_mfma_f32_16x16x4_f32: A = W_l^T (16 output units x 4
 // contracted units), B = S (4 contracted units x 16 Jacobian rows), the 4 contracted units of a k-step are four
-// consecutive entries of the sample's active list.  Rows 16..n-1 (n = 17: one row) stay on k_linearize_regs, which
-// takes a row window for them.
+// consecutive entries of the sample's active list.
+//  - rows 16..n-1 (n = 17: one row): group jobs of the same kernel body.  A wave owns a contiguous chunk of samples,
+//    and the relu masks of consecutive time steps of a trajectory differ in a few units only (about 5 of 200), so
+//    every column of a group job's tiles is row r of ANOTHER sample, up to 16 consecutive ones, and the list of a
+//    layer is the union of their active sets (about 115 units for 12 - 13 steps).  A column whose sample has unit u
+//    inactive must hold an exact +0 there: its extra terms are then fma(w, 0, c) == c, a subset of the zero terms the
+//    dense chain adds anyway.  The kernel computes all 200 outputs of a layer and a union list READS what the
+//    one-sample list skipped, so the hand-over selects mask(column's sample, unit) ? acc : +0 (keep_if: once per
+//    accumulator element and layer, nothing in the k-loop), and the seed is written into the S tile the same way.
+//    A strided sample set (samp_mul, samp_add: no caller today) has no consecutive samples: it keeps the strided
+//    split and sends rows 16..n-1 to k_linearize_regs, which takes a row window for them.
 //  - active lists: built per layer from the relu words with mbcnt (a prefix count, no scan), stored as 32-bit unit
 //    indices in the wave's LDS (no 16-bit extensions on the vector port) and padded with unit 200 -- a zero row of
 //    the padded W^T copies and a zero column of the S tile -- so the padded k-steps and the loads that run ahead of
@@ -33,6 +42,7 @@
 //    are read back at the list entries (four distinct units per read, no bank conflict inside a lane group).
 #include <cstdio>
 #include <type_traits>
+#include <utility>
 
 #include "gmpc_launch.h"
 
@@ -89,10 +99,30 @@ void gmpc_linsparse_prepare(const MlpDesc& dyn, int n, int m, float* p, LinPad* 
   }
 }
 
+// v if bit BIT of w is set, else +0.0f (bit -> all-ones word -> AND, as the seed of k_linearize_regs: written as a
+// select, hipcc builds every lane mask first and selects afterwards)
+template <int BIT>
+__device__ __forceinline__ float keep_if(float v, uint32_t w) {
+  unsigned full, vb = __float_as_uint(v);
+  asm("v_bfe_i32 %1, %2, %3, 1\n\tv_and_b32 %0, %0, %1" : "+v"(vb), "=&v"(full) : "v"(w), "n"(BIT));
+  return __uint_as_float(vb);
+}
+template <int... J>
+__device__ __forceinline__ f32x4 keep_if4(f32x4 v, uint32_t w, std::integer_sequence<int, J...>) {
+  return f32x4{keep_if<J>(v[J & 3], w)...};
+}
+// elements j = 0..3 of v kept where bit B0 + j of w is set
+template <int B0>
+__device__ __forceinline__ f32x4 keep_if4(f32x4 v, uint32_t w) {
+  return keep_if4(v, w, std::integer_sequence<int, B0, B0 + 1, B0 + 2, B0 + 3>{});
+}
+
 // LDS: GMPC_SP_WAVE_BYTES per wave, 65.1 KB per workgroup -- two workgroups (eight waves) per CU
+// grouped: contiguous sample chunks per wave and rows 16..n-1 in group jobs (needs samp_mul == 1, samp_add == 0);
+// otherwise the strided sample split and rows 0..15 only
 __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
     int NSamp, int T, int n, int m, int Lh, LinPad lp, const uint32_t* masks, const int* active, float* AB,
-    int samp_mul, int samp_add) {
+    int samp_mul, int samp_add, int grouped) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, l16 = lane & 15;
@@ -121,21 +151,56 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
   const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(lp.WTP[0]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * 32 * (int)sizeof(float), 0x00020000);
 
-  constexpr int WPB = GMPC_THREADS / 64;
-  for (int s = blockIdx.x * WPB + wave; s < NSamp; s += gridDim.x * WPB) {
-    const size_t sid = (size_t)s * samp_mul + samp_add;
-    if (active != nullptr && active[sid / T] == 0) continue;
+  // One job.  GRP = false: rows 0..15 of sample s, every column of the tiles is that sample.  GRP = true: row jr of
+  // the cnt <= 16 consecutive samples s.., one per column (s + cnt <= NSamp); a column past cnt or of a trajectory
+  // that is not active has an all-zero mask and is not stored.
+  auto job = [&](auto grpc, int s, int jr, int cnt) __attribute__((always_inline)) {
+    constexpr bool GRP = decltype(grpc)::value;
+    bool cvalid = true;                    // GRP: this lane's column is a live sample
+    size_t sid = (size_t)s * samp_mul + samp_add;
+    if constexpr (GRP) {
+      cvalid = l16 < cnt;
+      if (cvalid) sid = (size_t)s + l16;
+      if (cvalid && active != nullptr) cvalid = active[sid / T] != 0;
+      if (__ballot(cvalid) == 0ull) return;
+    } else {
+      if (active != nullptr && active[sid / T] == 0) return;
+    }
     const uint32_t* mrow = masks + sid * Lh * GMPC_MW;
+
+    // relu words 0..6 of hidden layer ml for this lane's column (GRP; word 6 cut to units 192..199)
+    auto colwords = [&](int ml, uint32_t (&w)[7]) {
+#pragma unroll
+      for (int i = 0; i < 7; ++i) w[i] = cvalid ? mrow[ml * GMPC_MW + i] : 0u;
+      w[6] &= 0xFFu;
+    };
+    // wave-uniform relu words of the job's list for layer ml: the sample's, or the union over the 16 columns
+    auto listwords = [&](int ml, uint32_t (&w)[7]) {
+      if constexpr (GRP) {
+        colwords(ml, w);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+#pragma unroll
+          for (int d = 1; d < 16; d <<= 1) w[i] |= (uint32_t)__shfl_xor((int)w[i], d);
+          w[i] = __builtin_amdgcn_readfirstlane(w[i]);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) w[i] = __builtin_amdgcn_readfirstlane(mrow[ml * GMPC_MW + i]);
+      }
+    };
 
     // active list of hidden layer ml: returns its length.  Entries from the length on, as far as the k-steps and the
     // loads that run ahead reach (4 np + 12), point at the zero unit
     auto build = [&](int ml) -> int {
       __builtin_amdgcn_wave_barrier();
+      uint32_t mw[7];
+      listwords(ml, mw);
       int base = 0;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const uint32_t lo = __builtin_amdgcn_readfirstlane(mrow[ml * GMPC_MW + 2 * c]);
-        uint32_t hi = c < 3 ? __builtin_amdgcn_readfirstlane(mrow[ml * GMPC_MW + 2 * c + 1]) : 0u;
+        const uint32_t lo = mw[2 * c];
+        uint32_t hi = c < 3 ? mw[2 * c + 1] : 0u;
         const uint32_t lo_m = c < 3 ? lo : (lo & 0xFFu);     // units 192..199 of word 6
         const uint32_t word = lane < 32 ? lo_m : hi;
         const int pos = base + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo_m, 0u));
@@ -162,6 +227,15 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<float*>(lp.WSP[l]), 0, (GMPC_SP_H + GMPC_LIN_PADROWS) * GMPC_SP_ROW * 4, 0x00020000);
       f32x4 acc[13];
+      // GRP: relu words of the layer this GEMM produces, for this lane's column (used in the hand-over), moved so
+      // that bit 16 hh + j of word nt is unit 32 nt + 16 hh + 4 g + j
+      uint32_t cw[7];
+      if constexpr (GRP) {
+        colwords(l - 1, cw);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) cw[i] >>= 4 * g;
+        cw[6] >>= 4 * (g & 1);
+      }
       struct Ops { float w[13]; float b; unsigned k, kt; };
       Ops r[GMPC_SP_RD];
       auto tables = [&](Ops& o, int p) {
@@ -217,6 +291,17 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       mfma_fence<false>(acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7], acc[8], acc[9], acc[10],
                         acc[11], acc[12]);
       __builtin_amdgcn_wave_barrier();
+      // GRP: the list of the next GEMM is a union, so an output of a unit this column's sample has inactive is read
+      // there: it becomes the exact +0 the dense chain's relu select leaves (both tail partials: 0 + 0)
+      if constexpr (GRP) {
+        acc[0] = keep_if4<0>(acc[0], cw[0]); acc[1] = keep_if4<16>(acc[1], cw[0]);
+        acc[2] = keep_if4<0>(acc[2], cw[1]); acc[3] = keep_if4<16>(acc[3], cw[1]);
+        acc[4] = keep_if4<0>(acc[4], cw[2]); acc[5] = keep_if4<16>(acc[5], cw[2]);
+        acc[6] = keep_if4<0>(acc[6], cw[3]); acc[7] = keep_if4<16>(acc[7], cw[3]);
+        acc[8] = keep_if4<0>(acc[8], cw[4]); acc[9] = keep_if4<16>(acc[9], cw[4]);
+        acc[10] = keep_if4<0>(acc[10], cw[5]); acc[11] = keep_if4<16>(acc[11], cw[5]);
+        acc[12] = keep_if4<0>(acc[12], cw[6]);
+      }
       // accumulator rows 4 g + j of tile 2 nt + hh = units 32 nt + 16 hh + 4 g + j, column = this lane's row
       float* srow = st + l16 * GMPC_SP_STR;
 #pragma unroll
@@ -232,8 +317,41 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       }
       __builtin_amdgcn_wave_barrier();
     };
-    layer(Lh - 1, std::true_type{});
-    for (int l = Lh - 2; l >= 1; --l) layer(l, std::false_type{});
+    if constexpr (GRP) {
+      // seed through the S tile: S[column][u] = W_L[u][jr] where the column's sample has unit u of layer Lh-1 active,
+      // else +0; the first GEMM then reads it over the union list like every other
+      __builtin_amdgcn_wave_barrier();
+      float* srow = st + l16 * GMPC_SP_STR + 4 * g;
+      const uint32_t* mcol = mrow + (Lh - 1) * GMPC_MW;
+      const int wo = (4 * g * n + jr) * 4;                 // W_L[4 g][jr], bytes
+      // units 32 nt + 16 hh + 4 g + j: bit 16 hh + j of word nt moved down by 4 g (a rolled loop: unrolled, the 50
+      // loads and their addresses are all live at once)
+#pragma unroll 1
+      for (int nt = 0; nt < 6; ++nt) {
+        const uint32_t cw = (cvalid ? mcol[nt] : 0u) >> (4 * g);
+        f32x4 v0, v1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          v0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, wo + (32 * nt + j) * n * 4, 0, 0));
+          v1[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, wo + (32 * nt + 16 + j) * n * 4, 0, 0));
+        }
+        *reinterpret_cast<f32x4*>(srow + 32 * nt) = keep_if4<0>(v0, cw);
+        *reinterpret_cast<f32x4*>(srow + 32 * nt + 16) = keep_if4<16>(v1, cw);
+      }
+      if (g < 2) {                                         // units 192..199
+        const uint32_t cw = (cvalid ? mcol[6] & 0xFFu : 0u) >> (4 * g);
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsl, wo + (192 + j) * n * 4, 0, 0));
+        *reinterpret_cast<f32x4*>(srow + 192) = keep_if4<0>(v, cw);
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (int l = Lh - 1; l >= 1; --l) layer(l, std::false_type{});
+    } else {
+      layer(Lh - 1, std::true_type{});
+      for (int l = Lh - 2; l >= 1; --l) layer(l, std::false_type{});
+    }
 
     // ---- input GEMM  out = W_1 S_1 over the active units of S_1: coordinates 16 t + l16 of W_1^T's 32-wide rows
     {
@@ -268,17 +386,42 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
       if (p < np) step(p, r[0], r[2]);
       if (p + 1 < np) step(p + 1, r[1], r[0]);
       mfma_fence<false>(acc0, acc1);
-      if (l16 < nrow) {
-        float* dst = AB + ((size_t)s * n + l16) * nm;
+      // this lane's column: Jacobian row l16 of sample s, or row jr of sample s + l16
+      const int orow = GRP ? jr : l16;
+      if (GRP ? cvalid : l16 < nrow) {
+        float* dst = AB + ((size_t)(GRP ? s + l16 : s) * n + orow) * nm;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int c = 4 * g + j;
-          if (c < nm) dst[c] = acc0[j] + (c == l16 ? 1.0f : 0.0f);
-          if (two && c + 16 < nm) dst[c + 16] = acc1[j] + (c + 16 == l16 ? 1.0f : 0.0f);
+          if (c < nm) dst[c] = acc0[j] + (c == orow ? 1.0f : 0.0f);
+          if (two && c + 16 < nm) dst[c + 16] = acc1[j] + (c + 16 == orow ? 1.0f : 0.0f);
         }
       }
     }
     __builtin_amdgcn_wave_barrier();
+  };
+
+  constexpr int WPB = GMPC_THREADS / 64;
+  const int w = blockIdx.x * WPB + wave, W = gridDim.x * WPB;
+  if (!grouped) {
+    for (int s = w; s < NSamp; s += W) job(std::false_type{}, s, 0, 0);
+    return;
+  }
+  // wave w: samples [c0, c1), a contiguous chunk of C (the last ones shorter or empty), so that consecutive time
+  // steps of a trajectory -- whose relu masks differ in a few units only -- share the tiles of a group job
+  const int C = (NSamp + W - 1) / W;
+  const long c0l = (long)w * C;
+  const int c0 = c0l < NSamp ? (int)c0l : NSamp;
+  const int len = NSamp - c0 < C ? NSamp - c0 : C;
+  for (int s = c0; s < c0 + len; ++s) job(std::false_type{}, s, 0, 0);
+  // rows 16..n-1: the chunk cut into near-equal groups of at most 16 consecutive samples
+  if (n > 16 && len > 0) {
+    const int ng = (len + 15) >> 4;
+    for (int r = 16; r < n; ++r)
+      for (int i = 0; i < ng; ++i) {
+        const int a = i * len / ng, b = (i + 1) * len / ng;
+        job(std::true_type{}, c0 + a, r, b - a);
+      }
   }
 }
 
@@ -288,14 +431,16 @@ int gmpc_launch_linearize_sparse(int NSamp, int T, int n, int m, const MlpDesc& 
   const int Lh = dyn.L - 1;
   if (!sparse_form(dyn.L, dyn.dims, n, m) || lp.NT != 7 || lp.NTF != 1 || lp.NGF != 1) return -1;
   if (NSamp <= 0) return 0;
-  // rows 16..n-1 first (any error leaves nothing launched)
-  if (n > 16 && gmpc_launch_linearize_regs_rows(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, 16,
-                                                s) != 0)
+  // rows 16..n-1 run inside the kernel as group jobs over consecutive samples; a strided sample set has none, its
+  // rows 16..n-1 go to the dense chain's row window first (any error leaves nothing launched)
+  const int grouped = samp_mul == 1 && samp_add == 0;
+  if (n > 16 && !grouped &&
+      gmpc_launch_linearize_regs_rows(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, 16, s) != 0)
     return -1;
   const size_t lds = (size_t)(GMPC_THREADS / 64) * GMPC_SP_WAVE_BYTES;
   int grid = (NSamp + 3) / 4;
   if (grid > 256 * 2) grid = 256 * 2;      // persistent: two workgroups per CU
   hipLaunchKernelGGL(k_linearize_sparse, dim3(grid), dim3(GMPC_THREADS), lds, s, NSamp, T, n, m, Lh, lp, masks,
-                     active, AB, samp_mul, samp_add);
+                     active, AB, samp_mul, samp_add, grouped);
   return 0;
 }
