@@ -64,6 +64,14 @@ class CemOpts(C.Structure):
     ]
 
 
+class MppiOpts(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int), ("num_samples", C.c_int), ("iter_offset", C.c_int),
+        ("sampling_smoothing", C.c_float), ("evolution_smoothing", C.c_float), ("temperature", C.c_float),
+        ("seed", C.c_ulonglong),
+    ]
+
+
 _P = C.c_void_p
 
 
@@ -115,6 +123,10 @@ SIGNATURES = {
     "gmpc_ilqr_solve_box_held": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(IlqrOpts), _P, _P, _P, _P, _P,
                                            _P, _P, _P, _P]),
     "gmpc_cem_solve": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(CemOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gmpc_mppi_solve": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(MppiOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  _P]),
+    "gmpc_mppi_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(MppiOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                _P, _P, _P, _P, _P]),
     "gmpc_box_qp_host": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_bilevel_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),

@@ -161,20 +161,11 @@ extern "C" int gmpc_bilevel_grad_dynamics(gmpc_ctx* c, int B, const float* lx, f
   return 0;
 }
 
-// The VJP of the rollout and its costs at (X, U, goal) (gmpc_rollout_vjp.hip).  Stateless: the masks and rows live in
-// the call workspace, no held solution is dropped; the GEMMs' partials use the shared scratch.
-extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float* U, const float* goal, const float* gX,
-                                const float* gcost, float* grad_x0, float* grad_U, float* grad_goal,
-                                float* grad_theta_sum, float* grad_dyn_sum, void* stream) {
-  TRY(check_call(c, B));
+// The launches of gmpc_rollout_vjp for B <= max_batch checked rows (gmpc_mppi_vjp runs them on its sample rows too)
+static int rollout_vjp_rows(gmpc_ctx* c, int B, const float* X, const float* U, const float* goal, const float* gX,
+                            const float* gcost, float* grad_x0, float* grad_U, float* grad_goal,
+                            float* grad_theta_sum, float* grad_dyn_sum, hipStream_t s) {
   const gmpc_shape& sh = c->sh;
-  if (c->dynl)
-    return fail(GMPC_EINVAL, "rollout vjp: relu-MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
-  if (!X || !U || !goal) return fail(GMPC_EINVAL, "rollout vjp: X, U and goal must not be null");
-  if (!gX && !gcost) return fail(GMPC_EINVAL, "rollout vjp: gX and gcost are both null: no cotangent");
-  if (!grad_x0 && !grad_U && !grad_goal && !grad_theta_sum && !grad_dyn_sum)
-    return fail(GMPC_EINVAL, "rollout vjp: every output is null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const int n = sh.n, m = sh.m, T = sh.T, Lh = sh.dyn_layers - 1;
   const size_t steps = (size_t)B * T;
   const bool want_theta = grad_theta_sum != nullptr && gcost != nullptr;
@@ -213,6 +204,121 @@ extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float*
   if (grad_dyn_sum)
     gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, k.acts.p, k.dels.p, c->drows,
                           grad_dyn_sum, c->wpart, c->wpart_floats, s);
+  return 0;
+}
+
+// The VJP of the rollout and its costs at (X, U, goal) (gmpc_rollout_vjp.hip).  Stateless: the masks and rows live in
+// the call workspace, no held solution is dropped; the GEMMs' partials use the shared scratch.
+extern "C" int gmpc_rollout_vjp(gmpc_ctx* c, int B, const float* X, const float* U, const float* goal, const float* gX,
+                                const float* gcost, float* grad_x0, float* grad_U, float* grad_goal,
+                                float* grad_theta_sum, float* grad_dyn_sum, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl)
+    return fail(GMPC_EINVAL, "rollout vjp: relu-MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
+  if (!X || !U || !goal) return fail(GMPC_EINVAL, "rollout vjp: X, U and goal must not be null");
+  if (!gX && !gcost) return fail(GMPC_EINVAL, "rollout vjp: gX and gcost are both null: no cotangent");
+  if (!grad_x0 && !grad_U && !grad_goal && !grad_theta_sum && !grad_dyn_sum)
+    return fail(GMPC_EINVAL, "rollout vjp: every output is null");
+  TRY(rollout_vjp_rows(c, B, X, U, goal, gX, gcost, grad_x0, grad_U, grad_goal, grad_theta_sum, grad_dyn_sum,
+                       static_cast<hipStream_t>(stream)));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The VJP of gmpc_mppi_solve: the adjoint of the weighted-mean recursion, last iteration first.  Per
+// iteration and chunk of floor(max_batch / N) problems: k_mppi_cotangent lays the samples out as rows, the rollout
+// kernel gives their states, rollout_vjp_rows the heavy VJP under one cost cotangent per sample, k_mppi_reduce the
+// masked sums.  The rollout writes the ctx's masks and objectives: a held solution is dropped.
+extern "C" int gmpc_mppi_vjp(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
+                             const float* u_hi, const gmpc_mppi_opts* o, const float* std, const float* means_trace,
+                             const float* costs_trace, const float* U, const float* X, const float* gU,
+                             const float* gX, const float* gobj, float* grad_x0, float* grad_Uinit, float* grad_goal,
+                             float* grad_theta_sum, float* grad_dyn_sum, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  TRY(gmpc_sampled_coverage(c, "mppi"));
+  TRY(gmpc_mppi_check_opts(o));
+  if (!x0 || !goal || !std || !U || !X) return fail(GMPC_EINVAL, "mppi: x0, goal, std, U and X must not be null");
+  if (o->max_iter > 0 && (!means_trace || !costs_trace))
+    return fail(GMPC_EINVAL, "mppi: the vjp needs means_trace and costs_trace of the forward call");
+  if (!gU && !gX && !gobj) return fail(GMPC_EINVAL, "mppi: gU, gX and gobj are all null: no cotangent");
+  if (!grad_x0 && !grad_Uinit && !grad_goal && !grad_theta_sum && !grad_dyn_sum)
+    return fail(GMPC_EINVAL, "mppi: every output is null");
+  const int N = o->num_samples;
+  if (N > c->maxB)
+    return fail(GMPC_EINVAL, "mppi: num_samples = %d above max_batch = %d (the vjp's rows are samples)", N, c->maxB);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = sh.n, m = sh.m, T = sh.T, K = o->max_iter;
+  const int chunk = c->maxB / N < B ? c->maxB / N : B;     // problems per chunk
+  const size_t R = (size_t)chunk * N, Tm = (size_t)T * m, Tn = (size_t)(T + 1) * n;
+  const size_t ntheta = 3 + (size_t)mlp_count(sh.cost_layers, sh.cost_dims);
+  const size_t ndyn = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims);
+  // the call's workspace, behind what rollout_vjp_rows reserves for itself
+  const size_t sizes[] = {R * Tm, R * Tn, R * Tn, R * n, R * (T + 1), R * Tm, R * n, R * Tn, R, chunk * Tm,
+                          ntheta, ndyn, B * Tm, (size_t)B * (T + 1)};
+  size_t total = 0;
+  for (size_t v : sizes) total += (v + 3) & ~(size_t)3;
+  TRY(c->cw.save.grow(c, total));
+  float* wp[sizeof(sizes) / sizeof(sizes[0])];
+  {
+    float* p = c->cw.save.p;
+    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) { wp[i] = p; p += (sizes[i] + 3) & ~(size_t)3; }
+  }
+  float *Us = wp[0], *Xr = wp[1], *goalr = wp[2], *x0r = wp[3], *gc = wp[4], *GU = wp[5], *Gx0 = wp[6],
+        *Ggoal = wp[7], *wn = wp[8], *nm = wp[9], *th_tmp = wp[10], *dyn_tmp = wp[11], *gbuf = wp[12], *gcB = wp[13];
+  float* g = grad_Uinit ? grad_Uinit : gbuf;
+  c->solB = 0;     // the sample rollouts overwrite the ctx's relu masks and objectives: any held solution is gone
+  c->gradB = 0;
+  if (grad_theta_sum) HIP_TRY(hipMemsetAsync(grad_theta_sum, 0, ntheta * sizeof(float), s));
+  if (grad_dyn_sum) HIP_TRY(hipMemsetAsync(grad_dyn_sum, 0, ndyn * sizeof(float), s));
+  // ---- the final mean's rollout under gX and gobj (broadcast over the T + 1 costs)
+  if (gX || gobj) {
+    if (gobj) gmpc_launch_mppi_bcast(B, T + 1, gobj, gcB, s);
+    TRY(rollout_vjp_rows(c, B, X, U, goal, gX, gobj ? gcB : nullptr, grad_x0, g, grad_goal,
+                         grad_theta_sum ? th_tmp : nullptr, grad_dyn_sum ? dyn_tmp : nullptr, s));
+    if (gU) gmpc_launch_mppi_add((long)(B * Tm), gU, g, s);
+    if (grad_theta_sum) gmpc_launch_mppi_add((long)ntheta, th_tmp, grad_theta_sum, s);
+    if (grad_dyn_sum) gmpc_launch_mppi_add((long)ndyn, dyn_tmp, grad_dyn_sum, s);
+  } else {
+    HIP_TRY(hipMemcpyAsync(g, gU, B * Tm * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (grad_x0) HIP_TRY(hipMemsetAsync(grad_x0, 0, (size_t)B * n * sizeof(float), s));
+    if (grad_goal) HIP_TRY(hipMemsetAsync(grad_goal, 0, B * Tn * sizeof(float), s));
+  }
+  // ---- the iterations, last first
+  MppiCotArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.N = N; ca.T = T; ca.n = n; ca.m = m;
+  ca.sd = std; ca.lo = u_lo; ca.hi = u_hi; ca.g = g; ca.x0 = x0; ca.goal = goal;
+  ca.gamma = o->evolution_smoothing; ca.lam = o->temperature;
+  ca.Us = Us; ca.gc = gc; ca.x0r = x0r; ca.goalr = goalr; ca.wn = wn; ca.nm = nm;
+  MppiRedArgs ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.N = N; ra.T = T; ra.n = n; ra.m = m;
+  ra.lo = u_lo; ra.hi = u_hi; ra.wn = wn; ra.Us = Us; ra.GU = GU; ra.Gx0 = Gx0; ra.Ggoal = Ggoal;
+  ra.gamma = o->evolution_smoothing; ra.g = g; ra.gx0 = grad_x0; ra.ggoal = grad_goal;
+  TrajArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.n = n; ta.m = m; ta.T = T; ta.dyn = c->dyn; ta.cost = c->cost; ta.mpc_w = c->mpc_w;
+  ta.goal = goalr; ta.x0 = x0r; ta.U = Us; ta.X = Xr; ta.obj = c->obj; ta.masks = c->masks;
+  for (int k = K - 1; k >= 0; --k) {
+    ca.rng = gmpc_mppi_rng(o, k);
+    ca.mean = means_trace + (size_t)k * B * Tm;
+    ca.costs = costs_trace + (size_t)k * B * N;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      const int Bc = B - b0 < chunk ? B - b0 : chunk, rows = Bc * N;
+      ca.b0 = ra.b0 = b0; ca.Bc = ra.Bc = Bc;
+      if (gmpc_launch_mppi_cotangent(ca, s)) return fail(GMPC_EINVAL, "mppi: shape not covered");
+      ta.B = rows;
+      gmpc_launch_rollout(ta, s);
+      TRY(rollout_vjp_rows(c, rows, Xr, Us, goalr, nullptr, gc, grad_x0 ? Gx0 : nullptr, GU,
+                           grad_goal ? Ggoal : nullptr, grad_theta_sum ? th_tmp : nullptr,
+                           grad_dyn_sum ? dyn_tmp : nullptr, s));
+      gmpc_launch_mppi_reduce(ra, s);
+      if (grad_theta_sum) gmpc_launch_mppi_add((long)ntheta, th_tmp, grad_theta_sum, s);
+      if (grad_dyn_sum) gmpc_launch_mppi_add((long)ndyn, dyn_tmp, grad_dyn_sum, s);
+    }
+  }
   HIP_TRY(hipGetLastError());
   return 0;
 }

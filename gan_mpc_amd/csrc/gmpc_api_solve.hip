@@ -346,6 +346,18 @@ extern "C" int gmpc_ilqr_solve_box_held(gmpc_ctx* c, int B, const float* x0, con
   return 0;
 }
 
+// The shapes k_cem_rollout covers, for the sampling solvers (`who`: "cem" / "mppi", the message's prefix)
+int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who) {
+  const gmpc_shape& sh = c->sh;
+  if (c->dynl) return fail(GMPC_EINVAL, "%s: MLP dynamics only (dyn_lstm_features = %d)", who, sh.dyn_lstm_features);
+  for (int l = 0; l <= sh.dyn_layers; ++l)
+    if (sh.dyn_dims[l] > 256) return fail(GMPC_EINVAL, "%s: dynamics width %d above 256", who, sh.dyn_dims[l]);
+  for (int l = 0; l <= sh.cost_layers; ++l)
+    if (sh.cost_dims[l] > 256) return fail(GMPC_EINVAL, "%s: cost width %d above 256", who, sh.cost_dims[l]);
+  if (sh.n + sh.m > 256) return fail(GMPC_EINVAL, "%s: n + m = %d above 256", who, sh.n + sh.m);
+  return 0;
+}
+
 // The cross-entropy method: 2 max_iter + 1 launches on the caller's stream, nothing waited for.
 // Stateless: it writes the caller's arrays and the call workspace only, so a held solution survives it.
 extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
@@ -353,12 +365,7 @@ extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* 
                               float* obj, float* costs, int* elites, float* samples, void* stream) {
   TRY(check_call(c, B));
   const gmpc_shape& sh = c->sh;
-  if (c->dynl) return fail(GMPC_EINVAL, "cem: MLP dynamics only (dyn_lstm_features = %d)", sh.dyn_lstm_features);
-  for (int l = 0; l <= sh.dyn_layers; ++l)
-    if (sh.dyn_dims[l] > 256) return fail(GMPC_EINVAL, "cem: dynamics width %d above 256", sh.dyn_dims[l]);
-  for (int l = 0; l <= sh.cost_layers; ++l)
-    if (sh.cost_dims[l] > 256) return fail(GMPC_EINVAL, "cem: cost width %d above 256", sh.cost_dims[l]);
-  if (sh.n + sh.m > 256) return fail(GMPC_EINVAL, "cem: n + m = %d above 256", sh.n + sh.m);
+  TRY(gmpc_sampled_coverage(c, "cem"));
   if (!o) return fail(GMPC_EINVAL, "cem: opts is null");
   if (!x0 || !goal || !mean_io || !std_io) return fail(GMPC_EINVAL, "cem: x0, goal, mean_io and std_io must not be null");
   if (o->num_samples < 1 || o->num_samples > 4096)
@@ -407,6 +414,87 @@ extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* 
     }
     r.N = 1; r.mean_row = 1; r.samples = nullptr; r.costs = obj; r.X = X;
     if (gmpc_launch_cem_rollout(r, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// What gmpc_mppi_solve and gmpc_mppi_vjp refuse in their options
+int gmpc_mppi_check_opts(const gmpc_mppi_opts* o) {
+  if (!o) return fail(GMPC_EINVAL, "mppi: opts is null");
+  if (o->num_samples < 1 || o->num_samples > 4096)
+    return fail(GMPC_EINVAL, "mppi: num_samples = %d outside [1, 4096]", o->num_samples);
+  if (o->max_iter < 0) return fail(GMPC_EINVAL, "mppi: max_iter = %d is negative", o->max_iter);
+  if (!(o->sampling_smoothing >= 0.f && o->sampling_smoothing < 1.f))
+    return fail(GMPC_EINVAL, "mppi: sampling_smoothing = %g outside [0, 1)", (double)o->sampling_smoothing);
+  if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
+    return fail(GMPC_EINVAL, "mppi: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
+  if (!(o->temperature > 0.f) || !(o->temperature < INFINITY))
+    return fail(GMPC_EINVAL, "mppi: temperature = %g is not positive and finite", (double)o->temperature);
+  return 0;
+}
+
+CemRng gmpc_mppi_rng(const gmpc_mppi_opts* o, int i) {
+  CemRng g;
+  g.key0 = (uint32_t)(o->seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(o->seed >> 32);
+  g.it = (uint32_t)(o->iter_offset + i);
+  g.beta = o->sampling_smoothing;
+  g.cbeta = sqrtf(1.f - g.beta * g.beta);
+  return g;
+}
+
+// Model-predictive path integral control: CEM's samples and costs (k_cem_rollout, unchanged), the elite
+// cut replaced by softmax weights.  2 max_iter + 1 launches on the caller's stream, nothing waited for; stateless as
+// gmpc_cem_solve is.
+extern "C" int gmpc_mppi_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
+                               const float* u_hi, const gmpc_mppi_opts* o, float* mean_io, const float* std, float* X,
+                               float* obj, float* costs, float* weights, float* samples, float* means_trace,
+                               float* costs_trace, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  TRY(gmpc_sampled_coverage(c, "mppi"));
+  TRY(gmpc_mppi_check_opts(o));
+  if (!x0 || !goal || !mean_io || !std) return fail(GMPC_EINVAL, "mppi: x0, goal, mean_io and std must not be null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = o->num_samples;
+  const size_t BN = (size_t)B * N, BTm = (size_t)B * sh.T * sh.m;
+  float* cost_buf = costs;
+  if (!cost_buf && !costs_trace && o->max_iter > 0) {
+    TRY(c->cw.aux.grow(c, BN));
+    cost_buf = c->cw.aux.p;
+  }
+  CemRollArgs r;
+  memset(&r, 0, sizeof(r));
+  r.B = B; r.N = N; r.T = sh.T; r.n = sh.n; r.m = sh.m;
+  r.dyn = c->dyn; r.cost = c->cost; r.mpc_w = c->mpc_w;
+  r.x0 = x0; r.goal = goal; r.mean = mean_io; r.sd = std; r.lo = u_lo; r.hi = u_hi;
+  MppiUpdArgs u;
+  memset(&u, 0, sizeof(u));
+  u.B = B; u.N = N; u.T = sh.T; u.m = sh.m;
+  u.lo = u_lo; u.hi = u_hi; u.mean = mean_io; u.sd = std;
+  u.gamma = o->evolution_smoothing; u.lam = o->temperature;
+  for (int i = 0; i < o->max_iter; ++i) {
+    const bool last = i == o->max_iter - 1;
+    r.rng = gmpc_mppi_rng(o, i);
+    r.samples = last ? samples : nullptr;
+    // with a trace the iteration's costs are written where they stay; `costs` gets the last iteration's copy
+    r.costs = costs_trace ? costs_trace + (size_t)i * BN : cost_buf;
+    u.rng = r.rng;
+    u.costs = r.costs;
+    u.costs_copy = last && costs_trace ? costs : nullptr;
+    u.weights = last ? weights : nullptr;
+    u.mean_trace = means_trace ? means_trace + (size_t)i * BTm : nullptr;
+    if (gmpc_launch_cem_rollout(r, s) || gmpc_launch_mppi_update(u, s))
+      return fail(GMPC_EINVAL, "mppi: shape not covered");
+  }
+  if (X || obj) {
+    // the final mean's own rollout: one row per problem, no noise, no clamp
+    if (!obj) {
+      TRY(c->cw.aux2.grow(c, (size_t)B));
+      obj = c->cw.aux2.p;
+    }
+    r.N = 1; r.mean_row = 1; r.samples = nullptr; r.costs = obj; r.X = X;
+    if (gmpc_launch_cem_rollout(r, s)) return fail(GMPC_EINVAL, "mppi: shape not covered");
   }
   HIP_TRY(hipGetLastError());
   return 0;

@@ -200,6 +200,11 @@ static void bind_expert(ExpertNet& e, int nx, int m, const gmpc_expert_shape* es
 
 // gmpc_api.hip: argument and state checks every entry point starts with
 int check_call(gmpc_ctx* c, int B, bool need_params = true);
+// gmpc_api_solve.hip: the sampling solvers' shared checks (`who`: the message's prefix) and MPPI's noise stream of
+// iteration iter_offset + i
+int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who);
+int gmpc_mppi_check_opts(const gmpc_mppi_opts* o);
+CemRng gmpc_mppi_rng(const gmpc_mppi_opts* o, int i);
 // gmpc_api_critic.hip: the upper-level loss at the solution held by the ctx (and, with want_lx, its gradient in c->lx)
 int upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired, const float* critic, float* loss, bool want_lx,
                hipStream_t s);

@@ -246,6 +246,44 @@ struct CemUpdArgs {
 int gmpc_launch_cem_rollout(const CemRollArgs& a, hipStream_t s);
 int gmpc_launch_cem_update(const CemUpdArgs& a, hipStream_t s);
 
+// gmpc_mppi.hip: the path-integral update on k_cem_rollout's costs, and its adjoint ------------------
+// k_mppi_update: w_s = exp(-(costs_s - min) / lam) over the finite costs [B][N], mean <- gamma mean + (1 - gamma)
+// sum_s w_s u_s / sum_s w_s in place; sd is read only.  weights [B][N] (normalised), mean_trace [B][T][m] (the mean
+// before the update) and costs_copy [B][N] may be null.
+struct MppiUpdArgs {
+  int B, N, T, m;
+  const float *costs, *lo, *hi, *sd;
+  float* mean;
+  CemRng rng;
+  float gamma, lam;
+  float *weights, *mean_trace, *costs_copy;
+  int stage;     // set by the launcher: samples per staged block of products (0: one element per thread)
+};
+// k_mppi_cotangent: problems b0 .. b0 + Bc - 1, row r = (b - b0) N + s of the chunk workspace.  mean / sd / g
+// [B][T][m], costs [B][N], x0 [B][n], goal [B][T+1][n] are indexed by b; Us [R][T][m], gc [R][T+1], x0r [R][n],
+// goalr [R][T+1][n], wn [R] (the normalised weights) and nm [Bc][T][m] (new_mean) by the chunk's rows.
+struct MppiCotArgs {
+  int b0, Bc, N, T, n, m;
+  const float *mean, *sd, *costs, *lo, *hi, *g, *x0, *goal;
+  CemRng rng;
+  float gamma, lam;
+  float *Us, *gc, *x0r, *goalr, *wn, *nm;
+};
+// k_mppi_reduce: g [B][T][m] <- gamma g + sum_s [lo < u_s < hi] ((1 - gamma) wn_s g + GU_s); gx0 [B][n] and ggoal
+// [B][T+1][n] (each may be null) += the sums of the rows Gx0 / Ggoal; all in sample order
+struct MppiRedArgs {
+  int b0, Bc, N, T, n, m;
+  const float *lo, *hi, *wn, *Us, *GU, *Gx0, *Ggoal;
+  float gamma;
+  float *g, *gx0, *ggoal;
+};
+// N <= 4096 and lam > 0: non-zero (nothing launched) otherwise
+int gmpc_launch_mppi_update(const MppiUpdArgs& a, hipStream_t s);
+int gmpc_launch_mppi_cotangent(const MppiCotArgs& a, hipStream_t s);
+void gmpc_launch_mppi_reduce(const MppiRedArgs& a, hipStream_t s);
+void gmpc_launch_mppi_add(long count, const float* v, float* out, hipStream_t s);                // out[i] += v[i]
+void gmpc_launch_mppi_bcast(int rows, int cols, const float* v, float* out, hipStream_t s);     // out[r][c] = v[r]
+
 // gmpc_rollout_vjp.hip ------------------------------------------------------------------------------------------------
 // masks: [B][T][Lh][GMPC_MW] relu bits at (X_t, U_t).  Null outputs are skipped; cacts / cdels (B rows in the cost
 // MLP's layout cr) and gm go together; dels: B T rows in the dynamics MLP's layout dr.

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CemOpts, IlqrOpts, Shape
+from ._lib import CemOpts, IlqrOpts, MppiOpts, Shape
 
 # trajax iLQR keywords exactly as the reference passes them (policy/eval.py:10-20)
 TRAJAX_iLQR_KWARGS = {
@@ -32,6 +32,16 @@ TRAJAX_CEM_KWARGS = {
     "evolution_smoothing": 0.1,
     "elite_portion": 0.1,
     "max_iter": 10,
+    "num_samples": 400,
+    "seed": 0,
+}
+
+# the path-integral solver's keywords: TRAJAX_CEM_KWARGS without the elites, plus the softmax temperature
+MPPI_KWARGS = {
+    "sampling_smoothing": 0.0,
+    "evolution_smoothing": 0.0,
+    "temperature": 1.0,
+    "max_iter": 5,
     "num_samples": 400,
     "seed": 0,
 }
@@ -101,6 +111,23 @@ def make_cem_opts(kwargs=None, iter_offset=0):
     o.iter_offset = int(iter_offset)
     o.sampling_smoothing = float(kw["sampling_smoothing"])
     o.evolution_smoothing = float(kw["evolution_smoothing"])
+    o.seed = int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF
+    return o
+
+
+def make_mppi_opts(kwargs=None, iter_offset=0):
+    """gmpc_mppi_opts from MPPI_KWARGS' keyword set."""
+    kw = dict(MPPI_KWARGS)
+    if kwargs:
+        unknown = set(kwargs) - set(kw)
+        if unknown:
+            raise _lib.GmpcError(f"mppi: unknown keyword(s) {sorted(unknown)}")
+        kw.update(kwargs)
+    o = MppiOpts()
+    o.max_iter, o.num_samples, o.iter_offset = int(kw["max_iter"]), int(kw["num_samples"]), int(iter_offset)
+    o.sampling_smoothing = float(kw["sampling_smoothing"])
+    o.evolution_smoothing = float(kw["evolution_smoothing"])
+    o.temperature = float(kw["temperature"])
     o.seed = int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF
     return o
 
@@ -284,17 +311,8 @@ class Engine:
         if unknown:
             raise _lib.GmpcError(f"cem: want has unknown entries {sorted(unknown)}; known: {self.CEM_WANT}")
         opts = make_cem_opts(kwargs, iter_offset)
-        lo, hi = self._bound_vector("u_lo", u_lo), self._bound_vector("u_hi", u_hi)
-        if init_std is None and (lo is None or hi is None or not (np.isfinite(lo).all() and np.isfinite(hi).all())):
-            raise _lib.GmpcError("cem: without init_std both bounds must be finite (std = (u_hi - u_lo) / 2)")
         lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
-        if init_std is None:
-            std = self.to_dev(np.broadcast_to((hi - lo) / np.float32(2), (B, T, m)))
-        elif torch.is_tensor(init_std) and tuple(init_std.shape) == (B, T, m):
-            std = self.to_dev(init_std).clone()
-        else:
-            v = self._bound_vector("init_std", init_std)
-            std = self.to_dev(np.broadcast_to(v, (B, T, m)))
+        std = self._sampling_std("cem", B, init_std, lo, hi)
         N, E = opts.num_samples, opts.num_elites
         out = dict(X=self.new(B, T + 1, n), U=U_init.clone(), obj=self.new(B), std=std)
         if "costs" in want:
@@ -306,6 +324,86 @@ class Engine:
         _lib.check(self.lib.gmpc_cem_solve(
             self.ctx, B, _ptr(x0), _ptr(goal), _ptr(lo_d), _ptr(hi_d), C.byref(opts), _ptr(out["U"]), _ptr(out["std"]),
             _ptr(out["X"]), _ptr(out["obj"]), _ptr(out.get("costs")), _ptr(out.get("elites")), _ptr(out.get("samples")),
+            self._stream()))
+        return out
+
+    MPPI_WANT = ("costs", "weights", "samples")
+
+    def _sampling_std(self, who, B, init_std, lo, hi):
+        """The (B, T, m) device std of a sampling solver: cem_solve's rules for init_std."""
+        T, m = self.T, self.m
+        if init_std is None and (lo is None or hi is None or not (np.isfinite(lo).all() and np.isfinite(hi).all())):
+            raise _lib.GmpcError(f"{who}: without init_std both bounds must be finite (std = (u_hi - u_lo) / 2)")
+        if init_std is None:
+            return self.to_dev(np.broadcast_to((hi - lo) / np.float32(2), (B, T, m)))
+        if torch.is_tensor(init_std) and tuple(init_std.shape) == (B, T, m):
+            return self.to_dev(init_std).clone()
+        return self.to_dev(np.broadcast_to(self._bound_vector("init_std", init_std), (B, T, m)))
+
+    def mppi_solve(self, x0, U_init, goal, u_lo, u_hi, kwargs=None, init_std=None, want=(), iter_offset=0,
+                   trace=False):
+        """Model-predictive path integral control from the mean U_init under u_lo <= u <= u_hi (gmpc_mppi_solve;
+        keywords MPPI_KWARGS): cem_solve's samples and costs, softmax weights exp(-(J - J_min) / temperature) instead
+        of the elite cut, std fixed.  u_lo, u_hi, init_std as for cem_solve.  -> dict(X, U (the final mean, not
+        clipped), obj, std) plus the last iteration's `want`ed debug outputs: "costs" (B, N), "weights" (B, N,
+        normalised), "samples" (B, N, T, m); trace: also means_trace (K, B, T, m), the mean before each iteration,
+        and costs_trace (K, B, N), what mppi_vjp needs.  Stateless: a held iLQR solution stays valid; nothing is
+        synchronised."""
+        B, n, m, T = x0.shape[0], self.n, self.m, self.T
+        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
+            if tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"mppi: {name} must be {shape}, got {tuple(t.shape)}")
+        unknown = set(want) - set(self.MPPI_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"mppi: want has unknown entries {sorted(unknown)}; known: {self.MPPI_WANT}")
+        opts = make_mppi_opts(kwargs, iter_offset)
+        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+        std = self._sampling_std("mppi", B, init_std, lo, hi)
+        N, K = opts.num_samples, max(opts.max_iter, 0)
+        out = dict(X=self.new(B, T + 1, n), U=U_init.clone(), obj=self.new(B), std=std)
+        if "costs" in want:
+            out["costs"] = self.new(B, max(N, 0))
+        if "weights" in want:
+            out["weights"] = self.new(B, max(N, 0))
+        if "samples" in want:
+            out["samples"] = self.new(B, max(N, 0), T, m)
+        if trace:
+            out["means_trace"] = self.new(K, B, T, m)
+            out["costs_trace"] = self.new(K, B, max(N, 0))
+        _lib.check(self.lib.gmpc_mppi_solve(
+            self.ctx, B, _ptr(x0), _ptr(goal), _ptr(lo_d), _ptr(hi_d), C.byref(opts), _ptr(out["U"]), _ptr(std),
+            _ptr(out["X"]), _ptr(out["obj"]), _ptr(out.get("costs")), _ptr(out.get("weights")),
+            _ptr(out.get("samples")), _ptr(out.get("means_trace")), _ptr(out.get("costs_trace")), self._stream()))
+        return out
+
+    def mppi_vjp(self, x0, goal, u_lo, u_hi, sol, gU=None, gX=None, gobj=None, kwargs=None, iter_offset=0,
+                 want_x0=True, want_U=True, want_goal=True, want_theta=True, want_dyn=True):
+        """The VJP of mppi_solve (gmpc_mppi_vjp): sol is the dict of a mppi_solve(..., trace=True) with the same x0,
+        goal, bounds, kwargs and iter_offset; gU (B, T, m), gX (B, T+1, n), gobj (B,) the cotangents of its U, X and
+        obj (any may be None, not all).  -> dict(x0 (B, n), U (B, T, m) w.r.t. U_init, goal (B, T+1, n), theta
+        [3 + cost_count], dyn [dyn_count]), None where not wanted; theta and dyn are summed over the batch.  The true
+        derivative through the sampler.  It drops a solution held by this engine (solve_count advances)."""
+        B, n, m, T = x0.shape[0], self.n, self.m, self.T
+        for name, t, shape in (("x0", x0, (B, n)), ("goal", goal, (B, T + 1, self.nx)), ("U", sol["U"], (B, T, m)),
+                               ("X", sol["X"], (B, T + 1, n)), ("std", sol["std"], (B, T, m)),
+                               ("gU", gU, (B, T, m)), ("gX", gX, (B, T + 1, n)), ("gobj", gobj, (B,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"mppi_vjp: {name} must be {shape}, got {tuple(t.shape)}")
+        opts = make_mppi_opts(kwargs, iter_offset)
+        K, N = max(opts.max_iter, 0), opts.num_samples
+        for name, shape in (("means_trace", (K, B, T, m)), ("costs_trace", (K, B, N))):
+            if name not in sol or tuple(sol[name].shape) != shape:
+                raise _lib.GmpcError(f"mppi_vjp: sol[{name!r}] must be {shape}: solve with trace=True and these kwargs")
+        _, _, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+        out = dict(x0=self.new(B, n) if want_x0 else None, U=self.new(B, T, m) if want_U else None,
+                   goal=self.new(B, T + 1, self.nx) if want_goal else None,
+                   theta=self.new(3 + self.cost_count) if want_theta else None,
+                   dyn=self.new(self.dyn_count) if want_dyn else None)
+        self.solve_count += 1     # the sample rollouts overwrite the ctx's masks: a held solution is gone
+        _lib.check(self.lib.gmpc_mppi_vjp(
+            self.ctx, B, _ptr(x0), _ptr(goal), _ptr(lo_d), _ptr(hi_d), C.byref(opts), _ptr(sol["std"]),
+            _ptr(sol["means_trace"]), _ptr(sol["costs_trace"]), _ptr(sol["U"]), _ptr(sol["X"]), _ptr(gU), _ptr(gX),
+            _ptr(gobj), _ptr(out["x0"]), _ptr(out["U"]), _ptr(out["goal"]), _ptr(out["theta"]), _ptr(out["dyn"]),
             self._stream()))
         return out
 

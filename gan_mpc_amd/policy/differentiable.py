@@ -45,13 +45,19 @@ The layer is differentiable twice in xseq: torch.autograd.grad(score.sum(), xseq
 gradient with a graph behind it, whose backward is one call of gmpc_critic_dir_vjp -- what a
 gradient penalty on the critic needs (gan_policy.gradient_penalty).  The parameter gradient is not differentiable again
 (NotImplementedError), third derivatives are refused, and critics with x_size + lstm_features > 256 are refused by the
-second backward.  Without create_graph the layer runs the same calls as before."""
+second backward.  Without create_graph the layer runs the same calls as before.
+
+X, U, obj = mppi_layer(policy, params, x0, goal, init_U, control_bounds, ...) is the path-integral solve
+(gmpc_mppi_solve) as a differentiable torch op: backward is one call of gmpc_mppi_vjp, the true
+derivative through the sampler w.r.t. x0, goal, init_U and the mpc_weights / cost_params (and, asked for,
+dynamics_params) ranges of params.flat.  It is the way to train through a control-limited controller at any horizon;
+it runs on the second engine, as rollout_layer does."""
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from gan_mpc_amd._lib import GmpcError
-from gan_mpc_amd.engine import Engine
+from gan_mpc_amd.engine import MPPI_KWARGS, Engine
 from gan_mpc_amd.policy import optimizers as opt
 
 _THETA_KEYS = ("mpc_weights", "cost_params")
@@ -190,6 +196,71 @@ def rollout_layer(policy, params, x0, U, goal, dynamics_grad=True):
     dparams = policy.to_device_params(params)
     eng = _rollout_engine(policy, dparams, x0.shape[0])
     return RolloutFunction.apply(eng, dparams, dparams.flat, x0, U, goal, bool(dynamics_grad))
+
+
+MPPI_CHUNK = 16     # problems whose sample rows mppi_layer's engine holds at once
+
+
+class MPPIFunction(torch.autograd.Function):
+    """forward(eng, dparams, bounds, kw, init_std, flat, x0, goal, init_U, dynamics_grad) -> (X, U, obj); eng is bound
+    to dparams.  backward is one gmpc_mppi_vjp call on the traces the forward kept."""
+
+    @staticmethod
+    def forward(ctx, eng, dparams, bounds, kw, init_std, flat, x0, goal, init_U, dynamics_grad):
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+        x32, goal32 = f32(x0), f32(goal)
+        sol = eng.mppi_solve(x32, f32(init_U), goal32, bounds[0], bounds[1], kw, init_std=init_std, trace=True)
+        ctx.eng, ctx.bounds, ctx.kw, ctx.sol = eng, bounds, kw, sol
+        ctx.views = eng._bound
+        ctx.theta = dparams.range_of(_THETA_KEYS)
+        ctx.dyn = dparams.range_of(("dynamics_params",)) if dynamics_grad else None
+        ctx.flat_shape = flat.shape
+        ctx.save_for_backward(x32, goal32)
+        ctx.set_materialize_grads(False)
+        return sol["X"], sol["U"], sol["obj"]
+
+    @staticmethod
+    def backward(ctx, gX, gU, gobj):
+        want_theta, want_x0, want_goal, want_U = ctx.needs_input_grad[5:9]
+        if (gX is None and gU is None and gobj is None) or not (want_theta or want_x0 or want_U or want_goal):
+            return (None,) * 10
+        eng = ctx.eng
+        x0, goal = ctx.saved_tensors
+        if eng._bound is None or any(a.data_ptr() != b.data_ptr() for a, b in zip(eng._bound, ctx.views)):
+            eng.set_params(*ctx.views)      # another layer rebound the engine in between
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        out = eng.mppi_vjp(x0, goal, ctx.bounds[0], ctx.bounds[1], ctx.sol, f32(gU), f32(gX), f32(gobj), ctx.kw,
+                           want_x0=want_x0, want_U=want_U, want_goal=want_goal, want_theta=want_theta,
+                           want_dyn=want_theta and ctx.dyn is not None)
+        gflat = None
+        if want_theta:
+            lo, cnt = ctx.theta
+            gflat = torch.zeros(ctx.flat_shape, dtype=torch.float32, device=x0.device)
+            gflat[lo:lo + cnt] = out["theta"]
+            if ctx.dyn is not None:
+                lo, cnt = ctx.dyn
+                gflat[lo:lo + cnt] = out["dyn"]
+        return None, None, None, None, None, gflat, out["x0"], out["goal"], out["U"], None
+
+
+def mppi_layer(policy, params, x0, goal, init_U, control_bounds, mppi_kwargs=None, init_std=None,
+               dynamics_grad=False):
+    """(X (B, T+1, n), U (B, T, m), obj (B,)) of the path-integral solve from init_U under control_bounds = (lo, hi)
+    (gmpc_mppi_solve; keywords engine.MPPI_KWARGS; init_std as for Engine.mppi_solve), differentiable w.r.t. x0, goal,
+    init_U and the mpc_weights / cost_params ranges of params.flat, and with dynamics_grad=True its dynamics_params
+    range: the true derivative through the sampler (gmpc_mppi_vjp), at any horizon.  U is the
+    solver's mean, not clipped.  It runs on the policy's second engine, so the solution the policy's own engine holds
+    stays usable; that engine is sized for max(B, num_samples * min(B, MPPI_CHUNK)) rows: the backward pass takes the
+    sample rows of floor(rows / num_samples) problems per chunk, and one problem per chunk is launch-bound (DESIGN.md
+    section 21).  params: the policy's DeviceParams (a parameter tree is converted, and then is not differentiable);
+    x0, goal, init_U: device tensors."""
+    dparams = policy.to_device_params(params)
+    kw = dict(mppi_kwargs or {})
+    N = int(kw.get("num_samples", MPPI_KWARGS["num_samples"]))
+    B = x0.shape[0]
+    eng = _rollout_engine(policy, dparams, max(B, N * min(B, MPPI_CHUNK)))
+    return MPPIFunction.apply(eng, dparams, tuple(control_bounds), kw, init_std, dparams.flat, x0, goal, init_U,
+                              bool(dynamics_grad))
 
 
 class ExpertFunction(torch.autograd.Function):

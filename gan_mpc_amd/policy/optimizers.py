@@ -17,10 +17,10 @@ def _solver(policy, eng, hold=False):
     may follow).  "rounds" and "fused" always hold their solution; "cem" (gmpc_cem_solve under the same bounds) holds none and refuses
     hold=True."""
     solver = getattr(policy, "solver", "rounds")
-    if solver == "cem":
+    if solver in ("cem", "mppi"):      # ("mppi": gmpc_mppi_solve, handled like "cem")
         if hold:
             refuse_cem(policy, "a solve held for the bilevel tail")
-        return functools.partial(_cem_solve, policy, eng)
+        return functools.partial(_cem_solve if solver == "cem" else _mppi_solve, policy, eng)
     if solver == "box":
         lo, hi = policy.control_bounds
         return functools.partial(_box_solve_held if hold else _box_solve, eng, lo, hi)
@@ -29,6 +29,9 @@ def _solver(policy, eng, hold=False):
 
 def refuse_cem(policy, what):
     """The training calls of a "cem" policy: the sampler has no derivative (raised before any device work)."""
+    if getattr(policy, "solver", "rounds") == "mppi":
+        raise NotImplementedError(f'solver="mppi": {what} does not go through the sampler; train through '
+                                  "policy.differentiable.mppi_layer, which differentiates the path-integral solve")
     if getattr(policy, "solver", "rounds") == "cem":
         raise NotImplementedError(f'solver="cem" has no gradient through the sampler: {what} needs an iLQR solver '
                                   '("rounds", "fused" or "box")')
@@ -49,6 +52,33 @@ def _cem_solve(policy, eng, x0, U, goal, kwargs=None):
     clamp = (lambda t: t) if lo_t is None and hi_t is None else (lambda t: torch.clamp(t, min=lo_t, max=hi_t))
     sol = eng.cem_solve(x0, clamp(U), goal, lo, hi, kw)
     sol["U"] = clamp(sol["U"])
+    sol["iterations"] = torch.full((x0.shape[0],), int(kw["max_iter"]), dtype=torch.int32, device=x0.device)
+    return sol
+
+
+def shift_warm_start(U):
+    """U (B, T, m) shifted one step towards the horizon's end, the last row repeated: the next solve's start."""
+    return torch.cat([U[:, 1:], U[:, -1:]], dim=1).contiguous()
+
+
+def _mppi_solve(policy, eng, x0, U, goal, kwargs=None):
+    """The policy's MPPI solve, handled like _cem_solve: the start clamped, U clamped after the solve, solve k under
+    seed + k.  With mppi_kwargs["warm_start"] the start is the previous solve's U of the same batch shape, shifted one
+    step (shift_warm_start), instead of the expert's U; policy.reset_warm_start() drops it."""
+    del kwargs
+    lo, hi = policy.control_bounds
+    kw = dict(policy.mppi_kwargs)
+    warm = bool(kw.pop("warm_start"))
+    kw["seed"] = int(kw["seed"]) + policy.mppi_solves
+    policy.mppi_solves += 1
+    _, _, lo_t, hi_t = eng._device_bounds(lo, hi)
+    clamp = (lambda t: t) if lo_t is None and hi_t is None else (lambda t: torch.clamp(t, min=lo_t, max=hi_t))
+    prev = policy._warm_U
+    if warm and prev is not None and prev.shape == U.shape and prev.device == U.device:
+        U = shift_warm_start(prev)
+    sol = eng.mppi_solve(x0, clamp(U), goal, lo, hi, kw)
+    sol["U"] = clamp(sol["U"])
+    policy._warm_U = sol["U"] if warm else None
     sol["iterations"] = torch.full((x0.shape[0],), int(kw["max_iter"]), dtype=torch.int32, device=x0.device)
     return sol
 

@@ -20,8 +20,9 @@
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
  *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp, gmpc_expert_vjp,
- *    gmpc_critic_vjp, gmpc_critic_dir_vjp and gmpc_cem_solve drop nothing: they may run between a solve and its bilevel calls, or
- *    between a bilevel call and gmpc_bilevel_grad_inputs / _dynamics.
+ *    gmpc_critic_vjp, gmpc_critic_dir_vjp, gmpc_cem_solve and gmpc_mppi_solve drop nothing: they may run between a
+ *    solve and its bilevel calls, or between a bilevel call and gmpc_bilevel_grad_inputs / _dynamics.  gmpc_mppi_vjp
+ *    rolls its samples out through the ctx's buffers and drops a held solution, as gmpc_rollout_cost does.
  *
  * Parameter layouts (flat fp32 vectors, flax Dense order: kernel (in,out) row-major, then bias):
  *   dyn    : for l in 0..dyn_layers-1:  W_l[dims[l]][dims[l+1]], b_l[dims[l+1]]
@@ -261,6 +262,69 @@ int gmpc_cem_solve(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
                    float* X, float* obj,
                    float* costs, int* elites, float* samples,
                    void* stream);
+
+/* Model-predictive path integral control on the same samples: gmpc_cem_solve with the elite cut replaced
+ * by softmax weights, so that the update is a smooth function of the sample costs (gmpc_mppi_vjp differentiates it).
+ * Per problem b and iteration it = iter_offset + i, i < max_iter: samples u_s and costs J_s exactly as gmpc_cem_solve
+ * forms them (same Philox counters, smoothing and clamp, same kernel); then
+ *   w_s = exp(-(J_s - J_min) / temperature), J_min over the finite costs, w_s = 0 for a NaN or infinite cost;
+ *   new_mean = sum_s w_s u_s / sum_s w_s (fp32, both sums in sample order, whatever B and the launch geometry);
+ *   mean <- gamma mean + (1 - gamma) new_mean (gamma = evolution_smoothing).
+ * A problem without a finite cost keeps its mean, bit for bit.  std [B][T][m] is read and never written (classic
+ * MPPI: the sampling distribution's width is fixed).  mean_io, u_lo / u_hi, X and obj as for gmpc_cem_solve.
+ * costs [B][N], weights [B][N] (normalised: w_s / sum w) and samples [B][N][T][m]: those of the last iteration, each
+ * may be NULL.  means_trace [max_iter][B][T][m]: the mean BEFORE each iteration; costs_trace [max_iter][B][N]: the
+ * costs of each iteration; each may be NULL (gmpc_mppi_vjp needs both).  One call with max_iter = K equals K chained
+ * calls with max_iter = 1 and iter_offset = 0 .. K-1, bit for bit, and the traces are the chained calls' inputs and
+ * costs.
+ * Coverage -- anything else fails with GMPC_EINVAL ("mppi: ...") before any launch: as gmpc_cem_solve without the
+ * elites, and temperature > 0 and finite.
+ * 2 max_iter + 1 launches on `stream` (2 max_iter with X and obj both NULL), no host synchronisation, no atomics;
+ * deterministic; stateless like gmpc_cem_solve (B N floats of call workspace when costs and costs_trace are NULL). */
+typedef struct gmpc_mppi_opts {
+  int max_iter, num_samples, iter_offset;
+  float sampling_smoothing, evolution_smoothing, temperature;
+  unsigned long long seed;
+} gmpc_mppi_opts;
+int gmpc_mppi_solve(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
+                    const float* u_lo, const float* u_hi,
+                    const gmpc_mppi_opts* opts, float* mean_io, const float* std,
+                    float* X, float* obj,
+                    float* costs, float* weights, float* samples,
+                    float* means_trace, float* costs_trace,
+                    void* stream);
+
+/* The VJP of gmpc_mppi_solve: the true derivative of (U, X, obj) = (final mean, its rollout, its objective) w.r.t. x0,
+ * the initial mean, the goals and the parameters, through the sampler (the normals are constants; the clamp passes a
+ * cotangent where the unclamped control lies strictly inside the bounds).  x0 .. std and opts: the forward call's;
+ * means_trace / costs_trace: what it wrote; U [B][T][m], X [B][T+1][n]: its final mean and rollout.  Cotangents
+ * gU [B][T][m], gX [B][T+1][n], gobj [B]: any may be NULL, not all.
+ *   -> grad_x0 [B][n], grad_Uinit [B][T][m], grad_goal [B][T+1][n] per problem; grad_theta_sum / grad_dyn_sum in
+ *   gmpc_rollout_vjp's layouts, SUMMED over the batch.  Any may be NULL, not all.
+ * g = gU + the gmpc_rollout_vjp of the final rollout under gX and gobj (on every cost of the row); then for
+ * k = max_iter - 1 .. 0, with w~ = w / sum w and new_mean = sum w~_s u_s of iteration k:
+ *   a_s = <g, u_s - new_mean>,  c_s = -(1 - gamma) / temperature  w~_s a_s: the cotangent of every cost of sample s;
+ *   the rollout VJP of the N sample rows under c gives GU_s, Gx0_s, Ggoal_s and the parameter sums;
+ *   g <- gamma g + sum_s mask_s ((1 - gamma) w~_s g + GU_s);  grad_x0 += sum_s Gx0_s, grad_goal likewise.
+ * grad_Uinit is the final g.  The sample rows run in chunks of floor(max_batch / num_samples) problems; every sum has a
+ * fixed order (samples, then chunks, then iterations): deterministic, no atomics.  A problem whose iteration had no
+ * finite cost passes g through that iteration (its NaN states still reach the sums over the batch, as NaN rows do in
+ * gmpc_rollout_vjp: grad_theta_sum and grad_dyn_sum are then NaN).
+ * Refusals (GMPC_EINVAL, "mppi: ...", before any launch): those of gmpc_mppi_solve; num_samples > max_batch; NULL
+ * traces with max_iter > 0; every cotangent or every output NULL.
+ * Ordering contract: like gmpc_rollout_cost, the sample rollouts overwrite the ctx's relu masks and objectives, so the
+ * call DROPS a solution held by the ctx (run it on a second context beside a solve whose bilevel calls are pending).
+ * Workspace, allocated by the first call that needs more than the ctx holds (a synchronising hipMalloc) and kept: with
+ * R = min(B, floor(max_batch / N)) N rows, R (2 T m + 3 (T + 1) n + 2 n + T + 2) + B (T m + T + 1) floats plus one
+ * copy of each parameter sum, beside gmpc_rollout_vjp's own workspace for R rows. */
+int gmpc_mppi_vjp(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
+                  const float* u_lo, const float* u_hi,
+                  const gmpc_mppi_opts* opts, const float* std,
+                  const float* means_trace, const float* costs_trace,
+                  const float* U, const float* X,
+                  const float* gU, const float* gX, const float* gobj,
+                  float* grad_x0, float* grad_Uinit, float* grad_goal,
+                  float* grad_theta_sum, float* grad_dyn_sum, void* stream);
 
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
