@@ -72,6 +72,15 @@ class MppiOpts(C.Structure):
     ]
 
 
+class IcemOpts(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int), ("num_samples", C.c_int), ("num_elites", C.c_int), ("num_keep", C.c_int),
+        ("carry_in", C.c_int), ("iter_offset", C.c_int), ("add_mean", C.c_int), ("return_best", C.c_int),
+        ("noise_beta", C.c_float), ("evolution_smoothing", C.c_float), ("decay", C.c_float),
+        ("seed", C.c_ulonglong),
+    ]
+
+
 _P = C.c_void_p
 
 
@@ -127,7 +136,10 @@ SIGNATURES = {
                                   _P]),
     "gmpc_mppi_vjp": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(MppiOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _P, _P, _P]),
-    "gmpc_box_qp_host": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gmpc_icem_solve": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(IcemOpts), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, _P]),
+    "gmpc_icem_plan_host": (C.c_int, [C.POINTER(IcemOpts), C.c_int, _P, _P]),
+    "gmpc_box_qp_host":(C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_bilevel_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),
     "gmpc_bilevel_grad_inputs": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),

@@ -500,6 +500,160 @@ extern "C" int gmpc_mppi_solve(gmpc_ctx* c, int B, const float* x0, const float*
   return 0;
 }
 
+// What gmpc_icem_solve and gmpc_icem_plan_host refuse in their options
+static int icem_check_opts(const gmpc_icem_opts* o) {
+  if (!o) return fail(GMPC_EINVAL, "icem: opts is null");
+  if (o->num_samples < 1 || o->num_samples > 4096)
+    return fail(GMPC_EINVAL, "icem: num_samples = %d outside [1, 4096]", o->num_samples);
+  if (o->num_elites < 1 || o->num_elites > o->num_samples)
+    return fail(GMPC_EINVAL, "icem: num_elites = %d outside [1, num_samples = %d]", o->num_elites, o->num_samples);
+  if (o->num_keep < 0 || o->num_keep > o->num_elites)
+    return fail(GMPC_EINVAL, "icem: num_keep = %d outside [0, num_elites = %d]", o->num_keep, o->num_elites);
+  if (o->carry_in < 0 || o->carry_in > o->num_keep)
+    return fail(GMPC_EINVAL, "icem: carry_in = %d outside [0, num_keep = %d]", o->carry_in, o->num_keep);
+  if (o->num_samples + o->num_keep + 1 > 4096)
+    return fail(GMPC_EINVAL, "icem: num_samples + num_keep + 1 = %d above 4096", o->num_samples + o->num_keep + 1);
+  if (o->max_iter < 0) return fail(GMPC_EINVAL, "icem: max_iter = %d is negative", o->max_iter);
+  if (o->iter_offset < 0) return fail(GMPC_EINVAL, "icem: iter_offset = %d is negative", o->iter_offset);
+  if (!(o->decay >= 1.f) || !(o->decay < INFINITY))
+    return fail(GMPC_EINVAL, "icem: decay = %g is not finite and >= 1", (double)o->decay);
+  if (!(o->noise_beta >= 0.f) || !(o->noise_beta < INFINITY))
+    return fail(GMPC_EINVAL, "icem: noise_beta = %g is not finite and >= 0", (double)o->noise_beta);
+  if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
+    return fail(GMPC_EINVAL, "icem: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
+  return 0;
+}
+
+// The one place the sample counts and the coloured sum's weights are computed (host only; IEEE double arithmetic, so a
+// NumPy restatement agrees: N_it exactly, cw to the rounding of libm's pow)
+extern "C" int gmpc_icem_plan_host(const gmpc_icem_opts* o, int T, int* N_it, float* cw) {
+  TRY(icem_check_opts(o));
+  if (T < 1) return fail(GMPC_EINVAL, "icem: T = %d is not positive", T);
+  if (N_it) {
+    const double decay = (double)o->decay;
+    const int floor_n = std::min(o->num_samples, 2 * o->num_elites);
+    double nk = (double)o->num_samples;
+    for (int it = 0; it < o->iter_offset && nk >= 1.0; ++it) nk = nk / decay;     // (below 1 the floor stays 0)
+    for (int i = 0; i < o->max_iter; ++i) {
+      N_it[i] = std::max((int)std::floor(nk), floor_n);
+      nk = nk / decay;
+    }
+  }
+  if (cw) {
+    const int Kf = T / 2;
+    std::vector<double> w(Kf + 1, 1.0);
+    for (int k = 1; k <= Kf; ++k) w[k] = std::pow((double)k / (double)T, -(double)o->noise_beta / 2.0);
+    if (Kf >= 1) w[0] = w[1];
+    double s2 = w[0] * w[0];
+    for (int k = 1; 2 * k < T; ++k) s2 += 2.0 * w[k] * w[k];
+    if (T % 2 == 0) s2 += w[Kf] * w[Kf];
+    const double s = std::sqrt(s2);
+    cw[0] = (float)(w[0] / s);
+    for (int k = 1; 2 * k < T; ++k) cw[k] = (float)(std::sqrt(2.0) * w[k] / s);
+    if (T % 2 == 0) cw[Kf] = (float)(w[Kf] / s);
+  }
+  return 0;
+}
+
+// The sample-efficient cross-entropy method: 2 max_iter + 1 launches on the caller's stream, nothing
+// waited for.  Stateless as gmpc_cem_solve is: the caller's arrays and the call workspace only.
+extern "C" int gmpc_icem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
+                               const float* u_hi, const gmpc_icem_opts* o, float* mean_io, float* std_io,
+                               float* keep_io, float* best_U_io, float* best_cost_io, float* U_out, float* X, float* obj,
+                               float* costs, int* elites, float* samples, void* stream) {
+  TRY(check_call(c, B));
+  const gmpc_shape& sh = c->sh;
+  TRY(gmpc_sampled_coverage(c, "icem"));
+  TRY(icem_check_opts(o));
+  if (!x0 || !goal || !mean_io || !std_io)
+    return fail(GMPC_EINVAL, "icem: x0, goal, mean_io and std_io must not be null");
+  if (o->num_keep > 0 && !keep_io) return fail(GMPC_EINVAL, "icem: keep_io must not be null with num_keep = %d", o->num_keep);
+  if ((best_U_io != nullptr) != (best_cost_io != nullptr))
+    return fail(GMPC_EINVAL, "icem: best_U_io and best_cost_io go together");
+  if (o->return_best && (!best_U_io || !U_out))
+    return fail(GMPC_EINVAL, "icem: best_U_io, best_cost_io and U_out must not be null with return_best");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = o->num_samples, nk = o->num_keep, K = o->max_iter, T = sh.T, m = sh.m;
+  const int ldc = N + nk + 1;
+  const size_t BTm = (size_t)B * T * m, keep_floats = (size_t)B * nk * T * m;
+  std::vector<int> Nit(K > 0 ? K : 1);
+  std::vector<float> cwh(T / 2 + 1);
+  TRY(gmpc_icem_plan_host(o, T, Nit.data(), cwh.data()));
+  const bool white = o->noise_beta == 0.f || T < 2;
+  if (!white && K > 0 && (!c->icem_cw || c->icem_cw_beta != o->noise_beta)) {
+    if (!c->icem_cw) TRY(dalloc(c, &c->icem_cw, cwh.size()));
+    c->icem_cw_host = cwh;
+    c->icem_cw_beta = o->noise_beta;
+    HIP_TRY(hipMemcpyAsync(c->icem_cw, c->icem_cw_host.data(), cwh.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+  float* cost_buf = costs;
+  if (!cost_buf && K > 0) {
+    TRY(c->cw.aux.grow(c, (size_t)B * ldc));
+    cost_buf = c->cw.aux.p;
+  }
+  // the kept rows ping-pong between two buffers of the call workspace (the update reads the old rows while it writes
+  // the new ones); the first iteration reads keep_io, the last one writes it.  With one iteration both are keep_io:
+  // its rows are copied aside first.
+  float* W[2] = {nullptr, nullptr};
+  const bool aside = K == 1 && o->carry_in > 0;
+  if (nk > 0 && (K >= 2 || aside)) {
+    TRY(c->cw.save.grow(c, 2 * keep_floats));
+    W[0] = c->cw.save.p;
+    W[1] = W[0] + keep_floats;
+  }
+  if (aside) HIP_TRY(hipMemcpyAsync(W[0], keep_io, keep_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
+  IcemRollArgs r;
+  memset(&r, 0, sizeof(r));
+  r.c.B = B; r.c.N = N; r.c.T = T; r.c.n = sh.n; r.c.m = m;
+  r.c.dyn = c->dyn; r.c.cost = c->cost; r.c.mpc_w = c->mpc_w;
+  r.c.x0 = x0; r.c.goal = goal; r.c.mean = mean_io; r.c.sd = std_io; r.c.lo = u_lo; r.c.hi = u_hi;
+  r.c.rng.key0 = (uint32_t)(o->seed & 0xFFFFFFFFull); r.c.rng.key1 = (uint32_t)(o->seed >> 32);
+  r.c.rng.beta = 0.f; r.c.rng.cbeta = 1.f;
+  r.c.costs = cost_buf;
+  r.ldc = ldc;
+  r.zlds = !white && gmpc_icem_zlds(T, m);
+  r.p.nkeep = nk; r.p.white = white; r.p.cw = white ? nullptr : c->icem_cw;
+  IcemUpdArgs u;
+  memset(&u, 0, sizeof(u));
+  u.B = B; u.E = o->num_elites; u.T = T; u.m = m; u.ldc = ldc;
+  u.costs = cost_buf; u.lo = u_lo; u.hi = u_hi; u.mean = mean_io; u.sd = std_io;
+  u.gamma = o->evolution_smoothing;
+  u.best_U = best_U_io; u.best_cost = best_cost_io; u.U_out = U_out; u.return_best = o->return_best != 0;
+  const float* keep_src = aside ? W[0] : keep_io;
+  for (int i = 0; i < K; ++i) {
+    const bool last = i == K - 1;
+    r.c.rng.it = (uint32_t)(o->iter_offset + i);
+    r.c.samples = last ? samples : nullptr;
+    r.p.Nit = Nit[i];
+    r.p.carry = i == 0 ? o->carry_in : nk;
+    r.p.addmean = o->add_mean && last;
+    r.p.keep = r.p.carry > 0 ? keep_src : nullptr;
+    u.p = r.p;
+    u.rng = r.c.rng;
+    u.elites = last ? elites : nullptr;
+    u.last = last;
+    u.keep_out = nk == 0 ? nullptr : last ? keep_io : W[i & 1];
+    if (gmpc_launch_icem_rollout(r, s) || gmpc_launch_icem_update(u, s))
+      return fail(GMPC_EINVAL, "icem: shape not covered");
+    keep_src = u.keep_out;
+  }
+  // without an iteration nothing was sampled: the returned sequence is the mean
+  if (K == 0 && U_out) HIP_TRY(hipMemcpyAsync(U_out, mean_io, BTm * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (X || obj) {
+    // the returned sequence's own rollout: one row per problem, no noise, no clamp (k_cem_rollout's mean_row form)
+    if (!obj) {
+      TRY(c->cw.aux2.grow(c, (size_t)B));
+      obj = c->cw.aux2.p;
+    }
+    CemRollArgs f = r.c;
+    f.N = 1; f.mean_row = 1; f.samples = nullptr; f.costs = obj; f.X = X;
+    f.mean = U_out ? U_out : mean_io;
+    if (gmpc_launch_cem_rollout(f, s)) return fail(GMPC_EINVAL, "icem: shape not covered");
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // single model evaluations (the reference's model protocol, base.py:4-49) -----------------------
 
 extern "C" int gmpc_get_cost(gmpc_ctx* c, int B, const float* x, const float* u, const float* goal_row,

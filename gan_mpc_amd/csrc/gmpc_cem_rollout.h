@@ -1,0 +1,163 @@
+// What the sampling solvers' kernels share beyond the sampler: the body of the sampled rollout (k_cem_rollout of
+// gmpc_cem.hip, k_icem_rollout of gmpc_icem.hip -- one body, instantiated over where a row's controls come from) and
+// the (cost, row) keys with their sort (k_cem_update, k_icem_update).
+#pragma once
+#include "gmpc_dg_gemm.h"
+#include "gmpc_cem_sampler.h"
+
+#define GMPC_CEM_ROWS 32          // samples per workgroup of the rollout (the two row halves of dg_gemm)
+#define GMPC_CEM_MAX_N 4096       // rows per problem (the sort's keys: 32 KiB of LDS)
+
+// ---- the rollout ----------------------------------------------------------------------------------------------
+// Sum over the 8 lanes of a row's group (lanes 8 i .. 8 i + 7 of a wave), the same value in each: a fixed butterfly,
+// so a row's sum does not depend on which row of which tile it is.
+__device__ __forceinline__ float cem_row8_sum(float v) {
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  return v;
+}
+
+// acc's rows into LDS columns 0 .. N-1 of the 32 operand rows (thread (wave, lane) holds D[4 kq + r][tile column])
+template <typename F>
+__device__ __forceinline__ void cem_store_tiles(float* Ab, const DgTiles& v, int N, int wave, int lane, F f) {
+  const int l16 = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci) {
+    const int j = (wave + 4 * ci) * 16 + l16;
+    if (j >= N) continue;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      Ab[(4 * kq + rr) * GMPC_DG_LDA + j] = f(v.p[ci][rr], j);
+      Ab[(16 + 4 * kq + rr) * GMPC_DG_LDA + j] = f(v.q[ci][rr], j);
+    }
+  }
+}
+
+// One 256-thread workgroup per 32 rows of one problem, the whole horizon.  `rows` rows per problem, costs [B][ldc];
+// Ab: the [32][GMPC_DG_LDA] operand block at the start of the dynamic LDS.  Src, where the controls come from:
+//   begin(b, s0, tid)         once, before the first step (it may fill LDS behind the operand block and synchronise)
+//   control(b, i, s, t, j)    the control j of step t of row s = s0 + i of problem b
+//   record(b, s, t, j, u)     the debug copy of that control, if the caller asked for one
+// A row's cost is a function of its controls alone: not of its place in the tile, of `rows` or of B.
+template <typename Src>
+__device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows, int ldc, float* Ab, Src& src) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
+  const int n = a.n, m = a.m, T = a.T;
+  const int tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
+  const int b = blockIdx.x / tiles, s0 = (blockIdx.x - b * tiles) * GMPC_CEM_ROWS;
+  const int rrow = tid >> 3, rc = tid & 7;   // the row whose sums this thread shares in, its lane of the row's 8
+  const float w0 = sigmoidf_(a.mpc_w[0]), w1 = sigmoidf_(a.mpc_w[1]), w2 = sigmoidf_(a.mpc_w[2]);
+  const float al = GMPC_ALPHA;
+  src.begin(b, s0, tid);
+  // x_t of the 32 rows, in dg_gemm's accumulator layout: the output layer's tile of a thread is its tile of x
+  DgTiles xs;
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci) {
+    const int j = (wave + 4 * ci) * 16 + l16;
+    const float v = j < n ? a.x0[(size_t)b * n + j] : 0.f;
+    xs.p[ci] = f32x4_t{v, v, v, v};
+    xs.q[ci] = f32x4_t{v, v, v, v};
+  }
+  if (a.X)
+    for (int j = tid; j < n; j += GMPC_DG_THREADS) a.X[(size_t)b * (T + 1) * n + j] = a.x0[(size_t)b * n + j];
+  float csum = 0.f;   // the cost of row rrow so far (the same in its 8 lanes)
+  DgTiles acc;
+  for (int t = 0; t < T; ++t) {
+    // ---- layer 0 input [x_t; u_t]
+    cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+    for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
+      const int i = e / m, j = e - i * m, s = s0 + i;
+      const float u = src.control(b, i, s, t, j);
+      Ab[i * GMPC_DG_LDA + n + j] = u;
+      src.record(b, s, t, j, u);
+    }
+    __syncthreads();
+    // ---- stage cost of (x_t, u_t) against goal_t
+    {
+      const float* row = Ab + rrow * GMPC_DG_LDA;
+      const float* g = a.goal + ((size_t)b * (T + 1) + t) * n;
+      float su = 0.f, sx = 0.f;
+      for (int j = rc; j < m; j += 8) su = fmaf(row[n + j], row[n + j], su);
+      for (int j = rc; j < n; j += 8) {
+        const float d = row[j] - g[j];
+        sx = fmaf(d, d, sx);
+      }
+      su = cem_row8_sum(su);
+      sx = cem_row8_sum(sx);
+      csum += w0 * (sqrtf(su + al * al) - al) + w1 * (sqrtf(sx + al * al) - al);
+    }
+    // ---- x_{t+1} = x_t + MLP([x_t; u_t])
+    for (int l = 0; l < a.dyn.L; ++l) {
+      const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
+      dg_gemm(Ab, K, Nl, a.dyn.W[l], wave, lane, acc);
+      __syncthreads();   // every wave has read its operand rows (and the stage cost its row)
+      const float* bias = a.dyn.b[l];
+      if (l < a.dyn.L - 1) {
+        cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); });
+        __syncthreads();
+      } else {
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+          const int j = (wave + 4 * ci) * 16 + l16;
+          if (j >= n) continue;
+          const float bj = bias[j];
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            xs.p[ci][rr] = (acc.p[ci][rr] + bj) + xs.p[ci][rr];
+            xs.q[ci][rr] = (acc.q[ci][rr] + bj) + xs.q[ci][rr];
+          }
+          if (a.X && kq == 0) a.X[((size_t)b * (T + 1) + t + 1) * n + j] = xs.p[ci][0];   // row 0
+        }
+      }
+    }
+  }
+  // ---- terminal cost w2 |MLP_c(x_T)|^2
+  cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+  __syncthreads();
+  for (int l = 0; l < a.cost.L; ++l) {
+    const int K = a.cost.dims[l], Nl = a.cost.dims[l + 1];
+    dg_gemm(Ab, K, Nl, a.cost.W[l], wave, lane, acc);
+    __syncthreads();
+    const float* bias = a.cost.b[l];
+    if (l < a.cost.L - 1)
+      cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); });
+    else
+      cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return v + bias[j]; });
+    __syncthreads();
+  }
+  {
+    const float* row = Ab + rrow * GMPC_DG_LDA;
+    const int fout = a.cost.dims[a.cost.L];
+    float sy = 0.f;
+    for (int j = rc; j < fout; j += 8) sy = fmaf(row[j], row[j], sy);
+    sy = cem_row8_sum(sy);
+    csum += w2 * sy;
+    if (rc == 0 && s0 + rrow < rows) a.costs[(size_t)b * ldc + s0 + rrow] = csum;
+  }
+}
+
+// ---- the keys of the update -----------------------------------------------------------------------------------
+// Order-preserving bits of a cost (a NaN sorts as +inf, -0 as +0), then the row index: ascending keys = the stable
+// order
+__device__ __forceinline__ unsigned long long cem_key(float c, int i) {
+  uint32_t u = c != c ? 0x7F800000u : c == 0.f ? 0u : __float_as_uint(c);
+  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
+  return ((unsigned long long)u << 32) | (uint32_t)i;
+}
+
+// Bitonic sort of keys [P] in LDS by the whole workgroup, P a power of two; the caller has synchronised behind the
+// writes of the keys, and every thread may read them on return
+__device__ __forceinline__ void cem_sort_keys(unsigned long long* keys, int P, int tid) {
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < P; i += GMPC_DG_THREADS) {
+        const int l = i ^ j;
+        if (l > i) {
+          const unsigned long long x = keys[i], y = keys[l];
+          if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[l] = x; }
+        }
+      }
+      __syncthreads();
+    }
+}

@@ -1,5 +1,5 @@
-// The counter-based sampler of the sampling solvers: gmpc_cem.hip and gmpc_mppi.hip include
-// it.  A control is a pure function of (seed, iteration, problem, sample, step, control) -- cem_control, the one place
+// The counter-based sampler of the sampling solvers: gmpc_cem.hip, gmpc_mppi.hip and
+// gmpc_icem.hip (through gmpc_cem_rollout.h) include it.  A control is a pure function of (seed, iteration, problem, sample, step, control) -- cem_control, the one place
 // a control is formed -- so no kernel stores noise or samples: each regenerates what it needs.  (CemRng itself is in
 // gmpc_launch.h, beside the argument blocks that carry it.)
 #pragma once

@@ -108,6 +108,11 @@ struct gmpc_ctx {
   int dfstride = 0;
   float* efloss = nullptr;     // per-window losses of gmpc_expert_loss_grad
   CallWork cw;
+  // gmpc_icem_solve: the device copy of the coloured sum's weights [T/2 + 1] and the noise_beta it was built for (the
+  // upload is repeated only when noise_beta changes; icem_cw_host is what the asynchronous copy reads)
+  float* icem_cw = nullptr;
+  float icem_cw_beta = -1.f;
+  std::vector<float> icem_cw_host;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;

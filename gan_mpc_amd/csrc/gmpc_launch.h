@@ -246,6 +246,44 @@ struct CemUpdArgs {
 int gmpc_launch_cem_rollout(const CemRollArgs& a, hipStream_t s);
 int gmpc_launch_cem_update(const CemUpdArgs& a, hipStream_t s);
 
+// gmpc_icem.hip: the sample-efficient cross-entropy method's two kernels --------------------------------
+// The rows of one iteration's pool, per problem: rows 0 .. Nit-1 fresh samples (sample index = row), rows Nit ..
+// Nit+carry-1 the first `carry` rows of keep [B][nkeep][T][m], then -- with addmean -- the mean itself; every row
+// clamped to the bounds.  white: the fresh rows are cem_control's (no colouring); otherwise cw [T/2 + 1] are the
+// weights of the coloured sum (gmpc_icem_plan_host).
+struct IcemPool {
+  int Nit, carry, addmean, nkeep, white;
+  const float *keep, *cw;
+};
+// k_icem_rollout: k_cem_rollout's body over the pool's rows; c.N is the stride of `samples` (fresh rows only), costs
+// [B][ldc].  zlds: the T normals of every (row, control) of a tile are formed once, in LDS behind the operand block.
+struct IcemRollArgs {
+  CemRollArgs c;
+  IcemPool p;
+  int ldc, zlds;
+};
+// k_icem_update: the E smallest of the pool's costs by (cost, row); mean / sd refit in place (left alone where no cost
+// is finite); keep_out [B][nkeep][T][m] <- the controls of ranks 0 .. nkeep-1; best_cost [B] / best_U [B][T][m]
+// (both or neither) take rank 0 where it is strictly cheaper; with `last`, U_out [B][T][m] (may be null) <- best_U
+// where return_best and the best cost is finite, the new mean otherwise.  elites [B][E] pool rows, or null.
+struct IcemUpdArgs {
+  int B, E, T, m, ldc;
+  IcemPool p;
+  const float *costs, *lo, *hi;
+  float *mean, *sd;
+  CemRng rng;
+  float gamma;
+  int* elites;
+  float *keep_out, *best_U, *best_cost, *U_out;
+  int return_best, last;
+  int stage;     // set by the launcher: elites per staged block of controls (0: one element per thread)
+};
+// CEM's shapes and Nit + carry + addmean <= 4096: non-zero (nothing launched) otherwise
+int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s);
+int gmpc_launch_icem_update(const IcemUpdArgs& a, hipStream_t s);
+// non-zero where 32 m T floats fit in LDS beside the rollout's operand block (what zlds may be set for)
+int gmpc_icem_zlds(int T, int m);
+
 // gmpc_mppi.hip: the path-integral update on k_cem_rollout's costs, and its adjoint ------------------
 // k_mppi_update: w_s = exp(-(costs_s - min) / lam) over the finite costs [B][N], mean <- gamma mean + (1 - gamma)
 // sum_s w_s u_s / sum_s w_s in place; sd is read only.  weights [B][N] (normalised), mean_trace [B][T][m] (the mean

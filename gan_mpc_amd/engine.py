@@ -46,6 +46,20 @@ MPPI_KWARGS = {
     "seed": 0,
 }
 
+# the sample-efficient CEM's keywords at the defaults of Pinneri et al. (CoRL 2020, table 2)
+ICEM_KWARGS = {
+    "noise_beta": 2.0,
+    "evolution_smoothing": 0.1,
+    "elite_portion": 0.1,
+    "keep_portion": 0.3,
+    "decay": 1.25,
+    "max_iter": 3,
+    "num_samples": 100,
+    "seed": 0,
+    "add_mean": True,
+    "return_best": True,
+}
+
 
 def make_shape(n, m, T, dyn_dims, cost_dims, lstm_features=0, head_dims=None, dyn_lstm=0, x_size=0):
     """dyn_lstm = F > 0: the LSTM dynamics variant -- n = x_size + 2F is the size of xc = [x, c, h],
@@ -128,6 +142,28 @@ def make_mppi_opts(kwargs=None, iter_offset=0):
     o.sampling_smoothing = float(kw["sampling_smoothing"])
     o.evolution_smoothing = float(kw["evolution_smoothing"])
     o.temperature = float(kw["temperature"])
+    o.seed = int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF
+    return o
+
+
+def make_icem_opts(kwargs=None, iter_offset=0, carry_in=0):
+    """gmpc_icem_opts from ICEM_KWARGS' keyword set: num_elites = int(num_samples * elite_portion) and num_keep =
+    int(num_elites * keep_portion), both on the host."""
+    kw = dict(ICEM_KWARGS)
+    if kwargs:
+        unknown = set(kwargs) - set(kw)
+        if unknown:
+            raise _lib.GmpcError(f"icem: unknown keyword(s) {sorted(unknown)}")
+        kw.update(kwargs)
+    o = _lib.IcemOpts()
+    o.max_iter, o.num_samples, o.iter_offset = int(kw["max_iter"]), int(kw["num_samples"]), int(iter_offset)
+    o.num_elites = int(kw["num_samples"] * kw["elite_portion"])
+    o.num_keep = int(o.num_elites * kw["keep_portion"])
+    o.carry_in = int(carry_in)
+    o.add_mean, o.return_best = int(bool(kw["add_mean"])), int(bool(kw["return_best"]))
+    o.noise_beta = float(kw["noise_beta"])
+    o.evolution_smoothing = float(kw["evolution_smoothing"])
+    o.decay = float(kw["decay"])
     o.seed = int(kw["seed"]) & 0xFFFFFFFFFFFFFFFF
     return o
 
@@ -374,6 +410,59 @@ class Engine:
             self.ctx, B, _ptr(x0), _ptr(goal), _ptr(lo_d), _ptr(hi_d), C.byref(opts), _ptr(out["U"]), _ptr(std),
             _ptr(out["X"]), _ptr(out["obj"]), _ptr(out.get("costs")), _ptr(out.get("weights")),
             _ptr(out.get("samples")), _ptr(out.get("means_trace")), _ptr(out.get("costs_trace")), self._stream()))
+        return out
+
+    ICEM_WANT = ("costs", "elites", "samples")
+
+    def icem_solve(self, x0, U_init, goal, u_lo, u_hi, kwargs=None, init_std=None, want=(), iter_offset=0, state=None):
+        """The sample-efficient cross-entropy method from the mean U_init under u_lo <= u <= u_hi (gmpc_icem_solve;
+        keywords ICEM_KWARGS).  u_lo, u_hi, init_std as for cem_solve.  state: None -- nothing is
+        carried in, the best cost starts at +inf --, or the `state` of an earlier call (dict(keep (B, num_keep, T, m),
+        best_U (B, T, m), best_cost (B,)), not written; an entry "carry" gives carry_in, default num_keep): its kept
+        rows join the first iteration's pool and its best row stays the one to beat.  -> dict(X, U (the returned
+        sequence: the best row seen with return_best, the final mean otherwise), obj, mean, std, state) plus the last
+        iteration's `want`ed debug outputs: "costs" (B, R) over the pool's rows, "elites" (B, E) int32 pool rows,
+        "samples" (B, N_last, T, m), the fresh rows.  iter_offset: the noise stream's (and the sample count's) first
+        iteration.  Stateless on the context: a held iLQR solution stays valid; nothing is synchronised."""
+        B, n, m, T = x0.shape[0], self.n, self.m, self.T
+        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
+            if tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"icem: {name} must be {shape}, got {tuple(t.shape)}")
+        unknown = set(want) - set(self.ICEM_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"icem: want has unknown entries {sorted(unknown)}; known: {self.ICEM_WANT}")
+        opts = make_icem_opts(kwargs, iter_offset)
+        N, E, nk, K = opts.num_samples, opts.num_elites, max(opts.num_keep, 0), max(opts.max_iter, 0)
+        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+        std = self._sampling_std("icem", B, init_std, lo, hi)
+        if state is None:
+            st = dict(keep=torch.zeros(B, nk, T, m, device=self.device),
+                      best_U=torch.zeros(B, T, m, device=self.device),
+                      best_cost=torch.full((B,), float("inf"), device=self.device))
+        else:
+            for name, shape in (("keep", (B, nk, T, m)), ("best_U", (B, T, m)), ("best_cost", (B,))):
+                if name not in state or tuple(state[name].shape) != shape:
+                    raise _lib.GmpcError(f"icem: state[{name!r}] must be {shape}: the state of a call with these kwargs")
+            st = {k: self.to_dev(state[k]).clone() for k in ("keep", "best_U", "best_cost")}
+            opts.carry_in = int(state.get("carry", nk))
+        nit = (C.c_int * max(K, 1))()
+        _lib.check(self.lib.gmpc_icem_plan_host(C.byref(opts), T, nit, None))
+        n_last = int(nit[K - 1]) if K else 0
+        rows = n_last + (opts.carry_in if K == 1 else nk) + int(bool(opts.add_mean)) if K else 0
+        out = dict(X=self.new(B, T + 1, n), U=self.new(B, T, m), obj=self.new(B), mean=U_init.clone(), std=std, state=st)
+        costs = self.new(B, N + nk + 1) if "costs" in want else None
+        elites = self.new(B, max(E, 0), dtype=torch.int32) if "elites" in want else None
+        samples = self.new(B, max(N, 0), T, m) if "samples" in want else None
+        _lib.check(self.lib.gmpc_icem_solve(
+            self.ctx, B, _ptr(x0), _ptr(goal), _ptr(lo_d), _ptr(hi_d), C.byref(opts), _ptr(out["mean"]), _ptr(std),
+            _ptr(st["keep"]) if nk else None, _ptr(st["best_U"]), _ptr(st["best_cost"]), _ptr(out["U"]),
+            _ptr(out["X"]), _ptr(out["obj"]), _ptr(costs), _ptr(elites), _ptr(samples), self._stream()))
+        if costs is not None:
+            out["costs"] = costs[:, :rows]
+        if elites is not None:
+            out["elites"] = elites
+        if samples is not None:
+            out["samples"] = samples[:, :n_last]
         return out
 
     def mppi_vjp(self, x0, goal, u_lo, u_hi, sol, gU=None, gX=None, gobj=None, kwargs=None, iter_offset=0,

@@ -5,7 +5,7 @@ batch (B, hist+1, n)."""
 import numpy as np
 import torch
 
-from gan_mpc_amd.engine import MPPI_KWARGS, TRAJAX_CEM_KWARGS, TRAJAX_iLQR_KWARGS, Engine
+from gan_mpc_amd.engine import ICEM_KWARGS, MPPI_KWARGS, TRAJAX_CEM_KWARGS, TRAJAX_iLQR_KWARGS, Engine
 from gan_mpc_amd.policy import optimizers as opt
 from gan_mpc_amd.policy.device_params import DeviceParams
 
@@ -44,11 +44,11 @@ class LqrBlock:
 
 
 class EvalMPC:
-    SOLVERS = ("rounds", "fused", "box", "cem", "mppi")
+    SOLVERS = ("rounds", "fused", "box", "cem", "mppi", "icem")
 
     def __init__(self, config, cost_model, dynamics_model, expert_model,
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None,
-                 cem_kwargs=None, mppi_kwargs=None):
+                 cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
@@ -60,11 +60,14 @@ class EvalMPC:
         advances by one per solve); "mppi" -- gmpc_mppi_solve, path-integral control under control_bounds with the
         keywords mppi_kwargs (engine.MPPI_KWARGS plus the policy keyword warm_start, default False: the next solve of
         the same batch shape starts from the previous U shifted one step), handled like "cem"; its
-        training calls raise NotImplementedError too and name policy.differentiable.mppi_layer, the way to train."""
+        training calls raise NotImplementedError too and name policy.differentiable.mppi_layer, the way to train;
+        "icem" -- gmpc_icem_solve, the sample-efficient cross-entropy method under control_bounds with the keywords
+        icem_kwargs (engine.ICEM_KWARGS plus the policy keyword shift_elites, default True: the next solve of the same
+        batch shape carries the previous solve's kept rows, shifted one step), handled like "cem"."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
-        if (solver in ("box", "cem", "mppi")) != (control_bounds is not None):
-            raise ValueError('control_bounds=(lo, hi) and solver="box" / "cem" / "mppi" go together: got '
+        if (solver in ("box", "cem", "mppi", "icem")) != (control_bounds is not None):
+            raise ValueError('control_bounds=(lo, hi) and solver="box" / "cem" / "mppi" / "icem" go together: got '
                              f"solver={solver!r}, control_bounds={control_bounds!r}")
         if cem_kwargs is not None and solver != "cem":
             raise ValueError(f'cem_kwargs and solver="cem" go together: got solver={solver!r}')
@@ -73,6 +76,11 @@ class EvalMPC:
         unknown = set(mppi_kwargs or {}) - set(MPPI_KWARGS) - {"warm_start"}
         if unknown:
             raise ValueError(f"mppi_kwargs has unknown keyword(s) {sorted(unknown)}")
+        if icem_kwargs is not None and solver != "icem":
+            raise ValueError(f'icem_kwargs and solver="icem" go together: got solver={solver!r}')
+        unknown = set(icem_kwargs or {}) - set(ICEM_KWARGS) - {"shift_elites"}
+        if unknown:
+            raise ValueError(f"icem_kwargs has unknown keyword(s) {sorted(unknown)}")
         if control_bounds is not None and len(control_bounds) != 2:
             raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
@@ -87,6 +95,9 @@ class EvalMPC:
         self.mppi_kwargs = {**MPPI_KWARGS, "warm_start": False, **(mppi_kwargs or {})}
         self.mppi_solves = 0      # the same for a "mppi" policy
         self._warm_U = None       # warm_start: the previous solve's clamped U
+        self.icem_kwargs = {**ICEM_KWARGS, "shift_elites": True, **(icem_kwargs or {})}
+        self.icem_solves = 0      # the same for an "icem" policy
+        self._icem_state = None   # shift_elites: the previous solve's state (its kept rows)
         self.critic_model = getattr(self, "critic_model", None)
         self._device = device
         self._engine = None
@@ -104,8 +115,10 @@ class EvalMPC:
         return params
 
     def reset_warm_start(self):
-        """Forget the previous solve's controls: the next "mppi" solve starts from the expert's init_U again."""
+        """Forget the previous solve's controls: the next "mppi" solve starts from the expert's init_U again, the
+        next "icem" solve carries no kept rows."""
         self._warm_U = None
+        self._icem_state = None
 
     def device(self):
         if self._device is None:
@@ -209,7 +222,7 @@ class EvalMPC:
             hu = hu[None] if single else hu
         _, sol = self._solve(params, hx, hu)
         B = sol["X"].shape[0]
-        if self.solver in ("cem", "mppi"):  # no gradient, adjoints or linearisation; every problem runs max_iter iterations
+        if self.solver in ("cem", "mppi", "icem"):  # no gradient, adjoints or linearisation; every problem runs max_iter iterations
             out = (sol["X"], sol["U"], sol["obj"], None, None, None, sol["iterations"])
             return tuple(o if o is None else o[0] for o in out) if single else out
         lqr = LqrBlock(self._engine, B)

@@ -17,10 +17,10 @@ def _solver(policy, eng, hold=False):
     may follow).  "rounds" and "fused" always hold their solution; "cem" (gmpc_cem_solve under the same bounds) holds none and refuses
     hold=True."""
     solver = getattr(policy, "solver", "rounds")
-    if solver in ("cem", "mppi"):      # ("mppi": gmpc_mppi_solve, handled like "cem")
+    if solver in ("cem", "mppi", "icem"):      # ("mppi": gmpc_mppi_solve, "icem": gmpc_icem_solve, handled like "cem")
         if hold:
             refuse_cem(policy, "a solve held for the bilevel tail")
-        return functools.partial(_cem_solve if solver == "cem" else _mppi_solve, policy, eng)
+        return functools.partial({"cem": _cem_solve, "mppi": _mppi_solve, "icem": _icem_solve}[solver], policy, eng)
     if solver == "box":
         lo, hi = policy.control_bounds
         return functools.partial(_box_solve_held if hold else _box_solve, eng, lo, hi)
@@ -32,9 +32,9 @@ def refuse_cem(policy, what):
     if getattr(policy, "solver", "rounds") == "mppi":
         raise NotImplementedError(f'solver="mppi": {what} does not go through the sampler; train through '
                                   "policy.differentiable.mppi_layer, which differentiates the path-integral solve")
-    if getattr(policy, "solver", "rounds") == "cem":
-        raise NotImplementedError(f'solver="cem" has no gradient through the sampler: {what} needs an iLQR solver '
-                                  '("rounds", "fused" or "box")')
+    if getattr(policy, "solver", "rounds") in ("cem", "icem"):
+        raise NotImplementedError(f'solver="{policy.solver}" has no gradient through the sampler: {what} needs an '
+                                  'iLQR solver ("rounds", "fused" or "box")')
 
 
 def _cem_solve(policy, eng, x0, U, goal, kwargs=None):
@@ -79,6 +79,32 @@ def _mppi_solve(policy, eng, x0, U, goal, kwargs=None):
     sol = eng.mppi_solve(x0, clamp(U), goal, lo, hi, kw)
     sol["U"] = clamp(sol["U"])
     policy._warm_U = sol["U"] if warm else None
+    sol["iterations"] = torch.full((x0.shape[0],), int(kw["max_iter"]), dtype=torch.int32, device=x0.device)
+    return sol
+
+
+def _icem_solve(policy, eng, x0, U, goal, kwargs=None):
+    """The policy's iCEM solve, handled like _cem_solve: the start clamped, U clamped after the solve (the best row is
+    inside the bounds already; the mean, returned where no cost was finite, need not be), solve k under seed + k.  With
+    icem_kwargs["shift_elites"] the next solve of the same batch shape carries the previous solve's kept rows, shifted
+    one step (shift_warm_start per row), as carry_in = num_keep; the best cost starts at +inf in every solve, since the
+    best row of another state prices nothing here.  policy.reset_warm_start() drops the kept rows."""
+    del kwargs
+    lo, hi = policy.control_bounds
+    kw = dict(policy.icem_kwargs)
+    shift = bool(kw.pop("shift_elites"))
+    kw["seed"] = int(kw["seed"]) + policy.icem_solves
+    policy.icem_solves += 1
+    _, _, lo_t, hi_t = eng._device_bounds(lo, hi)
+    clamp = (lambda t: t) if lo_t is None and hi_t is None else (lambda t: torch.clamp(t, min=lo_t, max=hi_t))
+    prev, state = policy._icem_state, None
+    if shift and prev is not None and prev["best_U"].shape == U.shape and prev["best_U"].device == U.device:
+        keep = prev["keep"]
+        state = dict(keep=shift_warm_start(keep.flatten(0, 1)).reshape(keep.shape),
+                     best_U=prev["best_U"], best_cost=torch.full_like(prev["best_cost"], float("inf")))
+    sol = eng.icem_solve(x0, clamp(U), goal, lo, hi, kw, state=state)
+    sol["U"] = clamp(sol["U"])
+    policy._icem_state = sol["state"] if shift else None
     sol["iterations"] = torch.full((x0.shape[0],), int(kw["max_iter"]), dtype=torch.int32, device=x0.device)
     return sol
 

@@ -20,7 +20,7 @@
  *    gmpc_lqr_backward(_after_rollout) and a failed or new gmpc_ilqr_solve overwrite parts of that
  *    state and therefore drop it: a later gmpc_bilevel_grad / gmpc_upper_loss fails with GMPC_EINVAL
  *    ("must precede") instead of differentiating a stale linearisation.  gmpc_rollout_vjp, gmpc_expert_vjp,
- *    gmpc_critic_vjp, gmpc_critic_dir_vjp, gmpc_cem_solve and gmpc_mppi_solve drop nothing: they may run between a
+ *    gmpc_critic_vjp, gmpc_critic_dir_vjp, gmpc_cem_solve, gmpc_icem_solve and gmpc_mppi_solve drop nothing: they may run between a
  *    solve and its bilevel calls, or between a bilevel call and gmpc_bilevel_grad_inputs / _dynamics.  gmpc_mppi_vjp
  *    rolls its samples out through the ctx's buffers and drops a held solution, as gmpc_rollout_cost does.
  *
@@ -325,6 +325,61 @@ int gmpc_mppi_vjp(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
                   const float* gU, const float* gX, const float* gobj,
                   float* grad_x0, float* grad_Uinit, float* grad_goal,
                   float* grad_theta_sum, float* grad_dyn_sum, void* stream);
+
+/* The sample-efficient cross-entropy method (iCEM: Pinneri et al., CoRL 2020) on gmpc_cem_solve's sampler,
+ * rollout and sort: coloured noise along the horizon, elites kept from one iteration (and one MPC step) to the next, a
+ * sample count that shrinks per iteration, the mean as a candidate in the last iteration, the best row seen returned.
+ * Per problem b and iteration it = iter_offset + i, i < max_iter, a pool of R_it = N_it + c_it + a_it rows:
+ *   rows 0 .. N_it-1   fresh: u = clamp(std zt + mean) with gmpc_cem_solve's Philox counters for sample index = row.
+ *     noise_beta == 0 or T < 2: zt = z, the control is gmpc_cem_solve's at sampling_smoothing 0, bit for bit.  Otherwise
+ *     with z_k the normal e = k m + j of the row (k < T) and cw the weights below, in fp32 fma, k ascending,
+ *       zt_t = cw_0 z_0 + sum_{1<=k, 2k<T} cw_k (z_{2k-1} cos(2 pi k t / T) + z_{2k} sin(2 pi k t / T))
+ *              + [T even] cw_{T/2} z_{T-1} (-1)^t,   the angle as cospi / sinpi of 2 ((k t) mod T) / T;
+ *     w_k = (k / T)^(-noise_beta / 2), w_0 = w_1;  cw_0 = w_0 / s, cw_k = sqrt(2) w_k / s (2k < T), cw_{T/2} = w_{T/2} / s;
+ *     s^2 = w_0^2 + 2 sum_{2k<T} w_k^2 + [T even] w_{T/2}^2 (float64 on the host, rounded to fp32): unit variance at
+ *     every step, power spectrum ~ f^-noise_beta;
+ *   rows N_it .. N_it+c_it-1   carried: the first c_it rows of the keep buffer [B][num_keep][T][m], clamped; c_it =
+ *     carry_in in the call's first iteration, num_keep afterwards;
+ *   a_it = 1 iff add_mean and i == max_iter - 1: the row clamp(mean).
+ *   N_it = max(floor(n_it), min(N, 2 E)) with n_0 = N, n_{k+1} = n_k / decay in float64.
+ * Every row is rolled out and costed as gmpc_cem_solve's samples are (carried rows again: nothing is cached).  The E
+ * smallest by (cost, pool row), NaN as +inf, refit mean and std as in gmpc_cem_solve (sums in rank order, gamma =
+ * evolution_smoothing); a problem without a finite cost keeps its mean and std, bit for bit.  The controls of ranks
+ * 0 .. num_keep-1 become the keep buffer; where the rank-0 cost is strictly below best_cost_io[b] (never for a NaN),
+ * best_cost_io[b] and best_U_io[b] take that row's cost and controls -- initialise best_cost_io to +inf.
+ * mean_io / std_io [B][T][m], u_lo / u_hi as for gmpc_cem_solve.  keep_io: in, its first carry_in rows; out, the last
+ * iteration's kept rows (may be NULL with num_keep 0).  best_U_io [B][T][m] / best_cost_io [B]: both or neither.
+ * U_out [B][T][m] (may be NULL without return_best): best_U where return_best is set and the best cost is finite, the
+ * final mean otherwise (and with max_iter 0); X [B][T+1][n], obj [B]: its rollout and objective, no clamp (either may
+ * be NULL; the mean's when U_out is NULL).  costs [B][N+num_keep+1] (the first R of the last iteration), elites [B][E]
+ * (pool rows in rank order), samples [B][N][T][m] (the fresh rows of the last iteration, its first N_it): each may be
+ * NULL.  One call of K iterations equals K chained calls of one (carry_in = num_keep and iter_offset = 1 .. K-1 after
+ * the first, add_mean in the last only), bit for bit.  With num_keep = carry_in = 0, decay = 1, noise_beta = 0,
+ * add_mean = return_best = 0: mean, std, X, obj, costs and elites are gmpc_cem_solve's at sampling_smoothing 0, bit
+ * for bit.
+ * Refused with GMPC_EINVAL ("icem: ...") before any launch: gmpc_cem_solve's shape coverage; 1 <= num_elites <=
+ * num_samples; 0 <= carry_in <= num_keep <= num_elites; num_samples + num_keep + 1 <= 4096; max_iter, iter_offset >= 0;
+ * decay >= 1, noise_beta >= 0, both finite; 0 <= evolution_smoothing <= 1; keep_io NULL with num_keep > 0; best_*_io
+ * or U_out NULL with return_best.
+ * 2 max_iter + 1 launches on `stream` (2 max_iter with X and obj NULL), no atomics, no host synchronisation;
+ * deterministic; stateless like gmpc_cem_solve.  Call workspace (grown by the first call that needs more): B (N +
+ * num_keep + 1) floats when costs is NULL, two keep buffers; the T/2 + 1 weights are uploaded when noise_beta changes;
+ * a one-iteration call with carry_in > 0 copies keep_io aside first (device to device, on `stream`).
+ * gmpc_icem_plan_host (host only, no ctx): N_it [max_iter] and cw [T/2 + 1] of the options, either may be NULL; the
+ * same refusals of the options. */
+typedef struct gmpc_icem_opts {
+  int max_iter, num_samples, num_elites, num_keep, carry_in, iter_offset, add_mean, return_best;
+  float noise_beta, evolution_smoothing, decay;
+  unsigned long long seed;
+} gmpc_icem_opts;
+int gmpc_icem_solve(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
+                    const float* u_lo, const float* u_hi,
+                    const gmpc_icem_opts* opts, float* mean_io, float* std_io, float* keep_io,
+                    float* best_U_io, float* best_cost_io, float* U_out,
+                    float* X, float* obj,
+                    float* costs, int* elites, float* samples,
+                    void* stream);
+int gmpc_icem_plan_host(const gmpc_icem_opts* opts, int T, int* N_it, float* cw);
 
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
