@@ -331,6 +331,7 @@ extern "C" int gmpc_set_params(gmpc_ctx* c, const float* mpc_w, const float* dyn
   c->mpc_w = mpc_w;
   c->solB = 0;   // a held solution belongs to the previous parameters
   c->gradB = 0;
+  c->w16_stale = true;   // the bf16 images of the sampled rollouts: rebuilt by the next bf16-mode solve
   bind_mlp(c->cost, c->sh.cost_layers, c->sh.cost_dims, cost, c->costT);
   transpose_mlp(c->cost, s);
   if (c->dynl) {

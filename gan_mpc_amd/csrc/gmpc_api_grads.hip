@@ -238,6 +238,8 @@ extern "C" int gmpc_mppi_vjp(gmpc_ctx* c, int B, const float* x0, const float* g
   TRY(check_call(c, B));
   const gmpc_shape& sh = c->sh;
   TRY(gmpc_sampled_coverage(c, "mppi"));
+  // the derivative of the fp32 solve: its rows are re-rolled in fp32, which a bf16-mode forward pass did not see
+  if (c->sampled_precision != GMPC_SAMPLED_FP32) return fail(GMPC_EINVAL, "mppi vjp: fp32 sampled rollouts only");
   TRY(gmpc_mppi_check_opts(o));
   if (!x0 || !goal || !std || !U || !X) return fail(GMPC_EINVAL, "mppi: x0, goal, std, U and X must not be null");
   if (o->max_iter > 0 && (!means_trace || !costs_trace))

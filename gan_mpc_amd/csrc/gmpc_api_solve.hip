@@ -358,6 +358,52 @@ int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who) {
   return 0;
 }
 
+extern "C" int gmpc_set_sampled_precision(gmpc_ctx* c, int precision) {
+  if (!c) return fail(GMPC_EINVAL, "ctx is null");
+  if (precision != GMPC_SAMPLED_FP32 && precision != GMPC_SAMPLED_BF16)
+    return fail(GMPC_EINVAL, "sampled precision: %d is neither GMPC_SAMPLED_FP32 (0) nor GMPC_SAMPLED_BF16 (1)",
+                precision);
+  c->sampled_precision = precision;
+  return 0;
+}
+
+// bf16 mode: the packed bf16 images of both MLPs, allocated by the first call and packed again behind
+// every gmpc_set_params (one launch on `s`, ahead of the solve's own); called behind gmpc_sampled_coverage
+int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s) {
+  if (c->sampled_precision != GMPC_SAMPLED_BF16) return 0;
+  const gmpc_shape& sh = c->sh;
+  if (!c->w16) {
+    __bf16* p = nullptr;
+    TRY(dalloc(c, &p, gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims) +
+                          gmpc_bf16_image_elems(sh.cost_layers, sh.cost_dims)));
+    c->w16 = p;
+    c->w16_stale = true;
+  }
+  if (c->w16_stale) {
+    gmpc_bind_bf16_images(c->dyn16, c->dyn, c->w16);
+    gmpc_bind_bf16_images(c->cost16, c->cost,
+                          static_cast<__bf16*>(c->w16) + gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims));
+    gmpc_launch_pack_bf16(c->dyn, c->dyn16, c->cost, c->cost16, s);
+    HIP_TRY(hipGetLastError());
+    c->w16_stale = false;
+  }
+  return 0;
+}
+
+// One launch over sampled rows in the context's precision (bf16 mode: the same arguments over the packed images)
+static int launch_sampled_rows(const gmpc_ctx* c, const CemRollArgs& r, hipStream_t s) {
+  if (c->sampled_precision != GMPC_SAMPLED_BF16) return gmpc_launch_cem_rollout(r, s);
+  CemRollArgs h = r;
+  h.dyn = c->dyn16; h.cost = c->cost16;
+  return gmpc_launch_cem_rollout_bf16(h, s);
+}
+static int launch_sampled_rows(const gmpc_ctx* c, const IcemRollArgs& r, hipStream_t s) {
+  if (c->sampled_precision != GMPC_SAMPLED_BF16) return gmpc_launch_icem_rollout(r, s);
+  IcemRollArgs h = r;
+  h.c.dyn = c->dyn16; h.c.cost = c->cost16;
+  return gmpc_launch_icem_rollout_bf16(h, s);
+}
+
 // The cross-entropy method: 2 max_iter + 1 launches on the caller's stream, nothing waited for.
 // Stateless: it writes the caller's arrays and the call workspace only, so a held solution survives it.
 extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
@@ -378,6 +424,7 @@ extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* 
   if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
     return fail(GMPC_EINVAL, "cem: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (o->max_iter > 0) TRY(gmpc_sampled_prepare(c, s));
   const int N = o->num_samples;
   float* cost_buf = costs;
   if (!cost_buf && o->max_iter > 0) {
@@ -404,7 +451,7 @@ extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* 
     r.samples = last ? samples : nullptr;
     u.rng = r.rng;
     u.elites = last ? elites : nullptr;
-    if (gmpc_launch_cem_rollout(r, s) || gmpc_launch_cem_update(u, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
+    if (launch_sampled_rows(c, r, s) || gmpc_launch_cem_update(u, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
   }
   if (X || obj) {
     // the final mean's own rollout: one row per problem, no noise, no clamp
@@ -456,6 +503,7 @@ extern "C" int gmpc_mppi_solve(gmpc_ctx* c, int B, const float* x0, const float*
   TRY(gmpc_mppi_check_opts(o));
   if (!x0 || !goal || !mean_io || !std) return fail(GMPC_EINVAL, "mppi: x0, goal, mean_io and std must not be null");
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (o->max_iter > 0) TRY(gmpc_sampled_prepare(c, s));
   const int N = o->num_samples;
   const size_t BN = (size_t)B * N, BTm = (size_t)B * sh.T * sh.m;
   float* cost_buf = costs;
@@ -484,7 +532,7 @@ extern "C" int gmpc_mppi_solve(gmpc_ctx* c, int B, const float* x0, const float*
     u.costs_copy = last && costs_trace ? costs : nullptr;
     u.weights = last ? weights : nullptr;
     u.mean_trace = means_trace ? means_trace + (size_t)i * BTm : nullptr;
-    if (gmpc_launch_cem_rollout(r, s) || gmpc_launch_mppi_update(u, s))
+    if (launch_sampled_rows(c, r, s) || gmpc_launch_mppi_update(u, s))
       return fail(GMPC_EINVAL, "mppi: shape not covered");
   }
   if (X || obj) {
@@ -574,6 +622,7 @@ extern "C" int gmpc_icem_solve(gmpc_ctx* c, int B, const float* x0, const float*
     return fail(GMPC_EINVAL, "icem: best_U_io, best_cost_io and U_out must not be null with return_best");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int N = o->num_samples, nk = o->num_keep, K = o->max_iter, T = sh.T, m = sh.m;
+  if (K > 0) TRY(gmpc_sampled_prepare(c, s));
   const int ldc = N + nk + 1;
   const size_t BTm = (size_t)B * T * m, keep_floats = (size_t)B * nk * T * m;
   std::vector<int> Nit(K > 0 ? K : 1);
@@ -611,7 +660,8 @@ extern "C" int gmpc_icem_solve(gmpc_ctx* c, int B, const float* x0, const float*
   r.c.rng.beta = 0.f; r.c.rng.cbeta = 1.f;
   r.c.costs = cost_buf;
   r.ldc = ldc;
-  r.zlds = !white && gmpc_icem_zlds(T, m);
+  r.zlds = !white &&
+           gmpc_icem_zlds(T, m, c->sampled_precision == GMPC_SAMPLED_BF16);
   r.p.nkeep = nk; r.p.white = white; r.p.cw = white ? nullptr : c->icem_cw;
   IcemUpdArgs u;
   memset(&u, 0, sizeof(u));
@@ -633,7 +683,7 @@ extern "C" int gmpc_icem_solve(gmpc_ctx* c, int B, const float* x0, const float*
     u.elites = last ? elites : nullptr;
     u.last = last;
     u.keep_out = nk == 0 ? nullptr : last ? keep_io : W[i & 1];
-    if (gmpc_launch_icem_rollout(r, s) || gmpc_launch_icem_update(u, s))
+    if (launch_sampled_rows(c, r, s) || gmpc_launch_icem_update(u, s))
       return fail(GMPC_EINVAL, "icem: shape not covered");
     keep_src = u.keep_out;
   }

@@ -8,6 +8,9 @@
 //                   registers (the accumulator layout of dg_gemm), the layer inputs in LDS, every dynamics / cost layer
 //                   on v_mfma_f32_16x16x4_f32 (dg_gemm, gmpc_dg_gemm.h), weights streamed from L2.  Its body is
 //                   cem_rollout_body (gmpc_cem_rollout.h), which k_icem_rollout (gmpc_icem.hip) shares.
+//   k_cem_rollout_bf16  the same body with bf16 matrix operands (gmpc_set_sampled_precision):
+//                   dg_gemm_bf16 on v_mfma_f32_16x16x32_bf16 over packed bf16 weight images, a bf16 operand block in
+//                   LDS behind the fp32 one.
 //   k_cem_update    one workgroup per problem: bitonic sort of 64-bit (cost, index) keys in LDS, then the elites'
 //                   sums in rank order, one (step, control) per thread.
 #include "gmpc_cem_rollout.h"
@@ -38,7 +41,16 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_cem_rollout(CemRollArgs a) 
   extern __shared__ __attribute__((aligned(16))) char smem_cem[];
   float* Ab = reinterpret_cast<float*>(smem_cem);   // [32][GMPC_DG_LDA]: the layer inputs of the 32 sample rows
   CemDrawn src{a, nullptr, nullptr};
-  cem_rollout_body(a, a.N, a.N, Ab, src);
+  cem_rollout_body<false>(a, a.N, a.N, Ab, nullptr, src);
+}
+
+// The same rows with bf16 matrix operands: a.dyn.W / a.cost.W are the packed bf16 images
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_cem_rollout_bf16(CemRollArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_cem16[];
+  float* Ab = reinterpret_cast<float*>(smem_cem16);   // [32][GMPC_DG_LDA] fp32: [x_t; u_t], the last cost output
+  __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);   // [32][GMPC_DG_LDH]: the layer inputs
+  CemDrawn src{a, nullptr, nullptr};
+  cem_rollout_body<true>(a, a.N, a.N, Ab, Hb, src);
 }
 
 // ---- the update -----------------------------------------------------------------------------------------------
@@ -74,15 +86,26 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_cem_update(CemUpdArgs a, in
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-int gmpc_launch_cem_rollout(const CemRollArgs& a, hipStream_t s) {
+static int cem_rollout_covered(const CemRollArgs& a) {
   for (int l = 0; l <= a.dyn.L; ++l)
-    if (a.dyn.dims[l] > 256) return 1;
+    if (a.dyn.dims[l] > 256) return 0;
   for (int l = 0; l <= a.cost.L; ++l)
-    if (a.cost.dims[l] > 256) return 1;
-  if (a.n + a.m > 256 || a.N < 1 || a.N > GMPC_CEM_MAX_N) return 1;
+    if (a.cost.dims[l] > 256) return 0;
+  return !(a.n + a.m > 256 || a.N < 1 || a.N > GMPC_CEM_MAX_N);
+}
+
+int gmpc_launch_cem_rollout(const CemRollArgs& a, hipStream_t s) {
+  if (!cem_rollout_covered(a)) return 1;
   const int tiles = (a.N + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
   const size_t lds = GMPC_CEM_ROWS * GMPC_DG_LDA * sizeof(float);
   hipLaunchKernelGGL(k_cem_rollout, dim3(a.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
+  return 0;
+}
+
+int gmpc_launch_cem_rollout_bf16(const CemRollArgs& a, hipStream_t s) {
+  if (!cem_rollout_covered(a) || a.mean_row) return 1;     // (the returned sequence's rollout is the fp32 kernel's)
+  const int tiles = (a.N + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
+  hipLaunchKernelGGL(k_cem_rollout_bf16, dim3(a.B * tiles), dim3(GMPC_DG_THREADS), GMPC_CEM_LDS16, s, a);
   return 0;
 }
 

@@ -7,6 +7,10 @@
 
 #define GMPC_CEM_ROWS 32          // samples per workgroup of the rollout (the two row halves of dg_gemm)
 #define GMPC_CEM_MAX_N 4096       // rows per problem (the sort's keys: 32 KiB of LDS)
+// LDS of the rollout's operand blocks, in bytes: the fp32 block [32][GMPC_DG_LDA]; in bf16 mode the bf16 block
+// [32][GMPC_DG_LDH] behind it (33,280 + 16,896 = 50,176: three workgroups per compute unit, as the registers allow)
+#define GMPC_CEM_LDS32 (GMPC_CEM_ROWS * GMPC_DG_LDA * 4)
+#define GMPC_CEM_LDS16 (GMPC_CEM_LDS32 + GMPC_CEM_ROWS * GMPC_DG_LDH * 2)
 
 // ---- the rollout ----------------------------------------------------------------------------------------------
 // Sum over the 8 lanes of a row's group (lanes 8 i .. 8 i + 7 of a wave), the same value in each: a fixed butterfly,
@@ -34,14 +38,49 @@ __device__ __forceinline__ void cem_store_tiles(float* Ab, const DgTiles& v, int
   }
 }
 
+// The bf16 mode's stores.  Columns 0 .. Kp-1 of the 32 rows of the bf16 operand block Hb, f's
+// values rounded to bf16 (to nearest even; a NaN stays one) in columns below N and zeros from N on -- the k-tail a
+// product pads to, whatever a wider layer left there; with F32 also the fp32 values into columns 0 .. N-1 of Ab
+// (what the cost terms read); without H16 only those.
+template <bool F32, bool H16, typename F>
+__device__ __forceinline__ void cem_store_tiles16(float* Ab, __bf16* Hb, const DgTiles& v, int N, int Kp, int wave,
+                                                  int lane, F f) {
+  const int l16 = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci) {
+    const int j = (wave + 4 * ci) * 16 + l16;
+    if (j >= Kp) continue;
+    const bool in = j < N;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const float x = in ? f(v.p[ci][rr], j) : 0.f, y = in ? f(v.q[ci][rr], j) : 0.f;
+      if constexpr (H16) {
+        Hb[(4 * kq + rr) * GMPC_DG_LDH + j] = static_cast<__bf16>(x);
+        Hb[(16 + 4 * kq + rr) * GMPC_DG_LDH + j] = static_cast<__bf16>(y);
+      }
+      if constexpr (F32) {
+        if (in) {
+          Ab[(4 * kq + rr) * GMPC_DG_LDA + j] = x;
+          Ab[(16 + 4 * kq + rr) * GMPC_DG_LDA + j] = y;
+        }
+      }
+    }
+  }
+}
+
 // One 256-thread workgroup per 32 rows of one problem, the whole horizon.  `rows` rows per problem, costs [B][ldc];
 // Ab: the [32][GMPC_DG_LDA] operand block at the start of the dynamic LDS.  Src, where the controls come from:
 //   begin(b, s0, tid)         once, before the first step (it may fill LDS behind the operand block and synchronise)
 //   control(b, i, s, t, j)    the control j of step t of row s = s0 + i of problem b
 //   record(b, s, t, j, u)     the debug copy of that control, if the caller asked for one
 // A row's cost is a function of its controls alone: not of its place in the tile, of `rows` or of B.
-template <typename Src>
-__device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows, int ldc, float* Ab, Src& src) {
+// BF16: the layer inputs are rounded to bf16 into Hb, the [32][GMPC_DG_LDH] block behind Ab,
+// the layers run on dg_gemm_bf16, and dyn.W[l] / cost.W[l] point at the layers' packed bf16 images (dg_kp, dg_np);
+// Ab keeps the fp32 [x_t; u_t] and the last cost layer's output, which the cost terms read as before.  Without BF16
+// Hb is not used.
+template <bool BF16, typename Src>
+__device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows, int ldc, float* Ab, __bf16* Hb,
+                                                 Src& src) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
   const int n = a.n, m = a.m, T = a.T;
   const int tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
@@ -65,12 +104,27 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
   DgTiles acc;
   for (int t = 0; t < T; ++t) {
     // ---- layer 0 input [x_t; u_t]
-    cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
-    for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
-      const int i = e / m, j = e - i * m, s = s0 + i;
-      const float u = src.control(b, i, s, t, j);
-      Ab[i * GMPC_DG_LDA + n + j] = u;
-      src.record(b, s, t, j, u);
+    if constexpr (BF16) {
+      cem_store_tiles16<true, true>(Ab, Hb, xs, n, n, wave, lane, [](float v, int) { return v; });
+      const int w = dg_kp(n + m) - n;     // the controls' columns and the zeros behind them
+      for (int e = tid; e < GMPC_CEM_ROWS * w; e += GMPC_DG_THREADS) {
+        const int i = e / w, j = e - i * w, s = s0 + i;
+        float u = 0.f;
+        if (j < m) {
+          u = src.control(b, i, s, t, j);
+          Ab[i * GMPC_DG_LDA + n + j] = u;
+          src.record(b, s, t, j, u);
+        }
+        Hb[i * GMPC_DG_LDH + n + j] = static_cast<__bf16>(u);
+      }
+    } else {
+      cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+      for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
+        const int i = e / m, j = e - i * m, s = s0 + i;
+        const float u = src.control(b, i, s, t, j);
+        Ab[i * GMPC_DG_LDA + n + j] = u;
+        src.record(b, s, t, j, u);
+      }
     }
     __syncthreads();
     // ---- stage cost of (x_t, u_t) against goal_t
@@ -90,11 +144,18 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     // ---- x_{t+1} = x_t + MLP([x_t; u_t])
     for (int l = 0; l < a.dyn.L; ++l) {
       const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
-      dg_gemm(Ab, K, Nl, a.dyn.W[l], wave, lane, acc);
+      if constexpr (BF16)
+        dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(a.dyn.W[l]), wave, lane, acc);
+      else
+        dg_gemm(Ab, K, Nl, a.dyn.W[l], wave, lane, acc);
       __syncthreads();   // every wave has read its operand rows (and the stage cost its row)
       const float* bias = a.dyn.b[l];
       if (l < a.dyn.L - 1) {
-        cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); });
+        auto act = [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); };
+        if constexpr (BF16)
+          cem_store_tiles16<false, true>(Ab, Hb, acc, Nl, dg_kp(Nl), wave, lane, act);
+        else
+          cem_store_tiles(Ab, acc, Nl, wave, lane, act);
         __syncthreads();
       } else {
 #pragma unroll
@@ -113,17 +174,32 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     }
   }
   // ---- terminal cost w2 |MLP_c(x_T)|^2
-  cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+  if constexpr (BF16)
+    cem_store_tiles16<false, true>(Ab, Hb, xs, n, dg_kp(n), wave, lane, [](float v, int) { return v; });
+  else
+    cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
   __syncthreads();
   for (int l = 0; l < a.cost.L; ++l) {
     const int K = a.cost.dims[l], Nl = a.cost.dims[l + 1];
-    dg_gemm(Ab, K, Nl, a.cost.W[l], wave, lane, acc);
+    if constexpr (BF16)
+      dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(a.cost.W[l]), wave, lane, acc);
+    else
+      dg_gemm(Ab, K, Nl, a.cost.W[l], wave, lane, acc);
     __syncthreads();
     const float* bias = a.cost.b[l];
-    if (l < a.cost.L - 1)
-      cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); });
-    else
-      cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return v + bias[j]; });
+    auto act = [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); };
+    auto lin = [bias](float v, int j) { return v + bias[j]; };
+    if constexpr (BF16) {
+      if (l < a.cost.L - 1)
+        cem_store_tiles16<false, true>(Ab, Hb, acc, Nl, dg_kp(Nl), wave, lane, act);
+      else
+        cem_store_tiles16<true, false>(Ab, Hb, acc, Nl, Nl, wave, lane, lin);     // fp32, unrounded: what |y|^2 reads
+    } else {
+      if (l < a.cost.L - 1)
+        cem_store_tiles(Ab, acc, Nl, wave, lane, act);
+      else
+        cem_store_tiles(Ab, acc, Nl, wave, lane, lin);
+    }
     __syncthreads();
   }
   {

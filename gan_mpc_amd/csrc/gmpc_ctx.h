@@ -113,6 +113,13 @@ struct gmpc_ctx {
   float* icem_cw = nullptr;
   float icem_cw_beta = -1.f;
   std::vector<float> icem_cw_host;
+  // gmpc_set_sampled_precision: the operand precision of the sampling solvers' sampled rollouts.  In bf16
+  // mode dyn16 / cost16 are dyn / cost with W[l] pointing at the layers' packed bf16 images in w16 (allocated by the
+  // first bf16-mode solve); gmpc_set_params marks them stale, the next bf16-mode solve packs them on its stream.
+  int sampled_precision = GMPC_SAMPLED_FP32;
+  void* w16 = nullptr;
+  bool w16_stale = true;
+  MlpDesc dyn16{}, cost16{};
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;
@@ -208,6 +215,8 @@ int check_call(gmpc_ctx* c, int B, bool need_params = true);
 // gmpc_api_solve.hip: the sampling solvers' shared checks (`who`: the message's prefix) and MPPI's noise stream of
 // iteration iter_offset + i
 int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who);
+// in bf16 mode: the packed weight images brought up to date on `s` (allocated on first use); nothing in fp32 mode
+int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s);
 int gmpc_mppi_check_opts(const gmpc_mppi_opts* o);
 CemRng gmpc_mppi_rng(const gmpc_mppi_opts* o, int i);
 // gmpc_api_critic.hip: the upper-level loss at the solution held by the ctx (and, with want_lx, its gradient in c->lx)

@@ -106,7 +106,17 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout(IcemRollArgs a
   extern __shared__ __attribute__((aligned(16))) char smem_icem[];
   float* Ab = reinterpret_cast<float*>(smem_icem);  // [32][GMPC_DG_LDA]: the layer inputs of the 32 pool rows
   IcemDrawn src{a, Ab + GMPC_CEM_ROWS * GMPC_DG_LDA, nullptr, nullptr, nullptr};
-  cem_rollout_body(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, src);
+  cem_rollout_body<false>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, nullptr, src);
+}
+
+// The same rows with bf16 matrix operands: a.c.dyn.W / a.c.cost.W are the packed bf16 images,
+// and the normals of zlds lie behind both operand blocks
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_bf16(IcemRollArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_icem16[];
+  float* Ab = reinterpret_cast<float*>(smem_icem16);
+  __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);
+  IcemDrawn src{a, reinterpret_cast<float*>(smem_icem16 + GMPC_CEM_LDS16), nullptr, nullptr, nullptr};
+  cem_rollout_body<true>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, Hb, src);
 }
 
 // ---- the update -----------------------------------------------------------------------------------------------
@@ -212,7 +222,7 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_update(IcemUpdArgs a, 
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s) {
+static int icem_launch_rollout(const IcemRollArgs& a, bool bf16, hipStream_t s) {
   const CemRollArgs& c = a.c;
   for (int l = 0; l <= c.dyn.L; ++l)
     if (c.dyn.dims[l] > 256) return 1;
@@ -224,17 +234,25 @@ int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s) {
     return 1;
   if (a.p.carry > 0 && !a.p.keep) return 1;
   if (!a.p.white && !a.p.cw) return 1;
-  size_t lds = GMPC_CEM_ROWS * GMPC_DG_LDA * sizeof(float);
+  size_t lds = bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32;
   if (a.zlds) lds += (size_t)GMPC_CEM_ROWS * c.m * c.T * sizeof(float);
   if (lds > GMPC_ICEM_LDS_BYTES) return 1;
   const int tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
-  hipLaunchKernelGGL(k_icem_rollout, dim3(c.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
+  if (bf16)
+    hipLaunchKernelGGL(k_icem_rollout_bf16, dim3(c.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
+  else
+    hipLaunchKernelGGL(k_icem_rollout, dim3(c.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
   return 0;
 }
 
-// The shapes whose normals k_icem_rollout forms once per tile in LDS: 32 m T floats beside the operand block
-int gmpc_icem_zlds(int T, int m) {
-  return (size_t)GMPC_CEM_ROWS * (GMPC_DG_LDA + (size_t)m * T) * sizeof(float) <= GMPC_ICEM_LDS_BYTES;
+int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s) { return icem_launch_rollout(a, false, s); }
+int gmpc_launch_icem_rollout_bf16(const IcemRollArgs& a, hipStream_t s) { return icem_launch_rollout(a, true, s); }
+
+// The shapes whose normals k_icem_rollout forms once per tile in LDS: 32 m T floats beside the operand block (bf16:
+// beside both blocks of k_icem_rollout_bf16; the controls are the same either way)
+int gmpc_icem_zlds(int T, int m, int bf16) {
+  return (size_t)(bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32) + (size_t)GMPC_CEM_ROWS * m * T * sizeof(float) <=
+         GMPC_ICEM_LDS_BYTES;
 }
 
 int gmpc_launch_icem_update(const IcemUpdArgs& a0, hipStream_t s) {

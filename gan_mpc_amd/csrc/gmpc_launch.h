@@ -281,8 +281,21 @@ struct IcemUpdArgs {
 // CEM's shapes and Nit + carry + addmean <= 4096: non-zero (nothing launched) otherwise
 int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s);
 int gmpc_launch_icem_update(const IcemUpdArgs& a, hipStream_t s);
-// non-zero where 32 m T floats fit in LDS beside the rollout's operand block (what zlds may be set for)
-int gmpc_icem_zlds(int T, int m);
+// non-zero where 32 m T floats fit in LDS beside the rollout's operand block (what zlds may be set for); bf16: beside
+// the two blocks of the bf16 kernel
+int gmpc_icem_zlds(int T, int m, int bf16 = 0);
+
+// The sampled rollouts with bf16 matrix operands: k_cem_rollout_bf16 / k_icem_rollout_bf16, the same
+// rows, controls and cost terms; dyn.W[l] / cost.W[l] of the arguments point at the layers' packed bf16 images
+// (MlpDesc::W reinterpreted), which gmpc_launch_pack_bf16 builds.  Never the mean_row form.
+int gmpc_launch_cem_rollout_bf16(const CemRollArgs& a, hipStream_t s);
+int gmpc_launch_icem_rollout_bf16(const IcemRollArgs& a, hipStream_t s);
+// gmpc_sampled_bf16.hip: bf16 elements of the packed images of an MLP's layers (each a multiple of 8), and the pack
+// of the fp32 weights src.W[l] into the images img.W[l] (one launch for both MLPs)
+size_t gmpc_bf16_image_elems(int L, const int* dims);
+void gmpc_bind_bf16_images(MlpDesc& img, const MlpDesc& src, void* base);
+void gmpc_launch_pack_bf16(const MlpDesc& dyn, const MlpDesc& dyn_img, const MlpDesc& cost, const MlpDesc& cost_img,
+                           hipStream_t s);
 
 // gmpc_mppi.hip: the path-integral update on k_cem_rollout's costs, and its adjoint ------------------
 // k_mppi_update: w_s = exp(-(costs_s - min) / lam) over the finite costs [B][N], mean <- gamma mean + (1 - gamma)

@@ -330,6 +330,19 @@ class Engine:
             cache[key] = (None if lo is None else self.to_dev(lo), None if hi is None else self.to_dev(hi))
         return (lo, hi) + cache[key]
 
+    SAMPLED_PRECISIONS = {"fp32": 0, "bf16": 1}     # GMPC_SAMPLED_FP32 / GMPC_SAMPLED_BF16
+
+    def set_sampled_precision(self, precision):
+        """The operand precision of the sampled rollouts of cem_solve / mppi_solve / icem_solve on this engine
+        (gmpc_set_sampled_precision): "fp32" (the default) or "bf16" -- the dynamics and cost
+        layers of every sampled row on the bf16 matrix instruction (weights and layer inputs rounded to bf16, fp32
+        accumulation, states and cost terms in fp32).  The samples are bitwise those of "fp32"; the costs, and with
+        them the elites, the weights and icem_solve's best_cost, are bf16-mode costs; X and obj are always the fp32
+        rollout of the returned U.  mppi_vjp is refused in "bf16" mode.  No device work."""
+        if not isinstance(precision, str) or precision not in self.SAMPLED_PRECISIONS:
+            raise _lib.GmpcError(f'sampled precision: {precision!r} is neither "fp32" nor "bf16"')
+        _lib.check(self.lib.gmpc_set_sampled_precision(self.ctx, self.SAMPLED_PRECISIONS[precision]))
+
     CEM_WANT = ("costs", "elites", "samples")
 
     def cem_solve(self, x0, U_init, goal, u_lo, u_hi, kwargs=None, init_std=None, want=(), iter_offset=0):

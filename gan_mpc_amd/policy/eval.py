@@ -48,7 +48,7 @@ class EvalMPC:
 
     def __init__(self, config, cost_model, dynamics_model, expert_model,
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None,
-                 cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None):
+                 cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None, sampled_precision=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
@@ -63,7 +63,10 @@ class EvalMPC:
         training calls raise NotImplementedError too and name policy.differentiable.mppi_layer, the way to train;
         "icem" -- gmpc_icem_solve, the sample-efficient cross-entropy method under control_bounds with the keywords
         icem_kwargs (engine.ICEM_KWARGS plus the policy keyword shift_elites, default True: the next solve of the same
-        batch shape carries the previous solve's kept rows, shifted one step), handled like "cem"."""
+        batch shape carries the previous solve's kept rows, shifted one step), handled like "cem".
+        sampled_precision: None, "fp32" or "bf16" -- with a "cem" / "mppi" / "icem" solver, the operand precision of
+        the sampled rollouts (Engine.set_sampled_precision, DESIGN §23), set wherever the policy binds its engine;
+        None leaves the engine's default, "fp32"."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
         if (solver in ("box", "cem", "mppi", "icem")) != (control_bounds is not None):
@@ -81,6 +84,11 @@ class EvalMPC:
         unknown = set(icem_kwargs or {}) - set(ICEM_KWARGS) - {"shift_elites"}
         if unknown:
             raise ValueError(f"icem_kwargs has unknown keyword(s) {sorted(unknown)}")
+        if sampled_precision is not None and solver not in ("cem", "mppi", "icem"):
+            raise ValueError('sampled_precision and solver="cem" / "mppi" / "icem" go together: got '
+                             f"solver={solver!r}")
+        if sampled_precision not in (None, "fp32", "bf16"):
+            raise ValueError(f'sampled_precision must be None, "fp32" or "bf16", got {sampled_precision!r}')
         if control_bounds is not None and len(control_bounds) != 2:
             raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
@@ -98,6 +106,7 @@ class EvalMPC:
         self.icem_kwargs = {**ICEM_KWARGS, "shift_elites": True, **(icem_kwargs or {})}
         self.icem_solves = 0      # the same for an "icem" policy
         self._icem_state = None   # shift_elites: the previous solve's state (its kept rows)
+        self.sampled_precision = sampled_precision
         self.critic_model = getattr(self, "critic_model", None)
         self._device = device
         self._engine = None
@@ -158,6 +167,8 @@ class EvalMPC:
         eng = self.engine_for(batch, dparams)
         eng.set_params(dparams.view("mpc_weights"), dparams.view("dynamics_params"),
                        dparams.view("cost_params"))
+        if self.sampled_precision is not None:
+            eng.set_sampled_precision(self.sampled_precision)
         return eng
 
     # ---- reference API ----------------------------------------------------------------------

@@ -381,6 +381,23 @@ int gmpc_icem_solve(gmpc_ctx* ctx, int B, const float* x0, const float* goal,
                     void* stream);
 int gmpc_icem_plan_host(const gmpc_icem_opts* opts, int T, int* N_it, float* cw);
 
+/* The operand precision of the sampling solvers' sampled rollouts: a property of the context, fp32 until set.  No
+ * stream, no device work; any other value is GMPC_EINVAL ("sampled precision: ...").
+ *   GMPC_SAMPLED_BF16: every launch of gmpc_cem_solve / gmpc_mppi_solve / gmpc_icem_solve that rolls out SAMPLED rows
+ *   runs the dynamics and cost layers on v_mfma_f32_16x16x32_bf16: the weight matrices rounded once to bf16 (to nearest
+ *   even; biases stay fp32), every layer input ([x_t; u_t], the relu outputs, x_T) rounded to bf16 when it becomes a
+ *   matrix operand, products accumulated in fp32; the bias add, the relu, the residual x += out + b (the states stay
+ *   fp32 across steps), the controls, the stage cost (fp32 x_t, u_t, goal) and the terminal w2 |y|^2 (the fp32,
+ *   unrounded output of the last cost layer) are what they are in fp32 mode.  `samples` is bitwise the fp32 mode's;
+ *   `costs` (and so the elites, the weights and iCEM's best_cost_io) are the bf16-mode costs.  The returned sequence's
+ *   own rollout always runs in fp32: X and obj are those of the true model at the returned controls in either mode.
+ *   The bf16 weight image is built by the first bf16-mode solve after a gmpc_set_params, on that solve's stream
+ *   (gmpc_set_params only marks it stale): weights changed in place need a gmpc_set_params, as for every other derived
+ *   copy.  gmpc_mppi_vjp is the derivative of the fp32 solve and is refused in bf16 mode ("mppi vjp: fp32 sampled
+ *   rollouts only").  Coverage and refusals are those of fp32 mode. */
+enum { GMPC_SAMPLED_FP32 = 0, GMPC_SAMPLED_BF16 = 1 };
+int gmpc_set_sampled_precision(gmpc_ctx* ctx, int precision);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
