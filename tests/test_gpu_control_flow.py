@@ -206,13 +206,15 @@ def test_each_threshold_of_the_continuation_criterion(kw):
     eng.close()
 
 
-def _noop_check(eng, pb, kw, stop):
+def _noop_check(eng, pb, kw, stop, more_keys=()):
+    """more_keys: outputs of ilqr_solve compared on top of X, U, obj, iterations (e.g. "grad", "adjoints")"""
     d = eng.to_dev
+    keys = ("X", "U", "obj", "iterations") + tuple(more_keys)
     ref = eng.ilqr_solve(d(pb["x0"]), d(pb["U"]), d(pb["goal"]), dict(kw, maxiter=stop))
-    snap = {k: ref[k].clone() for k in ("X", "U", "obj", "iterations")}
+    snap = {k: ref[k].clone() for k in keys}
     for extra in (POLL_DEPTH, 20):
         more = eng.ilqr_solve(d(pb["x0"]), d(pb["U"]), d(pb["goal"]), dict(kw, maxiter=stop + extra))
-        for k in ("X", "U", "obj", "iterations"):
+        for k in keys:
             assert torch.equal(more[k], snap[k]), f"maxiter = {stop} + {extra}: {k} changed after the last stop"
 
 

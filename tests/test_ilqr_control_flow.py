@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import control_flow_cases as cfc
 import gan_mpc_oracle as orc
 import torch_ref as tr
 
@@ -29,7 +30,9 @@ def _both(pb, kw, U=None):
     trace = []
     with np.errstate(all="ignore"):
         r = orc.ilqr(pb["dyn"], pb["cmlp"], pb["mpc_w"], pb["goal"], pb["x0"], U, kw, trace=trace)
-    dyn, cm, w = tr.layers64(pb["dyn"]), tr.layers64(pb["cmlp"]), tr.t64(pb["mpc_w"])
+    lstm = isinstance(pb["dyn"], dict)          # the LSTM dynamics variant: dict(Wx, Wh, b, tail)
+    dyn = tr.lstm_dynamics64(pb["dyn"]) if lstm else tr.layers64(pb["dyn"])
+    cm, w = tr.layers64(pb["cmlp"]), tr.t64(pb["mpc_w"])
     scal = [tr.ilqr_scalar(dyn, cm, w, tr.t64(pb["goal"][b]), tr.t64(pb["x0"][b]), tr.t64(U[b]), kw)
             for b in range(U.shape[0])]
     return r, trace, scal
@@ -111,3 +114,16 @@ def test_members_stop_at_different_iterations_and_stay_frozen():
                      pb["U"][b:b + 1], kw)
     np.testing.assert_allclose(alone[1][0], r[1][b], rtol=1e-10)    # BLAS batch size changes the last bits
     assert alone[6][0] == r[6][b]
+
+
+# The oracle's ilqr OFF the small-state MLP shapes -- the arbiter of tests/test_gpu_control_flow_paths.py there: the
+# LSTM dynamics variant (state [x, c, h], goals with the x columns only) and more controls than states
+@pytest.mark.parametrize("name,seed,opts", [
+    ("dynl-small", 7, {"obj_step_threshold": 0.003}),
+    ("m40", 3, {"alpha_min": 0.01}),
+])
+def test_the_lstm_variant_and_more_controls_than_states(name, seed, opts):
+    pb = orc.cast_problem(cfc.problem(name, seed), np.float64)
+    r, trace, scal = _both(pb, dict(opts, maxiter=12))
+    _assert_same(r, trace, scal, rtol=1e-5)     # (as the threshold rows above: up to a dozen Newton steps)
+    assert len(set(r[6].tolist())) > 1 and r[6].max() < 12
