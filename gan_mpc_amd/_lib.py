@@ -140,6 +140,7 @@ SIGNATURES = {
                                   _P, _P, _P]),
     "gmpc_icem_plan_host": (C.c_int, [C.POINTER(IcemOpts), C.c_int, _P, _P]),
     "gmpc_set_sampled_precision": (C.c_int, [_P, C.c_int]),
+    "gmpc_set_sampled_ensemble": (C.c_int, [_P, C.c_int, _P]),
     "gmpc_box_qp_host":(C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_bilevel_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),

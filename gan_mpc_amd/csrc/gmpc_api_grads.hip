@@ -240,6 +240,8 @@ extern "C" int gmpc_mppi_vjp(gmpc_ctx* c, int B, const float* x0, const float* g
   TRY(gmpc_sampled_coverage(c, "mppi"));
   // the derivative of the fp32 solve: its rows are re-rolled in fp32, which a bf16-mode forward pass did not see
   if (c->sampled_precision != GMPC_SAMPLED_FP32) return fail(GMPC_EINVAL, "mppi vjp: fp32 sampled rollouts only");
+  // ... and of the nominal model's costs: under an ensemble the forward pass weighted the samples by other costs
+  if (c->ens_P > 0) return fail(GMPC_EINVAL, "mppi vjp: not while a sampled ensemble is set (nominal dynamics only)");
   TRY(gmpc_mppi_check_opts(o));
   if (!x0 || !goal || !std || !U || !X) return fail(GMPC_EINVAL, "mppi: x0, goal, std, U and X must not be null");
   if (o->max_iter > 0 && (!means_trace || !costs_trace))

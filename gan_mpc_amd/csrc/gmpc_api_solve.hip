@@ -367,6 +367,23 @@ extern "C" int gmpc_set_sampled_precision(gmpc_ctx* c, int precision) {
   return 0;
 }
 
+// The dynamics ensemble of the sampled rollouts: the pointer is kept, not owned, and nothing is launched
+extern "C" int gmpc_set_sampled_ensemble(gmpc_ctx* c, int P, const float* dyn_members) {
+  if (!c) return fail(GMPC_EINVAL, "ensemble: ctx is null");
+  if (P < 0 || P > GMPC_MAX_ENSEMBLE)
+    return fail(GMPC_EINVAL, "ensemble: P = %d outside [0, %d]", P, GMPC_MAX_ENSEMBLE);
+  if (P == 0) {
+    c->ens_P = 0;
+    return 0;
+  }
+  if (!dyn_members) return fail(GMPC_EINVAL, "ensemble: dyn_members is null with P = %d", P);
+  TRY(gmpc_sampled_coverage(c, "ensemble"));
+  bind_mlp(c->ens_dyn, c->sh.dyn_layers, c->sh.dyn_dims, dyn_members, nullptr);
+  c->ens_P = P;
+  c->ens16_stale = true;   // the members changed: their bf16 images are packed again by the next bf16-mode solve
+  return 0;
+}
+
 // bf16 mode: the packed bf16 images of both MLPs, allocated by the first call and packed again behind
 // every gmpc_set_params (one launch on `s`, ahead of the solve's own); called behind gmpc_sampled_coverage
 int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s) {
@@ -387,24 +404,77 @@ int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s) {
     HIP_TRY(hipGetLastError());
     c->w16_stale = false;
   }
+  if (c->ens_P > 0 && (c->ens16_stale || !c->ens16.p)) {
+    // the members' images, one behind the other (each a multiple of 8 elements): k_pack_bf16 once per member, the
+    // dynamics layers only (the cost MLP's image is the shared one above)
+    const size_t elems = gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims);
+    const long count = mlp_count(sh.dyn_layers, sh.dyn_dims);
+    TRY(c->ens16.grow(c, (size_t)c->ens_P * elems / 2));
+    gmpc_bind_bf16_images(c->ens_dyn16, c->ens_dyn, c->ens16.p);
+    MlpDesc none{};
+    for (int p = 0; p < c->ens_P; ++p) {
+      MlpDesc src = c->ens_dyn, img = c->ens_dyn16;
+      for (int l = 0; l < src.L; ++l) {
+        src.W[l] += (size_t)p * count;
+        img.W[l] += (size_t)p * (elems / 2);
+      }
+      gmpc_launch_pack_bf16(src, img, none, none, s);
+    }
+    HIP_TRY(hipGetLastError());
+    c->ens16_stale = false;
+  }
   return 0;
 }
 
-// One launch over sampled rows in the context's precision (bf16 mode: the same arguments over the packed images)
-static int launch_sampled_rows(const gmpc_ctx* c, const CemRollArgs& r, hipStream_t s) {
-  if (c->sampled_precision != GMPC_SAMPLED_BF16) return gmpc_launch_cem_rollout(r, s);
+// What the launches over sampled rows need under an ensemble: the members' strides in the context's precision and the
+// cost planes [P][B][ldc] in the call workspace
+static int ensemble_args(gmpc_ctx* c, int B, int ldc, CemEnsemble& e) {
+  const gmpc_shape& sh = c->sh;
+  const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
+  e.P = c->ens_P;
+  e.bstride = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims);
+  e.wstride = bf16 ? gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims) / 2 : e.bstride;
+  e.invP = 1.0f / (float)c->ens_P;
+  TRY(c->cw.part.grow(c, (size_t)c->ens_P * B * ldc));
+  e.part = c->cw.part.p;
+  return 0;
+}
+
+// One launch over sampled rows in the context's precision (bf16 mode: the same arguments over the packed images).
+// With an ensemble set: the rows under every member, then the reduce of the members' costs into r's.
+static int launch_sampled_rows(gmpc_ctx* c, const CemRollArgs& r, hipStream_t s) {
+  const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
+  if (c->ens_P > 0) {
+    CemEnsemble e;
+    if (ensemble_args(c, r.B, r.N, e)) return 1;
+    CemRollArgs h = r;
+    h.dyn = bf16 ? c->ens_dyn16 : c->ens_dyn;
+    if (bf16) h.cost = c->cost16;
+    return gmpc_launch_cem_rollout_ens(h, e, bf16, s);
+  }
+  if (!bf16) return gmpc_launch_cem_rollout(r, s);
   CemRollArgs h = r;
   h.dyn = c->dyn16; h.cost = c->cost16;
   return gmpc_launch_cem_rollout_bf16(h, s);
 }
-static int launch_sampled_rows(const gmpc_ctx* c, const IcemRollArgs& r, hipStream_t s) {
-  if (c->sampled_precision != GMPC_SAMPLED_BF16) return gmpc_launch_icem_rollout(r, s);
+static int launch_sampled_rows(gmpc_ctx* c, const IcemRollArgs& r, hipStream_t s) {
+  const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
+  if (c->ens_P > 0) {
+    CemEnsemble e;
+    if (ensemble_args(c, r.c.B, r.ldc, e)) return 1;
+    IcemRollArgs h = r;
+    h.c.dyn = bf16 ? c->ens_dyn16 : c->ens_dyn;
+    if (bf16) h.c.cost = c->cost16;
+    return gmpc_launch_icem_rollout_ens(h, e, bf16, s);
+  }
+  if (!bf16) return gmpc_launch_icem_rollout(r, s);
   IcemRollArgs h = r;
   h.c.dyn = c->dyn16; h.c.cost = c->cost16;
   return gmpc_launch_icem_rollout_bf16(h, s);
 }
 
-// The cross-entropy method: 2 max_iter + 1 launches on the caller's stream, nothing waited for.
+// The cross-entropy method: 2 max_iter + 1 launches on the caller's stream (3 max_iter + 1 under an
+// ensemble, DESIGN §24: the reduce of the members' costs), nothing waited for.
 // Stateless: it writes the caller's arrays and the call workspace only, so a held solution survives it.
 extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
                               const float* u_hi, const gmpc_cem_opts* o, float* mean_io, float* std_io, float* X,

@@ -11,6 +11,11 @@
 //   k_cem_rollout_bf16  the same body with bf16 matrix operands (gmpc_set_sampled_precision):
 //                   dg_gemm_bf16 on v_mfma_f32_16x16x32_bf16 over packed bf16 weight images, a bf16 operand block in
 //                   LDS behind the fp32 one.
+//   k_cem_rollout_ens, k_cem_rollout_ens_bf16  the same body under every member of a dynamics ensemble
+//                   (gmpc_set_sampled_ensemble): blockIdx.y is the member, whose weights the
+//                   workgroup reads and whose plane of the call workspace takes its costs
+//   k_ens_reduce    one thread per (problem, row): the members' costs summed in member order, times 1 / P, into the
+//                   cost buffer the update kernels read (shared with gmpc_icem.hip)
 //   k_cem_update    one workgroup per problem: bitonic sort of 64-bit (cost, index) keys in LDS, then the elites'
 //                   sums in rank order, one (step, control) per thread.
 #include "gmpc_cem_rollout.h"
@@ -51,6 +56,36 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_cem_rollout_bf16(CemRollArg
   __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);   // [32][GMPC_DG_LDH]: the layer inputs
   CemDrawn src{a, nullptr, nullptr};
   cem_rollout_body<true>(a, a.N, a.N, Ab, Hb, src);
+}
+
+// The same rows under every member of a dynamics ensemble (gmpc_set_sampled_ensemble): the grid's
+// second dimension is the member, whose weights the workgroup reads and whose plane of e.part it writes
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_cem_rollout_ens(CemRollArgs a, CemMember e) {
+  extern __shared__ __attribute__((aligned(16))) char smem_cem_e[];
+  float* Ab = reinterpret_cast<float*>(smem_cem_e);
+  CemDrawn src{a, nullptr, nullptr};
+  cem_rollout_body<false>(a, a.N, a.N, Ab, nullptr, src, e);
+}
+
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_cem_rollout_ens_bf16(CemRollArgs a, CemMember e) {
+  extern __shared__ __attribute__((aligned(16))) char smem_cem_e16[];
+  float* Ab = reinterpret_cast<float*>(smem_cem_e16);
+  __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);
+  CemDrawn src{a, nullptr, nullptr};
+  cem_rollout_body<true>(a, a.N, a.N, Ab, Hb, src, e);
+}
+
+// The ensemble's cost of a row: the members' costs part [P][B][ldc] summed in ascending member order, times invP, into
+// costs [B][ldc]; one thread per (problem, row), rows below `rows` only (the rollouts wrote exactly those)
+__global__ __launch_bounds__(GMPC_THREADS) void k_ens_reduce(const float* __restrict__ part, int P, int B, int rows,
+                                                             int ldc, float invP, float* __restrict__ costs) {
+  const int i = blockIdx.x * GMPC_THREADS + threadIdx.x;
+  if (i >= B * rows) return;
+  const int b = i / rows, s = i - b * rows;
+  const size_t o = (size_t)b * ldc + s, plane = (size_t)B * ldc;
+  float sum = part[o];
+  for (int p = 1; p < P; ++p) sum = __fadd_rn(sum, part[p * plane + o]);
+  costs[o] = __fmul_rn(sum, invP);
 }
 
 // ---- the update -----------------------------------------------------------------------------------------------
@@ -106,6 +141,24 @@ int gmpc_launch_cem_rollout_bf16(const CemRollArgs& a, hipStream_t s) {
   if (!cem_rollout_covered(a) || a.mean_row) return 1;     // (the returned sequence's rollout is the fp32 kernel's)
   const int tiles = (a.N + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
   hipLaunchKernelGGL(k_cem_rollout_bf16, dim3(a.B * tiles), dim3(GMPC_DG_THREADS), GMPC_CEM_LDS16, s, a);
+  return 0;
+}
+
+void gmpc_launch_ens_reduce(const CemEnsemble& e, int B, int rows, int ldc, float* costs, hipStream_t s) {
+  const int blocks = (int)(((size_t)B * rows + GMPC_THREADS - 1) / GMPC_THREADS);
+  hipLaunchKernelGGL(k_ens_reduce, dim3(blocks), dim3(GMPC_THREADS), 0, s, e.part, e.P, B, rows, ldc, e.invP, costs);
+}
+
+// a.dyn: member 0 (bf16: its images); two launches, the members' rollouts and the reduce into a.costs
+int gmpc_launch_cem_rollout_ens(const CemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s) {
+  if (!cem_rollout_covered(a) || a.mean_row || a.X || e.P < 1 || e.P > GMPC_MAX_ENSEMBLE || !e.part) return 1;
+  const int tiles = (a.N + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
+  const CemMember mb{e.wstride, e.bstride, (size_t)a.B * a.N, e.part};
+  if (bf16)
+    hipLaunchKernelGGL(k_cem_rollout_ens_bf16, dim3(a.B * tiles, e.P), dim3(GMPC_DG_THREADS), GMPC_CEM_LDS16, s, a, mb);
+  else
+    hipLaunchKernelGGL(k_cem_rollout_ens, dim3(a.B * tiles, e.P), dim3(GMPC_DG_THREADS), GMPC_CEM_LDS32, s, a, mb);
+  gmpc_launch_ens_reduce(e, a.B, a.N, a.N, a.costs, s);
   return 0;
 }
 

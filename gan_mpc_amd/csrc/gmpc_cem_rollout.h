@@ -74,13 +74,37 @@ __device__ __forceinline__ void cem_store_tiles16(float* Ab, __bf16* Hb, const D
 //   control(b, i, s, t, j)    the control j of step t of row s = s0 + i of problem b
 //   record(b, s, t, j, u)     the debug copy of that control, if the caller asked for one
 // A row's cost is a function of its controls alone: not of its place in the tile, of `rows` or of B.
+// Ens, which dynamics network the workgroup rolls its rows out under and where their costs go:
+//   W(w) / b(v)               a dynamics layer's weights / biases, from the bound descriptor's pointers
+//   costs(c)                  the [B][ldc] plane the rows' costs are written to
+//   records()                 whether this workgroup writes the debug copy of the controls
+// CemOneModel: the arguments' own network and cost buffer (every kernel without an ensemble).
 // BF16: the layer inputs are rounded to bf16 into Hb, the [32][GMPC_DG_LDH] block behind Ab,
 // the layers run on dg_gemm_bf16, and dyn.W[l] / cost.W[l] point at the layers' packed bf16 images (dg_kp, dg_np);
 // Ab keeps the fp32 [x_t; u_t] and the last cost layer's output, which the cost terms read as before.  Without BF16
 // Hb is not used.
-template <bool BF16, typename Src>
+struct CemOneModel {
+  __device__ __forceinline__ const float* W(const float* w) const { return w; }
+  __device__ __forceinline__ const float* b(const float* v) const { return v; }
+  __device__ __forceinline__ float* costs(float* c) const { return c; }
+  __device__ __forceinline__ bool records() const { return true; }
+};
+
+// The member blockIdx.y of a dynamics ensemble: the arguments' dyn describes member 0, member p lies wstride / bstride
+// floats behind it (fp32 mode: both the members' parameter count; bf16 mode: W[l] are bf16 images, wstride half their
+// elements, the biases stay in the fp32 members), and its costs go to plane p of part [P][B][ldc].
+struct CemMember {
+  size_t wstride, bstride, plane;
+  float* part;
+  __device__ __forceinline__ const float* W(const float* w) const { return w + blockIdx.y * wstride; }
+  __device__ __forceinline__ const float* b(const float* v) const { return v + blockIdx.y * bstride; }
+  __device__ __forceinline__ float* costs(float*) const { return part + blockIdx.y * plane; }
+  __device__ __forceinline__ bool records() const { return blockIdx.y == 0; }
+};
+
+template <bool BF16, typename Src, typename Ens = CemOneModel>
 __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows, int ldc, float* Ab, __bf16* Hb,
-                                                 Src& src) {
+                                                 Src& src, const Ens& ens = Ens()) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
   const int n = a.n, m = a.m, T = a.T;
   const int tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
@@ -113,7 +137,7 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
         if (j < m) {
           u = src.control(b, i, s, t, j);
           Ab[i * GMPC_DG_LDA + n + j] = u;
-          src.record(b, s, t, j, u);
+          if (ens.records()) src.record(b, s, t, j, u);
         }
         Hb[i * GMPC_DG_LDH + n + j] = static_cast<__bf16>(u);
       }
@@ -123,7 +147,7 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
         const int i = e / m, j = e - i * m, s = s0 + i;
         const float u = src.control(b, i, s, t, j);
         Ab[i * GMPC_DG_LDA + n + j] = u;
-        src.record(b, s, t, j, u);
+        if (ens.records()) src.record(b, s, t, j, u);
       }
     }
     __syncthreads();
@@ -145,11 +169,12 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     for (int l = 0; l < a.dyn.L; ++l) {
       const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
       if constexpr (BF16)
-        dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(a.dyn.W[l]), wave, lane, acc);
+        dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(ens.W(a.dyn.W[l])), wave, lane,
+                     acc);
       else
-        dg_gemm(Ab, K, Nl, a.dyn.W[l], wave, lane, acc);
+        dg_gemm(Ab, K, Nl, ens.W(a.dyn.W[l]), wave, lane, acc);
       __syncthreads();   // every wave has read its operand rows (and the stage cost its row)
-      const float* bias = a.dyn.b[l];
+      const float* bias = ens.b(a.dyn.b[l]);
       if (l < a.dyn.L - 1) {
         auto act = [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); };
         if constexpr (BF16)
@@ -209,7 +234,7 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     for (int j = rc; j < fout; j += 8) sy = fmaf(row[j], row[j], sy);
     sy = cem_row8_sum(sy);
     csum += w2 * sy;
-    if (rc == 0 && s0 + rrow < rows) a.costs[(size_t)b * ldc + s0 + rrow] = csum;
+    if (rc == 0 && s0 + rrow < rows) ens.costs(a.costs)[(size_t)b * ldc + s0 + rrow] = csum;
   }
 }
 

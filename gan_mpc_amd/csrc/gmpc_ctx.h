@@ -49,6 +49,7 @@ struct CallWork {
   PadRows acts, dels;     // the rows of the call's main network
   PadRows acts2, dels2;   // a second network's (gmpc_rollout_vjp: the cost MLP's)
   GrowBuf save, aux, aux2;
+  GrowBuf part;           // the sampling solvers under an ensemble: the members' costs [P][B][ldc]
 };
 
 struct gmpc_ctx {
@@ -120,6 +121,14 @@ struct gmpc_ctx {
   void* w16 = nullptr;
   bool w16_stale = true;
   MlpDesc dyn16{}, cost16{};
+  // gmpc_set_sampled_ensemble: ens_P > 0 members of the caller's [P][dyn count] vectors, under each of
+  // which every launch over sampled rows rolls its rows out.  ens_dyn: member 0 bound like dyn (no transposes);
+  // ens_dyn16: the same over the members' packed bf16 images in ens16 (P images of the dynamics, one behind the other;
+  // grown and packed by the first bf16-mode solve behind every gmpc_set_sampled_ensemble).
+  int ens_P = 0;
+  MlpDesc ens_dyn{}, ens_dyn16{};
+  GrowBuf ens16;
+  bool ens16_stale = true;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;

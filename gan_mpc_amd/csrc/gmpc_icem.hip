@@ -11,6 +11,8 @@
 //                   a control needs the T normals of its (row, control): formed once per tile in LDS behind the
 //                   operand block where 32 m T floats fit there (zlds), regenerated per element otherwise -- the
 //                   same sum in the same order either way.
+//   k_icem_rollout_ens, k_icem_rollout_ens_bf16  the pool's rows under every member of a dynamics ensemble (DESIGN.md
+//                   section 24; blockIdx.y: the member), followed by k_ens_reduce of gmpc_cem.hip
 //   k_icem_update   one workgroup per problem: the sort of k_cem_update over the pool's rows, then the elites' sums in
 //                   rank order (for T m < 256 by the whole workgroup, in blocks of elites staged in LDS: the same
 //                   sums), the kept rows, the best row and the returned sequence.
@@ -119,6 +121,22 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_bf16(IcemRollA
   cem_rollout_body<true>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, Hb, src);
 }
 
+// The same pool rows under every member of a dynamics ensemble (blockIdx.y: the member)
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_ens(IcemRollArgs a, CemMember e) {
+  extern __shared__ __attribute__((aligned(16))) char smem_icem_e[];
+  float* Ab = reinterpret_cast<float*>(smem_icem_e);
+  IcemDrawn src{a, Ab + GMPC_CEM_ROWS * GMPC_DG_LDA, nullptr, nullptr, nullptr};
+  cem_rollout_body<false>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, nullptr, src, e);
+}
+
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_ens_bf16(IcemRollArgs a, CemMember e) {
+  extern __shared__ __attribute__((aligned(16))) char smem_icem_e16[];
+  float* Ab = reinterpret_cast<float*>(smem_icem_e16);
+  __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);
+  IcemDrawn src{a, reinterpret_cast<float*>(smem_icem_e16 + GMPC_CEM_LDS16), nullptr, nullptr, nullptr};
+  cem_rollout_body<true>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, Hb, src, e);
+}
+
 // ---- the update -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_update(IcemUpdArgs a, int P) {
   extern __shared__ __attribute__((aligned(16))) char smem_iu[];
@@ -222,8 +240,10 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_update(IcemUpdArgs a, 
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-static int icem_launch_rollout(const IcemRollArgs& a, bool bf16, hipStream_t s) {
+// ens: null, or the ensemble whose members all roll the pool out (a.c.dyn: member 0), followed by the reduce
+static int icem_launch_rollout(const IcemRollArgs& a, bool bf16, hipStream_t s, const CemEnsemble* ens = nullptr) {
   const CemRollArgs& c = a.c;
+  if (ens && (ens->P < 1 || ens->P > GMPC_MAX_ENSEMBLE || !ens->part || c.X || c.mean_row)) return 1;
   for (int l = 0; l <= c.dyn.L; ++l)
     if (c.dyn.dims[l] > 256) return 1;
   for (int l = 0; l <= c.cost.L; ++l)
@@ -238,6 +258,15 @@ static int icem_launch_rollout(const IcemRollArgs& a, bool bf16, hipStream_t s) 
   if (a.zlds) lds += (size_t)GMPC_CEM_ROWS * c.m * c.T * sizeof(float);
   if (lds > GMPC_ICEM_LDS_BYTES) return 1;
   const int tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
+  if (ens) {
+    const CemMember mb{ens->wstride, ens->bstride, (size_t)c.B * a.ldc, ens->part};
+    if (bf16)
+      hipLaunchKernelGGL(k_icem_rollout_ens_bf16, dim3(c.B * tiles, ens->P), dim3(GMPC_DG_THREADS), lds, s, a, mb);
+    else
+      hipLaunchKernelGGL(k_icem_rollout_ens, dim3(c.B * tiles, ens->P), dim3(GMPC_DG_THREADS), lds, s, a, mb);
+    gmpc_launch_ens_reduce(*ens, c.B, rows, a.ldc, c.costs, s);
+    return 0;
+  }
   if (bf16)
     hipLaunchKernelGGL(k_icem_rollout_bf16, dim3(c.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
   else
@@ -247,6 +276,9 @@ static int icem_launch_rollout(const IcemRollArgs& a, bool bf16, hipStream_t s) 
 
 int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s) { return icem_launch_rollout(a, false, s); }
 int gmpc_launch_icem_rollout_bf16(const IcemRollArgs& a, hipStream_t s) { return icem_launch_rollout(a, true, s); }
+int gmpc_launch_icem_rollout_ens(const IcemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s) {
+  return icem_launch_rollout(a, bf16, s, &e);
+}
 
 // The shapes whose normals k_icem_rollout forms once per tile in LDS: 32 m T floats beside the operand block (bf16:
 // beside both blocks of k_icem_rollout_bf16; the controls are the same either way)

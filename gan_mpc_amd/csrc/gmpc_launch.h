@@ -297,6 +297,21 @@ void gmpc_bind_bf16_images(MlpDesc& img, const MlpDesc& src, void* base);
 void gmpc_launch_pack_bf16(const MlpDesc& dyn, const MlpDesc& dyn_img, const MlpDesc& cost, const MlpDesc& cost_img,
                            hipStream_t s);
 
+// The sampled rollouts under a dynamics ensemble: k_cem_rollout_ens / k_icem_rollout_ens and their bf16
+// forms, one grid row of workgroups per member, then k_ens_reduce.  The arguments' dyn describes member 0 (bf16: with
+// W[l] at its packed images); member p's weights lie p wstride floats behind them, its biases p bstride floats; part
+// [P][B][ldc] takes the members' costs and the arguments' costs [B][ldc] their sum in member order times invP.
+#define GMPC_MAX_ENSEMBLE 16
+struct CemEnsemble {
+  int P;
+  size_t wstride, bstride;
+  float* part;
+  float invP;
+};
+int gmpc_launch_cem_rollout_ens(const CemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s);
+int gmpc_launch_icem_rollout_ens(const IcemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s);
+void gmpc_launch_ens_reduce(const CemEnsemble& e, int B, int rows, int ldc, float* costs, hipStream_t s);
+
 // gmpc_mppi.hip: the path-integral update on k_cem_rollout's costs, and its adjoint ------------------
 // k_mppi_update: w_s = exp(-(costs_s - min) / lam) over the finite costs [B][N], mean <- gamma mean + (1 - gamma)
 // sum_s w_s u_s / sum_s w_s in place; sd is read only.  weights [B][N] (normalised), mean_trace [B][T][m] (the mean

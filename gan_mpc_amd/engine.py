@@ -343,6 +343,34 @@ class Engine:
             raise _lib.GmpcError(f'sampled precision: {precision!r} is neither "fp32" nor "bf16"')
         _lib.check(self.lib.gmpc_set_sampled_precision(self.ctx, self.SAMPLED_PRECISIONS[precision]))
 
+    MAX_ENSEMBLE = 16     # GMPC_MAX_ENSEMBLE
+
+    def set_sampled_ensemble(self, members):
+        """A dynamics ensemble under the sampled rollouts of cem_solve / mppi_solve / icem_solve on this engine
+        (gmpc_set_sampled_ensemble).  members: None -- no ensemble (the default) --, or a float32
+        (P, dyn_count) tensor or array, 1 <= P <= 16, each row a dynamics parameter vector laid out like set_params'
+        `dyn`; moved to the device and kept alive here.  While set, a sampled row's cost is the mean of its costs
+        under the members (summed in member order, times float32(1 / P)); the samples are bitwise unchanged; X and obj
+        are the rollout of the returned U under the bound (nominal) dynamics; mppi_vjp is refused.  set_params keeps
+        the ensemble.  A tensor changed in place needs this call again.  No device work beyond the copy."""
+        if members is None:
+            _lib.check(self.lib.gmpc_set_sampled_ensemble(self.ctx, 0, None))
+            self._ensemble = None
+            return
+        shape = tuple(getattr(members, "shape", ()))
+        if len(shape) != 2:
+            raise _lib.GmpcError(f"ensemble: members must be (P, {self.dyn_count}), got shape {shape}")
+        if shape[1] != self.dyn_count:
+            raise _lib.GmpcError(f"ensemble: members must be (P, {self.dyn_count}), got {shape}")
+        if not 1 <= shape[0] <= self.MAX_ENSEMBLE:
+            raise _lib.GmpcError(f"ensemble: P = {shape[0]} outside [1, {self.MAX_ENSEMBLE}]")
+        dtype = members.dtype if torch.is_tensor(members) else np.asarray(members).dtype
+        if dtype not in (torch.float32, np.dtype(np.float32)):
+            raise _lib.GmpcError(f"ensemble: members must be float32, got {dtype}")
+        dev = self.to_dev(members)
+        _lib.check(self.lib.gmpc_set_sampled_ensemble(self.ctx, int(shape[0]), _ptr(dev)))
+        self._ensemble = dev      # keep the tensor alive: the ctx holds a raw pointer
+
     CEM_WANT = ("costs", "elites", "samples")
 
     def cem_solve(self, x0, U_init, goal, u_lo, u_hi, kwargs=None, init_std=None, want=(), iter_offset=0):

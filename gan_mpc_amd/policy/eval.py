@@ -5,6 +5,7 @@ batch (B, hist+1, n)."""
 import numpy as np
 import torch
 
+from gan_mpc_amd import params as params_lib
 from gan_mpc_amd.engine import ICEM_KWARGS, MPPI_KWARGS, TRAJAX_CEM_KWARGS, TRAJAX_iLQR_KWARGS, Engine
 from gan_mpc_amd.policy import optimizers as opt
 from gan_mpc_amd.policy.device_params import DeviceParams
@@ -48,7 +49,8 @@ class EvalMPC:
 
     def __init__(self, config, cost_model, dynamics_model, expert_model,
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None,
-                 cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None, sampled_precision=None):
+                 cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None, sampled_precision=None,
+                 dynamics_ensemble=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
@@ -66,7 +68,11 @@ class EvalMPC:
         batch shape carries the previous solve's kept rows, shifted one step), handled like "cem".
         sampled_precision: None, "fp32" or "bf16" -- with a "cem" / "mppi" / "icem" solver, the operand precision of
         the sampled rollouts (Engine.set_sampled_precision, DESIGN §23), set wherever the policy binds its engine;
-        None leaves the engine's default, "fp32"."""
+        None leaves the engine's default, "fp32".
+        dynamics_ensemble: None, or a sequence of 1 to 16 dynamics parameter trees shaped like
+        params["dynamics_params"] -- with a "cem" / "mppi" / "icem" solver, the members of the dynamics ensemble the
+        sampled rows are costed on (Engine.set_sampled_ensemble, DESIGN §24: a row's cost is its mean over the members;
+        X and obj stay those of params["dynamics_params"]), set wherever the policy binds its engine."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
         if (solver in ("box", "cem", "mppi", "icem")) != (control_bounds is not None):
@@ -89,6 +95,11 @@ class EvalMPC:
                              f"solver={solver!r}")
         if sampled_precision not in (None, "fp32", "bf16"):
             raise ValueError(f'sampled_precision must be None, "fp32" or "bf16", got {sampled_precision!r}')
+        if dynamics_ensemble is not None and solver not in ("cem", "mppi", "icem"):
+            raise ValueError('dynamics_ensemble and solver="cem" / "mppi" / "icem" go together: got '
+                             f"solver={solver!r}")
+        if dynamics_ensemble is not None and len(dynamics_ensemble) == 0:
+            raise ValueError("dynamics_ensemble must hold at least one dynamics parameter tree")
         if control_bounds is not None and len(control_bounds) != 2:
             raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
@@ -107,6 +118,10 @@ class EvalMPC:
         self.icem_solves = 0      # the same for an "icem" policy
         self._icem_state = None   # shift_elites: the previous solve's state (its kept rows)
         self.sampled_precision = sampled_precision
+        # the members' flat vectors, stacked (P, dyn count); its device copy is made by the first bind
+        self.dynamics_ensemble = None if dynamics_ensemble is None else np.stack(
+            [params_lib.pack_mlp(tree) for tree in dynamics_ensemble])
+        self._ensemble_dev = None
         self.critic_model = getattr(self, "critic_model", None)
         self._device = device
         self._engine = None
@@ -169,6 +184,10 @@ class EvalMPC:
                        dparams.view("cost_params"))
         if self.sampled_precision is not None:
             eng.set_sampled_precision(self.sampled_precision)
+        if self.dynamics_ensemble is not None:
+            if self._ensemble_dev is None or self._ensemble_dev.device != eng.device:
+                self._ensemble_dev = eng.to_dev(self.dynamics_ensemble)
+            eng.set_sampled_ensemble(self._ensemble_dev)
         return eng
 
     # ---- reference API ----------------------------------------------------------------------

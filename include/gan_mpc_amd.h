@@ -398,6 +398,24 @@ int gmpc_icem_plan_host(const gmpc_icem_opts* opts, int T, int* N_it, float* cw)
 enum { GMPC_SAMPLED_FP32 = 0, GMPC_SAMPLED_BF16 = 1 };
 int gmpc_set_sampled_precision(gmpc_ctx* ctx, int precision);
 
+/* A dynamics ensemble under the sampling solvers' sampled rollouts: a property of the context,
+ * off until set.  dyn_members: device, [P][dyn_param_count], each row a dynamics parameter vector in the layout of the
+ * `dyn` argument of gmpc_set_params; kept, not owned.  1 <= P <= 16; P == 0 (any pointer) switches the ensemble off;
+ * every call, also with the same pointer, means "the members changed".  No stream, no device work.  GMPC_EINVAL
+ * ("ensemble: ...") for a null ctx, P outside [0, 16], a null pointer with P > 0, and a context the sampling solvers
+ * refuse (LSTM dynamics, a width above 256).  gmpc_set_params neither drops nor changes the ensemble.
+ *   While set, every launch of gmpc_cem_solve / gmpc_mppi_solve / gmpc_icem_solve that rolls out SAMPLED rows rolls
+ *   each row out once per member p, under member p's dynamics weights and biases (the cost MLP, mpc_w, x0, the goals
+ *   and the controls are shared): J_p, the arithmetic of a solve without an ensemble.  The row's cost is
+ *   (((J_0 + J_1) + J_2) + ... + J_{P-1}) * (1.0f / (float)P) in fp32 (a NaN J_p makes it NaN), and everything that
+ *   reads costs -- elites, weights, kept rows, iCEM's best row and best_cost_io, `costs` / `costs_trace` -- reads that.
+ *   `samples` is bitwise that of a solve without an ensemble.  X and obj of the returned sequence stay on the
+ *   context's own dynamics (the nominal model).  In bf16 mode each member's weight matrices are rounded to bf16 images
+ *   by the first bf16-mode solve after this call, on that solve's stream; members changed in place need this call
+ *   again.  gmpc_mppi_vjp differentiates the nominal model only and is refused while an ensemble is set ("mppi vjp:
+ *   ..."). */
+int gmpc_set_sampled_ensemble(gmpc_ctx* ctx, int P, const float* dyn_members);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
