@@ -105,6 +105,16 @@ class BgemmDesc(C.Structure):
     ]
 
 
+class WgradDesc(C.Structure):
+    """gmpc_wgrad_desc: one weight-gradient problem and its partial-sum buffer (gmpc_wgrad_ex / gmpc_wgrad_route)."""
+    _fields_ = [
+        ("rows", C.c_int), ("M", C.c_int), ("N", C.c_int), ("lda", C.c_int), ("ldb", C.c_int), ("cs_rows", C.c_int),
+        ("A", _P), ("B", _P), ("C", _P), ("colsum", _P),
+        ("mfma_ok", C.c_int), ("form", C.c_int),
+        ("part", _P), ("part_floats", C.c_long),
+    ]
+
+
 # name -> (restype, argtypes); exactly the entry points declared in include/gan_mpc_amd.h
 SIGNATURES = {
     "gmpc_last_error": (C.c_char_p, []),
@@ -165,6 +175,10 @@ SIGNATURES = {
                                 _P]),
     "gmpc_bgemm_tn_ex": (C.c_int, [_P, C.POINTER(BgemmDesc), _P]),
     "gmpc_bgemm_route": (C.c_int, [C.POINTER(BgemmDesc), C.POINTER(C.c_int)]),
+    "gmpc_wgrad_ex": (C.c_int, [_P, C.POINTER(WgradDesc), _P]),
+    "gmpc_wgrad_batch_ex": (C.c_int, [_P, C.POINTER(WgradDesc), C.c_int, _P, C.c_long, _P, C.POINTER(C.c_int)]),
+    "gmpc_wgrad_route": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_int)]),
+    "gmpc_wgrad_batch_route": (C.c_int, [C.POINTER(WgradDesc), C.c_int, C.c_long, C.POINTER(C.c_int)]),
     "gmpc_linesearch_candidates": (C.c_long, [_P]),
     "gmpc_linesearch_stats": (C.c_int, [_P, C.POINTER(C.c_long), C.c_int]),
     "gmpc_profile_enable": (C.c_int, [_P, C.c_int]),

@@ -168,7 +168,8 @@ static int critic_forward_backward(gmpc_ctx* c, int Bc, const float* xseq, const
     // the rest one by one, after the batch (they reuse the partial-sum buffer: stream order)
     for (int i = 0; i < ns; ++i) {
       if (single[i].M == 0)
-        gmpc_launch_colsum(single[i].csr, single[i].N, single[i].Bm, single[i].ldb, single[i].cs, c->wpart, sw);
+        gmpc_launch_colsum(single[i].csr, single[i].N, single[i].Bm, single[i].ldb, single[i].cs, c->wpart,
+                           c->wpart_floats, sw);
       else
         gmpc_launch_wgrad(single[i].r, single[i].M, single[i].N, single[i].A, single[i].lda, single[i].Bm,
                           single[i].ldb, single[i].Cw, single[i].cs, single[i].csr, c->wpart, sw,
@@ -445,6 +446,76 @@ extern "C" int gmpc_bgemm_route(const gmpc_bgemm_desc* d, int* route4) {
   if (!bgemm_desc_ok(d) || !route4) return fail(GMPC_EINVAL, "bad argument");
   const BgemmRoute r = gmpc_bgemm_route_of(bgemm_desc_args(d));
   route4[0] = r.family; route4[1] = r.p[0]; route4[2] = r.p[1]; route4[3] = r.p[2];
+  return 0;
+}
+
+// The weight-gradient GEMM (gmpc_wgrad.hip) with every argument of its launchers in the caller's hands, the partial-sum
+// buffer included: the entry points of tests/wgrad_cases.py.
+static bool wgrad_desc_ok(const gmpc_wgrad_desc* d, bool in_batch) {
+  if (!d || !d->B || d->rows < 1 || d->N < 1 || d->ldb < d->N) return false;
+  if (!in_batch && (!d->part || d->part_floats < 1)) return false;
+  if (!in_batch && d->form == GMPC_WGRAD_COLSUM_ONLY) return d->colsum != nullptr;
+  if (!in_batch && d->form != GMPC_WGRAD_AUTO) return false;
+  if (d->colsum && (d->cs_rows < 1 || d->cs_rows > d->rows)) return false;
+  if (in_batch && d->M == 0) return d->colsum != nullptr && d->C == d->colsum;
+  return d->A && d->C && d->M >= 1 && d->lda >= d->M;
+}
+static WgradRoute wgrad_desc_route(const gmpc_wgrad_desc* d) {
+  if (d->form == GMPC_WGRAD_COLSUM_ONLY) return gmpc_wgrad_route_of(d->rows, 0, d->N, true, d->rows, d->part_floats, false);
+  return gmpc_wgrad_route_of(d->rows, d->M, d->N, d->colsum != nullptr, d->cs_rows, d->part_floats, d->mfma_ok != 0);
+}
+// the batch as the launcher takes it; false for a bad argument
+static bool wgrad_desc_batch(const gmpc_wgrad_desc* probs, int np, std::vector<WgProb>& pr) {
+  if (!probs || np < 1 || np > 64) return false;
+  pr.assign(np, WgProb{});
+  for (int i = 0; i < np; ++i) {
+    const gmpc_wgrad_desc* d = probs + i;
+    if (!wgrad_desc_ok(d, true)) return false;
+    WgProb& q = pr[i];
+    q.rows = d->rows; q.M = d->M; q.N = d->N; q.lda = d->lda; q.ldb = d->ldb; q.cs_rows = d->cs_rows;
+    q.A = d->A; q.B = d->B; q.C = d->C; q.colsum = d->colsum;
+  }
+  return true;
+}
+
+extern "C" int gmpc_wgrad_ex(gmpc_ctx* c, const gmpc_wgrad_desc* d, void* stream) {
+  if (!c || !wgrad_desc_ok(d, false)) return fail(GMPC_EINVAL, "bad argument");
+  if (d->form == GMPC_WGRAD_COLSUM_ONLY && d->part_floats < d->N) return fail(GMPC_EINVAL, "part holds fewer than N floats");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d->form == GMPC_WGRAD_COLSUM_ONLY)
+    gmpc_launch_colsum(d->rows, d->N, d->B, d->ldb, d->colsum, d->part, d->part_floats, s);
+  else
+    gmpc_launch_wgrad(d->rows, d->M, d->N, d->A, d->lda, d->B, d->ldb, d->C, d->colsum, d->cs_rows, d->part, s,
+                      d->part_floats, d->mfma_ok != 0);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmpc_wgrad_batch_ex(gmpc_ctx* c, const gmpc_wgrad_desc* probs, int np, float* part, long part_floats,
+                                   void* stream, int* taken) {
+  std::vector<WgProb> pr;
+  if (!c || !part || part_floats < 1 || !taken || !wgrad_desc_batch(probs, np, pr)) return fail(GMPC_EINVAL, "bad argument");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  *taken = gmpc_launch_wgrad_batch(pr.data(), np, part, part_floats, static_cast<hipStream_t>(stream)) ? 1 : 0;
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int gmpc_wgrad_route(const gmpc_wgrad_desc* d, int* route6) {
+  if (!wgrad_desc_ok(d, false) || !route6) return fail(GMPC_EINVAL, "bad argument");
+  const WgradRoute r = wgrad_desc_route(d);
+  route6[0] = r.form; route6[1] = r.ntw; route6[2] = r.rpc; route6[3] = r.nchunks; route6[4] = r.crpc; route6[5] = r.cchunks;
+  return 0;
+}
+
+extern "C" int gmpc_wgrad_batch_route(const gmpc_wgrad_desc* probs, int np, long part_floats, int* route2) {
+  std::vector<WgProb> pr;
+  if (part_floats < 1 || !route2 || !wgrad_desc_batch(probs, np, pr)) return fail(GMPC_EINVAL, "bad argument");
+  route2[1] = gmpc_wgrad_batch_plan(pr.data(), np, part_floats);
+  route2[0] = route2[1] != 0 ? 1 : 0;
   return 0;
 }
 

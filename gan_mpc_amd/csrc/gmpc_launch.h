@@ -130,27 +130,40 @@ void gmpc_launch_adam(long count, float* p, const float* g, float* m, float* v, 
 void gmpc_launch_polyak(long count, const float* prev, const float* cur, double f, float* out, hipStream_t s);
 
 // gmpc_wgrad.hip -----------------------------------------------------------------------------------------------------
-// The weight-gradient GEMM: C[M][N] = sum_r A[r][:M]^T B[r][:N]; colsum[N] = sum_{r < cs_rows} B[r][:N] (optional).
-// Its matrix-core kernels (k_wgrad_mfma, k_wgrad_batch) read B up to GMPC_WGRAD_PAD rows past `rows`; A is clamped to
-// its last row and masked to zero there, so those rows of B only have to be allocated and finite.
+// The weight-gradient GEMM: C[M][N] = sum_r A[r][:M]^T B[r][:N]; colsum[N] = sum_{r < cs_rows} B[r][:N] (optional; no
+// rows, cs_rows < 1, give zeros).
+// Its matrix-core kernel k_wgrad_mfma reads its streamed operand up to GMPC_WGRAD_PAD rows past `rows`; the other
+// operand is clamped to its last row and masked to zero there, so those rows only have to be allocated and finite.  The
+// streamed operand is B -- except on the transposed route (N == 1 and M % 32 == 0: C^T = sum_r B_r^T A_r), where it is
+// A.  So mfma_ok promises GMPC_WGRAD_PAD pad rows behind B, and behind A as well whenever N == 1 && M % 32 == 0.  The
+// batch kernel (k_wgrad_batch) and the VALU kernel (k_wgrad) read no row past `rows` of either operand.
 #define GMPC_WGRAD_PAD 8
 #define GMPC_WGRAD_MAX_SPLIT 256   // most row chunks of the VALU form (k_wgrad)
-// part holds part_floats floats: up to GMPC_WGRAD_MAX_SPLIT partial sums of M*N + N floats, fewer where they would not
-// fit; mfma_ok: B has its GMPC_WGRAD_PAD pad rows
+// The launcher's decision, apart from its launch (host only; gmpc_wgrad_route exports it for tests/wgrad_cases.py).
+// rpc / nchunks: rows per chunk and chunks of the GEMM part (VALU: rows per split, splits); crpc / cchunks: those of the
+// separate column-sum kernel (matrix-core forms and WGRAD_COLSUM; 0 without colsum).  direct: the VALU form with a
+// buffer too small for one partial sum writes its single split straight to C / colsum and leaves `part` alone.
+enum { WGRAD_VALU = 0, WGRAD_MFMA = 1, WGRAD_MFMA_SWAPPED = 2, WGRAD_COLSUM = 3 };
+struct WgradRoute { int form, ntw, rpc, nchunks, crpc, cchunks; bool direct; };
+WgradRoute gmpc_wgrad_route_of(int rows, int M, int N, bool colsum, int cs_rows, long part_floats, bool mfma_ok);
+// part holds part_floats floats (<= 0: unbounded) and no form writes past them: up to GMPC_WGRAD_MAX_SPLIT partial sums
+// of M*N + N floats, fewer where they would not fit; mfma_ok: the pad rows above are there
 void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
                        float* colsum, int cs_rows, float* part, hipStream_t s, long part_floats, bool mfma_ok);
-// MFMA path of gmpc_launch_wgrad; returns false when the shape does not qualify
-bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb, float* C,
-                            float* colsum, int cs_rows, float* part, long part_floats, hipStream_t s);
 // One MLP's rows summed into its packed gradient g = W_0 | b_0 | W_1 | b_1 | ... (the layout of a parameter vector):
 // `acts` and `dels` are [rows + GMPC_WGRAD_PAD][r.stride] in the layout of `r` (MlpRows); the biases sum the first
 // cs_rows rows.  Returns g behind the last layer.
 float* gmpc_launch_wgrad_mlp(int rows, int cs_rows, int L, const int* dims, const float* acts, const float* dels,
                              const MlpRows& r, float* g, float* part, long part_floats, hipStream_t s);
-// all problems in one launch (+ one reduction); false when one does not qualify (the caller issues them one by one)
+// all problems in one launch (+ one reduction); false when one does not qualify (the caller issues them one by one).
+// gmpc_wgrad_batch_plan is its decision without the launches: the common rows per chunk (0: the batch does not
+// qualify) and every problem's tiling and slices of `part` (host only, B is only tested for alignment).
+int gmpc_wgrad_batch_plan(WgProb* probs, int np, long part_floats);
 bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_floats, hipStream_t s);
-// colsum[N] = sum_{r < rows} B[r][:N] on its own (two launches; `part` holds the chunk sums)
-void gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum, float* part, hipStream_t s);
+// colsum[N] = sum_{r < rows} B[r][:N] on its own (two launches; `part` holds the chunk sums, at most part_floats of
+// them); false, and nothing launched, when part_floats < N
+bool gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum, float* part, long part_floats,
+                        hipStream_t s);
 
 // gmpc_critic_lstm.hip: second-generation LSTM kernels (n <= 32) and the head ----------------------------------------
 bool gmpc_lstm2_supported(const CriticDesc& cd);

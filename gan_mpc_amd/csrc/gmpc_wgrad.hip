@@ -86,7 +86,9 @@ __global__ __launch_bounds__(256) void k_reduce_splits(int count, int nsplit, co
 // r is row r of A, the B operand row r of B: both coalesced).  One wavefront owns a 32 x 32*NTW
 // strip of C over one chunk of rows; partial strips are summed in chunk order (deterministic).
 // Requires N % (32*NTW) == 0 and B followed by GMPC_WGRAD_PAD allocated, finite rows (gmpc_launch.h: they meet a
-// zero A operand); A is clamped (it may be a caller's buffer).  v_mfma_f32_32x32x2_f32 = k-ordered exact fp32 fmaf chain.
+// zero A operand); A is clamped (it may be a caller's buffer).  On the transposed route (gmpc_wgrad_route_of) the
+// launcher passes the caller's B as this A and the caller's A as this B: the pad rows are then wanted behind the
+// caller's A.  v_mfma_f32_32x32x2_f32 = k-ordered exact fp32 fmaf chain.
 // ---------------------------------------------------------------------------------------------
 template <int NTW>
 __global__ __launch_bounds__(GMPC_THREADS) void k_wgrad_mfma(int rows, int M, int N, const float* A,
@@ -155,7 +157,8 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_colsum(int cs_rows, int N, con
 // the chip (a few hundred wave-tiles): issued one by one they cost a launch, a tail and a reduction
 // launch each.  Here ONE launch covers the wave-tiles of all problems plus their bias column sums
 // (the trailing workgroups), and ONE launch reduces all the partial sums, in the same fixed chunk
-// order as before (deterministic).  Problems need N % 256 == 0.
+// order as before (deterministic).  Problems need N % 128 == 0 (32 * GMPC_WG_NTW columns per wave), rows >= 64, ldb % 4 == 0
+// and a 16-byte aligned B; a problem with M == 0 is its column sums alone (any N and ldb).
 // ---------------------------------------------------------------------------------------------
 // C(32 x 256) += A^T B over Kp rows for one wave: row r of A / B is the MFMA A / B operand of k-step r / 2.
 // B goes through 16-byte loads: lane l31 holds columns 4 l31 .. 4 l31 + 3 of each 128-column half, so tile j
@@ -334,20 +337,35 @@ __global__ __launch_bounds__(256) void k_reduce_batch(WgBatch bt, const float* p
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
-void gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum, float* part, hipStream_t s) {
-  int cchunks = (rows + 63) / 64;
-  if (cchunks > 2048) cchunks = 2048;
+// Row chunks of a column sum over cs_rows rows: about 64 rows each, at most `cap` chunks and at most as many as fit
+// part_floats (<= 0: unbounded) with N floats each; one empty chunk when there are no rows (the sum is zero).
+static void colsum_chunks(int cs_rows, int N, long part_floats, int cap, int& crpc, int& cchunks) {
+  cchunks = (cs_rows + 63) / 64;
+  if (cchunks > cap) cchunks = cap;
+  if (part_floats > 0 && (long)cchunks * N > part_floats) cchunks = (int)(part_floats / N);
   if (cchunks < 1) cchunks = 1;
-  const int crpc = (rows + cchunks - 1) / cchunks;
-  cchunks = (rows + crpc - 1) / crpc;
-  hipLaunchKernelGGL(k_colsum, dim3(cchunks), dim3(GMPC_THREADS), 0, s, rows, N, Bm, ldb, crpc, part);
+  crpc = (cs_rows + cchunks - 1) / cchunks;
+  if (crpc < 1) crpc = 1;
+  cchunks = (cs_rows + crpc - 1) / crpc;
+  if (cchunks < 1) cchunks = 1;
+}
+
+static void launch_colsum_chunks(int cs_rows, int N, const float* Bm, int ldb, float* colsum, float* part, int crpc,
+                                 int cchunks, hipStream_t s) {
+  hipLaunchKernelGGL(k_colsum, dim3(cchunks), dim3(GMPC_THREADS), 0, s, cs_rows, N, Bm, ldb, crpc, part);
   hipLaunchKernelGGL(k_reduce_splits, dim3((N + 63) / 64), dim3(256), 0, s, N, cchunks, part, colsum);
 }
 
-bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_floats, hipStream_t s) {
-  if (np < 1 || np > GMPC_WG_MAX) return false;
-  WgBatch bt;
-  bt.np = np;
+bool gmpc_launch_colsum(int rows, int N, const float* Bm, int ldb, float* colsum, float* part, long part_floats,
+                        hipStream_t s) {
+  if (part_floats > 0 && part_floats < N) return false;
+  const WgradRoute r = gmpc_wgrad_route_of(rows, 0, N, true, rows, part_floats, false);
+  launch_colsum_chunks(rows, N, Bm, ldb, colsum, part, r.crpc, r.cchunks, s);
+  return true;
+}
+
+int gmpc_wgrad_batch_plan(WgProb* probs, int np, long part_floats) {
+  if (np < 1 || np > GMPC_WG_MAX) return 0;
   for (int i = 0; i < np; ++i) {
     WgProb& q = probs[i];
     if (q.M == 0 && q.colsum != nullptr) {      // column sums only (no GEMM part)
@@ -356,7 +374,7 @@ bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_float
       continue;
     }
     if (q.N % (32 * GMPC_WG_NTW) != 0 || q.rows < 64 || q.ldb % 4 != 0 || (reinterpret_cast<uintptr_t>(q.B) & 15) != 0)
-      return false;
+      return 0;
     q.mstrips = (q.M + 31) / 32;
     q.ngroups = q.N / (32 * GMPC_WG_NTW);
   }
@@ -375,7 +393,7 @@ bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_float
     }
     if (need <= part_floats && items <= max_items) { rpc = cand; break; }
   }
-  if (rpc == 0) return false;
+  if (rpc == 0) return 0;
   int item = 0, cs_blocks = 0, red_blocks = 0;
   long off = 0;
   for (int i = 0; i < np; ++i) {
@@ -387,11 +405,7 @@ bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_float
     q.part_off = off;
     off += (long)q.nchunks * q.M * q.N;
     if (q.colsum != nullptr) {
-      int cchunks = (q.cs_rows + 63) / 64;
-      if (cchunks > 1024) cchunks = 1024;
-      if (cchunks < 1) cchunks = 1;
-      q.crpc = (q.cs_rows + cchunks - 1) / cchunks;
-      q.cchunks = (q.cs_rows + q.crpc - 1) / q.crpc;
+      colsum_chunks(q.cs_rows, q.N, 0, 1024, q.crpc, q.cchunks);
       q.cs_block0 = cs_blocks;
       cs_blocks += q.cchunks;
       q.cs_part_off = off;
@@ -404,25 +418,38 @@ bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_float
     red_blocks += (q.M * q.N + 63) / 64;
     q.cs_red_block0 = red_blocks;
     if (q.colsum != nullptr) red_blocks += (q.N + 63) / 64;
-    bt.p[i] = q;
   }
-  if (off > part_floats) return false;
+  return off > part_floats ? 0 : rpc;
+}
+
+bool gmpc_launch_wgrad_batch(WgProb* probs, int np, float* part, long part_floats, hipStream_t s) {
+  if (gmpc_wgrad_batch_plan(probs, np, part_floats) == 0) return false;
+  WgBatch bt;
+  bt.np = np;
+  int item = 0, cs_blocks = 0, red_blocks = 0;
+  for (int i = 0; i < np; ++i) {
+    const WgProb& q = probs[i];
+    bt.p[i] = q;
+    item += q.mstrips * q.ngroups * q.nchunks;
+    cs_blocks += q.cchunks;
+    red_blocks += (q.M * q.N + 63) / 64 + (q.colsum != nullptr ? (q.N + 63) / 64 : 0);
+  }
   bt.gemm_blocks = (item + 3) / 4;
   hipLaunchKernelGGL(k_wgrad_batch, dim3(bt.gemm_blocks + cs_blocks), dim3(GMPC_THREADS), 0, s, bt, part);
   hipLaunchKernelGGL(k_reduce_batch, dim3(red_blocks), dim3(256), 0, s, bt, part);
   return true;
 }
 
-bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb,
-                            float* C, float* colsum, int cs_rows, float* part, long part_floats,
-                            hipStream_t s) {
+// Tiling of the matrix-core form: 32*ntw columns per wave, chunks of >= 64 rows, about 1024 wave-tiles, the chunks
+// doubled until their partial sums fit; false when the shape does not qualify or one chunk's partial sum does not fit.
+static bool mfma_tiling(int rows, int M, int N, long part_floats, int& ntw, int& rpc, int& nchunks) {
   if (N % 32 != 0 || rows < 64) return false;
   const int nt_all = N / 32;
-  const int ntw = (nt_all % 8 == 0) ? 8 : (nt_all % 4 == 0) ? 4 : (nt_all % 2 == 0) ? 2 : 1;
+  ntw = (nt_all % 8 == 0) ? 8 : (nt_all % 4 == 0) ? 4 : (nt_all % 2 == 0) ? 2 : 1;
   const int mstrips = (M + 31) / 32, ngroups = nt_all / ntw;
-  int nchunks = 1024 / (mstrips * ngroups);
+  nchunks = 1024 / (mstrips * ngroups);
   if (nchunks < 1) nchunks = 1;
-  int rpc = (rows + nchunks - 1) / nchunks;
+  rpc = (rows + nchunks - 1) / nchunks;
   if (rpc < 64) rpc = 64;
   rpc = (rpc + 1) & ~1;
   nchunks = (rows + rpc - 1) / rpc;
@@ -430,64 +457,82 @@ bool gmpc_launch_wgrad_mfma(int rows, int M, int N, const float* A, int lda, con
     rpc *= 2;
     nchunks = (rows + rpc - 1) / rpc;
   }
-  if ((long)nchunks * M * N > part_floats) return false;
-  const int total = mstrips * ngroups * nchunks;
-  const dim3 grid((total + 3) / 4), blk(GMPC_THREADS);
-  switch (ntw) {
-    case 8: hipLaunchKernelGGL(k_wgrad_mfma<8>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
-    case 4: hipLaunchKernelGGL(k_wgrad_mfma<4>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
-    case 2: hipLaunchKernelGGL(k_wgrad_mfma<2>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
-    default: hipLaunchKernelGGL(k_wgrad_mfma<1>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
-  }
-  hipLaunchKernelGGL(k_reduce_splits, dim3((M * N + 63) / 64), dim3(256), 0, s, M * N, nchunks, part, C);
-  if (colsum) {
-    int cchunks = (cs_rows + 63) / 64;
-    if (cchunks > 2048) cchunks = 2048;
-    if (cchunks < 1) cchunks = 1;
-    const int crpc = (cs_rows + cchunks - 1) / cchunks;
-    cchunks = (cs_rows + crpc - 1) / crpc;
-    hipLaunchKernelGGL(k_colsum, dim3(cchunks), dim3(GMPC_THREADS), 0, s, cs_rows, N, Bm, ldb, crpc, part);
-    hipLaunchKernelGGL(k_reduce_splits, dim3((N + 63) / 64), dim3(256), 0, s, N, cchunks, part, colsum);
-  }
-  return true;
+  return (long)nchunks * M * N <= part_floats;
 }
 
-void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb,
-                       float* C, float* colsum, int cs_rows, float* part, hipStream_t s,
-                       long part_floats, bool mfma_ok) {
-  if (mfma_ok && gmpc_launch_wgrad_mfma(rows, M, N, A, lda, Bm, ldb, C, colsum, cs_rows, part,
-                                        part_floats, s))
-    return;
-  // narrow N (e.g. the critic head's last layer, N = 1): compute C^T = sum_r B_r^T A_r instead;
-  // C^T (N x M) has the same memory image as C when N == 1, otherwise it is transposed afterwards
-  if (mfma_ok && N == 1 && M % 32 == 0 &&
-      gmpc_launch_wgrad_mfma(rows, 1, M, Bm, ldb, A, lda, C, nullptr, 0, part, part_floats, s)) {
-    if (colsum) {
-      const float* Bc_ = Bm;
-      int cchunks = (cs_rows + 63) / 64;
-      if (cchunks > 2048) cchunks = 2048;
-      const int crpc = (cs_rows + cchunks - 1) / cchunks;
-      cchunks = (cs_rows + crpc - 1) / crpc;
-      hipLaunchKernelGGL(k_colsum, dim3(cchunks), dim3(GMPC_THREADS), 0, s, cs_rows, N, Bc_, ldb, crpc,
-                         part);
-      hipLaunchKernelGGL(k_reduce_splits, dim3((N + 63) / 64), dim3(256), 0, s, N, cchunks, part,
-                         colsum);
-    }
-    return;
+// The decision of gmpc_launch_wgrad (M >= 1) and gmpc_launch_colsum (M == 0) without their launches.
+WgradRoute gmpc_wgrad_route_of(int rows, int M, int N, bool colsum, int cs_rows, long part_floats, bool mfma_ok) {
+  WgradRoute r{};
+  if (M == 0) {
+    r.form = WGRAD_COLSUM;
+    colsum_chunks(cs_rows, N, part_floats, 2048, r.crpc, r.cchunks);
+    return r;
   }
+  if (mfma_ok && mfma_tiling(rows, M, N, part_floats, r.ntw, r.rpc, r.nchunks)) {
+    r.form = WGRAD_MFMA;
+    // the column sums reuse the buffer after the reduction of C (stream order): N <= M * N <= part_floats
+    if (colsum) colsum_chunks(cs_rows, N, part_floats, 2048, r.crpc, r.cchunks);
+    return r;
+  }
+  // narrow N (e.g. the critic head's last layer, N = 1): compute C^T = sum_r B_r^T A_r instead;
+  // C^T (N x M) has the same memory image as C when N == 1
+  if (mfma_ok && N == 1 && M % 32 == 0 && mfma_tiling(rows, 1, M, part_floats, r.ntw, r.rpc, r.nchunks)) {
+    r.form = WGRAD_MFMA_SWAPPED;
+    if (colsum) colsum_chunks(cs_rows, N, part_floats, 2048, r.crpc, r.cchunks);
+    return r;
+  }
+  r = WgradRoute{};
+  r.form = WGRAD_VALU;
   int nsplit = (rows + 511) / 512;
   if (nsplit > GMPC_WGRAD_MAX_SPLIT) nsplit = GMPC_WGRAD_MAX_SPLIT;
   // the partial sums must fit the scratch buffer (wide layers: n + m = 1088 inputs at C5)
   const long per_split = (long)M * N + (colsum ? N : 0);
   if (part_floats > 0 && (long)nsplit * per_split > part_floats) nsplit = (int)(part_floats / per_split);
-  if (nsplit < 1) nsplit = 1;
+  if (nsplit < 1) {        // not even one partial sum fits: one split needs no partial sums
+    nsplit = 1;
+    r.direct = true;
+  }
   int rps = (rows + nsplit - 1) / nsplit;
   rps = (rps + 15) / 16 * 16;
-  nsplit = (rows + rps - 1) / rps;
+  r.rpc = rps;
+  r.nchunks = (rows + rps - 1) / rps;
+  return r;
+}
+
+static void launch_wgrad_mfma(const WgradRoute& r, int rows, int M, int N, const float* A, int lda, const float* Bm,
+                              int ldb, float* C, float* part, hipStream_t s) {
+  const int total = ((M + 31) / 32) * (N / (32 * r.ntw)) * r.nchunks;
+  const dim3 grid((total + 3) / 4), blk(GMPC_THREADS);
+  const int rpc = r.rpc;
+  switch (r.ntw) {
+    case 8: hipLaunchKernelGGL(k_wgrad_mfma<8>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
+    case 4: hipLaunchKernelGGL(k_wgrad_mfma<4>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
+    case 2: hipLaunchKernelGGL(k_wgrad_mfma<2>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
+    default: hipLaunchKernelGGL(k_wgrad_mfma<1>, grid, blk, 0, s, rows, M, N, A, lda, Bm, ldb, rpc, part); break;
+  }
+  hipLaunchKernelGGL(k_reduce_splits, dim3((M * N + 63) / 64), dim3(256), 0, s, M * N, r.nchunks, part, C);
+}
+
+void gmpc_launch_wgrad(int rows, int M, int N, const float* A, int lda, const float* Bm, int ldb,
+                       float* C, float* colsum, int cs_rows, float* part, hipStream_t s,
+                       long part_floats, bool mfma_ok) {
+  const WgradRoute r = gmpc_wgrad_route_of(rows, M, N, colsum != nullptr, cs_rows, part_floats, mfma_ok);
+  if (r.form == WGRAD_MFMA || r.form == WGRAD_MFMA_SWAPPED) {
+    if (r.form == WGRAD_MFMA) launch_wgrad_mfma(r, rows, M, N, A, lda, Bm, ldb, C, part, s);
+    else launch_wgrad_mfma(r, rows, 1, M, Bm, ldb, A, lda, C, part, s);
+    if (colsum) launch_colsum_chunks(cs_rows, N, Bm, ldb, colsum, part, r.crpc, r.cchunks, s);
+    return;
+  }
+  const int nsplit = r.nchunks;
+  if (r.direct) {
+    hipLaunchKernelGGL(k_wgrad, dim3((M + 63) / 64, (N + 63) / 64, 1), dim3(GMPC_THREADS), 0, s, rows, M, N, A, lda, Bm,
+                       ldb, r.rpc, C, colsum, cs_rows);
+    return;
+  }
   float* cpart = part;
   float* cspart = colsum ? part + (size_t)nsplit * M * N : nullptr;
   hipLaunchKernelGGL(k_wgrad, dim3((M + 63) / 64, (N + 63) / 64, nsplit), dim3(GMPC_THREADS), 0, s,
-                     rows, M, N, A, lda, Bm, ldb, rps, cpart, cspart, cs_rows);
+                     rows, M, N, A, lda, Bm, ldb, r.rpc, cpart, cspart, cs_rows);
   hipLaunchKernelGGL(k_reduce_splits, dim3((M * N + 63) / 64), dim3(256), 0, s, M * N, nsplit, cpart,
                      C);
   if (colsum)

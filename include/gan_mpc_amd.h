@@ -684,6 +684,38 @@ int gmpc_bgemm_tn_ex(gmpc_ctx* ctx, const gmpc_bgemm_desc* d, void* stream);
  * {2, WNT, KC, VEC} LDS-staged k_bgemm_tn_lds<2, WNT, KC, VEC>. */
 int gmpc_bgemm_route(const gmpc_bgemm_desc* d, int* route4);
 
+/* The weight-gradient GEMM behind every weight and bias gradient, for the unit tests (tests/wgrad_cases.py):
+ *   C[M][N] = sum_{r < rows} A[r][0:M]^T B[r][0:N],   colsum[N] = sum_{r < cs_rows} B[r][0:N]   (colsum = NULL: none)
+ * with leading dimensions lda >= M, ldb >= N and 1 <= cs_rows <= rows.  `part` is the caller's buffer of part_floats
+ * floats for the partial sums: its content afterwards is unspecified, nothing is written behind it.  mfma_ok allows the
+ * matrix-core kernels and promises GMPC_WGRAD_PAD = 8 allocated, finite rows behind row rows - 1 of B, and of A as well
+ * when N == 1 && M % 32 == 0; no other float outside the logical matrices is used.  form = GMPC_WGRAD_AUTO: the
+ * launcher every gradient call uses; GMPC_WGRAD_COLSUM_ONLY: the column sums alone (over `rows` rows; A, C, M, lda and
+ * cs_rows are ignored).  In a batch, a problem with M == 0 and C == colsum is its column sums alone (over cs_rows). */
+enum { GMPC_WGRAD_AUTO = 0, GMPC_WGRAD_COLSUM_ONLY = 1 };
+typedef struct gmpc_wgrad_desc {
+  int rows, M, N, lda, ldb, cs_rows;
+  const float* A; const float* B;
+  float* C; float* colsum;
+  int mfma_ok, form;
+  float* part; long part_floats;
+} gmpc_wgrad_desc;
+/* One problem.  GMPC_EINVAL (before any GPU call) for a bad argument, colsum with cs_rows < 1 among them, and for a
+ * column-sum-only call whose `part` holds fewer than N floats. */
+int gmpc_wgrad_ex(gmpc_ctx* ctx, const gmpc_wgrad_desc* d, void* stream);
+/* np problems through the batch kernel with one partial-sum buffer (the problems' own part / part_floats / mfma_ok /
+ * form are ignored).  *taken = 0: the batch does not qualify (np > 8, a problem with N % 128 != 0, rows < 64,
+ * ldb % 4 != 0 or B not 16-byte aligned, a buffer too small); nothing was launched and nothing written. */
+int gmpc_wgrad_batch_ex(gmpc_ctx* ctx, const gmpc_wgrad_desc* probs, int np, float* part, long part_floats,
+                        void* stream, int* taken);
+/* The launcher's decision for `d` without GPU work (the pointers are compared with NULL, never followed):
+ * route6 = {form, NTW, rows per chunk, chunks, rows per column-sum chunk, column-sum chunks}; form 0 = the VALU kernel
+ * k_wgrad (NTW = 0; chunks = its row splits), 1 = k_wgrad_mfma<NTW>, 2 = k_wgrad_mfma<NTW> on swapped operands
+ * (N == 1), 3 = column sums alone.  The last two are 0 where no separate column-sum kernel runs. */
+int gmpc_wgrad_route(const gmpc_wgrad_desc* d, int* route6);
+/* Whether gmpc_wgrad_batch_ex would take the batch: route2 = {taken, rows per chunk} (B is tested for alignment). */
+int gmpc_wgrad_batch_route(const gmpc_wgrad_desc* probs, int np, long part_floats, int* route2);
+
 /* Number of candidate rollouts (trajectory, step size) the line searches of the last gmpc_ilqr_solve
  * evaluated -- the work count behind bench.py's secondary roofline.  Synchronises the whole device
  * (hipDeviceSynchronize). */
