@@ -1,5 +1,5 @@
 // C-ABI entry points of libgan_mpc_amd.so (include/gan_mpc_amd.h): errors, shapes, the context's life, parameter
-// layouts, profile and debug accessors.  gmpc_api_solve.hip, gmpc_api_critic.hip and gmpc_api_grads.hip hold the rest.
+// layouts, profile and debug accessors.  gmpc_api_{solve,sampled,critic,grads}.hip hold the rest.
 #include <cstdarg>
 #include <new>
 

@@ -306,7 +306,7 @@ extern "C" int gmpc_mppi_vjp(gmpc_ctx* c, int B, const float* x0, const float* g
   ta.n = n; ta.m = m; ta.T = T; ta.dyn = c->dyn; ta.cost = c->cost; ta.mpc_w = c->mpc_w;
   ta.goal = goalr; ta.x0 = x0r; ta.U = Us; ta.X = Xr; ta.obj = c->obj; ta.masks = c->masks;
   for (int k = K - 1; k >= 0; --k) {
-    ca.rng = gmpc_mppi_rng(o, k);
+    ca.rng = gmpc_sampled_rng(o->seed, o->iter_offset + k, o->sampling_smoothing);
     ca.mean = means_trace + (size_t)k * B * Tm;
     ca.costs = costs_trace + (size_t)k * B * N;
     for (int b0 = 0; b0 < B; b0 += chunk) {

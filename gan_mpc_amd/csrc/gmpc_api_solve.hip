@@ -346,434 +346,6 @@ extern "C" int gmpc_ilqr_solve_box_held(gmpc_ctx* c, int B, const float* x0, con
   return 0;
 }
 
-// The shapes k_cem_rollout covers, for the sampling solvers (`who`: "cem" / "mppi", the message's prefix)
-int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who) {
-  const gmpc_shape& sh = c->sh;
-  if (c->dynl) return fail(GMPC_EINVAL, "%s: MLP dynamics only (dyn_lstm_features = %d)", who, sh.dyn_lstm_features);
-  for (int l = 0; l <= sh.dyn_layers; ++l)
-    if (sh.dyn_dims[l] > 256) return fail(GMPC_EINVAL, "%s: dynamics width %d above 256", who, sh.dyn_dims[l]);
-  for (int l = 0; l <= sh.cost_layers; ++l)
-    if (sh.cost_dims[l] > 256) return fail(GMPC_EINVAL, "%s: cost width %d above 256", who, sh.cost_dims[l]);
-  if (sh.n + sh.m > 256) return fail(GMPC_EINVAL, "%s: n + m = %d above 256", who, sh.n + sh.m);
-  return 0;
-}
-
-extern "C" int gmpc_set_sampled_precision(gmpc_ctx* c, int precision) {
-  if (!c) return fail(GMPC_EINVAL, "ctx is null");
-  if (precision != GMPC_SAMPLED_FP32 && precision != GMPC_SAMPLED_BF16)
-    return fail(GMPC_EINVAL, "sampled precision: %d is neither GMPC_SAMPLED_FP32 (0) nor GMPC_SAMPLED_BF16 (1)",
-                precision);
-  c->sampled_precision = precision;
-  return 0;
-}
-
-// The dynamics ensemble of the sampled rollouts: the pointer is kept, not owned, and nothing is launched
-extern "C" int gmpc_set_sampled_ensemble(gmpc_ctx* c, int P, const float* dyn_members) {
-  if (!c) return fail(GMPC_EINVAL, "ensemble: ctx is null");
-  if (P < 0 || P > GMPC_MAX_ENSEMBLE)
-    return fail(GMPC_EINVAL, "ensemble: P = %d outside [0, %d]", P, GMPC_MAX_ENSEMBLE);
-  if (P == 0) {
-    c->ens_P = 0;
-    return 0;
-  }
-  if (!dyn_members) return fail(GMPC_EINVAL, "ensemble: dyn_members is null with P = %d", P);
-  TRY(gmpc_sampled_coverage(c, "ensemble"));
-  bind_mlp(c->ens_dyn, c->sh.dyn_layers, c->sh.dyn_dims, dyn_members, nullptr);
-  c->ens_P = P;
-  c->ens16_stale = true;   // the members changed: their bf16 images are packed again by the next bf16-mode solve
-  return 0;
-}
-
-// bf16 mode: the packed bf16 images of both MLPs, allocated by the first call and packed again behind
-// every gmpc_set_params (one launch on `s`, ahead of the solve's own); called behind gmpc_sampled_coverage
-int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s) {
-  if (c->sampled_precision != GMPC_SAMPLED_BF16) return 0;
-  const gmpc_shape& sh = c->sh;
-  if (!c->w16) {
-    __bf16* p = nullptr;
-    TRY(dalloc(c, &p, gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims) +
-                          gmpc_bf16_image_elems(sh.cost_layers, sh.cost_dims)));
-    c->w16 = p;
-    c->w16_stale = true;
-  }
-  if (c->w16_stale) {
-    gmpc_bind_bf16_images(c->dyn16, c->dyn, c->w16);
-    gmpc_bind_bf16_images(c->cost16, c->cost,
-                          static_cast<__bf16*>(c->w16) + gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims));
-    gmpc_launch_pack_bf16(c->dyn, c->dyn16, c->cost, c->cost16, s);
-    HIP_TRY(hipGetLastError());
-    c->w16_stale = false;
-  }
-  if (c->ens_P > 0 && (c->ens16_stale || !c->ens16.p)) {
-    // the members' images, one behind the other (each a multiple of 8 elements): k_pack_bf16 once per member, the
-    // dynamics layers only (the cost MLP's image is the shared one above)
-    const size_t elems = gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims);
-    const long count = mlp_count(sh.dyn_layers, sh.dyn_dims);
-    TRY(c->ens16.grow(c, (size_t)c->ens_P * elems / 2));
-    gmpc_bind_bf16_images(c->ens_dyn16, c->ens_dyn, c->ens16.p);
-    MlpDesc none{};
-    for (int p = 0; p < c->ens_P; ++p) {
-      MlpDesc src = c->ens_dyn, img = c->ens_dyn16;
-      for (int l = 0; l < src.L; ++l) {
-        src.W[l] += (size_t)p * count;
-        img.W[l] += (size_t)p * (elems / 2);
-      }
-      gmpc_launch_pack_bf16(src, img, none, none, s);
-    }
-    HIP_TRY(hipGetLastError());
-    c->ens16_stale = false;
-  }
-  return 0;
-}
-
-// What the launches over sampled rows need under an ensemble: the members' strides in the context's precision and the
-// cost planes [P][B][ldc] in the call workspace
-static int ensemble_args(gmpc_ctx* c, int B, int ldc, CemEnsemble& e) {
-  const gmpc_shape& sh = c->sh;
-  const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
-  e.P = c->ens_P;
-  e.bstride = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims);
-  e.wstride = bf16 ? gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims) / 2 : e.bstride;
-  e.invP = 1.0f / (float)c->ens_P;
-  TRY(c->cw.part.grow(c, (size_t)c->ens_P * B * ldc));
-  e.part = c->cw.part.p;
-  return 0;
-}
-
-// One launch over sampled rows in the context's precision (bf16 mode: the same arguments over the packed images).
-// With an ensemble set: the rows under every member, then the reduce of the members' costs into r's.
-static int launch_sampled_rows(gmpc_ctx* c, const CemRollArgs& r, hipStream_t s) {
-  const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
-  if (c->ens_P > 0) {
-    CemEnsemble e;
-    if (ensemble_args(c, r.B, r.N, e)) return 1;
-    CemRollArgs h = r;
-    h.dyn = bf16 ? c->ens_dyn16 : c->ens_dyn;
-    if (bf16) h.cost = c->cost16;
-    return gmpc_launch_cem_rollout_ens(h, e, bf16, s);
-  }
-  if (!bf16) return gmpc_launch_cem_rollout(r, s);
-  CemRollArgs h = r;
-  h.dyn = c->dyn16; h.cost = c->cost16;
-  return gmpc_launch_cem_rollout_bf16(h, s);
-}
-static int launch_sampled_rows(gmpc_ctx* c, const IcemRollArgs& r, hipStream_t s) {
-  const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
-  if (c->ens_P > 0) {
-    CemEnsemble e;
-    if (ensemble_args(c, r.c.B, r.ldc, e)) return 1;
-    IcemRollArgs h = r;
-    h.c.dyn = bf16 ? c->ens_dyn16 : c->ens_dyn;
-    if (bf16) h.c.cost = c->cost16;
-    return gmpc_launch_icem_rollout_ens(h, e, bf16, s);
-  }
-  if (!bf16) return gmpc_launch_icem_rollout(r, s);
-  IcemRollArgs h = r;
-  h.c.dyn = c->dyn16; h.c.cost = c->cost16;
-  return gmpc_launch_icem_rollout_bf16(h, s);
-}
-
-// The cross-entropy method: 2 max_iter + 1 launches on the caller's stream (3 max_iter + 1 under an
-// ensemble, DESIGN §24: the reduce of the members' costs), nothing waited for.
-// Stateless: it writes the caller's arrays and the call workspace only, so a held solution survives it.
-extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
-                              const float* u_hi, const gmpc_cem_opts* o, float* mean_io, float* std_io, float* X,
-                              float* obj, float* costs, int* elites, float* samples, void* stream) {
-  TRY(check_call(c, B));
-  const gmpc_shape& sh = c->sh;
-  TRY(gmpc_sampled_coverage(c, "cem"));
-  if (!o) return fail(GMPC_EINVAL, "cem: opts is null");
-  if (!x0 || !goal || !mean_io || !std_io) return fail(GMPC_EINVAL, "cem: x0, goal, mean_io and std_io must not be null");
-  if (o->num_samples < 1 || o->num_samples > 4096)
-    return fail(GMPC_EINVAL, "cem: num_samples = %d outside [1, 4096]", o->num_samples);
-  if (o->num_elites < 1 || o->num_elites > o->num_samples)
-    return fail(GMPC_EINVAL, "cem: num_elites = %d outside [1, num_samples = %d]", o->num_elites, o->num_samples);
-  if (o->max_iter < 0) return fail(GMPC_EINVAL, "cem: max_iter = %d is negative", o->max_iter);
-  if (!(o->sampling_smoothing >= 0.f && o->sampling_smoothing < 1.f))
-    return fail(GMPC_EINVAL, "cem: sampling_smoothing = %g outside [0, 1)", (double)o->sampling_smoothing);
-  if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
-    return fail(GMPC_EINVAL, "cem: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (o->max_iter > 0) TRY(gmpc_sampled_prepare(c, s));
-  const int N = o->num_samples;
-  float* cost_buf = costs;
-  if (!cost_buf && o->max_iter > 0) {
-    TRY(c->cw.aux.grow(c, (size_t)B * N));
-    cost_buf = c->cw.aux.p;
-  }
-  CemRollArgs r;
-  memset(&r, 0, sizeof(r));
-  r.B = B; r.N = N; r.T = sh.T; r.n = sh.n; r.m = sh.m;
-  r.dyn = c->dyn; r.cost = c->cost; r.mpc_w = c->mpc_w;
-  r.x0 = x0; r.goal = goal; r.mean = mean_io; r.sd = std_io; r.lo = u_lo; r.hi = u_hi;
-  r.rng.key0 = (uint32_t)(o->seed & 0xFFFFFFFFull); r.rng.key1 = (uint32_t)(o->seed >> 32);
-  r.rng.beta = o->sampling_smoothing;
-  r.rng.cbeta = sqrtf(1.f - r.rng.beta * r.rng.beta);
-  r.costs = cost_buf;
-  CemUpdArgs u;
-  memset(&u, 0, sizeof(u));
-  u.B = B; u.N = N; u.E = o->num_elites; u.T = sh.T; u.m = sh.m;
-  u.costs = cost_buf; u.lo = u_lo; u.hi = u_hi; u.mean = mean_io; u.sd = std_io;
-  u.gamma = o->evolution_smoothing;
-  for (int i = 0; i < o->max_iter; ++i) {
-    const bool last = i == o->max_iter - 1;
-    r.rng.it = (uint32_t)(o->iter_offset + i);
-    r.samples = last ? samples : nullptr;
-    u.rng = r.rng;
-    u.elites = last ? elites : nullptr;
-    if (launch_sampled_rows(c, r, s) || gmpc_launch_cem_update(u, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
-  }
-  if (X || obj) {
-    // the final mean's own rollout: one row per problem, no noise, no clamp
-    if (!obj) {
-      TRY(c->cw.aux2.grow(c, (size_t)B));
-      obj = c->cw.aux2.p;
-    }
-    r.N = 1; r.mean_row = 1; r.samples = nullptr; r.costs = obj; r.X = X;
-    if (gmpc_launch_cem_rollout(r, s)) return fail(GMPC_EINVAL, "cem: shape not covered");
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// What gmpc_mppi_solve and gmpc_mppi_vjp refuse in their options
-int gmpc_mppi_check_opts(const gmpc_mppi_opts* o) {
-  if (!o) return fail(GMPC_EINVAL, "mppi: opts is null");
-  if (o->num_samples < 1 || o->num_samples > 4096)
-    return fail(GMPC_EINVAL, "mppi: num_samples = %d outside [1, 4096]", o->num_samples);
-  if (o->max_iter < 0) return fail(GMPC_EINVAL, "mppi: max_iter = %d is negative", o->max_iter);
-  if (!(o->sampling_smoothing >= 0.f && o->sampling_smoothing < 1.f))
-    return fail(GMPC_EINVAL, "mppi: sampling_smoothing = %g outside [0, 1)", (double)o->sampling_smoothing);
-  if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
-    return fail(GMPC_EINVAL, "mppi: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
-  if (!(o->temperature > 0.f) || !(o->temperature < INFINITY))
-    return fail(GMPC_EINVAL, "mppi: temperature = %g is not positive and finite", (double)o->temperature);
-  return 0;
-}
-
-CemRng gmpc_mppi_rng(const gmpc_mppi_opts* o, int i) {
-  CemRng g;
-  g.key0 = (uint32_t)(o->seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(o->seed >> 32);
-  g.it = (uint32_t)(o->iter_offset + i);
-  g.beta = o->sampling_smoothing;
-  g.cbeta = sqrtf(1.f - g.beta * g.beta);
-  return g;
-}
-
-// Model-predictive path integral control: CEM's samples and costs (k_cem_rollout, unchanged), the elite
-// cut replaced by softmax weights.  2 max_iter + 1 launches on the caller's stream, nothing waited for; stateless as
-// gmpc_cem_solve is.
-extern "C" int gmpc_mppi_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
-                               const float* u_hi, const gmpc_mppi_opts* o, float* mean_io, const float* std, float* X,
-                               float* obj, float* costs, float* weights, float* samples, float* means_trace,
-                               float* costs_trace, void* stream) {
-  TRY(check_call(c, B));
-  const gmpc_shape& sh = c->sh;
-  TRY(gmpc_sampled_coverage(c, "mppi"));
-  TRY(gmpc_mppi_check_opts(o));
-  if (!x0 || !goal || !mean_io || !std) return fail(GMPC_EINVAL, "mppi: x0, goal, mean_io and std must not be null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (o->max_iter > 0) TRY(gmpc_sampled_prepare(c, s));
-  const int N = o->num_samples;
-  const size_t BN = (size_t)B * N, BTm = (size_t)B * sh.T * sh.m;
-  float* cost_buf = costs;
-  if (!cost_buf && !costs_trace && o->max_iter > 0) {
-    TRY(c->cw.aux.grow(c, BN));
-    cost_buf = c->cw.aux.p;
-  }
-  CemRollArgs r;
-  memset(&r, 0, sizeof(r));
-  r.B = B; r.N = N; r.T = sh.T; r.n = sh.n; r.m = sh.m;
-  r.dyn = c->dyn; r.cost = c->cost; r.mpc_w = c->mpc_w;
-  r.x0 = x0; r.goal = goal; r.mean = mean_io; r.sd = std; r.lo = u_lo; r.hi = u_hi;
-  MppiUpdArgs u;
-  memset(&u, 0, sizeof(u));
-  u.B = B; u.N = N; u.T = sh.T; u.m = sh.m;
-  u.lo = u_lo; u.hi = u_hi; u.mean = mean_io; u.sd = std;
-  u.gamma = o->evolution_smoothing; u.lam = o->temperature;
-  for (int i = 0; i < o->max_iter; ++i) {
-    const bool last = i == o->max_iter - 1;
-    r.rng = gmpc_mppi_rng(o, i);
-    r.samples = last ? samples : nullptr;
-    // with a trace the iteration's costs are written where they stay; `costs` gets the last iteration's copy
-    r.costs = costs_trace ? costs_trace + (size_t)i * BN : cost_buf;
-    u.rng = r.rng;
-    u.costs = r.costs;
-    u.costs_copy = last && costs_trace ? costs : nullptr;
-    u.weights = last ? weights : nullptr;
-    u.mean_trace = means_trace ? means_trace + (size_t)i * BTm : nullptr;
-    if (launch_sampled_rows(c, r, s) || gmpc_launch_mppi_update(u, s))
-      return fail(GMPC_EINVAL, "mppi: shape not covered");
-  }
-  if (X || obj) {
-    // the final mean's own rollout: one row per problem, no noise, no clamp
-    if (!obj) {
-      TRY(c->cw.aux2.grow(c, (size_t)B));
-      obj = c->cw.aux2.p;
-    }
-    r.N = 1; r.mean_row = 1; r.samples = nullptr; r.costs = obj; r.X = X;
-    if (gmpc_launch_cem_rollout(r, s)) return fail(GMPC_EINVAL, "mppi: shape not covered");
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// What gmpc_icem_solve and gmpc_icem_plan_host refuse in their options
-static int icem_check_opts(const gmpc_icem_opts* o) {
-  if (!o) return fail(GMPC_EINVAL, "icem: opts is null");
-  if (o->num_samples < 1 || o->num_samples > 4096)
-    return fail(GMPC_EINVAL, "icem: num_samples = %d outside [1, 4096]", o->num_samples);
-  if (o->num_elites < 1 || o->num_elites > o->num_samples)
-    return fail(GMPC_EINVAL, "icem: num_elites = %d outside [1, num_samples = %d]", o->num_elites, o->num_samples);
-  if (o->num_keep < 0 || o->num_keep > o->num_elites)
-    return fail(GMPC_EINVAL, "icem: num_keep = %d outside [0, num_elites = %d]", o->num_keep, o->num_elites);
-  if (o->carry_in < 0 || o->carry_in > o->num_keep)
-    return fail(GMPC_EINVAL, "icem: carry_in = %d outside [0, num_keep = %d]", o->carry_in, o->num_keep);
-  if (o->num_samples + o->num_keep + 1 > 4096)
-    return fail(GMPC_EINVAL, "icem: num_samples + num_keep + 1 = %d above 4096", o->num_samples + o->num_keep + 1);
-  if (o->max_iter < 0) return fail(GMPC_EINVAL, "icem: max_iter = %d is negative", o->max_iter);
-  if (o->iter_offset < 0) return fail(GMPC_EINVAL, "icem: iter_offset = %d is negative", o->iter_offset);
-  if (!(o->decay >= 1.f) || !(o->decay < INFINITY))
-    return fail(GMPC_EINVAL, "icem: decay = %g is not finite and >= 1", (double)o->decay);
-  if (!(o->noise_beta >= 0.f) || !(o->noise_beta < INFINITY))
-    return fail(GMPC_EINVAL, "icem: noise_beta = %g is not finite and >= 0", (double)o->noise_beta);
-  if (!(o->evolution_smoothing >= 0.f && o->evolution_smoothing <= 1.f))
-    return fail(GMPC_EINVAL, "icem: evolution_smoothing = %g outside [0, 1]", (double)o->evolution_smoothing);
-  return 0;
-}
-
-// The one place the sample counts and the coloured sum's weights are computed (host only; IEEE double arithmetic, so a
-// NumPy restatement agrees: N_it exactly, cw to the rounding of libm's pow)
-extern "C" int gmpc_icem_plan_host(const gmpc_icem_opts* o, int T, int* N_it, float* cw) {
-  TRY(icem_check_opts(o));
-  if (T < 1) return fail(GMPC_EINVAL, "icem: T = %d is not positive", T);
-  if (N_it) {
-    const double decay = (double)o->decay;
-    const int floor_n = std::min(o->num_samples, 2 * o->num_elites);
-    double nk = (double)o->num_samples;
-    for (int it = 0; it < o->iter_offset && nk >= 1.0; ++it) nk = nk / decay;     // (below 1 the floor stays 0)
-    for (int i = 0; i < o->max_iter; ++i) {
-      N_it[i] = std::max((int)std::floor(nk), floor_n);
-      nk = nk / decay;
-    }
-  }
-  if (cw) {
-    const int Kf = T / 2;
-    std::vector<double> w(Kf + 1, 1.0);
-    for (int k = 1; k <= Kf; ++k) w[k] = std::pow((double)k / (double)T, -(double)o->noise_beta / 2.0);
-    if (Kf >= 1) w[0] = w[1];
-    double s2 = w[0] * w[0];
-    for (int k = 1; 2 * k < T; ++k) s2 += 2.0 * w[k] * w[k];
-    if (T % 2 == 0) s2 += w[Kf] * w[Kf];
-    const double s = std::sqrt(s2);
-    cw[0] = (float)(w[0] / s);
-    for (int k = 1; 2 * k < T; ++k) cw[k] = (float)(std::sqrt(2.0) * w[k] / s);
-    if (T % 2 == 0) cw[Kf] = (float)(w[Kf] / s);
-  }
-  return 0;
-}
-
-// The sample-efficient cross-entropy method: 2 max_iter + 1 launches on the caller's stream, nothing
-// waited for.  Stateless as gmpc_cem_solve is: the caller's arrays and the call workspace only.
-extern "C" int gmpc_icem_solve(gmpc_ctx* c, int B, const float* x0, const float* goal, const float* u_lo,
-                               const float* u_hi, const gmpc_icem_opts* o, float* mean_io, float* std_io,
-                               float* keep_io, float* best_U_io, float* best_cost_io, float* U_out, float* X, float* obj,
-                               float* costs, int* elites, float* samples, void* stream) {
-  TRY(check_call(c, B));
-  const gmpc_shape& sh = c->sh;
-  TRY(gmpc_sampled_coverage(c, "icem"));
-  TRY(icem_check_opts(o));
-  if (!x0 || !goal || !mean_io || !std_io)
-    return fail(GMPC_EINVAL, "icem: x0, goal, mean_io and std_io must not be null");
-  if (o->num_keep > 0 && !keep_io) return fail(GMPC_EINVAL, "icem: keep_io must not be null with num_keep = %d", o->num_keep);
-  if ((best_U_io != nullptr) != (best_cost_io != nullptr))
-    return fail(GMPC_EINVAL, "icem: best_U_io and best_cost_io go together");
-  if (o->return_best && (!best_U_io || !U_out))
-    return fail(GMPC_EINVAL, "icem: best_U_io, best_cost_io and U_out must not be null with return_best");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int N = o->num_samples, nk = o->num_keep, K = o->max_iter, T = sh.T, m = sh.m;
-  if (K > 0) TRY(gmpc_sampled_prepare(c, s));
-  const int ldc = N + nk + 1;
-  const size_t BTm = (size_t)B * T * m, keep_floats = (size_t)B * nk * T * m;
-  std::vector<int> Nit(K > 0 ? K : 1);
-  std::vector<float> cwh(T / 2 + 1);
-  TRY(gmpc_icem_plan_host(o, T, Nit.data(), cwh.data()));
-  const bool white = o->noise_beta == 0.f || T < 2;
-  if (!white && K > 0 && (!c->icem_cw || c->icem_cw_beta != o->noise_beta)) {
-    if (!c->icem_cw) TRY(dalloc(c, &c->icem_cw, cwh.size()));
-    c->icem_cw_host = cwh;
-    c->icem_cw_beta = o->noise_beta;
-    HIP_TRY(hipMemcpyAsync(c->icem_cw, c->icem_cw_host.data(), cwh.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  }
-  float* cost_buf = costs;
-  if (!cost_buf && K > 0) {
-    TRY(c->cw.aux.grow(c, (size_t)B * ldc));
-    cost_buf = c->cw.aux.p;
-  }
-  // the kept rows ping-pong between two buffers of the call workspace (the update reads the old rows while it writes
-  // the new ones); the first iteration reads keep_io, the last one writes it.  With one iteration both are keep_io:
-  // its rows are copied aside first.
-  float* W[2] = {nullptr, nullptr};
-  const bool aside = K == 1 && o->carry_in > 0;
-  if (nk > 0 && (K >= 2 || aside)) {
-    TRY(c->cw.save.grow(c, 2 * keep_floats));
-    W[0] = c->cw.save.p;
-    W[1] = W[0] + keep_floats;
-  }
-  if (aside) HIP_TRY(hipMemcpyAsync(W[0], keep_io, keep_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
-  IcemRollArgs r;
-  memset(&r, 0, sizeof(r));
-  r.c.B = B; r.c.N = N; r.c.T = T; r.c.n = sh.n; r.c.m = m;
-  r.c.dyn = c->dyn; r.c.cost = c->cost; r.c.mpc_w = c->mpc_w;
-  r.c.x0 = x0; r.c.goal = goal; r.c.mean = mean_io; r.c.sd = std_io; r.c.lo = u_lo; r.c.hi = u_hi;
-  r.c.rng.key0 = (uint32_t)(o->seed & 0xFFFFFFFFull); r.c.rng.key1 = (uint32_t)(o->seed >> 32);
-  r.c.rng.beta = 0.f; r.c.rng.cbeta = 1.f;
-  r.c.costs = cost_buf;
-  r.ldc = ldc;
-  r.zlds = !white &&
-           gmpc_icem_zlds(T, m, c->sampled_precision == GMPC_SAMPLED_BF16);
-  r.p.nkeep = nk; r.p.white = white; r.p.cw = white ? nullptr : c->icem_cw;
-  IcemUpdArgs u;
-  memset(&u, 0, sizeof(u));
-  u.B = B; u.E = o->num_elites; u.T = T; u.m = m; u.ldc = ldc;
-  u.costs = cost_buf; u.lo = u_lo; u.hi = u_hi; u.mean = mean_io; u.sd = std_io;
-  u.gamma = o->evolution_smoothing;
-  u.best_U = best_U_io; u.best_cost = best_cost_io; u.U_out = U_out; u.return_best = o->return_best != 0;
-  const float* keep_src = aside ? W[0] : keep_io;
-  for (int i = 0; i < K; ++i) {
-    const bool last = i == K - 1;
-    r.c.rng.it = (uint32_t)(o->iter_offset + i);
-    r.c.samples = last ? samples : nullptr;
-    r.p.Nit = Nit[i];
-    r.p.carry = i == 0 ? o->carry_in : nk;
-    r.p.addmean = o->add_mean && last;
-    r.p.keep = r.p.carry > 0 ? keep_src : nullptr;
-    u.p = r.p;
-    u.rng = r.c.rng;
-    u.elites = last ? elites : nullptr;
-    u.last = last;
-    u.keep_out = nk == 0 ? nullptr : last ? keep_io : W[i & 1];
-    if (launch_sampled_rows(c, r, s) || gmpc_launch_icem_update(u, s))
-      return fail(GMPC_EINVAL, "icem: shape not covered");
-    keep_src = u.keep_out;
-  }
-  // without an iteration nothing was sampled: the returned sequence is the mean
-  if (K == 0 && U_out) HIP_TRY(hipMemcpyAsync(U_out, mean_io, BTm * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (X || obj) {
-    // the returned sequence's own rollout: one row per problem, no noise, no clamp (k_cem_rollout's mean_row form)
-    if (!obj) {
-      TRY(c->cw.aux2.grow(c, (size_t)B));
-      obj = c->cw.aux2.p;
-    }
-    CemRollArgs f = r.c;
-    f.N = 1; f.mean_row = 1; f.samples = nullptr; f.costs = obj; f.X = X;
-    f.mean = U_out ? U_out : mean_io;
-    if (gmpc_launch_cem_rollout(f, s)) return fail(GMPC_EINVAL, "icem: shape not covered");
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
 // single model evaluations (the reference's model protocol, base.py:4-49) -----------------------
 
 extern "C" int gmpc_get_cost(gmpc_ctx* c, int B, const float* x, const float* u, const float* goal_row,

@@ -1,16 +1,17 @@
-// What the sampling solvers' kernels share beyond the sampler: the body of the sampled rollout (k_cem_rollout of
-// gmpc_cem.hip, k_icem_rollout of gmpc_icem.hip -- one body, instantiated over where a row's controls come from) and
-// the (cost, row) keys with their sort (k_cem_update, k_icem_update).
+// What the sampling solvers' kernels share beyond the sampler: the sampled rollout -- one body (cem_rollout_body), one
+// kernel template around it (k_sampled_rollout) and one launcher (sampled_launch_rollout), each instantiated over where
+// a row's controls come from (CemDrawn of gmpc_cem.hip, IcemDrawn of gmpc_icem.hip) -- and the (cost, row) keys with
+// their sort (k_cem_update, k_icem_update).
 #pragma once
 #include "gmpc_dg_gemm.h"
 #include "gmpc_cem_sampler.h"
 
 #define GMPC_CEM_ROWS 32          // samples per workgroup of the rollout (the two row halves of dg_gemm)
-#define GMPC_CEM_MAX_N 4096       // rows per problem (the sort's keys: 32 KiB of LDS)
 // LDS of the rollout's operand blocks, in bytes: the fp32 block [32][GMPC_DG_LDA]; in bf16 mode the bf16 block
 // [32][GMPC_DG_LDH] behind it (33,280 + 16,896 = 50,176: three workgroups per compute unit, as the registers allow)
 #define GMPC_CEM_LDS32 (GMPC_CEM_ROWS * GMPC_DG_LDA * 4)
 #define GMPC_CEM_LDS16 (GMPC_CEM_LDS32 + GMPC_CEM_ROWS * GMPC_DG_LDH * 2)
+#define GMPC_SAMPLED_LDS_BYTES 65536     // dynamic LDS a launch may ask for without opting in to more
 
 // ---- the rollout ----------------------------------------------------------------------------------------------
 // Sum over the 8 lanes of a row's group (lanes 8 i .. 8 i + 7 of a wave), the same value in each: a fixed butterfly,
@@ -69,10 +70,16 @@ __device__ __forceinline__ void cem_store_tiles16(float* Ab, __bf16* Hb, const D
 }
 
 // One 256-thread workgroup per 32 rows of one problem, the whole horizon.  `rows` rows per problem, costs [B][ldc];
-// Ab: the [32][GMPC_DG_LDA] operand block at the start of the dynamic LDS.  Src, where the controls come from:
-//   begin(b, s0, tid)         once, before the first step (it may fill LDS behind the operand block and synchronise)
+// Ab: the [32][GMPC_DG_LDA] operand block at the start of the dynamic LDS.  Src, where the controls come from.  What
+// the body asks of it:
+//   begin(b, s0, tid)         once, before the first step (it may fill LDS behind the operand blocks and synchronise)
 //   control(b, i, s, t, j)    the control j of step t of row s = s0 + i of problem b
 //   record(b, s, t, j, u)     the debug copy of that control, if the caller asked for one
+// and what the kernel template and the launcher ask of it (static, host and device, over its arguments Src::Args):
+//   roll(a) / rows(a) / ldc(a)   the CemRollArgs inside a, the rows per problem, the stride of the costs
+//   Src(a, behind)            `behind`: the dynamic LDS behind the operand block or blocks
+//   plan(a, blocks, &extra)   host only: non-zero when the launcher refuses a; otherwise a's launch-time fields are set
+//                             and extra is the bytes of LDS the source wants behind the `blocks` bytes of operands
 // A row's cost is a function of its controls alone: not of its place in the tile, of `rows` or of B.
 // Ens, which dynamics network the workgroup rolls its rows out under and where their costs go:
 //   W(w) / b(v)               a dynamics layer's weights / biases, from the bound descriptor's pointers
@@ -236,6 +243,62 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     csum += w2 * sy;
     if (rc == 0 && s0 + rrow < rows) ens.costs(a.costs)[(size_t)b * ldc + s0 + rrow] = csum;
   }
+}
+
+// The one kernel of the sampled rollout: the operand block or blocks at the start of the dynamic LDS, the source's own
+// LDS behind them, then the body.  Eight instantiations, {CemDrawn, IcemDrawn} x {fp32, bf16} x {CemOneModel,
+// CemMember}, explicit in gmpc_cem.hip and gmpc_icem.hip.
+template <typename Src, bool BF16, typename Ens>
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_sampled_rollout(typename Src::Args a, Ens e) {
+  extern __shared__ __attribute__((aligned(16))) char smem_roll[];
+  float* Ab = reinterpret_cast<float*>(smem_roll);   // [32][GMPC_DG_LDA] fp32: the layer inputs of the 32 rows (bf16
+                                                     // mode: [x_t; u_t] and the last cost output)
+  __bf16* Hb = BF16 ? reinterpret_cast<__bf16*>(smem_roll + GMPC_CEM_LDS32) : nullptr;   // [32][GMPC_DG_LDH]
+  Src src(a, smem_roll + (BF16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32));
+  cem_rollout_body<BF16>(Src::roll(a), Src::rows(a), Src::ldc(a), Ab, Hb, src, e);
+}
+
+// Host side.  The launch of one precision: the grid -- tiles of 32 rows per problem by members -- and, under an
+// ensemble, the reduce of the members' costs behind it
+template <typename Src, bool BF16>
+static void sampled_launch_form(const typename Src::Args& a, size_t lds, const CemEnsemble* ens, hipStream_t s) {
+  const CemRollArgs& c = Src::roll(a);
+  const int rows = Src::rows(a), ldc = Src::ldc(a), tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
+  const dim3 grid(c.B * tiles, ens ? ens->P : 1);
+  if (!ens) {
+    hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemOneModel>), grid, dim3(GMPC_DG_THREADS), lds, s, a,
+                       CemOneModel());
+    return;
+  }
+  const CemMember mb{ens->wstride, ens->bstride, (size_t)c.B * ldc, ens->part};
+  hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemMember>), grid, dim3(GMPC_DG_THREADS), lds, s, a, mb);
+  gmpc_launch_ens_reduce(*ens, c.B, rows, ldc, c.costs, s);
+}
+
+// The one launcher.  Non-zero (nothing launched) outside the covered shapes -- widths and n + m up to
+// GMPC_SAMPLED_MAX_WIDTH, 1 .. GMPC_CEM_MAX_N rows -- for the mean_row form in anything but fp32 on one model, for X
+// under an ensemble, and where the source refuses.  ens: null, or the ensemble whose members all roll the rows out
+// (the arguments' dyn: member 0; bf16: its images).
+template <typename Src>
+static int sampled_launch_rollout(const typename Src::Args& a0, bool bf16, const CemEnsemble* ens, hipStream_t s) {
+  typename Src::Args a = a0;
+  const CemRollArgs& c = Src::roll(a);
+  for (int l = 0; l <= c.dyn.L; ++l)
+    if (c.dyn.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
+  for (int l = 0; l <= c.cost.L; ++l)
+    if (c.cost.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
+  const int rows = Src::rows(a);
+  if (c.n + c.m > GMPC_SAMPLED_MAX_WIDTH || rows < 1 || rows > GMPC_CEM_MAX_N || Src::ldc(a) < rows) return 1;
+  if (c.mean_row && (bf16 || ens)) return 1;     // (the returned sequence's rollout is the fp32 kernel's)
+  if (ens && (c.X || ens->P < 1 || ens->P > GMPC_MAX_ENSEMBLE || !ens->part)) return 1;
+  const size_t blocks = bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32;
+  size_t extra = 0;
+  if (Src::plan(a, blocks, &extra)) return 1;
+  if (bf16)
+    sampled_launch_form<Src, true>(a, blocks + extra, ens, s);
+  else
+    sampled_launch_form<Src, false>(a, blocks + extra, ens, s);
+  return 0;
 }
 
 // ---- the keys of the update -----------------------------------------------------------------------------------

@@ -221,13 +221,13 @@ static void bind_expert(ExpertNet& e, int nx, int m, const gmpc_expert_shape* es
 
 // gmpc_api.hip: argument and state checks every entry point starts with
 int check_call(gmpc_ctx* c, int B, bool need_params = true);
-// gmpc_api_solve.hip: the sampling solvers' shared checks (`who`: the message's prefix) and MPPI's noise stream of
-// iteration iter_offset + i
+// gmpc_api_sampled.hip: the sampling solvers' shared checks (`who`: the message's prefix) and the noise stream of
+// iteration `it` under `seed` (beta: the smoothing along time)
 int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who);
 // in bf16 mode: the packed weight images brought up to date on `s` (allocated on first use); nothing in fp32 mode
 int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s);
 int gmpc_mppi_check_opts(const gmpc_mppi_opts* o);
-CemRng gmpc_mppi_rng(const gmpc_mppi_opts* o, int i);
+CemRng gmpc_sampled_rng(uint64_t seed, int it, float beta);
 // gmpc_api_critic.hip: the upper-level loss at the solution held by the ctx (and, with want_lx, its gradient in c->lx)
 int upper_loss(gmpc_ctx* c, int B, int loss_kind, const float* desired, const float* critic, float* loss, bool want_lx,
                hipStream_t s);

@@ -1,18 +1,17 @@
 // The sample-efficient cross-entropy method (gmpc_icem_solve; Pinneri et al., CoRL 2020) on the
 // sampled rollout of the cross-entropy method.  Per iteration a pool of rows per problem -- fresh samples with
 // power-law ("coloured") noise along the horizon, the rows kept from the iteration before, in the last iteration the
-// mean itself -- is rolled out and costed (k_icem_rollout: the body of k_cem_rollout over another source of
+// mean itself -- is rolled out and costed (k_sampled_rollout over IcemDrawn: CEM's rollout over another source of
 // controls); the E cheapest by (cost, row) refit mean and std, the cheapest of them become the next kept rows, and
 // the best row seen so far is remembered (k_icem_update).  As in gmpc_cem.hip no noise and no sample is stored: a
 // fresh control is a pure function of (seed, iteration, problem, sample, step, control) -- icem_control, the one
 // place a pool row's control is formed -- and the update regenerates the elites' controls.
 //
-//   k_icem_rollout  one 256-thread workgroup per 32 pool rows of one problem (cem_rollout_body).  The coloured sum of
-//                   a control needs the T normals of its (row, control): formed once per tile in LDS behind the
-//                   operand block where 32 m T floats fit there (zlds), regenerated per element otherwise -- the
-//                   same sum in the same order either way.
-//   k_icem_rollout_ens, k_icem_rollout_ens_bf16  the pool's rows under every member of a dynamics ensemble (DESIGN.md
-//                   section 24; blockIdx.y: the member), followed by k_ens_reduce of gmpc_cem.hip
+//   k_sampled_rollout<IcemDrawn, BF16, Ens>  (gmpc_cem_rollout.h) the rollout kernel over the pool's rows, four forms
+//                   as in gmpc_cem.hip: fp32 or bf16 operands, one model or every member of a dynamics ensemble.  The
+//                   coloured sum of a control needs the T normals of its (row, control): formed once per tile in LDS
+//                   behind the operand blocks where 32 m T floats fit there (zlds), regenerated per element otherwise
+//                   -- the same sum in the same order either way.
 //   k_icem_update   one workgroup per problem: the sort of k_cem_update over the pool's rows, then the elites' sums in
 //                   rank order (for T m < 256 by the whole workgroup, in blocks of elites staged in LDS: the same
 //                   sums), the kept rows, the best row and the returned sequence.
@@ -21,7 +20,6 @@
 #include <cstring>
 
 #define GMPC_ICEM_STAGE_FLOATS 4096   // k_icem_update's staged controls (16 KiB of LDS behind the keys)
-#define GMPC_ICEM_LDS_BYTES 65536     // dynamic LDS a launch may ask for without opting in to more
 
 // ---- the controls of a pool row -------------------------------------------------------------------------------
 // zt_t = cw_0 z_0 + sum_{1 <= k, 2k < T} cw_k (z_{2k-1} cos(2 pi k t / T) + z_{2k} sin(2 pi k t / T))
@@ -51,7 +49,7 @@ __device__ __forceinline__ int icem_row_kind(const IcemPool& p, int s) {
   return s == p.Nit + p.carry && p.addmean ? 2 : 0;
 }
 
-// The control j of step t of pool row s of problem b: the only place a pool row's control is formed (k_icem_rollout
+// The control j of step t of pool row s of problem b: the only place a pool row's control is formed (the rollout
 // and k_icem_update both call it).  mean / sd: the problem's [T][m]; keep: the problem's [nkeep][T][m]; z(k): the k-th
 // normal of (s, j), asked for on coloured fresh rows only.  The clamp is cem_control's: two selects.
 template <typename Z>
@@ -72,9 +70,27 @@ __device__ __forceinline__ float icem_control(const IcemPool& p, const CemRng& g
 
 // ---- the rollout ----------------------------------------------------------------------------------------------
 struct IcemDrawn {
+  using Args = IcemRollArgs;
+  static __host__ __device__ __forceinline__ const CemRollArgs& roll(const Args& a) { return a.c; }
+  static __host__ __device__ __forceinline__ int rows(const Args& a) { return a.p.Nit + a.p.carry + a.p.addmean; }
+  static __host__ __device__ __forceinline__ int ldc(const Args& a) { return a.ldc; }
+  // The pool's own refusals; zlds where the normals of a tile -- 32 m T floats -- fit behind the operand blocks (the
+  // controls are the same either way)
+  static int plan(Args& a, size_t blocks, size_t* extra) {
+    if (a.p.Nit < 1 || a.p.Nit > a.c.N || a.p.carry < 0 || a.p.carry > a.p.nkeep) return 1;
+    if (a.p.carry > 0 && !a.p.keep) return 1;
+    if (!a.p.white && !a.p.cw) return 1;
+    const size_t z = (size_t)GMPC_CEM_ROWS * a.c.m * a.c.T * sizeof(float);
+    a.zlds = !a.p.white && blocks + z <= GMPC_SAMPLED_LDS_BYTES;
+    *extra = a.zlds ? z : 0;
+    return 0;
+  }
+
   const IcemRollArgs& q;
-  float* zl;                  // zlds: [32][m][T] normals of the tile's fresh rows, behind the operand block
+  float* zl;                  // zlds: [32][m][T] normals of the tile's fresh rows, behind the operand blocks
   const float *mean, *sd, *keep;
+  __device__ __forceinline__ IcemDrawn(const Args& a, char* behind)
+      : q(a), zl(reinterpret_cast<float*>(behind)), mean(nullptr), sd(nullptr), keep(nullptr) {}
   __device__ __forceinline__ void begin(int b, int s0, int tid) {
     const int T = q.c.T, m = q.c.m;
     mean = q.c.mean + (size_t)b * T * m;
@@ -104,38 +120,10 @@ struct IcemDrawn {
   }
 };
 
-__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout(IcemRollArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_icem[];
-  float* Ab = reinterpret_cast<float*>(smem_icem);  // [32][GMPC_DG_LDA]: the layer inputs of the 32 pool rows
-  IcemDrawn src{a, Ab + GMPC_CEM_ROWS * GMPC_DG_LDA, nullptr, nullptr, nullptr};
-  cem_rollout_body<false>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, nullptr, src);
-}
-
-// The same rows with bf16 matrix operands: a.c.dyn.W / a.c.cost.W are the packed bf16 images,
-// and the normals of zlds lie behind both operand blocks
-__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_bf16(IcemRollArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_icem16[];
-  float* Ab = reinterpret_cast<float*>(smem_icem16);
-  __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);
-  IcemDrawn src{a, reinterpret_cast<float*>(smem_icem16 + GMPC_CEM_LDS16), nullptr, nullptr, nullptr};
-  cem_rollout_body<true>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, Hb, src);
-}
-
-// The same pool rows under every member of a dynamics ensemble (blockIdx.y: the member)
-__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_ens(IcemRollArgs a, CemMember e) {
-  extern __shared__ __attribute__((aligned(16))) char smem_icem_e[];
-  float* Ab = reinterpret_cast<float*>(smem_icem_e);
-  IcemDrawn src{a, Ab + GMPC_CEM_ROWS * GMPC_DG_LDA, nullptr, nullptr, nullptr};
-  cem_rollout_body<false>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, nullptr, src, e);
-}
-
-__global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_rollout_ens_bf16(IcemRollArgs a, CemMember e) {
-  extern __shared__ __attribute__((aligned(16))) char smem_icem_e16[];
-  float* Ab = reinterpret_cast<float*>(smem_icem_e16);
-  __bf16* Hb = reinterpret_cast<__bf16*>(Ab + GMPC_CEM_ROWS * GMPC_DG_LDA);
-  IcemDrawn src{a, reinterpret_cast<float*>(smem_icem_e16 + GMPC_CEM_LDS16), nullptr, nullptr, nullptr};
-  cem_rollout_body<true>(a.c, a.p.Nit + a.p.carry + a.p.addmean, a.ldc, Ab, Hb, src, e);
-}
+template __global__ void k_sampled_rollout<IcemDrawn, false, CemOneModel>(IcemRollArgs, CemOneModel);
+template __global__ void k_sampled_rollout<IcemDrawn, true, CemOneModel>(IcemRollArgs, CemOneModel);
+template __global__ void k_sampled_rollout<IcemDrawn, false, CemMember>(IcemRollArgs, CemMember);
+template __global__ void k_sampled_rollout<IcemDrawn, true, CemMember>(IcemRollArgs, CemMember);
 
 // ---- the update -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_update(IcemUpdArgs a, int P) {
@@ -240,51 +228,8 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_update(IcemUpdArgs a, 
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-// ens: null, or the ensemble whose members all roll the pool out (a.c.dyn: member 0), followed by the reduce
-static int icem_launch_rollout(const IcemRollArgs& a, bool bf16, hipStream_t s, const CemEnsemble* ens = nullptr) {
-  const CemRollArgs& c = a.c;
-  if (ens && (ens->P < 1 || ens->P > GMPC_MAX_ENSEMBLE || !ens->part || c.X || c.mean_row)) return 1;
-  for (int l = 0; l <= c.dyn.L; ++l)
-    if (c.dyn.dims[l] > 256) return 1;
-  for (int l = 0; l <= c.cost.L; ++l)
-    if (c.cost.dims[l] > 256) return 1;
-  const int rows = a.p.Nit + a.p.carry + a.p.addmean;
-  if (c.n + c.m > 256 || a.p.Nit < 1 || a.p.carry < 0 || a.p.carry > a.p.nkeep || rows > GMPC_CEM_MAX_N ||
-      a.ldc < rows || a.p.Nit > c.N)
-    return 1;
-  if (a.p.carry > 0 && !a.p.keep) return 1;
-  if (!a.p.white && !a.p.cw) return 1;
-  size_t lds = bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32;
-  if (a.zlds) lds += (size_t)GMPC_CEM_ROWS * c.m * c.T * sizeof(float);
-  if (lds > GMPC_ICEM_LDS_BYTES) return 1;
-  const int tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
-  if (ens) {
-    const CemMember mb{ens->wstride, ens->bstride, (size_t)c.B * a.ldc, ens->part};
-    if (bf16)
-      hipLaunchKernelGGL(k_icem_rollout_ens_bf16, dim3(c.B * tiles, ens->P), dim3(GMPC_DG_THREADS), lds, s, a, mb);
-    else
-      hipLaunchKernelGGL(k_icem_rollout_ens, dim3(c.B * tiles, ens->P), dim3(GMPC_DG_THREADS), lds, s, a, mb);
-    gmpc_launch_ens_reduce(*ens, c.B, rows, a.ldc, c.costs, s);
-    return 0;
-  }
-  if (bf16)
-    hipLaunchKernelGGL(k_icem_rollout_bf16, dim3(c.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
-  else
-    hipLaunchKernelGGL(k_icem_rollout, dim3(c.B * tiles), dim3(GMPC_DG_THREADS), lds, s, a);
-  return 0;
-}
-
-int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s) { return icem_launch_rollout(a, false, s); }
-int gmpc_launch_icem_rollout_bf16(const IcemRollArgs& a, hipStream_t s) { return icem_launch_rollout(a, true, s); }
-int gmpc_launch_icem_rollout_ens(const IcemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s) {
-  return icem_launch_rollout(a, bf16, s, &e);
-}
-
-// The shapes whose normals k_icem_rollout forms once per tile in LDS: 32 m T floats beside the operand block (bf16:
-// beside both blocks of k_icem_rollout_bf16; the controls are the same either way)
-int gmpc_icem_zlds(int T, int m, int bf16) {
-  return (size_t)(bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32) + (size_t)GMPC_CEM_ROWS * m * T * sizeof(float) <=
-         GMPC_ICEM_LDS_BYTES;
+int gmpc_launch_sampled_rollout(const IcemRollArgs& a, bool bf16, const CemEnsemble* ens, hipStream_t s) {
+  return sampled_launch_rollout<IcemDrawn>(a, bf16, ens, s);
 }
 
 int gmpc_launch_icem_update(const IcemUpdArgs& a0, hipStream_t s) {

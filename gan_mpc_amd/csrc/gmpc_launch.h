@@ -232,13 +232,31 @@ int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const f
                          const float* dX, const float* H, const float* w, const float* lam, float* acts, float* dels,
                          const MlpRows& lay, hipStream_t s);
 
+// The sampled rollout of the sampling solvers: k_sampled_rollout of gmpc_cem_rollout.h, instantiated over
+// CEM's rows (gmpc_cem.hip; MPPI's too) and iCEM's pool (gmpc_icem.hip), each with fp32 or bf16 matrix operands (§23)
+// and under one model or every member of a dynamics ensemble (§24).  What it covers -- here for the launcher and for
+// the entry points' messages:
+#define GMPC_SAMPLED_MAX_WIDTH 256   // every layer width of both MLPs, and n + m
+#define GMPC_CEM_MAX_N 4096          // rows per problem (the sort's keys: 32 KiB of LDS)
+// A dynamics ensemble: one grid row of workgroups per member, then k_ens_reduce.  The arguments' dyn describes member
+// 0 (bf16: with W[l] at its packed images); member p's weights lie p wstride floats behind them, its biases p bstride
+// floats; part [P][B][ldc] takes the members' costs and the arguments' costs [B][ldc] their sum in member order times
+// invP.
+#define GMPC_MAX_ENSEMBLE 16
+struct CemEnsemble {
+  int P;
+  size_t wstride, bstride;
+  float* part;
+  float invP;
+};
+
 // gmpc_cem.hip: the cross-entropy method's two kernels --------------------------------------------------
 // The noise stream of one iteration: Philox4x32-10 under the key (key0, key1), counter (element group, sample,
 // problem, it); cbeta = sqrt(1 - beta^2) of the smoothing along time.
 struct CemRng { uint32_t key0, key1, it; float beta, cbeta; };
-// k_cem_rollout: N sample rows per problem in tiles of 32; mean / sd [B][T][m]; lo / hi [m] or null.  mean_row: the
-// rows are the mean itself (std 0, no bounds; N = 1, and X [B][T+1][n] may be set).  costs [B][N]; samples
-// [B][N][T][m] or null.
+// The rollout over CEM's rows: N sample rows per problem in tiles of 32; mean / sd [B][T][m]; lo / hi [m] or null.
+// mean_row: the rows are the mean itself (std 0, no bounds; N = 1, and X [B][T+1][n] may be set).  costs [B][N];
+// samples [B][N][T][m] or null.
 struct CemRollArgs {
   int B, N, T, n, m, mean_row;
   MlpDesc dyn, cost;
@@ -255,9 +273,12 @@ struct CemUpdArgs {
   float gamma;
   int* elites;
 };
-// widths up to 256 and n + m <= 256, N <= 4096: non-zero (nothing launched) otherwise
-int gmpc_launch_cem_rollout(const CemRollArgs& a, hipStream_t s);
+// Non-zero (nothing launched) outside the limits above.  bf16: dyn.W[l] / cost.W[l] point at the layers' packed bf16
+// images (MlpDesc::W reinterpreted; gmpc_launch_pack_bf16).  ens: null, or the ensemble every member of which rolls the
+// rows out, followed by the reduce into a.costs (two launches; no X).  mean_row: fp32 on one model only.
+int gmpc_launch_sampled_rollout(const CemRollArgs& a, bool bf16, const CemEnsemble* ens, hipStream_t s);
 int gmpc_launch_cem_update(const CemUpdArgs& a, hipStream_t s);
+void gmpc_launch_ens_reduce(const CemEnsemble& e, int B, int rows, int ldc, float* costs, hipStream_t s);
 
 // gmpc_icem.hip: the sample-efficient cross-entropy method's two kernels --------------------------------
 // The rows of one iteration's pool, per problem: rows 0 .. Nit-1 fresh samples (sample index = row), rows Nit ..
@@ -268,12 +289,13 @@ struct IcemPool {
   int Nit, carry, addmean, nkeep, white;
   const float *keep, *cw;
 };
-// k_icem_rollout: k_cem_rollout's body over the pool's rows; c.N is the stride of `samples` (fresh rows only), costs
-// [B][ldc].  zlds: the T normals of every (row, control) of a tile are formed once, in LDS behind the operand block.
+// The rollout over the pool's rows; c.N is the stride of `samples` (fresh rows only), costs [B][ldc].
 struct IcemRollArgs {
   CemRollArgs c;
   IcemPool p;
-  int ldc, zlds;
+  int ldc;
+  int zlds;      // set by the launcher: the T normals of every (row, control) of a tile are formed once, in LDS behind
+                 // the operand blocks (where 32 m T floats fit there)
 };
 // k_icem_update: the E smallest of the pool's costs by (cost, row); mean / sd refit in place (left alone where no cost
 // is finite); keep_out [B][nkeep][T][m] <- the controls of ranks 0 .. nkeep-1; best_cost [B] / best_U [B][T][m]
@@ -291,18 +313,10 @@ struct IcemUpdArgs {
   int return_best, last;
   int stage;     // set by the launcher: elites per staged block of controls (0: one element per thread)
 };
-// CEM's shapes and Nit + carry + addmean <= 4096: non-zero (nothing launched) otherwise
-int gmpc_launch_icem_rollout(const IcemRollArgs& a, hipStream_t s);
+// CEM's limits with Nit + carry + addmean rows, bf16 and ens as there: non-zero (nothing launched) otherwise
+int gmpc_launch_sampled_rollout(const IcemRollArgs& a, bool bf16, const CemEnsemble* ens, hipStream_t s);
 int gmpc_launch_icem_update(const IcemUpdArgs& a, hipStream_t s);
-// non-zero where 32 m T floats fit in LDS beside the rollout's operand block (what zlds may be set for); bf16: beside
-// the two blocks of the bf16 kernel
-int gmpc_icem_zlds(int T, int m, int bf16 = 0);
 
-// The sampled rollouts with bf16 matrix operands: k_cem_rollout_bf16 / k_icem_rollout_bf16, the same
-// rows, controls and cost terms; dyn.W[l] / cost.W[l] of the arguments point at the layers' packed bf16 images
-// (MlpDesc::W reinterpreted), which gmpc_launch_pack_bf16 builds.  Never the mean_row form.
-int gmpc_launch_cem_rollout_bf16(const CemRollArgs& a, hipStream_t s);
-int gmpc_launch_icem_rollout_bf16(const IcemRollArgs& a, hipStream_t s);
 // gmpc_sampled_bf16.hip: bf16 elements of the packed images of an MLP's layers (each a multiple of 8), and the pack
 // of the fp32 weights src.W[l] into the images img.W[l] (one launch for both MLPs)
 size_t gmpc_bf16_image_elems(int L, const int* dims);
@@ -310,22 +324,7 @@ void gmpc_bind_bf16_images(MlpDesc& img, const MlpDesc& src, void* base);
 void gmpc_launch_pack_bf16(const MlpDesc& dyn, const MlpDesc& dyn_img, const MlpDesc& cost, const MlpDesc& cost_img,
                            hipStream_t s);
 
-// The sampled rollouts under a dynamics ensemble: k_cem_rollout_ens / k_icem_rollout_ens and their bf16
-// forms, one grid row of workgroups per member, then k_ens_reduce.  The arguments' dyn describes member 0 (bf16: with
-// W[l] at its packed images); member p's weights lie p wstride floats behind them, its biases p bstride floats; part
-// [P][B][ldc] takes the members' costs and the arguments' costs [B][ldc] their sum in member order times invP.
-#define GMPC_MAX_ENSEMBLE 16
-struct CemEnsemble {
-  int P;
-  size_t wstride, bstride;
-  float* part;
-  float invP;
-};
-int gmpc_launch_cem_rollout_ens(const CemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s);
-int gmpc_launch_icem_rollout_ens(const IcemRollArgs& a, const CemEnsemble& e, bool bf16, hipStream_t s);
-void gmpc_launch_ens_reduce(const CemEnsemble& e, int B, int rows, int ldc, float* costs, hipStream_t s);
-
-// gmpc_mppi.hip: the path-integral update on k_cem_rollout's costs, and its adjoint ------------------
+// gmpc_mppi.hip: the path-integral update on the costs of CEM's rollout, and its adjoint ----------------
 // k_mppi_update: w_s = exp(-(costs_s - min) / lam) over the finite costs [B][N], mean <- gamma mean + (1 - gamma)
 // sum_s w_s u_s / sum_s w_s in place; sd is read only.  weights [B][N] (normalised), mean_trace [B][T][m] (the mean
 // before the update) and costs_copy [B][N] may be null.

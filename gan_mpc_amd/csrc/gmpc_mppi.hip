@@ -1,5 +1,5 @@
 // Model-predictive path integral control on the sampled rollouts of the cross-entropy method (gmpc_mppi_solve,
-// gmpc_mppi_vjp).  The samples and their costs are CEM's (k_cem_rollout, the sampler of
+// gmpc_mppi_vjp).  The samples and their costs are CEM's (k_sampled_rollout over CemDrawn, the sampler of
 // gmpc_cem_sampler.h); the elite cut becomes the softmax weights w_s = exp(-(J_s - J_min) / lambda), so the update is
 // a smooth function of the costs and has a derivative.
 //

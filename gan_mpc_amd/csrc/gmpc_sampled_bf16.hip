@@ -1,5 +1,5 @@
 // The packed bf16 weight images of the sampled rollouts in bf16 mode (gmpc_set_sampled_precision; DESIGN.md section
-// 23): k_cem_rollout_bf16 (gmpc_cem.hip) and k_icem_rollout_bf16 (gmpc_icem.hip) read them through dg_gemm_bf16
+// 23): the BF16 instantiations of k_sampled_rollout (gmpc_cem_rollout.h) read them through dg_gemm_bf16
 // (gmpc_dg_gemm.h, where the layout is stated).
 //
 //   k_pack_bf16   one thread per 16-byte group (8 k-consecutive values of one column) of one layer's image: the fp32

@@ -111,14 +111,17 @@ def make_opts(kwargs=None):
     return o
 
 
+def _merged_kwargs(who, defaults, kwargs):
+    """A sampling solver's keyword set: `defaults` under the caller's `kwargs`, which may name known keywords only."""
+    unknown = set(kwargs or ()) - set(defaults)
+    if unknown:
+        raise _lib.GmpcError(f"{who}: unknown keyword(s) {sorted(unknown)}")
+    return {**defaults, **(kwargs or {})}
+
+
 def make_cem_opts(kwargs=None, iter_offset=0):
     """gmpc_cem_opts from trajax' keyword set: num_elites = int(num_samples * elite_portion), as trajax computes it."""
-    kw = dict(TRAJAX_CEM_KWARGS)
-    if kwargs:
-        unknown = set(kwargs) - set(kw)
-        if unknown:
-            raise _lib.GmpcError(f"cem: unknown keyword(s) {sorted(unknown)}")
-        kw.update(kwargs)
+    kw = _merged_kwargs("cem", TRAJAX_CEM_KWARGS, kwargs)
     o = CemOpts()
     o.max_iter, o.num_samples = int(kw["max_iter"]), int(kw["num_samples"])
     o.num_elites = int(kw["num_samples"] * kw["elite_portion"])
@@ -131,12 +134,7 @@ def make_cem_opts(kwargs=None, iter_offset=0):
 
 def make_mppi_opts(kwargs=None, iter_offset=0):
     """gmpc_mppi_opts from MPPI_KWARGS' keyword set."""
-    kw = dict(MPPI_KWARGS)
-    if kwargs:
-        unknown = set(kwargs) - set(kw)
-        if unknown:
-            raise _lib.GmpcError(f"mppi: unknown keyword(s) {sorted(unknown)}")
-        kw.update(kwargs)
+    kw = _merged_kwargs("mppi", MPPI_KWARGS, kwargs)
     o = MppiOpts()
     o.max_iter, o.num_samples, o.iter_offset = int(kw["max_iter"]), int(kw["num_samples"]), int(iter_offset)
     o.sampling_smoothing = float(kw["sampling_smoothing"])
@@ -149,12 +147,7 @@ def make_mppi_opts(kwargs=None, iter_offset=0):
 def make_icem_opts(kwargs=None, iter_offset=0, carry_in=0):
     """gmpc_icem_opts from ICEM_KWARGS' keyword set: num_elites = int(num_samples * elite_portion) and num_keep =
     int(num_elites * keep_portion), both on the host."""
-    kw = dict(ICEM_KWARGS)
-    if kwargs:
-        unknown = set(kwargs) - set(kw)
-        if unknown:
-            raise _lib.GmpcError(f"icem: unknown keyword(s) {sorted(unknown)}")
-        kw.update(kwargs)
+    kw = _merged_kwargs("icem", ICEM_KWARGS, kwargs)
     o = _lib.IcemOpts()
     o.max_iter, o.num_samples, o.iter_offset = int(kw["max_iter"]), int(kw["num_samples"]), int(iter_offset)
     o.num_elites = int(kw["num_samples"] * kw["elite_portion"])
@@ -381,15 +374,8 @@ class Engine:
         (B, E) int32, "samples" (B, N, T, m).  iter_offset: the noise stream's first iteration (chained calls).
         Stateless: a held iLQR solution stays valid; nothing is synchronised."""
         B, n, m, T = x0.shape[0], self.n, self.m, self.T
-        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
-            if tuple(t.shape) != shape:
-                raise _lib.GmpcError(f"cem: {name} must be {shape}, got {tuple(t.shape)}")
-        unknown = set(want) - set(self.CEM_WANT)
-        if unknown:
-            raise _lib.GmpcError(f"cem: want has unknown entries {sorted(unknown)}; known: {self.CEM_WANT}")
-        opts = make_cem_opts(kwargs, iter_offset)
-        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
-        std = self._sampling_std("cem", B, init_std, lo, hi)
+        opts, lo_d, hi_d, std = self._sampling_prologue(
+            "cem", self.CEM_WANT, make_cem_opts, kwargs, iter_offset, x0, U_init, goal, u_lo, u_hi, init_std, want)
         N, E = opts.num_samples, opts.num_elites
         out = dict(X=self.new(B, T + 1, n), U=U_init.clone(), obj=self.new(B), std=std)
         if "costs" in want:
@@ -405,6 +391,22 @@ class Engine:
         return out
 
     MPPI_WANT = ("costs", "weights", "samples")
+
+    def _sampling_prologue(self, who, known_want, make_opts, kwargs, iter_offset, x0, U_init, goal, u_lo, u_hi,
+                           init_std, want):
+        """What cem_solve, mppi_solve and icem_solve check and build first, in this order: the shapes, `want` against
+        the solver's known entries, the options (make_opts), the device bounds and the std.  -> opts, lo_d, hi_d,
+        std."""
+        B, n, m, T = x0.shape[0], self.n, self.m, self.T
+        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
+            if tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"{who}: {name} must be {shape}, got {tuple(t.shape)}")
+        unknown = set(want) - set(known_want)
+        if unknown:
+            raise _lib.GmpcError(f"{who}: want has unknown entries {sorted(unknown)}; known: {known_want}")
+        opts = make_opts(kwargs, iter_offset)
+        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+        return opts, lo_d, hi_d, self._sampling_std(who, B, init_std, lo, hi)
 
     def _sampling_std(self, who, B, init_std, lo, hi):
         """The (B, T, m) device std of a sampling solver: cem_solve's rules for init_std."""
@@ -427,15 +429,8 @@ class Engine:
         and costs_trace (K, B, N), what mppi_vjp needs.  Stateless: a held iLQR solution stays valid; nothing is
         synchronised."""
         B, n, m, T = x0.shape[0], self.n, self.m, self.T
-        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
-            if tuple(t.shape) != shape:
-                raise _lib.GmpcError(f"mppi: {name} must be {shape}, got {tuple(t.shape)}")
-        unknown = set(want) - set(self.MPPI_WANT)
-        if unknown:
-            raise _lib.GmpcError(f"mppi: want has unknown entries {sorted(unknown)}; known: {self.MPPI_WANT}")
-        opts = make_mppi_opts(kwargs, iter_offset)
-        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
-        std = self._sampling_std("mppi", B, init_std, lo, hi)
+        opts, lo_d, hi_d, std = self._sampling_prologue(
+            "mppi", self.MPPI_WANT, make_mppi_opts, kwargs, iter_offset, x0, U_init, goal, u_lo, u_hi, init_std, want)
         N, K = opts.num_samples, max(opts.max_iter, 0)
         out = dict(X=self.new(B, T + 1, n), U=U_init.clone(), obj=self.new(B), std=std)
         if "costs" in want:
@@ -466,16 +461,9 @@ class Engine:
         "samples" (B, N_last, T, m), the fresh rows.  iter_offset: the noise stream's (and the sample count's) first
         iteration.  Stateless on the context: a held iLQR solution stays valid; nothing is synchronised."""
         B, n, m, T = x0.shape[0], self.n, self.m, self.T
-        for name, t, shape in (("x0", x0, (B, n)), ("U_init", U_init, (B, T, m)), ("goal", goal, (B, T + 1, self.nx))):
-            if tuple(t.shape) != shape:
-                raise _lib.GmpcError(f"icem: {name} must be {shape}, got {tuple(t.shape)}")
-        unknown = set(want) - set(self.ICEM_WANT)
-        if unknown:
-            raise _lib.GmpcError(f"icem: want has unknown entries {sorted(unknown)}; known: {self.ICEM_WANT}")
-        opts = make_icem_opts(kwargs, iter_offset)
+        opts, lo_d, hi_d, std = self._sampling_prologue(
+            "icem", self.ICEM_WANT, make_icem_opts, kwargs, iter_offset, x0, U_init, goal, u_lo, u_hi, init_std, want)
         N, E, nk, K = opts.num_samples, opts.num_elites, max(opts.num_keep, 0), max(opts.max_iter, 0)
-        lo, hi, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
-        std = self._sampling_std("icem", B, init_std, lo, hi)
         if state is None:
             st = dict(keep=torch.zeros(B, nk, T, m, device=self.device),
                       best_U=torch.zeros(B, T, m, device=self.device),

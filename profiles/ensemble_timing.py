@@ -13,8 +13,8 @@ p10 / p90 per setting and the three ratios of DESIGN.md section 24 -- (a) P = 1 
 
     python profiles/ensemble_timing.py [--calls 200] [--shapes cheetah1,cheetah128] [--out FILE.jsonl]
 
-Kernel times come from a run of their own (tracing slows the host): k_cem_rollout_ens, k_icem_rollout_ens, their bf16
-forms and k_ens_reduce in
+Kernel times come from a run of their own (tracing slows the host): k_sampled_rollout<CemDrawn, BF16, CemMember>,
+k_sampled_rollout<IcemDrawn, BF16, CemMember> (BF16 false / true) and k_ens_reduce in
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python profiles/ensemble_timing.py --calls 20
 """
 

@@ -12,7 +12,8 @@ each mode's result (gmpc_cem_solve's obj: always the fp32 rollout of the returne
 
     python profiles/sampled_bf16_timing.py [--calls 200] [--shapes cheetah1,cheetah128,c3] [--out FILE.jsonl]
 
-Kernel times come from a run of their own (tracing slows the host): k_cem_rollout and k_cem_rollout_bf16 in
+Kernel times come from a run of their own (tracing slows the host): k_sampled_rollout<CemDrawn, false, CemOneModel> and
+k_sampled_rollout<CemDrawn, true, CemOneModel> (the fp32 and the bf16 form) in
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python profiles/sampled_bf16_timing.py --calls 20
 """
 
