@@ -380,6 +380,53 @@ extern "C" int gmpc_dynamics_loss_grad(gmpc_ctx* c, int B, int S, const float* x
   return 0;
 }
 
+// The same regression for the P members of an ensemble: the members' transposes, k_dynfit_rows over the
+// grid (tiles of 32 sequences, members), the loss sums, then the weight-gradient GEMMs member by member.  Everything it
+// writes is the caller's or the call workspace's: save = the transposes [P][count], aux = the losses [P][B], acts /
+// dels = per member B S + GMPC_WGRAD_PAD rows (the kernel zeroes the pad rows).
+extern "C" int gmpc_dynamics_ensemble_loss_grad(gmpc_ctx* c, int P, const float* dyn_members, int D, int B, int S,
+                                                const float* xseq, const float* useq, const float* next_xseq,
+                                                const int* rows, double discount, int teacher_forcing,
+                                                float* loss_sum, float* grad_sum, void* stream) {
+  if (!c) return fail(GMPC_EINVAL, "ensemble fit: ctx is null");
+  const gmpc_shape& sh = c->sh;
+  if (P < 1 || P > GMPC_MAX_ENSEMBLE)
+    return fail(GMPC_EINVAL, "ensemble fit: P = %d outside [1, %d]", P, GMPC_MAX_ENSEMBLE);
+  if (B < 1 || B > c->maxB) return fail(GMPC_EINVAL, "ensemble fit: B = %d outside [1, max_batch = %d]", B, c->maxB);
+  if (S < 1 || S > sh.T) return fail(GMPC_EINVAL, "ensemble fit: S = %d outside [1, T = %d]", S, sh.T);
+  if (D < 1) return fail(GMPC_EINVAL, "ensemble fit: D = %d dataset rows", D);
+  if (!rows && D != B) return fail(GMPC_EINVAL, "ensemble fit: D = %d is not B = %d and rows is null", D, B);
+  if (!dyn_members || !xseq || !useq || !next_xseq || !loss_sum || !grad_sum)
+    return fail(GMPC_EINVAL, "ensemble fit: null argument");
+  TRY(gmpc_sampled_coverage(c, "ensemble fit"));
+  if (hipSetDevice(c->device) != hipSuccess) return fail(GMPC_EHIP, "hipSetDevice failed");
+  (void)hipGetLastError();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t count = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims), steps = (size_t)B * S;
+  DynFitRowsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lay = mlp_rows(sh.dyn_layers, sh.dyn_dims);
+  a.mstride = count;
+  a.rstride = (steps + GMPC_WGRAD_PAD) * a.lay.stride;
+  CallWork& k = c->cw;
+  TRY(k.save.grow(c, (size_t)P * count));
+  TRY(k.aux.grow(c, (size_t)P * B));
+  TRY(k.acts.grow(c, (size_t)P * a.rstride));
+  TRY(k.dels.grow(c, (size_t)P * a.rstride));
+  bind_mlp(a.dyn, sh.dyn_layers, sh.dyn_dims, dyn_members, k.save.p);
+  a.B = B; a.S = S; a.n = sh.n; a.m = sh.m;
+  a.xseq = xseq; a.useq = useq; a.yseq = next_xseq; a.rows = rows;
+  a.gamma = (float)discount; a.teacher_forcing = teacher_forcing != 0;
+  a.acts = k.acts.p; a.dels = k.dels.p; a.loss = k.aux.p;
+  if (gmpc_launch_dynfit_rows(a, P, k.save.p, loss_sum, s) != 0)
+    return fail(GMPC_EINVAL, "ensemble fit: S = %d discounts do not fit the workgroup's LDS", S);
+  for (int p = 0; p < P; ++p)
+    gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, a.acts + p * a.rstride,
+                          a.dels + p * a.rstride, a.lay, grad_sum + p * count, c->wpart, c->wpart_floats, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // expert sequence model (N2) --------------------------------------------------------------------
 
 static int check_expert_shape(const gmpc_expert_shape* es, int n, int m) {

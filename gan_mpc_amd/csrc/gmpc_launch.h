@@ -378,6 +378,27 @@ int gmpc_launch_dynfit(int B, int S, int n, int m, const MlpDesc& dyn, const flo
                        const float* yseq, float gamma, int teacher_forcing, float* pred, float* acts, float* dels,
                        const MlpRows& rows, float* loss, hipStream_t s);
 
+// gmpc_dynfit_rows.hip: the same regression for the P members of an ensemble, on the matrix cores ---------
+// dyn describes member 0 -- W / b in the caller's [P][count] vectors, WT in the call's transposes, laid out alike --,
+// member p lies p mstride floats behind it.  xseq / yseq [D][S][n], useq [D][S][m]; rows [P][B] names the dataset row of
+// each member's b-th sequence (null: D = B, the identity).  acts / dels: per member B S + GMPC_WGRAD_PAD rows in the
+// layout `lay`, rstride floats apart; loss [P][B].
+struct DynFitRowsArgs {
+  int B, S, n, m;
+  MlpDesc dyn;
+  size_t mstride, rstride;
+  MlpRows lay;
+  const float *xseq, *useq, *yseq;
+  const int* rows;
+  float gamma;
+  int teacher_forcing;
+  float *acts, *dels, *loss;
+};
+// The transposes of every member into WT0 (= a.dyn.WT[0]), the sweeps and loss_sum [P]: three launches.  Non-zero, and
+// nothing launched, outside widths and n + m <= GMPC_SAMPLED_MAX_WIDTH, 1 <= P <= GMPC_MAX_ENSEMBLE, or where the S
+// discounts do not fit the workgroup's LDS.
+int gmpc_launch_dynfit_rows(const DynFitRowsArgs& a, int P, float* WT0, float* loss_sum, hipStream_t s);
+
 // gmpc_dynl.hip: LSTM dynamics variant --------------------------------------------------------------------------------
 void gmpc_launch_dynl_rollout(DynlTrajArgs a, hipStream_t s);
 void gmpc_launch_dynl_candidates(DynlTrajArgs a, int max_items, hipStream_t s);

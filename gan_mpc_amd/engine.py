@@ -685,6 +685,65 @@ class Engine:
             int(bool(teacher_forcing)), _ptr(loss_sum), _ptr(grad_sum), self._stream()))
         return loss_sum, grad_sum
 
+    def dynamics_ensemble_loss_grad(self, members, xseq, useq, next_xseq, discount, teacher_forcing, rows=None,
+                                    loss_sum=None, grad_sum=None):
+        """dynamics_loss_grad for the P members of a dynamics ensemble in one call (gmpc_dynamics_ensemble_loss_grad;
+        DESIGN.md section 25).  members: float32 device tensor (P, dyn_count), 1 <= P <= 16, each row laid out like
+        set_params' `dyn`; xseq, next_xseq (D, S, n), useq (D, S, m): the dataset, float32 device tensors; rows: None
+        -- every member takes the D = B dataset rows in order --, or an int32 (P, B) tensor or array of dataset rows in
+        [0, D), duplicates allowed (checked here: the device trusts them).  -> (loss_sum (P,), grad_sum (P, dyn_count)):
+        sums over each member's B sequences.  Relu-MLP dynamics, widths and n + m up to 256.  Reads nothing of the bound
+        parameters (set_params need not have been called); a held solution, the bilevel tail and a set sampled ensemble
+        stay as they are."""
+        who = "ensemble fit"
+        P = self._check_ensemble_members(who, members)
+        if not torch.is_tensor(members):
+            raise _lib.GmpcError(f"{who}: members must be a device tensor, got {type(members).__name__}")
+        for name, t, width in (("xseq", xseq, self.n), ("useq", useq, self.m), ("next_xseq", next_xseq, self.n)):
+            if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != width:
+                raise _lib.GmpcError(f"{who}: {name} must be (D, S, {width}), got {tuple(getattr(t, 'shape', ()))}")
+            if t.dtype != torch.float32:
+                raise _lib.GmpcError(f"{who}: {name} must be float32, got {t.dtype}")
+            if tuple(t.shape[:2]) != tuple(xseq.shape[:2]):
+                raise _lib.GmpcError(f"{who}: {name} must share xseq's (D, S) = {tuple(xseq.shape[:2])}, got "
+                                     f"{tuple(t.shape[:2])}")
+        D, S = int(xseq.shape[0]), int(xseq.shape[1])
+        B = D
+        if rows is not None:
+            shape = tuple(getattr(rows, "shape", ()))
+            if len(shape) != 2 or shape[0] != P:
+                raise _lib.GmpcError(f"{who}: rows must be ({P}, B), got shape {shape}")
+            dtype = rows.dtype if torch.is_tensor(rows) else np.asarray(rows).dtype
+            if dtype not in (torch.int32, np.dtype(np.int32)):
+                raise _lib.GmpcError(f"{who}: rows must be int32, got {dtype}")
+            B = int(shape[1])
+            if B > 0:
+                lo, hi = int(rows.min()), int(rows.max())
+                if lo < 0 or hi >= D:
+                    raise _lib.GmpcError(f"{who}: rows must lie in [0, D = {D}), got [{lo}, {hi}]")
+            rows = self.to_dev(rows, dtype=torch.int32)
+        for name, t, shape in (("loss_sum", loss_sum, (P,)), ("grad_sum", grad_sum, (P, self.dyn_count))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"{who}: {name} must be {shape}, got {tuple(t.shape)}")
+        loss_sum = self.new(P) if loss_sum is None else loss_sum
+        grad_sum = self.new(P, self.dyn_count) if grad_sum is None else grad_sum
+        _lib.check(self.lib.gmpc_dynamics_ensemble_loss_grad(
+            self.ctx, P, _ptr(members), D, B, S, _ptr(xseq), _ptr(useq), _ptr(next_xseq), _ptr(rows), float(discount),
+            int(bool(teacher_forcing)), _ptr(loss_sum), _ptr(grad_sum), self._stream()))
+        return loss_sum, grad_sum
+
+    def _check_ensemble_members(self, who, members):
+        """The rank, width, count and dtype of a (P, dyn_count) float32 tensor or array -> P."""
+        shape = tuple(getattr(members, "shape", ()))
+        if len(shape) != 2 or shape[1] != self.dyn_count:
+            raise _lib.GmpcError(f"{who}: members must be (P, {self.dyn_count}), got shape {shape}")
+        if not 1 <= shape[0] <= self.MAX_ENSEMBLE:
+            raise _lib.GmpcError(f"{who}: P = {shape[0]} outside [1, {self.MAX_ENSEMBLE}]")
+        dtype = members.dtype if torch.is_tensor(members) else np.asarray(members).dtype
+        if dtype not in (torch.float32, np.dtype(np.float32)):
+            raise _lib.GmpcError(f"{who}: members must be float32, got {dtype}")
+        return int(shape[0])
+
     def polyak(self, prev, cur, factor, out=None):
         out = cur if out is None else out
         _lib.check(self.lib.gmpc_polyak(self.ctx, prev.numel(), _ptr(prev), _ptr(cur), float(factor),

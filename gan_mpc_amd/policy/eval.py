@@ -190,6 +190,42 @@ class EvalMPC:
             eng.set_sampled_ensemble(self._ensemble_dev)
         return eng
 
+    def set_dynamics_ensemble(self, members):
+        """Replace the dynamics ensemble of a "cem" / "mppi" / "icem" policy (the constructor's dynamics_ensemble=):
+        None -- no ensemble --, a sequence of 1 to 16 dynamics parameter trees, or the members' flat vectors as a
+        (P, dyn_count) float32 array or device tensor (norm/ensemble_trainer's; a device tensor is used as it is, not
+        copied: train it further in place and call this again).  Set on the bound engine now and by every later bind."""
+        if members is not None and self.solver not in ("cem", "mppi", "icem"):
+            raise ValueError('dynamics_ensemble and solver="cem" / "mppi" / "icem" go together: got '
+                             f"solver={self.solver!r}")
+        dev = None
+        if members is None:
+            flat = None
+        elif torch.is_tensor(members) or isinstance(members, np.ndarray):
+            flat = members
+            if len(members.shape) != 2 or not 1 <= members.shape[0] <= 16:
+                raise ValueError("dynamics_ensemble must be (P, dyn_count) with 1 <= P <= 16, got shape "
+                                 f"{tuple(members.shape)}")
+            if members.dtype not in (torch.float32, np.dtype(np.float32)):
+                raise ValueError(f"dynamics_ensemble must be float32, got {members.dtype}")
+            if torch.is_tensor(members):
+                dev = members if members.is_cuda else None
+                flat = members.detach().cpu().numpy()
+        else:
+            if len(members) == 0:
+                raise ValueError("dynamics_ensemble must hold at least one dynamics parameter tree")
+            flat = np.stack([params_lib.pack_mlp(tree) for tree in members])
+        self.dynamics_ensemble = flat
+        self._ensemble_dev = dev
+        eng = self._engine
+        if eng is not None:
+            if flat is None:
+                eng.set_sampled_ensemble(None)
+            else:
+                if self._ensemble_dev is None or self._ensemble_dev.device != eng.device:
+                    self._ensemble_dev = eng.to_dev(flat)
+                eng.set_sampled_ensemble(self._ensemble_dev)
+
     # ---- reference API ----------------------------------------------------------------------
     def get_dynamics_carry(self, history_x, history_u, params):
         """reference policy/eval.py:75-85: the carry the dynamics model reaches after the history (empty

@@ -647,6 +647,24 @@ int gmpc_dynamics_loss_grad(gmpc_ctx* ctx, int B, int S, const float* xseq, cons
                             const float* next_xseq, double discount, int teacher_forcing,
                             float* loss_sum, float* grad_sum, void* stream);
 
+/* The same regression for the P members of a dynamics ensemble in one call, on the matrix cores (DESIGN.md section
+ * 25): member p's weights are dyn_members + p * (dynamics parameter count), each laid out like gmpc_set_params' dyn.
+ *   xseq, next_xseq [D][S][n], useq [D][S][m]: the dataset, D >= 1 rows; 1 <= S <= T
+ *   rows [P][B] (int32, each in [0, D): trusted, the host binding checks them): the dataset row that member p uses as
+ *        its b-th sequence -- duplicates allowed, so a dataset is uploaded once and every member draws its own
+ *        bootstrap minibatch; NULL: D == B and the identity for every member
+ *   -> loss_sum [P], grad_sum [P][dynamics parameter count]: sums over member p's B sequences, 1 <= B <= max_batch
+ * Relu-MLP dynamics with every width and n + m up to 256 (what gmpc_sampled_coverage accepts), 1 <= P <= 16.  Reads
+ * nothing of the dynamics bound by gmpc_set_params (which need not have been called) and leaves a held solution, the
+ * bilevel tail and a set sampled ensemble untouched.  Asynchronous on `stream`; deterministic.  Every refusal is
+ * GMPC_EINVAL with a message starting "ensemble fit: ", before any launch.  Workspace: the call workspace, grown (a
+ * synchronising hipMalloc) by the first call that needs more: 2 P (B S + 8) row strides, P parameter counts for the
+ * transposed weights and P B losses. */
+int gmpc_dynamics_ensemble_loss_grad(gmpc_ctx* ctx, int P, const float* dyn_members, int D, int B, int S,
+                                     const float* xseq, const float* useq, const float* next_xseq, const int* rows,
+                                     double discount, int teacher_forcing, float* loss_sum, float* grad_sum,
+                                     void* stream);
+
 /* Building block of the large-state (n > 64) Riccati path, exported for its unit test: batched
  * C[b] = alpha * X[b]^T Y[b] + beta * C[b] on the fp32 matrix cores; X[b] is K x M, Y[b] K x N,
  * C[b] M x N, row-major, densely packed per batch element; Y must be followed by >= 8 readable rows
