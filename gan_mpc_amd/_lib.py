@@ -81,6 +81,11 @@ class IcemOpts(C.Structure):
     ]
 
 
+class EnsembleMode(C.Structure):
+    """gmpc_ensemble_mode: how a set dynamics ensemble is propagated and aggregated."""
+    _fields_ = [("aggregate", C.c_int), ("risk", C.c_float), ("propagation", C.c_int), ("particles", C.c_int)]
+
+
 _P = C.c_void_p
 
 
@@ -151,6 +156,7 @@ SIGNATURES = {
     "gmpc_icem_plan_host": (C.c_int, [C.POINTER(IcemOpts), C.c_int, _P, _P]),
     "gmpc_set_sampled_precision": (C.c_int, [_P, C.c_int]),
     "gmpc_set_sampled_ensemble": (C.c_int, [_P, C.c_int, _P]),
+    "gmpc_set_sampled_ensemble_mode": (C.c_int, [_P, C.POINTER(EnsembleMode)]),
     "gmpc_box_qp_host":(C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_bilevel_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),

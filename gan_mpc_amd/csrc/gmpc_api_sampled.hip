@@ -1,6 +1,6 @@
-// C-ABI entry points of the sampling solvers (DESIGN §20 - §24): the cross-entropy method, MPPI and the
-// sample-efficient cross-entropy method on one sampled rollout (gmpc_launch_sampled_rollout), its precision and its
-// dynamics ensemble.  What the three solves share is written once, ahead of them.
+// C-ABI entry points of the sampling solvers (DESIGN §20 - §24, §26): the cross-entropy method, MPPI and the
+// sample-efficient cross-entropy method on one sampled rollout (gmpc_launch_sampled_rollout), its precision, its
+// dynamics ensemble and the ensemble's mode.  What the three solves share is written once, ahead of them.
 #include "gmpc_ctx.h"
 
 // The shapes the sampled rollout covers, for the sampling solvers (`who`: the message's prefix)
@@ -39,6 +39,27 @@ extern "C" int gmpc_set_sampled_ensemble(gmpc_ctx* c, int P, const float* dyn_me
   bind_mlp(c->ens_dyn, c->sh.dyn_layers, c->sh.dyn_dims, dyn_members, nullptr);
   c->ens_P = P;
   c->ens16_stale = true;   // the members changed: their bf16 images are packed again by the next bf16-mode solve
+  return 0;
+}
+
+// How a set ensemble is propagated and aggregated: checked whole, then stored; nothing is launched
+extern "C" int gmpc_set_sampled_ensemble_mode(gmpc_ctx* c, const gmpc_ensemble_mode* mode) {
+  if (!c) return fail(GMPC_EINVAL, "ensemble mode: ctx is null");
+  if (!mode) return fail(GMPC_EINVAL, "ensemble mode: mode is null");
+  const gmpc_ensemble_mode& m = *mode;
+  if (m.aggregate < GMPC_ENS_MEAN || m.aggregate > GMPC_ENS_MAX)
+    return fail(GMPC_EINVAL, "ensemble mode: aggregate = %d outside [0, 2]", m.aggregate);
+  if (m.propagation != GMPC_ENS_FIXED && m.propagation != GMPC_ENS_TS1)
+    return fail(GMPC_EINVAL, "ensemble mode: propagation = %d outside [0, 1]", m.propagation);
+  if (!std::isfinite(m.risk)) return fail(GMPC_EINVAL, "ensemble mode: risk = %g is not finite", (double)m.risk);
+  if (m.risk != 0.f && m.aggregate != GMPC_ENS_MEAN_STD)
+    return fail(GMPC_EINVAL, "ensemble mode: risk = %g goes with GMPC_ENS_MEAN_STD only (aggregate = %d)",
+                (double)m.risk, m.aggregate);
+  if (m.propagation == GMPC_ENS_FIXED && m.particles != 0)
+    return fail(GMPC_EINVAL, "ensemble mode: particles = %d goes with GMPC_ENS_TS1 only", m.particles);
+  if (m.propagation == GMPC_ENS_TS1 && (m.particles < 1 || m.particles > GMPC_MAX_ENSEMBLE))
+    return fail(GMPC_EINVAL, "ensemble mode: particles = %d outside [1, %d]", m.particles, GMPC_MAX_ENSEMBLE);
+  c->ens_mode = m;
   return 0;
 }
 
@@ -84,16 +105,20 @@ int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s) {
   return 0;
 }
 
-// What the launches over sampled rows need under an ensemble: the members' strides in the context's precision and the
-// cost planes [P][B][ldc] in the call workspace
+// What the launches over sampled rows need under an ensemble: the members' strides in the context's precision, the
+// context's mode and the cost planes [Q][B][ldc] in the call workspace
 static int ensemble_args(gmpc_ctx* c, int B, int ldc, CemEnsemble& e) {
   const gmpc_shape& sh = c->sh;
   const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16;
   e.P = c->ens_P;
   e.bstride = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims);
   e.wstride = bf16 ? gmpc_bf16_image_elems(sh.dyn_layers, sh.dyn_dims) / 2 : e.bstride;
-  e.invP = 1.0f / (float)c->ens_P;
-  TRY(c->cw.part.grow(c, (size_t)c->ens_P * B * ldc));
+  e.ts1 = c->ens_mode.propagation == GMPC_ENS_TS1;
+  e.Q = e.ts1 ? c->ens_mode.particles : c->ens_P;
+  e.aggregate = c->ens_mode.aggregate;
+  e.risk = c->ens_mode.risk;
+  e.invQ = 1.0f / (float)e.Q;
+  TRY(c->cw.part.grow(c, (size_t)e.Q * B * ldc));
   e.part = c->cw.part.p;
   return 0;
 }
@@ -105,8 +130,8 @@ static int ldc_of(const CemRollArgs& r) { return r.N; }
 static int ldc_of(const IcemRollArgs& r) { return r.ldc; }
 
 // One launch over sampled rows (CEM's or iCEM's pool) in the context's precision (bf16 mode: the same arguments over
-// the packed images).  With an ensemble set: the rows under every member, then the reduce of the members'
-// costs into r's.
+// the packed images).  With an ensemble set: the rows under every member or particle, then the
+// reduce of the planes' costs into r's.
 template <typename Args>
 static int launch_sampled_rows(gmpc_ctx* c, const Args& r, hipStream_t s) {
   const bool bf16 = c->sampled_precision == GMPC_SAMPLED_BF16, ens = c->ens_P > 0;

@@ -7,11 +7,14 @@
 //   k_sampled_rollout<CemDrawn, BF16, Ens>  (gmpc_cem_rollout.h) one 256-thread workgroup per 32
 //                   samples of one problem, the whole horizon: the states stay in registers (the accumulator layout of
 //                   dg_gemm), the layer inputs in LDS, every dynamics / cost layer on the matrix cores (dg_gemm,
-//                   gmpc_dg_gemm.h), weights streamed from L2.  This file instantiates its four forms over CEM's rows:
-//                   fp32 or bf16 operands (gmpc_set_sampled_precision, section 23), one model or every member of a
-//                   dynamics ensemble (gmpc_set_sampled_ensemble, section 24).  MPPI launches the same four.
-//   k_ens_reduce    one thread per (problem, row): the members' costs summed in member order, times 1 / P, into the
+//                   gmpc_dg_gemm.h), weights streamed from L2.  This file instantiates its six forms over CEM's rows:
+//                   fp32 or bf16 operands (gmpc_set_sampled_precision, section 23); one model, every member of a
+//                   dynamics ensemble (gmpc_set_sampled_ensemble, section 24) or particles that draw their member
+//                   per step (gmpc_set_sampled_ensemble_mode, section 26).  MPPI launches the same six.
+//   k_ens_reduce    one thread per (problem, row): the planes' costs summed in plane order, times 1 / Q, into the
 //                   cost buffer the update kernels read (shared with gmpc_icem.hip)
+//   k_ens_reduce_risk  the same thread for the other two aggregates of section 26: mean plus a multiple of the
+//                   planes' spread, or the worst plane
 //   k_cem_update    one workgroup per problem: bitonic sort of 64-bit (cost, index) keys in LDS, then the elites'
 //                   sums in rank order, one (step, control) per thread.
 #include "gmpc_cem_rollout.h"
@@ -49,9 +52,12 @@ template __global__ void k_sampled_rollout<CemDrawn, false, CemOneModel>(CemRoll
 template __global__ void k_sampled_rollout<CemDrawn, true, CemOneModel>(CemRollArgs, CemOneModel);
 template __global__ void k_sampled_rollout<CemDrawn, false, CemMember>(CemRollArgs, CemMember);
 template __global__ void k_sampled_rollout<CemDrawn, true, CemMember>(CemRollArgs, CemMember);
+template __global__ void k_sampled_rollout<CemDrawn, false, CemParticle>(CemRollArgs, CemParticle);
+template __global__ void k_sampled_rollout<CemDrawn, true, CemParticle>(CemRollArgs, CemParticle);
 
-// The ensemble's cost of a row: the members' costs part [P][B][ldc] summed in ascending member order, times invP, into
-// costs [B][ldc]; one thread per (problem, row), rows below `rows` only (the rollouts wrote exactly those)
+// The ensemble's cost of a row under GMPC_ENS_MEAN: the planes' costs part [P][B][ldc] (P: the planes, members or
+// particles) summed in ascending plane order, times invP, into costs [B][ldc]; one thread per (problem, row), rows
+// below `rows` only (the rollouts wrote exactly those)
 __global__ __launch_bounds__(GMPC_THREADS) void k_ens_reduce(const float* __restrict__ part, int P, int B, int rows,
                                                              int ldc, float invP, float* __restrict__ costs) {
   const int i = blockIdx.x * GMPC_THREADS + threadIdx.x;
@@ -61,6 +67,46 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_ens_reduce(const float* __rest
   float sum = part[o];
   for (int p = 1; p < P; ++p) sum = __fadd_rn(sum, part[p * plane + o]);
   costs[o] = __fmul_rn(sum, invP);
+}
+
+// The risk-sensitive aggregates over the planes part [Q][B][ldc], the same thread per (problem,
+// row) and every operation one IEEE fp32 operation in ascending plane order, so NumPy restates it bit for bit.
+//   MAX false: mean = (((J_0 + J_1) + ...) + J_{Q-1}) * invQ, ss = (((0 + d_0 d_0) + d_1 d_1) + ...) with d_q = J_q -
+//              mean, cost = mean + risk * sqrt(ss * invQ); a NaN plane makes the mean, and with it the cost, NaN
+//   MAX true:  the largest plane, a NaN sticky: w = J_0; w = (J_q > w || J_q != J_q) ? J_q : w
+// One operation each: the arithmetic is written out under `fp contract(off)` -- in this build __fmul_rn / __fadd_rn are
+// the plain operators, which the compiler's default contraction fuses into v_fmac_f32 (one rounding instead of two),
+// and __fsqrt_rn is the native v_sqrt_f32 (1 ulp) -- and the root is sqrtf, correctly rounded.
+template <bool MAX>
+__global__ __launch_bounds__(GMPC_THREADS) void k_ens_reduce_risk(const float* __restrict__ part, int Q, int B, int rows,
+                                                                  int ldc, float invQ, float risk,
+                                                                  float* __restrict__ costs) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * GMPC_THREADS + threadIdx.x;
+  if (i >= B * rows) return;
+  const int b = i / rows, s = i - b * rows;
+  const size_t o = (size_t)b * ldc + s, plane = (size_t)B * ldc;
+  if constexpr (MAX) {
+    float w = part[o];
+    for (int q = 1; q < Q; ++q) {
+      const float J = part[q * plane + o];
+      w = (J > w || J != J) ? J : w;
+    }
+    costs[o] = w;
+  } else {
+    float sum = part[o];
+    for (int q = 1; q < Q; ++q) sum = sum + part[q * plane + o];
+    const float mean = sum * invQ;
+    float ss = 0.f;
+    for (int q = 0; q < Q; ++q) {
+      const float d = part[q * plane + o] - mean;
+      const float dd = d * d;
+      ss = ss + dd;
+    }
+    const float var = ss * invQ;
+    const float rs = risk * sqrtf(var);
+    costs[o] = mean + rs;
+  }
 }
 
 // ---- the update -----------------------------------------------------------------------------------------------
@@ -102,7 +148,14 @@ int gmpc_launch_sampled_rollout(const CemRollArgs& a, bool bf16, const CemEnsemb
 
 void gmpc_launch_ens_reduce(const CemEnsemble& e, int B, int rows, int ldc, float* costs, hipStream_t s) {
   const int blocks = (int)(((size_t)B * rows + GMPC_THREADS - 1) / GMPC_THREADS);
-  hipLaunchKernelGGL(k_ens_reduce, dim3(blocks), dim3(GMPC_THREADS), 0, s, e.part, e.P, B, rows, ldc, e.invP, costs);
+  if (e.aggregate == GMPC_ENS_MEAN)
+    hipLaunchKernelGGL(k_ens_reduce, dim3(blocks), dim3(GMPC_THREADS), 0, s, e.part, e.Q, B, rows, ldc, e.invQ, costs);
+  else if (e.aggregate == GMPC_ENS_MEAN_STD)
+    hipLaunchKernelGGL(k_ens_reduce_risk<false>, dim3(blocks), dim3(GMPC_THREADS), 0, s, e.part, e.Q, B, rows, ldc,
+                       e.invQ, e.risk, costs);
+  else
+    hipLaunchKernelGGL(k_ens_reduce_risk<true>, dim3(blocks), dim3(GMPC_THREADS), 0, s, e.part, e.Q, B, rows, ldc,
+                       e.invQ, e.risk, costs);
 }
 
 int gmpc_launch_cem_update(const CemUpdArgs& a, hipStream_t s) {

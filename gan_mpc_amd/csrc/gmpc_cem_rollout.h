@@ -82,17 +82,20 @@ __device__ __forceinline__ void cem_store_tiles16(float* Ab, __bf16* Hb, const D
 //                             and extra is the bytes of LDS the source wants behind the `blocks` bytes of operands
 // A row's cost is a function of its controls alone: not of its place in the tile, of `rows` or of B.
 // Ens, which dynamics network the workgroup rolls its rows out under and where their costs go:
-//   W(w) / b(v)               a dynamics layer's weights / biases, from the bound descriptor's pointers
+//   step(t)                   once per step, ahead of its layers: the step's member index (0 where the step plays no part)
+//   W(w, p) / b(v, p)         a dynamics layer's weights / biases under step()'s p, from the bound descriptor's pointers
 //   costs(c)                  the [B][ldc] plane the rows' costs are written to
 //   records()                 whether this workgroup writes the debug copy of the controls
-// CemOneModel: the arguments' own network and cost buffer (every kernel without an ensemble).
+// CemOneModel: the arguments' own network and cost buffer (every kernel without an ensemble).  It and CemMember ignore
+// the step; CemParticle draws its member in step().
 // BF16: the layer inputs are rounded to bf16 into Hb, the [32][GMPC_DG_LDH] block behind Ab,
 // the layers run on dg_gemm_bf16, and dyn.W[l] / cost.W[l] point at the layers' packed bf16 images (dg_kp, dg_np);
 // Ab keeps the fp32 [x_t; u_t] and the last cost layer's output, which the cost terms read as before.  Without BF16
 // Hb is not used.
 struct CemOneModel {
-  __device__ __forceinline__ const float* W(const float* w) const { return w; }
-  __device__ __forceinline__ const float* b(const float* v) const { return v; }
+  __device__ __forceinline__ uint32_t step(int) const { return 0; }
+  __device__ __forceinline__ const float* W(const float* w, uint32_t) const { return w; }
+  __device__ __forceinline__ const float* b(const float* v, uint32_t) const { return v; }
   __device__ __forceinline__ float* costs(float* c) const { return c; }
   __device__ __forceinline__ bool records() const { return true; }
 };
@@ -103,8 +106,31 @@ struct CemOneModel {
 struct CemMember {
   size_t wstride, bstride, plane;
   float* part;
-  __device__ __forceinline__ const float* W(const float* w) const { return w + blockIdx.y * wstride; }
-  __device__ __forceinline__ const float* b(const float* v) const { return v + blockIdx.y * bstride; }
+  __device__ __forceinline__ uint32_t step(int) const { return 0; }
+  __device__ __forceinline__ const float* W(const float* w, uint32_t) const { return w + blockIdx.y * wstride; }
+  __device__ __forceinline__ const float* b(const float* v, uint32_t) const { return v + blockIdx.y * bstride; }
+  __device__ __forceinline__ float* costs(float*) const { return part + blockIdx.y * plane; }
+  __device__ __forceinline__ bool records() const { return blockIdx.y == 0; }
+};
+
+// The particle blockIdx.y of the TS1 propagation: CemMember's strides and planes, but the
+// member is drawn anew at every step t, member = umulhi(philox(t, particle, 0xFFFFFFFF, it)[0], P) under the launch's
+// key.  Counter word 2 is the problem index in every normal draw (below max_batch), so 0xFFFFFFFF is a stream of its
+// own.  Nothing of the draw depends on the row, the tile or the problem: every workgroup of a grid row runs the same
+// member sequence (one weight operand per tile of 32 rows), and the draw is uniform over the workgroup --
+// evaluated by step(), once per step (W and b of the step's layers take its result), and read back as a scalar, so the
+// layers' pointers stay in scalar registers as CemMember's do.  Its costs go to plane `particle` of part [Q][B][ldc].
+struct CemParticle {
+  size_t wstride, bstride, plane;
+  float* part;
+  uint32_t P, key0, key1, it;
+  __device__ __forceinline__ uint32_t step(int t) const {
+    uint32_t r[4];
+    cem_philox((uint32_t)t, blockIdx.y, 0xFFFFFFFFu, it, key0, key1, r);
+    return __builtin_amdgcn_readfirstlane(__umulhi(r[0], P));
+  }
+  __device__ __forceinline__ const float* W(const float* w, uint32_t p) const { return w + p * wstride; }
+  __device__ __forceinline__ const float* b(const float* v, uint32_t p) const { return v + p * bstride; }
   __device__ __forceinline__ float* costs(float*) const { return part + blockIdx.y * plane; }
   __device__ __forceinline__ bool records() const { return blockIdx.y == 0; }
 };
@@ -134,6 +160,7 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
   float csum = 0.f;   // the cost of row rrow so far (the same in its 8 lanes)
   DgTiles acc;
   for (int t = 0; t < T; ++t) {
+    const uint32_t mem = ens.step(t);     // the member this step runs under (CemParticle; 0 and unused otherwise)
     // ---- layer 0 input [x_t; u_t]
     if constexpr (BF16) {
       cem_store_tiles16<true, true>(Ab, Hb, xs, n, n, wave, lane, [](float v, int) { return v; });
@@ -176,12 +203,12 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     for (int l = 0; l < a.dyn.L; ++l) {
       const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
       if constexpr (BF16)
-        dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(ens.W(a.dyn.W[l])), wave, lane,
+        dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(ens.W(a.dyn.W[l], mem)), wave, lane,
                      acc);
       else
-        dg_gemm(Ab, K, Nl, ens.W(a.dyn.W[l]), wave, lane, acc);
+        dg_gemm(Ab, K, Nl, ens.W(a.dyn.W[l], mem), wave, lane, acc);
       __syncthreads();   // every wave has read its operand rows (and the stage cost its row)
-      const float* bias = ens.b(a.dyn.b[l]);
+      const float* bias = ens.b(a.dyn.b[l], mem);
       if (l < a.dyn.L - 1) {
         auto act = [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); };
         if constexpr (BF16)
@@ -246,8 +273,8 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
 }
 
 // The one kernel of the sampled rollout: the operand block or blocks at the start of the dynamic LDS, the source's own
-// LDS behind them, then the body.  Eight instantiations, {CemDrawn, IcemDrawn} x {fp32, bf16} x {CemOneModel,
-// CemMember}, explicit in gmpc_cem.hip and gmpc_icem.hip.
+// LDS behind them, then the body.  Twelve instantiations, {CemDrawn, IcemDrawn} x {fp32, bf16} x {CemOneModel,
+// CemMember, CemParticle}, explicit in gmpc_cem.hip and gmpc_icem.hip.
 template <typename Src, bool BF16, typename Ens>
 __global__ __launch_bounds__(GMPC_DG_THREADS) void k_sampled_rollout(typename Src::Args a, Ens e) {
   extern __shared__ __attribute__((aligned(16))) char smem_roll[];
@@ -258,20 +285,26 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_sampled_rollout(typename Sr
   cem_rollout_body<BF16>(Src::roll(a), Src::rows(a), Src::ldc(a), Ab, Hb, src, e);
 }
 
-// Host side.  The launch of one precision: the grid -- tiles of 32 rows per problem by members -- and, under an
-// ensemble, the reduce of the members' costs behind it
+// Host side.  The launch of one precision: the grid -- tiles of 32 rows per problem by members (TS1: by particles) --
+// and, under an ensemble, the reduce of the planes' costs behind it
 template <typename Src, bool BF16>
 static void sampled_launch_form(const typename Src::Args& a, size_t lds, const CemEnsemble* ens, hipStream_t s) {
   const CemRollArgs& c = Src::roll(a);
   const int rows = Src::rows(a), ldc = Src::ldc(a), tiles = (rows + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS;
-  const dim3 grid(c.B * tiles, ens ? ens->P : 1);
+  const dim3 grid(c.B * tiles, ens ? ens->Q : 1);
   if (!ens) {
     hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemOneModel>), grid, dim3(GMPC_DG_THREADS), lds, s, a,
                        CemOneModel());
     return;
   }
-  const CemMember mb{ens->wstride, ens->bstride, (size_t)c.B * ldc, ens->part};
-  hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemMember>), grid, dim3(GMPC_DG_THREADS), lds, s, a, mb);
+  if (ens->ts1) {
+    const CemParticle pt{ens->wstride, ens->bstride, (size_t)c.B * ldc, ens->part, (uint32_t)ens->P, c.rng.key0,
+                         c.rng.key1, c.rng.it};
+    hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemParticle>), grid, dim3(GMPC_DG_THREADS), lds, s, a, pt);
+  } else {
+    const CemMember mb{ens->wstride, ens->bstride, (size_t)c.B * ldc, ens->part};
+    hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemMember>), grid, dim3(GMPC_DG_THREADS), lds, s, a, mb);
+  }
   gmpc_launch_ens_reduce(*ens, c.B, rows, ldc, c.costs, s);
 }
 
@@ -291,6 +324,7 @@ static int sampled_launch_rollout(const typename Src::Args& a0, bool bf16, const
   if (c.n + c.m > GMPC_SAMPLED_MAX_WIDTH || rows < 1 || rows > GMPC_CEM_MAX_N || Src::ldc(a) < rows) return 1;
   if (c.mean_row && (bf16 || ens)) return 1;     // (the returned sequence's rollout is the fp32 kernel's)
   if (ens && (c.X || ens->P < 1 || ens->P > GMPC_MAX_ENSEMBLE || !ens->part)) return 1;
+  if (ens && (ens->Q < 1 || ens->Q > GMPC_MAX_ENSEMBLE || (!ens->ts1 && ens->Q != ens->P))) return 1;
   const size_t blocks = bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32;
   size_t extra = 0;
   if (Src::plan(a, blocks, &extra)) return 1;

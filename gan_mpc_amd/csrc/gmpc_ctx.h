@@ -129,6 +129,9 @@ struct gmpc_ctx {
   MlpDesc ens_dyn{}, ens_dyn16{};
   GrowBuf ens16;
   bool ens16_stale = true;
+  // gmpc_set_sampled_ensemble_mode: how the planes of a set ensemble are propagated and aggregated; read
+  // by every launch over sampled rows, inert while ens_P == 0
+  gmpc_ensemble_mode ens_mode{GMPC_ENS_MEAN, 0.f, GMPC_ENS_FIXED, 0};
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;

@@ -241,13 +241,18 @@ int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const f
 // A dynamics ensemble: one grid row of workgroups per member, then k_ens_reduce.  The arguments' dyn describes member
 // 0 (bf16: with W[l] at its packed images); member p's weights lie p wstride floats behind them, its biases p bstride
 // floats; part [P][B][ldc] takes the members' costs and the arguments' costs [B][ldc] their sum in member order times
-// invP.
+// 1 / P (the default mode).
+// The ensemble mode (gmpc_set_sampled_ensemble_mode): Q cost planes instead of P -- Q = P with ts1 == 0,
+// plane q member q as above; with ts1 the grid row q is a particle that draws its member anew at every step
+// (CemParticle of gmpc_cem_rollout.h) and Q is the number of particles -- and `aggregate` (GMPC_ENS_MEAN / MEAN_STD /
+// MAX) is the rule that takes part [Q][B][ldc] to costs; invQ = 1.0f / (float)Q, risk the multiple of the spread.
 #define GMPC_MAX_ENSEMBLE 16
 struct CemEnsemble {
   int P;
   size_t wstride, bstride;
   float* part;
-  float invP;
+  int Q, ts1, aggregate;
+  float invQ, risk;
 };
 
 // gmpc_cem.hip: the cross-entropy method's two kernels --------------------------------------------------

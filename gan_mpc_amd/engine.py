@@ -204,6 +204,8 @@ class Engine:
                                         C.byref(ctx)))
         self.ctx = ctx
         self._bound = None
+        self._ensemble = None          # set_sampled_ensemble's members, kept alive
+        self._ensemble_mode = None     # set_sampled_ensemble_mode's keywords; None: never set (the default mode)
         self.solve_count = 0      # solves issued on this ctx (policy.differentiable: a backward checks it is current)
 
     def close(self):
@@ -363,6 +365,49 @@ class Engine:
         dev = self.to_dev(members)
         _lib.check(self.lib.gmpc_set_sampled_ensemble(self.ctx, int(shape[0]), _ptr(dev)))
         self._ensemble = dev      # keep the tensor alive: the ctx holds a raw pointer
+
+    ENSEMBLE_AGGREGATES = {"mean": 0, "mean_std": 1, "max": 2}     # GMPC_ENS_MEAN / MEAN_STD / MAX
+    ENSEMBLE_PROPAGATIONS = {"fixed": 0, "ts1": 1}                 # GMPC_ENS_FIXED / TS1
+
+    def set_sampled_ensemble_mode(self, aggregate="mean", risk=0.0, propagation="fixed", particles=None):
+        """What cem_solve / mppi_solve / icem_solve do with a set ensemble (gmpc_set_sampled_ensemble_mode; DESIGN.md
+        section 26); the defaults are the mean over the members of set_sampled_ensemble.
+        propagation: "fixed" -- one cost plane per member (particles must be None) --, or "ts1" -- `particles` planes,
+        1 to 16, each a particle that draws its member anew at every step from a schedule shared by all rows and
+        problems of an iteration.
+        aggregate over the planes' costs of a row: "mean"; "mean_std" -- mean + risk * (population standard deviation
+        of the planes), risk < 0 is optimism --; "max" -- the worst plane.  risk goes with "mean_std" only.
+        Independent of the members: it may be set before them, set_sampled_ensemble and set_params keep it, and it
+        does nothing while no ensemble is set.  Every refusal is a GmpcError("ensemble mode: ...") raised here, before
+        the library is called.  No device work."""
+        who = "ensemble mode"
+        if not isinstance(aggregate, str) or aggregate not in self.ENSEMBLE_AGGREGATES:
+            raise _lib.GmpcError(f'{who}: aggregate {aggregate!r} is none of "mean", "mean_std", "max"')
+        if not isinstance(propagation, str) or propagation not in self.ENSEMBLE_PROPAGATIONS:
+            raise _lib.GmpcError(f'{who}: propagation {propagation!r} is neither "fixed" nor "ts1"')
+        if isinstance(risk, bool) or not isinstance(risk, (int, float, np.integer, np.floating)):
+            raise _lib.GmpcError(f"{who}: risk must be a number, got {risk!r}")
+        with np.errstate(over="ignore"):
+            risk32 = float(np.float32(risk))
+        if not np.isfinite(risk32):
+            raise _lib.GmpcError(f"{who}: risk = {risk!r} is not finite in float32")
+        if risk32 != 0.0 and aggregate != "mean_std":
+            raise _lib.GmpcError(f'{who}: risk = {risk!r} goes with aggregate "mean_std" only, got {aggregate!r}')
+        if propagation == "fixed":
+            if particles is not None:
+                raise _lib.GmpcError(f'{who}: particles = {particles!r} goes with propagation "ts1" only')
+            count = 0
+        else:
+            if isinstance(particles, bool) or not isinstance(particles, (int, np.integer)):
+                raise _lib.GmpcError(f'{who}: propagation "ts1" needs particles, an integer in [1, '
+                                     f"{self.MAX_ENSEMBLE}], got {particles!r}")
+            if not 1 <= particles <= self.MAX_ENSEMBLE:
+                raise _lib.GmpcError(f"{who}: particles = {particles} outside [1, {self.MAX_ENSEMBLE}]")
+            count = int(particles)
+        mode = _lib.EnsembleMode(self.ENSEMBLE_AGGREGATES[aggregate], risk32, self.ENSEMBLE_PROPAGATIONS[propagation],
+                                 count)
+        _lib.check(self.lib.gmpc_set_sampled_ensemble_mode(self.ctx, C.byref(mode)))
+        self._ensemble_mode = dict(aggregate=aggregate, risk=risk32, propagation=propagation, particles=particles)
 
     CEM_WANT = ("costs", "elites", "samples")
 

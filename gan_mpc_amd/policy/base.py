@@ -18,12 +18,12 @@ class BaseMPC(eval_policy.EvalMPC):
     def __init__(self, config, cost_model, dynamics_model, expert_model, loss_vmap=(0,),
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, bilevel_sign=1.0, solver="rounds",
                  control_bounds=None, cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None,
-                 sampled_precision=None, dynamics_ensemble=None):
+                 sampled_precision=None, dynamics_ensemble=None, ensemble_mode=None):
         super().__init__(config=config, cost_model=cost_model, dynamics_model=dynamics_model,
                          expert_model=expert_model, trajax_ilqr_kwargs=trajax_ilqr_kwargs,
                          device=device, solver=solver, control_bounds=control_bounds, cem_kwargs=cem_kwargs,
                          mppi_kwargs=mppi_kwargs, icem_kwargs=icem_kwargs, sampled_precision=sampled_precision,
-                         dynamics_ensemble=dynamics_ensemble)
+                         dynamics_ensemble=dynamics_ensemble, ensemble_mode=ensemble_mode)
         self.loss_vmap = loss_vmap
         # +1 reproduces the reference as written; -1 is the implicit-function gradient
         self.bilevel_sign = float(bilevel_sign)

@@ -50,7 +50,7 @@ class EvalMPC:
     def __init__(self, config, cost_model, dynamics_model, expert_model,
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None,
                  cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None, sampled_precision=None,
-                 dynamics_ensemble=None):
+                 dynamics_ensemble=None, ensemble_mode=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
@@ -72,7 +72,12 @@ class EvalMPC:
         dynamics_ensemble: None, or a sequence of 1 to 16 dynamics parameter trees shaped like
         params["dynamics_params"] -- with a "cem" / "mppi" / "icem" solver, the members of the dynamics ensemble the
         sampled rows are costed on (Engine.set_sampled_ensemble, DESIGN §24: a row's cost is its mean over the members;
-        X and obj stay those of params["dynamics_params"]), set wherever the policy binds its engine."""
+        X and obj stay those of params["dynamics_params"]), set wherever the policy binds its engine.
+        ensemble_mode: None, or a dict of Engine.set_sampled_ensemble_mode's keywords (aggregate, risk, propagation,
+        particles) -- with a "cem" / "mppi" / "icem" solver, what the solver does with the ensemble: mean plus
+        a multiple of the members' spread or the worst member instead of the mean, and particles that draw their member
+        per step.  Set next to the ensemble wherever the policy binds its engine; without dynamics_ensemble it is
+        accepted and inert."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
         if (solver in ("box", "cem", "mppi", "icem")) != (control_bounds is not None):
@@ -103,6 +108,7 @@ class EvalMPC:
         if control_bounds is not None and len(control_bounds) != 2:
             raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
+        self.ensemble_mode = self._checked_ensemble_mode(ensemble_mode)
         self.control_bounds = None if control_bounds is None else tuple(control_bounds)
         self.config = config
         self.cost_model = cost_model
@@ -188,7 +194,33 @@ class EvalMPC:
             if self._ensemble_dev is None or self._ensemble_dev.device != eng.device:
                 self._ensemble_dev = eng.to_dev(self.dynamics_ensemble)
             eng.set_sampled_ensemble(self._ensemble_dev)
+        if self.ensemble_mode is not None:
+            eng.set_sampled_ensemble_mode(**self.ensemble_mode)
         return eng
+
+    ENSEMBLE_MODE_KEYS = ("aggregate", "risk", "propagation", "particles")
+
+    def _checked_ensemble_mode(self, mode):
+        """The constructor's / set_ensemble_mode's keywords as a dict, or None (the values are the engine's to check)."""
+        if mode is None:
+            return None
+        if self.solver not in ("cem", "mppi", "icem"):
+            raise ValueError('ensemble_mode and solver="cem" / "mppi" / "icem" go together: got '
+                             f"solver={self.solver!r}")
+        mode = dict(mode)
+        unknown = set(mode) - set(self.ENSEMBLE_MODE_KEYS)
+        if unknown:
+            raise ValueError(f"ensemble_mode has unknown keyword(s) {sorted(unknown, key=str)}")
+        return mode
+
+    def set_ensemble_mode(self, **kw):
+        """Replace the ensemble mode of a "cem" / "mppi" / "icem" policy (the constructor's ensemble_mode=) by
+        Engine.set_sampled_ensemble_mode's keywords; none: the default mode.  Set on the bound engine now and by every
+        later bind."""
+        mode = self._checked_ensemble_mode(kw)
+        if self._engine is not None:
+            self._engine.set_sampled_ensemble_mode(**mode)      # the engine checks the values: a refused mode is not kept
+        self.ensemble_mode = mode
 
     def set_dynamics_ensemble(self, members):
         """Replace the dynamics ensemble of a "cem" / "mppi" / "icem" policy (the constructor's dynamics_ensemble=):

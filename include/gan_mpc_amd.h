@@ -406,7 +406,8 @@ int gmpc_set_sampled_precision(gmpc_ctx* ctx, int precision);
  * refuse (LSTM dynamics, a width above 256).  gmpc_set_params neither drops nor changes the ensemble.
  *   While set, every launch of gmpc_cem_solve / gmpc_mppi_solve / gmpc_icem_solve that rolls out SAMPLED rows rolls
  *   each row out once per member p, under member p's dynamics weights and biases (the cost MLP, mpc_w, x0, the goals
- *   and the controls are shared): J_p, the arithmetic of a solve without an ensemble.  The row's cost is
+ *   and the controls are shared): J_p, the arithmetic of a solve without an ensemble.  The row's cost is (in the
+ *   default mode; gmpc_set_sampled_ensemble_mode below has the others)
  *   (((J_0 + J_1) + J_2) + ... + J_{P-1}) * (1.0f / (float)P) in fp32 (a NaN J_p makes it NaN), and everything that
  *   reads costs -- elites, weights, kept rows, iCEM's best row and best_cost_io, `costs` / `costs_trace` -- reads that.
  *   `samples` is bitwise that of a solve without an ensemble.  X and obj of the returned sequence stay on the
@@ -415,6 +416,32 @@ int gmpc_set_sampled_precision(gmpc_ctx* ctx, int precision);
  *   again.  gmpc_mppi_vjp differentiates the nominal model only and is refused while an ensemble is set ("mppi vjp:
  *   ..."). */
 int gmpc_set_sampled_ensemble(gmpc_ctx* ctx, int P, const float* dyn_members);
+
+/* What the sampling solvers do with a set ensemble: a property of the context, like the precision
+ * and the ensemble; the default is {GMPC_ENS_MEAN, 0, GMPC_ENS_FIXED, 0}, the rule above.  No stream, no device work.
+ * Independent of the members: gmpc_set_sampled_ensemble and gmpc_set_params neither reset nor change it, it may be set
+ * before an ensemble is, and it has no effect while none is set.
+ *   propagation  GMPC_ENS_FIXED: cost plane q is member q, Q = P planes (particles must be 0).
+ *                GMPC_ENS_TS1:   Q = particles planes, 1 <= particles <= 16; particle q at step t of iteration `it`
+ *                                runs under member umulhi(philox4x32_10(counter (t, q, 0xFFFFFFFF, it), key (seed low
+ *                                word, seed high word))[0], P), `it` the solve's iter_offset + i.  The schedule is
+ *                                shared by every row and problem: the rows of an iteration are ranked under the same
+ *                                model sequences (common random numbers).
+ *   aggregate    over the planes' costs J_0 .. J_{Q-1} of a row, every operation one IEEE fp32 operation in ascending
+ *                q, invQ = 1.0f / (float)Q:
+ *                GMPC_ENS_MEAN      (((J_0 + J_1) + ...) + J_{Q-1}) * invQ
+ *                GMPC_ENS_MEAN_STD  mean + risk * sqrt(ss * invQ), ss = (((0 + d_0 d_0) + d_1 d_1) + ...), d_q = J_q -
+ *                                   mean; risk < 0 is optimism
+ *                GMPC_ENS_MAX       w = J_0; w = (J_q > w || J_q != J_q) ? J_q : w
+ *                A NaN J_q makes the cost NaN in every mode.
+ * `samples`, X and obj are as under gmpc_set_sampled_ensemble; gmpc_mppi_vjp stays refused while an ensemble is set.
+ * GMPC_EINVAL ("ensemble mode: ...", the mode left as it was) for a null ctx or mode, an aggregate outside 0..2, a
+ * propagation outside 0..1, a non-finite risk, risk != 0 with an aggregate other than GMPC_ENS_MEAN_STD, particles != 0
+ * with GMPC_ENS_FIXED, and particles outside [1, 16] with GMPC_ENS_TS1. */
+enum { GMPC_ENS_MEAN = 0, GMPC_ENS_MEAN_STD = 1, GMPC_ENS_MAX = 2 };   /* aggregate   */
+enum { GMPC_ENS_FIXED = 0, GMPC_ENS_TS1 = 1 };                         /* propagation */
+typedef struct { int aggregate; float risk; int propagation; int particles; } gmpc_ensemble_mode;
+int gmpc_set_sampled_ensemble_mode(gmpc_ctx* ctx, const gmpc_ensemble_mode* mode);
 
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
