@@ -187,6 +187,8 @@ SIGNATURES = {
     "gmpc_wgrad_batch_ex": (C.c_int, [_P, C.POINTER(WgradDesc), C.c_int, _P, C.c_long, _P, C.POINTER(C.c_int)]),
     "gmpc_wgrad_route": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(C.c_int)]),
     "gmpc_wgrad_batch_route": (C.c_int, [C.POINTER(WgradDesc), C.c_int, C.c_long, C.POINTER(C.c_int)]),
+    "gmpc_linearize_ex": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "gmpc_linearize_route": (C.c_int, [C.POINTER(Shape), C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "gmpc_linesearch_candidates": (C.c_long, [_P]),
     "gmpc_linesearch_stats": (C.c_int, [_P, C.POINTER(C.c_long), C.c_int]),
     "gmpc_profile_enable": (C.c_int, [_P, C.c_int]),

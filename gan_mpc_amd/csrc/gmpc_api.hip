@@ -159,7 +159,7 @@ extern "C" int gmpc_create(const gmpc_shape* shape, int max_batch, int device, g
       const size_t hl = s.dyn_dims[s.dyn_layers - 1];
       size_t hmax = 0;
       for (int l = 1; l < s.dyn_layers; ++l) hmax = (size_t)s.dyn_dims[l] > hmax ? s.dyn_dims[l] : hmax;
-      if (!c->dynl && 2 * hl < n && getenv("GMPC_BIG_DENSE") == nullptr) {
+      if (gmpc_big_lowrank_h(&c->sh) > 0) {
         c->bw.h = (int)hl;
         B_(Vt, B * hl * nm + pad);
         B_(W1b, B * hl * n + pad);
@@ -480,6 +480,69 @@ extern "C" int gmpc_pack_layout(const gmpc_shape* s, int which, gmpc_leaf* leave
 extern "C" int gmpc_set_linearize_event(gmpc_ctx* c, void* ev) {
   if (!c) return fail(GMPC_EINVAL, "ctx is null");
   c->lin_event = static_cast<hipEvent_t>(ev);
+  return 0;
+}
+
+void set_lin_kernel(gmpc_ctx* c, int family) {
+  switch (family) {
+    case LIN_DYNL: c->lin_kernel = "k_dynl_jac"; break;
+    case LIN_SPARSE:
+      c->lin_kernel = c->sh.n > 16 ? "k_linearize_sparse (rows 0..15 per sample, rows 16..n-1 per time group)"
+                                   : "k_linearize_sparse";
+      break;
+    case LIN_REGS:
+      snprintf(c->lin_kernel_buf, sizeof(c->lin_kernel_buf), "%s", gmpc_linearize_regs_last_name());
+      c->lin_kernel = c->lin_kernel_buf;
+      break;
+    case LIN_MFMA: c->lin_kernel = "k_linearize_mfma"; break;
+    case LIN_VALU: c->lin_kernel = "k_linearize (vector ALU)"; break;
+    case LIN_LOWRANK: c->lin_kernel = "low-rank factors (k_mask_scale, k_bgemm_tn)"; break;
+    default: break;
+  }
+}
+
+// The Jacobian chain a ctx of `shape` runs for nsamp samples (strided != 0: a strided sample set, as the large-state
+// pass takes one time step of every trajectory), and the plan of k_linearize_mfma for it; host only.
+extern "C" int gmpc_linearize_route(const gmpc_shape* shape, int nsamp, int strided, int* route) {
+  TRY(check_shape(shape));
+  if (nsamp < 1 || !route) return fail(GMPC_EINVAL, "bad argument");
+  const gmpc_shape& s = *shape;
+  const bool dynl = s.dyn_lstm_features > 0, big = s.n > 64 || s.m > 32;
+  for (int i = 0; i < GMPC_LIN_ROUTE_INTS; ++i) route[i] = 0;
+  route[0] = gmpc_linearize_family_of(big, gmpc_big_lowrank_h(shape), dynl, nsamp, s.n, s.m, s.dyn_layers, s.dyn_dims,
+                                      strided != 0);
+  if (dynl) return 0;
+  LinMfmaPlan p;
+  const int rc = gmpc_linearize_mfma_plan(nsamp, s.n, s.m, s.dyn_layers, s.dyn_dims, &p);
+  route[1] = p.NT; route[2] = p.NTF; route[3] = p.NGF; route[4] = p.stage_w1; route[5] = p.stage_wl;
+  route[6] = p.body; route[7] = p.ntiles; route[8] = p.grid; route[9] = (int)p.lds; route[10] = p.nsmax;
+  route[11] = rc == 0 ? 1 : 0;
+  return 0;
+}
+
+// The chain of the ctx's shape on the caller's masks, into the caller's AB [nsamp][n][n + m], with the weights and
+// padded operands of the last gmpc_set_params: what the backward passes launch, for tests/linearize_cases.py.
+extern "C" int gmpc_linearize_ex(gmpc_ctx* c, int nsamp, const unsigned* masks, const int* active, float* AB,
+                                 int samp_mul, int samp_add, void* stream) {
+  if (!c || !masks || !AB || nsamp < 1 || samp_mul < 1 || samp_add < 0) return fail(GMPC_EINVAL, "bad argument");
+  if (!c->params_set) return fail(GMPC_EINVAL, "gmpc_set_params has not been called");
+  const gmpc_shape& sh = c->sh;
+  const bool strided = !(samp_mul == 1 && samp_add == 0);
+  const int fam = gmpc_linearize_family_of(c->big, c->bw.h, c->dynl, nsamp, sh.n, sh.m, sh.dyn_layers, sh.dyn_dims,
+                                           strided);
+  if (fam == LIN_DYNL || fam == LIN_LOWRANK)
+    return fail(GMPC_EINVAL, "gmpc_linearize_ex: LSTM dynamics and the low-rank form keep no Jacobian chain");
+  // (the sparse chain's time groups and the VALU chain take whole horizons)
+  if ((fam == LIN_SPARSE || fam == LIN_VALU) && !strided && nsamp % sh.T != 0)
+    return fail(GMPC_EINVAL, "gmpc_linearize_ex: nsamp must be a multiple of T for this shape's chain");
+  HIP_TRY(hipSetDevice(c->device));
+  (void)hipGetLastError();   // clean slate (see check_call)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (gmpc_launch_linearize_family(fam, nsamp, sh.T, sh.n, sh.m, c->dyn, c->lp, masks, active, AB, samp_mul, samp_add,
+                                   s) != 0)
+    return fail(GMPC_EINVAL, "gmpc_linearize_ex: no Jacobian chain covers this launch");
+  set_lin_kernel(c, fam);
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 

@@ -62,6 +62,9 @@ static int backward_pass(gmpc_ctx* c, int B, const float* X, const float* U, con
                             c->Ks, k, grad ? grad : c->grads, adj ? adj : c->adjs, nullptr, nullptr, s,
                             c->dynl ? &c->dl : nullptr) != 0)
         return fail(GMPC_EINVAL, "large-state backward: Jacobian kernel does not cover this shape");
+      // (the chain every step of the pass launched: the same call of the same function as big_step_jacobians)
+      set_lin_kernel(c, gmpc_linearize_family_of(true, c->bw.h, c->dynl, B, sh.n, sh.m, sh.dyn_layers, sh.dyn_dims,
+                                                 true));
       if (K != c->Ks)
         HIP_TRY(hipMemcpyAsync(K, c->Ks, (size_t)B * sh.T * sh.m * sh.n * sizeof(float),
                                hipMemcpyDeviceToDevice, s));
@@ -89,28 +92,16 @@ static int backward_pass(gmpc_ctx* c, int B, const float* X, const float* U, con
     // 1st choice: the chain over each sample's active relu units (200-wide hidden layers; bitwise the dense
     // chain's result), 2nd: register-resident dense chain (compiled for the common equal-width shapes), 3rd: the
     // LDS-operand chain (any shape), 4th: VALU.  GMPC_LIN=dense skips the first (read per call: the tests compare
-    // the two routes inside one process).
-    const char* lin_env = getenv("GMPC_LIN");
-    const bool lin_dense = lin_env != nullptr && strcmp(lin_env, "dense") == 0;
-    if (c->dynl) {
+    // the two routes inside one process).  The order itself is gmpc_linearize_family_of's.
+    const int fam = gmpc_linearize_family_of(false, 0, c->dynl, (long)B * sh.T, sh.n, sh.m, sh.dyn_layers, sh.dyn_dims,
+                                             false);
+    if (fam == LIN_DYNL) {
       gmpc_launch_dynl_jac(B, sh.T, sh.T, 0, c->dl, X, U, active, AB, s);
-      c->lin_kernel = "k_dynl_jac";
-    } else if (!lin_dense && gmpc_launch_linearize_sparse(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks,
-                                                          active, AB, 1, 0, s) == 0) {
-      c->lin_kernel = sh.n > 16 ? "k_linearize_sparse (rows 0..15 per sample, rows 16..n-1 per time group)"
-                                : "k_linearize_sparse";
-    } else if (gmpc_launch_linearize_regs(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
-                                          s) == 0) {
-      snprintf(c->lin_kernel_buf, sizeof(c->lin_kernel_buf), "%s", gmpc_linearize_regs_last_name());
-      c->lin_kernel = c->lin_kernel_buf;
-    } else if (gmpc_launch_linearize_mfma(B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1, 0,
-                                          s) != 0) {
-      if (gmpc_launch_linearize(B, sh.T, sh.n, sh.m, c->dyn, c->masks, active, AB, s) != 0)
-        return fail(GMPC_EINVAL, "linearize: unsupported row count for n=%d", sh.n);
-      c->lin_kernel = "k_linearize (vector ALU)";
-    } else {
-      c->lin_kernel = "k_linearize_mfma";
+    } else if (gmpc_launch_linearize_family(fam, B * sh.T, sh.T, sh.n, sh.m, c->dyn, c->lp, c->masks, active, AB, 1,
+                                            0, s) != 0) {
+      return fail(GMPC_EINVAL, "linearize: unsupported row count for n=%d", sh.n);
     }
+    set_lin_kernel(c, fam);
   }
   HIP_TRY(hipGetLastError());
   if (c->lin_event) HIP_TRY(hipEventRecord(c->lin_event, s));     // gmpc_set_linearize_event

@@ -620,12 +620,23 @@ static void launch_lin(int B, int T, int n, int m, int SP, const MlpDesc& dyn, c
                      masks, active, AB);
 }
 
+// rows per pass: as many whole samples as fit in 24 rows, at least one sample; R4 = float4 rows of a pass
+static int lin_valu_r4(int n, int* SP) {
+  *SP = 24 / n;
+  if (*SP < 1) *SP = 1;
+  return (*SP * n + 3) / 4;
+}
+
+bool gmpc_linearize_valu_covers(int n) {
+  int SP;
+  const int R4 = lin_valu_r4(n, &SP);
+  return R4 >= 1 && R4 <= 16;
+}
+
 int gmpc_launch_linearize(int B, int T, int n, int m, const MlpDesc& dyn, const uint32_t* masks,
                           const int* active, float* AB, hipStream_t s) {
-  // rows per pass: as many whole samples as fit in 24 rows, at least one sample
-  int SP = 24 / n;
-  if (SP < 1) SP = 1;
-  const int R4 = (SP * n + 3) / 4;
+  int SP;
+  const int R4 = lin_valu_r4(n, &SP);
   switch (R4) {
 #define GMPC_LIN_CASE(q) case q: launch_lin<q>(B, T, n, m, SP, dyn, masks, active, AB, s); return 0;
     GMPC_LIN_CASE(1) GMPC_LIN_CASE(2) GMPC_LIN_CASE(3) GMPC_LIN_CASE(4) GMPC_LIN_CASE(5)

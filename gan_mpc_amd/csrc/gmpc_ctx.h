@@ -224,6 +224,8 @@ static void bind_expert(ExpertNet& e, int nx, int m, const gmpc_expert_shape* es
 
 // gmpc_api.hip: argument and state checks every entry point starts with
 int check_call(gmpc_ctx* c, int B, bool need_params = true);
+// gmpc_api.hip: c->lin_kernel after a launch of the chain `family` (LIN_* of gmpc_launch.h)
+void set_lin_kernel(gmpc_ctx* c, int family);
 // gmpc_api_sampled.hip: the sampling solvers' shared checks (`who`: the message's prefix) and the noise stream of
 // iteration `it` under `seed` (beta: the smoothing along time)
 int gmpc_sampled_coverage(const gmpc_ctx* c, const char* who);

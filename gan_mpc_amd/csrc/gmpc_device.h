@@ -433,8 +433,9 @@ struct BigWork {
 // zero-padded weight copies read by the MFMA Jacobian chain (gmpc_linearize_mfma.hip)
 struct LinPad {
   int NT, NTF, NGF;                     // column tiles: hidden GEMMs / input GEMM per group, groups
-  const float* WLP;                     // [dims[Lh]+2][n]            rows >= dims[Lh] are zero
-  const float* WTP[GMPC_MAX_LAYERS];    // l>=1: [dims[l+1]+2][32*NT]; l==0: [dims[1]+2][32*NTF]
+  // (PAD = GMPC_LIN_PADROWS = 24 zero rows behind every copy: the GEMM bodies read up to row K + 20)
+  const float* WLP;                     // [dims[Lh]+PAD][n]          rows >= dims[Lh] are zero
+  const float* WTP[GMPC_MAX_LAYERS];    // l>=1: [dims[l+1]+PAD][32 lanes][8 tiles]; l==0: [dims[1]+PAD][32*NTF*NGF]
   const float* WSP[GMPC_MAX_LAYERS];    // 1 <= l < Lh: W_l^T packed for k_linearize_sparse (null for other shapes)
   unsigned long long* dbg;              // diagnostic: per-segment cycle sums (null in production)
 };

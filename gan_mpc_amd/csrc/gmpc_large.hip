@@ -263,6 +263,14 @@ static void big_lowrank_factors(const BigWork& w, int B, const MlpDesc& dyn, con
                             nm), s);
 }
 
+// MLP dynamics on the large-state path whose last hidden width is below n / 2 take the low-rank form (8 n^2 h instead
+// of 4 n^3 flops per Riccati step); GMPC_BIG_DENSE=1 keeps the dense form (A/B timing).  Read when a ctx is created.
+int gmpc_big_lowrank_h(const gmpc_shape* sh) {
+  if (!(sh->n > 64 || sh->m > 32) || sh->dyn_lstm_features > 0) return 0;
+  const int hl = sh->dyn_dims[sh->dyn_layers - 1];
+  return 2 * hl < sh->n && getenv("GMPC_BIG_DENSE") == nullptr ? hl : 0;
+}
+
 // The Jacobians of step t for the B samples (b, t), enqueued on `s`: the low-rank form's factors V_t^T into w.Vt
 // (MLP dynamics with w.h > 0; AB is not written), else [A_t | B_t] into AB -- from the LSTM variant's kernel (dl) or
 // the MFMA chains (k_linearize_regs, else k_linearize_mfma).  Non-zero when no chain covers the shape.
@@ -270,12 +278,12 @@ static int big_step_jacobians(const BigWork& w, int B, const MlpDesc& dyn, const
                               const DynlDesc* dl, const float* X, const float* U, int t, const int* active,
                               float* AB, hipStream_t s) {
   const int n = w.n, m = w.m, T = w.T;
-  if (dl != nullptr) {
+  const int fam = gmpc_linearize_family_of(true, w.h, dl != nullptr, B, n, m, dyn.L, dyn.dims, true);
+  if (fam == LIN_DYNL) {
     gmpc_launch_dynl_jac(B, T, 1, t, *dl, X, U, active, AB, s);
-  } else if (w.h > 0) {
+  } else if (fam == LIN_LOWRANK) {
     big_lowrank_factors(w, B, dyn, masks, t, active, s);
-  } else if (gmpc_launch_linearize_regs(B, T, n, m, dyn, lp, masks, active, AB, T, t, s) != 0 &&
-             gmpc_launch_linearize_mfma(B, T, n, m, dyn, lp, masks, active, AB, T, t, s) != 0) {
+  } else if (gmpc_launch_linearize_family(fam, B, T, n, m, dyn, lp, masks, active, AB, T, t, s) != 0) {
     return -1;
   }
   return 0;

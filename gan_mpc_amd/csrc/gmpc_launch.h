@@ -80,6 +80,48 @@ const char* gmpc_linearize_regs_last_name();   // instantiation the last gmpc_la
 int gmpc_launch_linearize_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
                                hipStream_t s);
+// The mask contract of every chain.  masks holds GMPC_MW words per (sample, hidden layer), at
+// [((s * samp_mul + samp_add) * Lh + l) * GMPC_MW + word]; bit u & 31 of word u >> 5 is the relu bit of unit u of hidden
+// layer l (0-based; its width is dims[l + 1]).  Bits at or past a layer's width MAY be set.  k_linearize_mfma reads
+// all GMPC_MW words of every (sample, layer) of the launch and only meets such bits in k-steps whose weight rows are
+// the zero pad rows of both operands (odd widths, the read-ahead), so they select zeros; k_linearize_regs (widths 64,
+// 128, 200) reads only the words its width spans; k_linearize_sparse (200-wide layers) reads words 0..6 and clips
+// word 6 to its 8 units, so it never sees them.  (tests/linearize_cases.py sets such bits for k_linearize_mfma.)  `active` (null: everything) is read at
+// (s * samp_mul + samp_add) / T; a sample whose entry is 0 is either left untouched or written with its Jacobian (a
+// 32-row tile is skipped only when every sample it touches is inactive).
+//
+// The decisions of the chains apart from their launches (host only; gmpc_linearize_route exports them for
+// tests/linearize_cases.py).  Column tiles of the padded operands: NT of the hidden GEMMs, NTF per group of the input
+// GEMM, NGF groups.
+void gmpc_linpad_tiles(int L, const int* dims, int n, int m, int* NT, int* NTF, int* NGF);
+enum { LIN_BODY_SINGLE = 0, LIN_BODY_RING = 1, LIN_BODY_MULTI = 2 };   // input GEMM: seed-fed / gemm_tile_1 / gemm_tile
+struct LinMfmaPlan {
+  int NT, NTF, NGF;
+  int ntiles, nsmax;          // 32-row tiles; most samples a tile touches (the slab's mask rows)
+  int stage_w1, stage_wl;     // the padded W_1^T / W_L are copied to LDS (W_1^T first, each when it still fits)
+  int grid, body;
+  size_t lds;                 // dynamic LDS of one workgroup, <= GMPC_LIN_LDS_MAX
+};
+#define GMPC_LIN_LDS_MAX (160 * 1024)
+// non-zero: k_linearize_mfma does not take the launch (2^31 rows or more, or the slabs alone exceed the LDS)
+int gmpc_linearize_mfma_plan(long NSamp, int n, int m, int L, const int* dims, LinMfmaPlan* p);
+// whether gmpc_launch_linearize_sparse / _regs / the VALU chain take a launch (what their launchers test first)
+bool gmpc_linearize_sparse_covers(long NSamp, int n, int m, int L, const int* dims, bool strided);
+bool gmpc_linearize_regs_covers(long NSamp, int n, int m, int L, const int* dims, int row0);
+bool gmpc_linearize_valu_covers(int n);
+// The order of the chains, in one place for gmpc_api_solve.hip's backward pass, gmpc_large.hip's step and
+// gmpc_linearize_ex: LSTM dynamics -> their own kernel; large state (big) with lowrank_h > 0 -> the low-rank factors;
+// then sparse (small state, unless GMPC_LIN=dense, read per call), regs, mfma, VALU (small state, whole batch only).
+enum { LIN_NONE = 0, LIN_SPARSE = 1, LIN_REGS = 2, LIN_MFMA = 3, LIN_VALU = 4, LIN_DYNL = 5, LIN_LOWRANK = 6 };
+int gmpc_linearize_family_of(bool big, int lowrank_h, bool dynl, long NSamp, int n, int m, int L, const int* dims,
+                             bool strided);
+// launches the chain of `family` (sparse, regs, mfma or VALU); non-zero when it is none of them or its launcher
+// declines.  The VALU chain takes whole batches only: NSamp = B * T, samp_mul = 1, samp_add = 0.
+int gmpc_launch_linearize_family(int family, int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                 const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                                 hipStream_t s);
+// last hidden width when the large-state pass takes the low-rank form of the Jacobians for `sh`, else 0 (gmpc_large.hip)
+int gmpc_big_lowrank_h(const gmpc_shape* sh);
 // padded weight copies of the chains: floats of the buffer, and the build on every gmpc_set_params
 size_t gmpc_linpad_floats(const gmpc_shape* sh);
 void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pad_floats, LinPad* out, hipStream_t s);

@@ -17,7 +17,8 @@
 //     layer below in the epilogue and written back to G as the next A operand.
 // Waves never talk to each other: no workgroup barrier in the kernel.
 #include "gmpc_launch.h"
-
+#include <cstdlib>
+#include <cstring>
 
 
 // out[o][i] = W[i][o] (W is (in,out) row-major) into a zero-initialised (rows x ldo) buffer
@@ -234,12 +235,19 @@ __global__ __launch_bounds__(GMPC_THREADS, 1) void k_linearize_mfma(
 }
 
 // ---------------------------------------------------------------------------------------------
+void gmpc_linpad_tiles(int L, const int* dims, int n, int m, int* NT, int* NTF, int* NGF) {
+  int wmax = 1;
+  for (int l = 1; l < L; ++l) wmax = dims[l] > wmax ? dims[l] : wmax;
+  *NT = (wmax + 31) / 32;
+  const int tilesF = (n + m + 31) / 32;
+  *NTF = tilesF <= 3 ? tilesF : 8;
+  *NGF = (tilesF + *NTF - 1) / *NTF;
+}
+
 size_t gmpc_linpad_floats(const gmpc_shape* sh) {
   const int L = sh->dyn_layers, Lh = L - 1;
-  int wmax = 1;
-  for (int l = 1; l < L; ++l) wmax = sh->dyn_dims[l] > wmax ? sh->dyn_dims[l] : wmax;
-  const int tilesF = (sh->n + sh->m + 31) / 32;
-  const int NTF = tilesF <= 3 ? tilesF : 8, NGF = (tilesF + NTF - 1) / NTF;
+  int NT, NTF, NGF;
+  gmpc_linpad_tiles(L, sh->dyn_dims, sh->n, sh->m, &NT, &NTF, &NGF);
   size_t f = (size_t)(sh->dyn_dims[Lh] + GMPC_LIN_PADROWS) * sh->n;
   f += (size_t)(sh->dyn_dims[1] + GMPC_LIN_PADROWS) * 32 * NTF * NGF;
   for (int l = 1; l < Lh; ++l) f += (size_t)(sh->dyn_dims[l + 1] + GMPC_LIN_PADROWS) * 256;
@@ -249,12 +257,7 @@ size_t gmpc_linpad_floats(const gmpc_shape* sh) {
 void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pad_floats, LinPad* out,
                          hipStream_t s) {
   const int Lh = dyn.L - 1;
-  int wmax = 1;
-  for (int l = 1; l < dyn.L; ++l) wmax = dyn.dims[l] > wmax ? dyn.dims[l] : wmax;
-  out->NT = (wmax + 31) / 32;
-  const int tilesF = (n + m + 31) / 32;
-  out->NTF = tilesF <= 3 ? tilesF : 8;
-  out->NGF = (tilesF + out->NTF - 1) / out->NTF;
+  gmpc_linpad_tiles(dyn.L, dyn.dims, n, m, &out->NT, &out->NTF, &out->NGF);
   out->dbg = nullptr;
   (void)hipMemsetAsync(pad, 0, pad_floats * sizeof(float), s);
   float* p = pad;
@@ -278,46 +281,62 @@ void gmpc_linpad_prepare(const MlpDesc& dyn, int n, int m, float* pad, size_t pa
   gmpc_linsparse_prepare(dyn, n, m, p, out, s);
 }
 
-template <int NT, int NTF>
-static int launch_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
-                       const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
-                       hipStream_t s) {
-  const long Rtot = (long)NSamp * n;
-  if (Rtot >= (1L << 31) - 64) return -1;
-  const int ntiles = (int)((Rtot + 31) / 32);
-  const int nsmax = 32 / n + 2;
-  const int Lh = dyn.L - 1;
-  const size_t wave_bytes = (size_t)(32 * (32 * NT + 1) + 8) * sizeof(float) +
-                            (size_t)Lh * nsmax * GMPC_MW * sizeof(uint32_t);
+// Everything launch_mfma decides (host only).  The furthest pad row a GEMM body reads behind the K rows of its
+// operand: gemm_tile / gemm_tile_x4 request k-step k0 + 8 with k0 + 6 <= Kp, row Kp + 3 at most; the ring gemm_tile_1
+// requests k-step k0 + 20 of its last trip k0 <= Kp - 2, row Kp + 19 <= K + 20 -- inside GMPC_LIN_PADROWS = 24.
+int gmpc_linearize_mfma_plan(long NSamp, int n, int m, int L, const int* dims, LinMfmaPlan* p) {
+  gmpc_linpad_tiles(L, dims, n, m, &p->NT, &p->NTF, &p->NGF);
+  const int Lh = L - 1;
+  p->body = Lh == 1 ? LIN_BODY_SINGLE : p->NTF == 1 ? LIN_BODY_RING : LIN_BODY_MULTI;
+  p->ntiles = p->nsmax = p->stage_w1 = p->stage_wl = p->grid = 0;
+  p->lds = 0;
+  const long Rtot = NSamp * n;
+  if (NSamp < 1 || p->NT > 8 || Rtot >= (1L << 31) - 64) return -1;
+  p->ntiles = (int)((Rtot + 31) / 32);
+  p->nsmax = 32 / n + 2;
+  const size_t wave_bytes = (size_t)(32 * (32 * p->NT + 1) + 8) * sizeof(float) +
+                            (size_t)Lh * p->nsmax * GMPC_MW * sizeof(uint32_t);
   size_t lds = wave_bytes * (GMPC_THREADS / 64);
-  const size_t lds_max = 160 * 1024;
+  const size_t lds_max = GMPC_LIN_LDS_MAX;
+  p->lds = lds;
   if (lds > lds_max) return -1;
   // stage the two small operands in LDS when they fit (W_1^T first: its GEMM has one MFMA per
   // k-step and is latency-bound from L2)
-  const size_t w1_bytes = (size_t)(dyn.dims[1] + GMPC_LIN_PADROWS) * 32 * NTF * lp.NGF * sizeof(float);
-  const size_t wl_bytes = (size_t)(dyn.dims[Lh] + GMPC_LIN_PADROWS) * n * sizeof(float);
-  int stage_w1 = 0, stage_wl = 0;
-  if (lp.NGF == 1 && lds + w1_bytes <= lds_max) { stage_w1 = 1; lds += w1_bytes; }
-  if (lds + wl_bytes <= lds_max) { stage_wl = 1; lds += wl_bytes; }
+  const size_t w1_bytes = (size_t)(dims[1] + GMPC_LIN_PADROWS) * 32 * p->NTF * p->NGF * sizeof(float);
+  const size_t wl_bytes = (size_t)(dims[Lh] + GMPC_LIN_PADROWS) * n * sizeof(float);
+  if (p->NGF == 1 && lds + w1_bytes <= lds_max) { p->stage_w1 = 1; lds += w1_bytes; }
+  if (lds + wl_bytes <= lds_max) { p->stage_wl = 1; lds += wl_bytes; }
+  p->lds = lds;
+  p->grid = (p->ntiles + 3) / 4;
+  if (p->grid > 256) p->grid = 256;   // one persistent workgroup per CU (LDS-limited to 1 anyway)
+  return 0;
+}
+
+template <int NT, int NTF>
+static int launch_mfma(const LinMfmaPlan& p, int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                       const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                       hipStream_t s) {
+  // (once per process and instantiation, not per device: a second device would launch without the raised limit)
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_linearize_mfma<NT, NTF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GMPC_LIN_LDS_MAX);
     attr_set = true;
   }
-  int grid = (ntiles + 3) / 4;
-  if (grid > 256) grid = 256;   // one persistent workgroup per CU (LDS-limited to 1 anyway)
-  hipLaunchKernelGGL((k_linearize_mfma<NT, NTF>), dim3(grid), dim3(GMPC_THREADS), lds, s, NSamp, T, n, m,
-                     dyn, lp, masks, active, AB, ntiles, nsmax, stage_wl, stage_w1, samp_mul, samp_add);
+  hipLaunchKernelGGL((k_linearize_mfma<NT, NTF>), dim3(p.grid), dim3(GMPC_THREADS), p.lds, s, NSamp, T, n, m,
+                     dyn, lp, masks, active, AB, p.ntiles, p.nsmax, p.stage_wl, p.stage_w1, samp_mul, samp_add);
   return 0;
 }
 
 int gmpc_launch_linearize_mfma(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                const uint32_t* masks, const int* active, float* AB, int samp_mul,
                                int samp_add, hipStream_t s) {
+  LinMfmaPlan p;
+  if (gmpc_linearize_mfma_plan(NSamp, n, m, dyn.L, dyn.dims, &p) != 0) return -1;
+  if (p.NT != lp.NT || p.NTF != lp.NTF || p.NGF != lp.NGF) return -1;   // the padded operands are another shape's
 #define GMPC_LM(a, b)                                                                              \
   if (lp.NT == a && lp.NTF == b)                                                                   \
-    return launch_mfma<a, b>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    return launch_mfma<a, b>(p, NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
   GMPC_LM(1, 1) GMPC_LM(2, 1) GMPC_LM(3, 1) GMPC_LM(4, 1) GMPC_LM(5, 1) GMPC_LM(6, 1) GMPC_LM(7, 1)
   GMPC_LM(8, 1) GMPC_LM(1, 2) GMPC_LM(2, 2) GMPC_LM(3, 2) GMPC_LM(4, 2) GMPC_LM(5, 2) GMPC_LM(6, 2)
   GMPC_LM(7, 2) GMPC_LM(8, 2) GMPC_LM(1, 3) GMPC_LM(2, 3) GMPC_LM(3, 3) GMPC_LM(4, 3) GMPC_LM(5, 3)
@@ -325,4 +344,37 @@ int gmpc_launch_linearize_mfma(int NSamp, int T, int n, int m, const MlpDesc& dy
   GMPC_LM(5, 8) GMPC_LM(6, 8) GMPC_LM(7, 8) GMPC_LM(8, 8)
 #undef GMPC_LM
   return -1;
+}
+
+// ---- the order of the chains ------------------------------------------------------------------
+int gmpc_linearize_family_of(bool big, int lowrank_h, bool dynl, long NSamp, int n, int m, int L, const int* dims,
+                             bool strided) {
+  if (dynl) return LIN_DYNL;
+  if (big && lowrank_h > 0) return LIN_LOWRANK;
+  const char* lin_env = getenv("GMPC_LIN");   // read per call: the tests compare the two routes inside one process
+  const bool lin_dense = lin_env != nullptr && strcmp(lin_env, "dense") == 0;
+  if (!big && !lin_dense && gmpc_linearize_sparse_covers(NSamp, n, m, L, dims, strided)) return LIN_SPARSE;
+  if (gmpc_linearize_regs_covers(NSamp, n, m, L, dims, 0)) return LIN_REGS;
+  LinMfmaPlan p;
+  if (gmpc_linearize_mfma_plan(NSamp, n, m, L, dims, &p) == 0) return LIN_MFMA;
+  if (!big && !strided && gmpc_linearize_valu_covers(n)) return LIN_VALU;
+  return LIN_NONE;
+}
+
+int gmpc_launch_linearize_family(int family, int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
+                                 const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
+                                 hipStream_t s) {
+  switch (family) {
+    case LIN_SPARSE:
+      return gmpc_launch_linearize_sparse(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    case LIN_REGS:
+      return gmpc_launch_linearize_regs(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    case LIN_MFMA:
+      return gmpc_launch_linearize_mfma(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, s);
+    case LIN_VALU:
+      if (samp_mul != 1 || samp_add != 0 || T < 1 || NSamp % T != 0) return -1;
+      return gmpc_launch_linearize(NSamp / T, T, n, m, dyn, masks, active, AB, s);
+    default:
+      return -1;
+  }
 }

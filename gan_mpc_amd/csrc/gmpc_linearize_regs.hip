@@ -363,6 +363,48 @@ __global__ __launch_bounds__(GMPC_THREADS, GMPC_REGS_OCC(NT, TAIL)) void k_linea
 static char g_last_name[64] = "";
 const char* gmpc_linearize_regs_last_name() { return g_last_name; }
 
+// dynamic LDS of one workgroup of k_linearize_regs<., KS, TAIL, WIDE>
+static size_t regs_lds(int KS, int TAIL, bool WIDE, int Lh, int hl, int n) {
+  size_t lds = WIDE ? (size_t)4 * 32 * 33 * sizeof(float) : (size_t)(hl + GMPC_LIN_PADROWS) * n * sizeof(float);
+  if (TAIL > 0) lds += (size_t)(Lh - 1) * 2 * KS * 8 * sizeof(float);
+  if (!WIDE) lds += (size_t)2 * KS * 32 * sizeof(float);
+  return lds;
+}
+
+// The instantiation that takes a shape and a row window: 0 none, 1 <6, 100, 8, true> (wide inputs), 2 <6, 100, 8>,
+// 3 <4, 64>, 4 <2, 32> (host only: the launcher and gmpc_linearize_regs_covers)
+static int regs_form(int n, int m, int L, const int* dims, int NT, int NTF, int NGF, int row0) {
+  const int Lh = L - 1;
+  if (row0 < 0 || row0 >= n || (row0 > 0 && n + m > 32)) return 0;
+  if (Lh < 2) return 0;
+  const int H = dims[1];
+  for (int l = 1; l <= Lh; ++l)
+    if (dims[l] != H) return 0;
+  if (n + m > 32) {
+    // wide inputs (large-state path): the 200-wide instantiation only
+    if (H != 200 || NT != 7 || 32 * NTF * NGF < ((n + m + 31) / 32 + 3) / 4 * 4 * 32) return 0;
+    return 1;
+  }
+  if (NTF != 1 || NGF != 1) return 0;
+  if (H == 200 && NT == 7) return 2;
+  if (H == 128 && NT == 4) return 3;
+  if (H == 64 && NT == 2) return 4;
+  return 0;
+}
+
+bool gmpc_linearize_regs_covers(long NSamp, int n, int m, int L, const int* dims, int row0) {
+  int NT, NTF, NGF;
+  gmpc_linpad_tiles(L, dims, n, m, &NT, &NTF, &NGF);
+  const int form = regs_form(n, m, L, dims, NT, NTF, NGF, row0);
+  if (form == 0 || NSamp * (n - row0) >= (1L << 31) - 64) return false;
+  const int Lh = L - 1;
+  const size_t lds = form == 1   ? regs_lds(100, 8, true, Lh, dims[Lh], n)
+                     : form == 2 ? regs_lds(100, 8, false, Lh, dims[Lh], n)
+                     : form == 3 ? regs_lds(64, 0, false, Lh, dims[Lh], n)
+                                 : regs_lds(32, 0, false, Lh, dims[Lh], n);
+  return lds <= 64 * 1024;
+}
+
 // returns 0 on launch, -1 on an unsupported shape
 template <int NT, int KS, int TAIL = 0, bool WIDE = false>
 static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
@@ -372,10 +414,7 @@ static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const
   if (Rtot >= (1L << 31) - 64) return -1;
   const int ntiles = (int)((Rtot + 31) / 32);
   const int Lh = dyn.L - 1;
-  size_t lds = WIDE ? (size_t)4 * 32 * 33 * sizeof(float)
-                    : (size_t)(dyn.dims[Lh] + GMPC_LIN_PADROWS) * n * sizeof(float);
-  if (TAIL > 0) lds += (size_t)(Lh - 1) * 2 * KS * 8 * sizeof(float);
-  if (!WIDE) lds += (size_t)2 * KS * 32 * sizeof(float);
+  const size_t lds = regs_lds(KS, TAIL, WIDE, Lh, dyn.dims[Lh], n);
   if (lds > 64 * 1024) return -1;
   int grid = (ntiles + 3) / 4;
   constexpr int occ = GMPC_REGS_OCC(NT, TAIL);
@@ -393,25 +432,18 @@ static int launch_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const
 int gmpc_launch_linearize_regs_rows(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                     const uint32_t* masks, const int* active, float* AB, int samp_mul,
                                     int samp_add, int row0, hipStream_t s) {
-  const int Lh = dyn.L - 1;
-  if (row0 < 0 || row0 >= n || (row0 > 0 && n + m > 32)) return -1;
-  if (Lh < 2) return -1;
-  const int H = dyn.dims[1];
-  for (int l = 1; l <= Lh; ++l)
-    if (dyn.dims[l] != H) return -1;
-  if (n + m > 32) {
-    // wide inputs (large-state path): the 200-wide instantiation only
-    if (H != 200 || lp.NT != 7 || 32 * lp.NTF * lp.NGF < ((n + m + 31) / 32 + 3) / 4 * 4 * 32) return -1;
-    return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
+  switch (regs_form(n, m, dyn.L, dyn.dims, lp.NT, lp.NTF, lp.NGF, row0)) {
+    case 1:
+      return launch_regs<6, 100, 8, true>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
+    case 2:
+      return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
+    case 3:
+      return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
+    case 4:
+      return launch_regs<2, 32>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
+    default:
+      return -1;
   }
-  if (lp.NTF != 1 || lp.NGF != 1) return -1;
-  if (H == 200 && lp.NT == 7)
-    return launch_regs<6, 100, 8>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
-  if (H == 128 && lp.NT == 4)
-    return launch_regs<4, 64>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
-  if (H == 64 && lp.NT == 2)
-    return launch_regs<2, 32>(NSamp, T, n, m, dyn, lp, masks, active, AB, samp_mul, samp_add, row0, s);
-  return -1;
 }
 
 int gmpc_launch_linearize_regs(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,

@@ -425,6 +425,13 @@ __global__ __launch_bounds__(GMPC_THREADS, 2) void k_linearize_sparse(
   }
 }
 
+// what the launcher below tests before it launches anything (host only)
+bool gmpc_linearize_sparse_covers(long NSamp, int n, int m, int L, const int* dims, bool strided) {
+  if (!sparse_form(L, dims, n, m)) return false;
+  // a strided sample set sends rows 16..n-1 to the dense chain's row window
+  return !(n > 16 && strided) || gmpc_linearize_regs_covers(NSamp, n, m, L, dims, 16);
+}
+
 int gmpc_launch_linearize_sparse(int NSamp, int T, int n, int m, const MlpDesc& dyn, const LinPad& lp,
                                  const uint32_t* masks, const int* active, float* AB, int samp_mul, int samp_add,
                                  hipStream_t s) {

@@ -82,6 +82,19 @@ def make_shape(n, m, T, dyn_dims, cost_dims, lstm_features=0, head_dims=None, dy
     return s
 
 
+LIN_ROUTE_INTS = 12       # GMPC_LIN_ROUTE_INTS
+
+
+def linearize_route_of(shape, nsamp, strided=False, lib=None):
+    """gmpc_linearize_route as a dict (host only, no GPU): the family of Jacobian chain a ctx of `shape` launches for
+    nsamp samples, and the plan of k_linearize_mfma<NT, NTF> for that launch."""
+    lib = lib or _lib.load()
+    r = (C.c_int * LIN_ROUTE_INTS)()
+    _lib.check(lib.gmpc_linearize_route(C.byref(shape), int(nsamp), int(bool(strided)), r))
+    return dict(family=Engine.LIN_FAMILIES[r[0]], NT=r[1], NTF=r[2], NGF=r[3], stage_w1=r[4], stage_wl=r[5],
+                body=Engine.LIN_BODIES[r[6]], ntiles=r[7], grid=r[8], lds=r[9], nsmax=r[10], mfma_ok=bool(r[11]))
+
+
 def make_expert_shape(lstm_features, head_dims_x, head_dims_u):
     """gmpc_expert_shape: y width (= lstm_features, or the first dense width of the MLP variant),
     hidden widths, then n / m."""
@@ -283,6 +296,31 @@ class Engine:
         _lib.check(fn(self.ctx, B, _ptr(X), _ptr(U), _ptr(goal), _ptr(out["K"]), _ptr(out["k"]),
                       _ptr(out["grad"]), _ptr(out["adjoints"]), _ptr(out.get("AB")), self._stream()))
         return out
+
+    LIN_FAMILIES = ("none", "sparse", "regs", "mfma", "valu", "dynl", "lowrank")
+    LIN_BODIES = ("single", "ring", "multi")
+
+    def linearize_route(self, nsamp, strided=False):
+        """The Jacobian chain this engine's shape runs for nsamp samples: linearize_route_of(self.shape, ...)."""
+        return linearize_route_of(self.shape, nsamp, strided, lib=self.lib)
+
+    def linearize(self, masks, AB, nsamp, active=None, samp_mul=1, samp_add=0):
+        """The Jacobian chain on the caller's relu bits (gmpc_linearize_ex): masks int32 words
+        [(s * samp_mul + samp_add) * Lh + l][8], AB (at least nsamp * n * (n + m) floats) is written in place."""
+        nsamp, samp_mul, samp_add = int(nsamp), int(samp_mul), int(samp_add)
+        if nsamp < 1 or samp_mul < 1 or samp_add < 0:
+            raise _lib.GmpcError(f"linearize: nsamp={nsamp}, samp_mul={samp_mul}, samp_add={samp_add} out of range")
+        last = (nsamp - 1) * samp_mul + samp_add                       # the furthest sample of `masks` the launch reads
+        Lh = self.shape.dyn_layers - 1
+        if masks is None or masks.dtype != torch.int32 or masks.numel() < (last + 1) * Lh * 8:
+            raise _lib.GmpcError(f"linearize: masks must hold {(last + 1) * Lh * 8} int32 words")
+        if AB is None or AB.dtype != torch.float32 or AB.numel() < nsamp * self.n * (self.n + self.m):
+            raise _lib.GmpcError(f"linearize: AB must hold {nsamp * self.n * (self.n + self.m)} floats")
+        if active is not None and (active.dtype != torch.int32 or active.numel() < last // self.T + 1):
+            raise _lib.GmpcError(f"linearize: active must hold {last // self.T + 1} int32 entries")
+        _lib.check(self.lib.gmpc_linearize_ex(self.ctx, int(nsamp), _ptr(masks), _ptr(active), _ptr(AB), int(samp_mul),
+                                              int(samp_add), self._stream()))
+        return AB
 
     def ilqr_solve(self, x0, U, goal, kwargs=None):
         return self._solve(self.lib.gmpc_ilqr_solve, x0, U, goal, kwargs)

@@ -761,6 +761,28 @@ int gmpc_wgrad_route(const gmpc_wgrad_desc* d, int* route6);
 /* Whether gmpc_wgrad_batch_ex would take the batch: route2 = {taken, rows per chunk} (B is tested for alignment). */
 int gmpc_wgrad_batch_route(const gmpc_wgrad_desc* probs, int np, long part_floats, int* route2);
 
+/* The dynamics Jacobian chain on its own, for the unit tests (tests/linearize_cases.py):
+ *   AB[s] = [A | B] = W_L^T D_{L-1}(s) W_{L-1}^T ... D_1(s) W_1^T + [I | 0],   s = 0 .. nsamp - 1,   AB [nsamp][n][n+m]
+ * with the weights (and their padded copies) of the ctx's last gmpc_set_params, through the dispatch of the backward
+ * passes.  D_l(s) comes from the caller's relu bits: masks holds 8 words per (sample, hidden layer), the words of
+ * sample s and hidden layer l (0-based) at [((s * samp_mul + samp_add) * Lh + l) * 8], unit u in bit u & 31 of word
+ * u >> 5; all 8 words are read, and bits at or past the layer's width may be set (they select zero pad rows).
+ * `active` (NULL: every sample) is read at (s * samp_mul + samp_add) / T: a sample whose entry is 0 is either left
+ * untouched or written with its Jacobian.  GMPC_EINVAL for a NULL ctx / masks / AB, nsamp < 1, samp_mul < 1,
+ * samp_add < 0, before gmpc_set_params, and for a ctx with LSTM dynamics or the low-rank large-state form. */
+int gmpc_linearize_ex(gmpc_ctx* ctx, int nsamp, const unsigned* masks, const int* active, float* AB, int samp_mul,
+                      int samp_add, void* stream);
+/* The chain gmpc_linearize_ex and the backward passes launch for a ctx of `shape` and nsamp samples (strided != 0: any
+ * samp_mul / samp_add but 1 / 0), without GPU work.  route[0] = family: 0 none, 1 k_linearize_sparse,
+ * 2 k_linearize_regs, 3 k_linearize_mfma, 4 the VALU k_linearize, 5 LSTM dynamics, 6 low-rank factors.  For MLP
+ * dynamics the rest is the plan of k_linearize_mfma<NT, NTF> for the launch, whichever family takes it: route[1..3] =
+ * NT, NTF, NGF (column tiles of the hidden GEMMs, of one group of the input GEMM, groups), route[4] / route[5] = the
+ * padded W_1^T / W_L staged in LDS, route[6] = input-GEMM body (0 fed from the seed: one hidden layer; 1 the six-deep
+ * ring: NTF = 1; 2 multi-tile), route[7] = 32-row tiles, route[8] = workgroups, route[9] = LDS bytes of one,
+ * route[10] = mask rows of a tile's slab, route[11] = 1 when k_linearize_mfma accepts the launch. */
+#define GMPC_LIN_ROUTE_INTS 12
+int gmpc_linearize_route(const gmpc_shape* shape, int nsamp, int strided, int* route);
+
 /* Number of candidate rollouts (trajectory, step size) the line searches of the last gmpc_ilqr_solve
  * evaluated -- the work count behind bench.py's secondary roofline.  Synchronises the whole device
  * (hipDeviceSynchronize). */
