@@ -1,0 +1,180 @@
+// A plan's rollout under every member of a dynamics ensemble (gmpc_ensemble_rollout): forward
+// only, B different problems, each with its own x0, goals and controls.
+//
+//   k_ens_rollout   one 256-thread workgroup per 32 PROBLEMS under one member (grid: tiles of 32 problems by members).
+//                   The arithmetic is cem_rollout_body's (gmpc_cem_rollout.h), reused: the 32 states in registers in
+//                   dg_gemm's accumulator layout, the layer inputs in one [32][GMPC_DG_LDA] fp32 LDS block, every
+//                   layer on dg_gemm, the row sums by cem_row8_sum -- so a problem's X and obj are bitwise those of
+//                   the sampled rollout's mean_row form under the same network.  What differs: x0, goal and U are per
+//                   row, every row's states are written (from the LDS block, rows of n floats), the costs are kept
+//                   per step, and the horizon may be cut short (S <= T steps, then without costs).
+//   k_ens_moments   one thread per (problem, step, state): mean and population variance over the members' planes,
+//                   both sums sequential in ascending member order.
+#include "gmpc_cem_rollout.h"
+
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ab[GMPC_CEM_ROWS * GMPC_DG_LDA];   // the layer inputs of the 32 rows
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
+  const int n = a.n, m = a.m, T = a.T, S = a.S, B = a.B;
+  const int b0 = blockIdx.x * GMPC_CEM_ROWS;     // row i of the tile is problem b0 + i
+  const size_t p = blockIdx.y;                   // the member
+  const int rrow = tid >> 3, rc = tid & 7;       // the row whose sums this thread shares in, its lane of the row's 8
+  const bool costed = a.goal != nullptr;         // (the launcher: only with S == T)
+  // Rows past B (the last tile): every read goes to problem B - 1, a valid one, and nothing is written for them.
+  const int last = B - 1;
+  const int rb = min(b0 + rrow, last);           // the problem whose goals this thread's row reads
+  const bool rlive = b0 + rrow < B;
+  float w0 = 0.f, w1 = 0.f, w2 = 0.f;
+  if (costed) {
+    w0 = sigmoidf_(a.mpc_w[0]); w1 = sigmoidf_(a.mpc_w[1]); w2 = sigmoidf_(a.mpc_w[2]);
+  }
+  const float al = GMPC_ALPHA;
+  // x_t of the 32 rows, in dg_gemm's accumulator layout: the output layer's tile of a thread is its tile of x
+  DgTiles xs;
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci) {
+    const int j = (wave + 4 * ci) * 16 + l16;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int bp = min(b0 + 4 * kq + rr, last), bq = min(b0 + 16 + 4 * kq + rr, last);
+      xs.p[ci][rr] = j < n ? a.x0[(size_t)bp * n + j] : 0.f;
+      xs.q[ci][rr] = j < n ? a.x0[(size_t)bq * n + j] : 0.f;
+    }
+  }
+  float* Xp = a.X ? a.X + p * B * (size_t)(S + 1) * n : nullptr;          // the member's planes
+  float* Cp = a.costs ? a.costs + p * B * (size_t)(T + 1) : nullptr;
+  float csum = 0.f;   // the cost of row rrow so far (the same in its 8 lanes)
+  DgTiles acc;
+  for (int t = 0; t < S; ++t) {
+    // ---- layer 0 input [x_t; u_t]
+    cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+    for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
+      const int i = e / m, j = e - i * m;
+      Ab[i * GMPC_DG_LDA + n + j] = a.U[((size_t)min(b0 + i, last) * S + t) * m + j];
+    }
+    __syncthreads();
+    // ---- x_t of every live row, from the operand block
+    if (Xp)
+      for (int e = tid; e < GMPC_CEM_ROWS * n; e += GMPC_DG_THREADS) {
+        const int i = e / n, j = e - i * n;
+        if (b0 + i < B) Xp[((size_t)(b0 + i) * (S + 1) + t) * n + j] = Ab[i * GMPC_DG_LDA + j];
+      }
+    // ---- stage cost of (x_t, u_t) against goal_t
+    if (costed) {
+      const float* row = Ab + rrow * GMPC_DG_LDA;
+      const float* g = a.goal + ((size_t)rb * (T + 1) + t) * n;
+      float su = 0.f, sx = 0.f;
+      for (int j = rc; j < m; j += 8) su = fmaf(row[n + j], row[n + j], su);
+      for (int j = rc; j < n; j += 8) {
+        const float d = row[j] - g[j];
+        sx = fmaf(d, d, sx);
+      }
+      su = cem_row8_sum(su);
+      sx = cem_row8_sum(sx);
+      // (the roundings of the sampled body's `csum += w0 * .. + w1 * ..` as the compiler contracts it there, written
+      // out: here the two products would be paired into one packed multiply and stay unfused)
+      const float c = fmaf(w0, sqrtf(su + al * al) - al, w1 * (sqrtf(sx + al * al) - al));
+      csum += c;
+      if (Cp && rc == 0 && rlive) Cp[(size_t)(b0 + rrow) * (T + 1) + t] = c;
+    }
+    // ---- x_{t+1} = x_t + MLP([x_t; u_t]) under member p
+    for (int l = 0; l < a.dyn.L; ++l) {
+      const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
+      dg_gemm(Ab, K, Nl, a.dyn.W[l] + p * a.mstride, wave, lane, acc);
+      __syncthreads();   // every wave has read its operand rows (and the stage cost and the copy of x_t theirs)
+      const float* bias = a.dyn.b[l] + p * a.mstride;
+      if (l < a.dyn.L - 1) {
+        cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); });
+        __syncthreads();
+      } else {
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+          const int j = (wave + 4 * ci) * 16 + l16;
+          if (j >= n) continue;
+          const float bj = bias[j];
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            xs.p[ci][rr] = (acc.p[ci][rr] + bj) + xs.p[ci][rr];
+            xs.q[ci][rr] = (acc.q[ci][rr] + bj) + xs.q[ci][rr];
+          }
+        }
+      }
+    }
+  }
+  // ---- x_S into the operand block: the last copy of the states and the cost MLP's input
+  cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+  __syncthreads();
+  if (Xp)
+    for (int e = tid; e < GMPC_CEM_ROWS * n; e += GMPC_DG_THREADS) {
+      const int i = e / n, j = e - i * n;
+      if (b0 + i < B) Xp[((size_t)(b0 + i) * (S + 1) + S) * n + j] = Ab[i * GMPC_DG_LDA + j];
+    }
+  if (!costed) return;     // (uniform over the workgroup)
+  // ---- terminal cost w2 |MLP_c(x_T)|^2
+  for (int l = 0; l < a.cost.L; ++l) {
+    const int K = a.cost.dims[l], Nl = a.cost.dims[l + 1];
+    dg_gemm(Ab, K, Nl, a.cost.W[l], wave, lane, acc);
+    __syncthreads();
+    const float* bias = a.cost.b[l];
+    if (l < a.cost.L - 1)
+      cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return fmaxf(v + bias[j], 0.f); });
+    else
+      cem_store_tiles(Ab, acc, Nl, wave, lane, [bias](float v, int j) { return v + bias[j]; });
+    __syncthreads();
+  }
+  {
+    const float* row = Ab + rrow * GMPC_DG_LDA;
+    const int fout = a.cost.dims[a.cost.L];
+    float sy = 0.f;
+    for (int j = rc; j < fout; j += 8) sy = fmaf(row[j], row[j], sy);
+    sy = cem_row8_sum(sy);
+    const float c = w2 * sy;
+    csum = fmaf(w2, sy, csum);     // (the sampled body's `csum += w2 * sy`, one rounding, as it is contracted there)
+    if (rc == 0 && rlive) {
+      if (Cp) Cp[(size_t)(b0 + rrow) * (T + 1) + T] = c;
+      if (a.obj) a.obj[p * B + b0 + rrow] = csum;
+    }
+  }
+}
+
+// Mean and population variance over the planes X [P][count] of one element each: sum_p x_p, then / P; sum_p (x_p -
+// mean)^2, then / P -- every operation one IEEE fp32 operation in ascending p (no contraction), so the result is a
+// function of the planes alone and NumPy restates it bit for bit.  mean / var: either may be null.
+__global__ __launch_bounds__(GMPC_THREADS) void k_ens_moments(const float* __restrict__ X, int P, size_t count,
+                                                              float* __restrict__ mean, float* __restrict__ var) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * GMPC_THREADS + threadIdx.x;
+  if (i >= count) return;
+  const float fP = (float)P;
+  float sum = X[i];
+  for (int p = 1; p < P; ++p) sum = sum + X[p * count + i];
+  const float mu = sum / fP;
+  if (mean) mean[i] = mu;
+  if (!var) return;
+  float ss = 0.f;
+  for (int p = 0; p < P; ++p) {
+    const float d = X[p * count + i] - mu;
+    const float dd = d * d;
+    ss = ss + dd;
+  }
+  var[i] = ss / fP;
+}
+
+// Host-side launchers ---------------------------------------------------------------------------
+int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s) {
+  for (int l = 0; l <= a.dyn.L; ++l)
+    if (a.dyn.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
+  for (int l = 0; l <= a.cost.L; ++l)
+    if (a.cost.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
+  if (a.n + a.m > GMPC_SAMPLED_MAX_WIDTH || a.B < 1 || a.S < 1 || a.S > a.T || P < 1 || P > GMPC_MAX_ENSEMBLE) return 1;
+  if ((a.costs || a.obj) && !a.goal) return 1;
+  if (a.goal && a.S != a.T) return 1;
+  const dim3 grid((a.B + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS, P);
+  hipLaunchKernelGGL(k_ens_rollout, grid, dim3(GMPC_DG_THREADS), 0, s, a);
+  return 0;
+}
+
+void gmpc_launch_ens_moments(const float* X, int P, size_t count, float* mean, float* var, hipStream_t s) {
+  const unsigned blocks = (unsigned)((count + GMPC_THREADS - 1) / GMPC_THREADS);
+  hipLaunchKernelGGL(k_ens_moments, dim3(blocks), dim3(GMPC_THREADS), 0, s, X, P, count, mean, var);
+}

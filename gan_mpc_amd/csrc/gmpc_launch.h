@@ -327,6 +327,25 @@ int gmpc_launch_sampled_rollout(const CemRollArgs& a, bool bf16, const CemEnsemb
 int gmpc_launch_cem_update(const CemUpdArgs& a, hipStream_t s);
 void gmpc_launch_ens_reduce(const CemEnsemble& e, int B, int rows, int ldc, float* costs, hipStream_t s);
 
+// gmpc_ens_rollout.hip: a plan's rollout under every member of a dynamics ensemble -----------------------
+// B problems in tiles of 32, one grid row of workgroups per member: x0 [B][n], U [B][S][m], 1 <= S <= T; dyn describes
+// member 0 (fp32), member p lies p mstride floats behind it.  goal [B][T+1][n] or null: null skips the cost terms and
+// the cost MLP; set, it needs S == T.  X [P][B][S+1][n], costs [P][B][T+1] (stage costs, the terminal cost at T) and
+// obj [P][B] (their sum in step order) may each be null; costs and obj need goal.
+struct EnsRollArgs {
+  int B, S, T, n, m;
+  MlpDesc dyn, cost;
+  size_t mstride;
+  const float *mpc_w, *x0, *U, *goal;
+  float *X, *costs, *obj;
+};
+// Non-zero (nothing launched) outside the sampled rollout's coverage, 1 <= S <= T, 1 <= P <= GMPC_MAX_ENSEMBLE and the
+// rules above
+int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s);
+// mean / var [count] (either may be null) over the planes X [P][count]: the sum in member order / P, the squared
+// deviations' sum in member order / P
+void gmpc_launch_ens_moments(const float* X, int P, size_t count, float* mean, float* var, hipStream_t s);
+
 // gmpc_icem.hip: the sample-efficient cross-entropy method's two kernels --------------------------------
 // The rows of one iteration's pool, per problem: rows 0 .. Nit-1 fresh samples (sample index = row), rows Nit ..
 // Nit+carry-1 the first `carry` rows of keep [B][nkeep][T][m], then -- with addmean -- the mean itself; every row

@@ -815,6 +815,50 @@ class Engine:
             int(bool(teacher_forcing)), _ptr(loss_sum), _ptr(grad_sum), self._stream()))
         return loss_sum, grad_sum
 
+    ENSEMBLE_ROLLOUT_WANT = ("X", "costs", "obj", "mean", "var")
+
+    def ensemble_rollout(self, members, x0, U, goal=None, want=("X", "obj")):
+        """A plan's rollout under every member of a dynamics ensemble, in one launch (gmpc_ensemble_rollout; DESIGN.md
+        section 27).  members: float32 (P, dyn_count) tensor or array, 1 <= P <= 16, as set_sampled_ensemble takes
+        them, passed per call; x0 (B, n), U (B, S, m) with 1 <= S <= T, goal (B, T + 1, n) or None: float32 device
+        tensors.  -> a dict of the `want`ed tensors: "X" (P, B, S + 1, n) the members' states, "costs" (P, B, T + 1)
+        the stage costs and the terminal cost, "obj" (P, B) their sum, "mean" / "var" (B, S + 1, n) the members' mean
+        and population variance per step and state.  "costs" and "obj" need goal and S == T.  X[p] and obj[p] are
+        bitwise what cem_solve(max_iter=0) returns for U on an engine bound to member p.  Stateless: the bound mpc_w
+        and cost network are read; a set ensemble, its mode, the sampled precision and a held solution stay as they
+        are.  Every refusal is a GmpcError("ensemble rollout: ..."); nothing is synchronised."""
+        who = "ensemble rollout"
+        P = self._check_ensemble_members(who, members)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - set(self.ENSEMBLE_ROLLOUT_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"{who}: want has unknown entries {sorted(unknown, key=str)}; known: "
+                                 f"{self.ENSEMBLE_ROLLOUT_WANT}")
+        if not want:
+            raise _lib.GmpcError(f"{who}: want is empty; known: {self.ENSEMBLE_ROLLOUT_WANT}")
+        if goal is None and ("costs" in want or "obj" in want):
+            raise _lib.GmpcError(f'{who}: "costs" and "obj" need goal (want = {want})')
+        n, m, T = self.n, self.m, self.T
+        for name, t in (("x0", x0), ("U", U), ("goal", goal)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+                raise _lib.GmpcError(f"{who}: {name} must be a float32 tensor, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)}")
+        if x0.dim() != 2 or x0.shape[1] != n:
+            raise _lib.GmpcError(f"{who}: x0 must be (B, {n}), got {tuple(x0.shape)}")
+        B = int(x0.shape[0])
+        if U.dim() != 3 or U.shape[0] != B or U.shape[2] != m:
+            raise _lib.GmpcError(f"{who}: U must be ({B}, S, {m}), got {tuple(U.shape)}")
+        S = int(U.shape[1])
+        if goal is not None and tuple(goal.shape) != (B, T + 1, n):
+            raise _lib.GmpcError(f"{who}: goal must be {(B, T + 1, n)}, got {tuple(goal.shape)}")
+        shapes = dict(X=(P, B, S + 1, n), costs=(P, B, T + 1), obj=(P, B), mean=(B, S + 1, n), var=(B, S + 1, n))
+        out = {k: self.new(*shapes[k]) for k in self.ENSEMBLE_ROLLOUT_WANT if k in want}
+        dev = self.to_dev(members)
+        _lib.check(self.lib.gmpc_ensemble_rollout(
+            self.ctx, B, S, P, _ptr(dev), _ptr(x0), _ptr(U), _ptr(goal), _ptr(out.get("X")), _ptr(out.get("costs")),
+            _ptr(out.get("obj")), _ptr(out.get("mean")), _ptr(out.get("var")), self._stream()))
+        return out
+
     def _check_ensemble_members(self, who, members):
         """The rank, width, count and dtype of a (P, dyn_count) float32 tensor or array -> P."""
         shape = tuple(getattr(members, "shape", ()))

@@ -7,6 +7,9 @@ fused clip+Adam on each member's slice with the member's own moments and norm.  
 its own minibatches (with replacement, like the reference's `jax.random.choice`): the members see different data and
 differ for that reason as well as for their initial weights.  Relu-MLP dynamics only; one rank only.
 
+Validation: holdout_errors rolls held-out sequences out under every member in one call per chunk
+(Engine.ensemble_rollout) and returns each member's open-loop error per step; elite_members picks the best k.
+
 `key` is a NumPy seed / Generator.  `train_args` = (policy, opt): the policy lends its engine (policy.engine_for; it
 must have been bound once, its engine takes the shapes from the bound parameters), opt is an optim.ClipAdam."""
 
@@ -128,3 +131,38 @@ def train_params(train_args, opt_state, members, dataset, num_updates, batch_siz
                                    opt.lr, inv, opt.max_norm, opt.b1, opt.b2, opt.eps)
         out.append((total * (inv / steps)).cpu().numpy())
     return members, opt_state, np.stack(out).astype(np.float32) if out else losses
+
+
+def holdout_errors(engine, members, xseq, useq, next_xseq):
+    """The members' multi-step open-loop error on recorded sequences: every sequence is rolled
+    out from xseq[:, 0] under useq by every member (Engine.ensemble_rollout, in chunks of engine.max_batch sequences)
+    and compared with next_xseq.  members (P, dyn_count); xseq, next_xseq (D, S, n), useq (D, S, m), S <= T, tensors
+    on the engine's device.  -> (P, S) float32: the mean over sequences and state entries of the squared error of
+    member p's prediction of step s + 1.  No gradient, nothing of the engine's state is touched."""
+    shapes = tuple(tuple(getattr(t, "shape", ())) for t in (xseq, useq, next_xseq))
+    if any(len(s) != 3 for s in shapes) or shapes[2] != shapes[0] or shapes[1][:2] != shapes[0][:2] or shapes[0][0] < 1:
+        raise ValueError("ensemble trainer: holdout data must be (D, S, n), (D, S, m), (D, S, n) with D >= 1, got "
+                         f"{shapes[0]}, {shapes[1]}, {shapes[2]}")
+    D, S, n = shapes[0]
+    total = None
+    for b0 in range(0, D, int(engine.max_batch)):
+        b1 = min(D, b0 + int(engine.max_batch))
+        X = engine.ensemble_rollout(members, xseq[b0:b1, 0].contiguous(), useq[b0:b1].contiguous(), want=("X",))["X"]
+        err = X[:, :, 1:] - next_xseq[b0:b1].unsqueeze(0)
+        part = (err * err).to(torch.float64).sum(dim=(1, 3))           # (P, S): the chunk's sum
+        total = part if total is None else total + part
+    return (total / float(D * n)).to(torch.float32)
+
+
+def elite_members(errors, k):
+    """The indices of the k members with the smallest holdout error summed over the steps, best first; ties go to the
+    lower index, a member with a non-finite error comes last.  errors: holdout_errors' (P, S).  -> int64 tensor (k,)
+    that indexes the members (members[elite_members(errors, k)] is what set_dynamics_ensemble takes)."""
+    e = errors.detach().cpu().numpy() if torch.is_tensor(errors) else np.asarray(errors)
+    if e.ndim != 2 or e.shape[0] < 1:
+        raise ValueError(f"ensemble trainer: errors must be (P, S), got shape {e.shape}")
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= e.shape[0]:
+        raise ValueError(f"ensemble trainer: k = {k!r} outside [1, P = {e.shape[0]}]")
+    total = e.astype(np.float64).sum(axis=1)
+    total = np.where(np.isfinite(total), total, np.inf)
+    return torch.as_tensor(np.argsort(total, kind="stable")[:int(k)].astype(np.int64))

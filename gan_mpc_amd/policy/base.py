@@ -39,6 +39,21 @@ class BaseMPC(eval_policy.EvalMPC):
         del args
         return super().get_optimal_values(params, history_x)
 
+    def plan_spread(self, params, x, U):
+        """Where the members of the policy's dynamics ensemble disagree along a plan (Engine.ensemble_rollout, DESIGN.md
+        section 27): x (B, n) initial states, U (B, T, m) controls.  -> (X_members (P, B, T+1, n), the members'
+        predicted states; disagreement (B, T+1), the members' population variance per step summed over the state
+        entries).  Forward only: a disagreement bonus or penalty, or a check before acting."""
+        if self.dynamics_ensemble is None:
+            raise ValueError("plan_spread needs a dynamics_ensemble (the constructor's, or set_dynamics_ensemble): "
+                             "none is set")
+        xs, Us = tuple(getattr(x, "shape", np.shape(x))), tuple(getattr(U, "shape", np.shape(U)))
+        if len(xs) != 2 or len(Us) != 3 or Us[0] != xs[0]:
+            raise ValueError(f"plan_spread: x must be (B, n) and U (B, T, m), got {xs} and {Us}")
+        eng = self.bind(self.to_device_params(params), xs[0])
+        out = eng.ensemble_rollout(self._ensemble_dev, eng.to_dev(x), eng.to_dev(U), want=("X", "var"))
+        return out["X"], out["var"].sum(-1)
+
     def loss(self, xcseq, useq, params, *args):
         """The upper-level loss of ONE trajectory (reference policy/base.py:84-85): xcseq (T+1, n) -- xc, carry
         columns included --, useq (T, m), params the device parameters; a scalar torch tensor.  A subclass with

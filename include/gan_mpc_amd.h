@@ -443,6 +443,33 @@ enum { GMPC_ENS_FIXED = 0, GMPC_ENS_TS1 = 1 };                         /* propag
 typedef struct { int aggregate; float risk; int propagation; int particles; } gmpc_ensemble_mode;
 int gmpc_set_sampled_ensemble_mode(gmpc_ctx* ctx, const gmpc_ensemble_mode* mode);
 
+/* A plan's rollout under every member of a dynamics ensemble, and the members' spread: B
+ * problems, each with its own initial state, goals and controls, rolled S steps under each of the P members in one
+ * launch; forward only.
+ *   dyn_members [P][dyn_param_count]: the layout of gmpc_set_sampled_ensemble, passed per call (nothing is kept)
+ *   x0 [B][n], U [B][S][m], 1 <= S <= T, 1 <= B <= max_batch, 1 <= P <= 16
+ *   goal [B][T+1][n] or NULL: NULL skips the cost terms and the cost MLP
+ *   -> X      [P][B][S+1][n]  member p's states, X[p][b][0] = x0[b]
+ *      costs  [P][B][T+1]     stage costs w0 (sqrt(|u_t|^2 + a^2) - a) + w1 (sqrt(|x_t - goal_t|^2 + a^2) - a), t < T, and
+ *                             the terminal cost w2 |MLP_c(x_T)|^2 at t = T
+ *      obj    [P][B]          their fp32 sum, t ascending, the terminal cost last
+ *      x_mean [B][S+1][n]     (sum_p x_p) / P, the sum sequential in ascending p
+ *      x_var  [B][S+1][n]     (sum_p (x_p - x_mean)^2) / P, the population variance, summed likewise
+ *   each output may be NULL, not all of them; costs and obj need goal and S == T.
+ * The arithmetic of a row is that of the sampling solvers' rollout: X[p] and obj[p] are bitwise what gmpc_cem_solve
+ * with max_iter = 0 returns for U on a context whose bound dynamics are member p, and they depend on neither B, the
+ * problem's place in the batch, nor P.  A non-finite member makes its own planes and the moments non-finite and leaves
+ * the other members' planes as they are.
+ * Stateless: mpc_w and the cost MLP come from the parameters bound by gmpc_set_params; a set sampled ensemble, its
+ * mode, the sampled precision and a held solution are neither read nor changed.  Asynchronous on `stream` (two
+ * launches at most), deterministic.  With moments but no X the members' planes live in the call workspace, grown (a
+ * synchronising hipMalloc) by the first call that needs more.  Every refusal is GMPC_EINVAL with a message starting
+ * "ensemble rollout: ", before any launch: a null ctx, dyn_members, x0 or U; B, S or P out of range; parameters not
+ * set; every output NULL; costs or obj with goal == NULL or S != T; LSTM dynamics, a width or n + m above 256. */
+int gmpc_ensemble_rollout(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_members, const float* x0,
+                          const float* U, const float* goal, float* X, float* costs, float* obj, float* x_mean,
+                          float* x_var, void* stream);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
