@@ -66,6 +66,53 @@ __device__ __forceinline__ void rw_hidden_epilogue(f32x4_t d, int nn, int H, flo
   if (valid) hout[nn] = make_float4(on0 ? d[0] : 0.f, on1 ? d[1] : 0.f, on2 ? d[2] : 0.f, on3 ? d[3] : 0.f);
 }
 
+// A lane offset past the end of a raw buffer resource: the hardware drops the store and answers a load with 0.  The
+// plain rollout's time loop issues every global load and store that way, in straight-line code: hipcc counts memory
+// operations per basic block, and behind one that sits in an `if` body it waits for ALL outstanding ones
+// (s_waitcnt vmcnt(0)) -- here for the acknowledgement of the stores issued moments before, once per step.
+#define GMPC_RW_OOB 0xFFFFFFF0u
+// (the four words through v_readfirstlane: a base that went through the vector ALU's 64-bit multiply otherwise stays in
+// vector registers, and every access through it becomes a loop over the lanes' distinct resources)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rw_rsrc(const void* p, size_t bytes) {
+  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  void* q = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
+  return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+}
+
+// (lo, hi) of lane c = the two halves of wc for c = 0, 1, 2; the other lanes keep theirs.  One statement that opens
+// with its own wait states: hipcc pads nothing for an asm string, and a v_writelane straight behind the v_cmp that
+// wrote the ballot it reads took the register's OLD value (measured: one statement per v_writelane, scheduled between
+// the v_cmp, gave wrong mask words for slots 0 and 1 -- same states, different Jacobians).
+__device__ __forceinline__ void rw_writelanes(unsigned& lo, unsigned& hi, unsigned long long w0, unsigned long long w1,
+                                              unsigned long long w2) {
+  asm("s_nop 4\n\t"
+      "v_writelane_b32 %0, %2, 0\n\tv_writelane_b32 %1, %3, 0\n\t"
+      "v_writelane_b32 %0, %4, 1\n\tv_writelane_b32 %1, %5, 1\n\t"
+      "v_writelane_b32 %0, %6, 2\n\tv_writelane_b32 %1, %7, 2"
+      : "+v"(lo), "+v"(hi)
+      : "s"((unsigned)w0), "s"((unsigned)(w0 >> 32)), "s"((unsigned)w1), "s"((unsigned)(w1 >> 32)), "s"((unsigned)w2),
+        "s"((unsigned)(w2 >> 32)));
+}
+
+// rw_hidden_epilogue for the plain rollout: the same bits, the mask words through the buffer resource `rsm` (the
+// workgroup's mask words, this step's and layer's `soff` bytes in): lane c < 4 stores the two words of slot c at
+// `moff` = its byte offset, GMPC_RW_OOB where the slot writes nothing and in lanes 4 .. 63
+__device__ __forceinline__ void rw_hidden_epilogue_counted(f32x4_t d, int nn, int H, float4* hout,
+                                                           __amdgpu_buffer_rsrc_t rsm, unsigned moff, int soff) {
+  // (no `&& nn < H`: a lane without a neuron holds zero weights and a zero bias, its d is 0 or NaN, never > 0)
+  const bool on0 = d[0] > 0.f, on1 = d[1] > 0.f, on2 = d[2] > 0.f, on3 = d[3] > 0.f;
+  const unsigned long long w0 = __ballot(on0), w1 = __ballot(on1), w2 = __ballot(on2), w3 = __ballot(on3);
+  // lane c's words: slot 3's everywhere, slots 0 .. 2 written into lanes 0 .. 2 (v_writelane; a select by lane is a
+  // chain of 64-bit v_cndmask that hipcc turns into branches)
+  unsigned lo = (unsigned)w3, hi = (unsigned)(w3 >> 32);
+  rw_writelanes(lo, hi, w0, w1, w2);
+  typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
+  const v2u_t wv = {lo, hi};
+  __builtin_amdgcn_raw_buffer_store_b64(wv, rsm, moff, soff, 0);
+  if (nn < H) hout[nn] = make_float4(on0 ? d[0] : 0.f, on1 ? d[1] : 0.f, on2 ? d[2] : 0.f, on3 ? d[3] : 0.f);
+}
+
 // one H x H hidden layer: hin ([k] float4 of the 4 slots) -> accumulator of this lane's neuron.
 // XK weight rows live in LDS (two full layers, 400 registers, plus the loop's working set do not fit
 // 512 registers): rows 8 q + {2, 3, 6, 7} for q < XK / 4, one float4 of wx ([XK / 4][256 threads]) each,
@@ -240,13 +287,51 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
     }
   }
   float objacc = 0.f;  // lane 0 of wave c accumulates trajectory c
+
+  // ---- plain rollout: the layer-0 operand stays in registers over the horizon.  Lane l of operand register r is
+  // element (row 16 r + l / 4, slot l & 3) of the input (x ; u ; 0).  After the output layer EVERY wave forms its own
+  // copy: a state row from the four partial sums in `part`, the bias and the old state -- which is that same register
+  // -- with the additions of the form that went through xcur, in its order; a control row from the load it issued one
+  // step ahead; zero elsewhere (lanes without a control load past the end of the buffer resource, which gives 0).  No
+  // write of xcur, no barrier and no read of xcur between the output layer and layer 0; wave 0 alone stores X.
+  constexpr int NR0 = (K0Q + 3) / 4;
+  float ar0[NR0], pfu[NR0], blr[NR0];
+  unsigned uoff[NR0], xoff[NR0], moff = GMPC_RW_OOB;
+  bool isx[NR0];
+  __amdgpu_buffer_rsrc_t rsU, rsX, rsM;
+  if constexpr (!LS) {
+    // the workgroup's part of U, X and the mask words (offsets inside stay far below 2^31: rw_width bounds T)
+    const size_t nsl = min(GMPC_TB, a.B - b0);            // trajectories of this workgroup
+    rsU = rw_rsrc(a.U + (size_t)b0 * T * m, nsl * T * m * 4);
+    rsX = rw_rsrc(a.X + (size_t)b0 * (T + 1) * n, nsl * (T + 1) * n * 4);
+    rsM = rw_rsrc(a.masks + (size_t)b0 * mstride, nsl * mstride * 4);
+    const int c = lane & 3;
+    const bool wen = (wbits >> c) & 1u;
+    const int dc = BI(c) - b0;                            // (a slot past the batch re-reads the last trajectory)
+    if (lane < 4 && wen && a.masks != nullptr) moff = (unsigned)(((size_t)lane * mstride + 2 * wave) * 4);
+#pragma unroll
+    for (int r = 0; r < NR0; ++r) {
+      const int row = 16 * r + (lane >> 2);
+      isx[r] = row < n;
+      const bool isu = row >= n && row < n + m;
+      blr[r] = isx[r] ? a.dyn.b[Lh][row] : 0.f;
+      ar0[r] = isx[r] ? a.x0[(size_t)BI(c) * n + row] : 0.f;
+      uoff[r] = isu ? (unsigned)((dc * T * m + (row - n)) * 4) : GMPC_RW_OOB;
+      xoff[r] = (isx[r] && wen && wave == 0) ? (unsigned)((dc * (T + 1) * n + row) * 4) : GMPC_RW_OOB;
+      const float u0 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsU, uoff[r], 0, 0));
+      pfu[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsU, uoff[r], min(1, T - 1) * m * 4, 0));
+      if (!isx[r]) ar0[r] = u0;
+    }
+    // vmcnt(0): the weight loads above have landed.  Left to the loop, their first use is a wait at the loop's head
+    // that is paid at every step -- for that step's stores.
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+  }
   __syncthreads();
   TS_BEGIN();
 
-  // The operands of the step's controls are loaded one step ahead (every global round trip inside the step
-  // is ~1k cycles of a ~8k-cycle step).  Plain rollout: thread (c, j) holds u_t[j] of slot c.  Line search:
-  // 8 lanes share one (slot, control) pair of u = U + alpha k + K (x - X_nominal) and hold its gain row and
-  // nominal state, 4 elements each (n <= 32).
+  // Line search: the operands of the step's controls are loaded one step ahead (every global round trip inside the
+  // step is ~1k cycles of a ~8k-cycle step): 8 lanes share one (slot, control) pair of
+  // u = U + alpha k + K (x - X_nominal) and hold its gain row and nominal state, 4 elements each (n <= 32).
   const bool rw_pf = GMPC_TB * m <= (int)(blockDim.x >> 3);   // all pairs in one pass
   const int rw_pp = tid >> 3, rw_l8 = tid & 7;
   const int rw_c = rw_pp / m, rw_j = rw_pp - rw_c * m;
@@ -256,27 +341,22 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
     if (!rw_on) return;
     const int bc = BI(rw_c);
     const size_t ub = ((size_t)bc * T + t) * m + rw_j;
-    if (LS) {
-      const float* Kr = a.Kg + ub * n;
-      const float* Xo = a.X + ((size_t)bc * (T + 1) + t) * n;
+    const float* Kr = a.Kg + ub * n;
+    const float* Xo = a.X + ((size_t)bc * (T + 1) + t) * n;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int i = rw_l8 + 8 * e;
-        pfK[e] = i < n ? Kr[i] : 0.f;
-        pfX[e] = i < n ? Xo[i] : 0.f;
-      }
-      pfk = a.kg[ub];
-      pfU = a.Uio[ub];
-    } else if (rw_l8 == 0) {
-      pfU = a.U[ub];
+    for (int e = 0; e < 4; ++e) {
+      const int i = rw_l8 + 8 * e;
+      pfK[e] = i < n ? Kr[i] : 0.f;
+      pfX[e] = i < n ? Xo[i] : 0.f;
     }
+    pfk = a.kg[ub];
+    pfU = a.Uio[ub];
   };
-  rw_prefetch(0);
+  if constexpr (LS) rw_prefetch(0);
   for (int t = 0; t < T; ++t) {
-    // ---- controls (the stage costs are evaluated after the horizon, see below)
-    if (rw_on) {
-      float u = pfU;
-      if (LS) {
+    if constexpr (LS) {
+      // ---- controls (the stage costs are evaluated after the horizon, see below)
+      if (rw_on) {
         float du = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -286,15 +366,13 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
         du += __shfl_xor(du, 4);
         du += __shfl_xor(du, 2);
         du += __shfl_xor(du, 1);
-        u = pfU + fmaf(s_alpha[rw_c], pfk, du);
-      }
-      if (rw_l8 == 0) {
-        if (LS && ((wbits >> rw_c) & 1u)) a.Uc[(CI(rw_c) * T + t) * m + rw_j] = u;
-        put_u(rw_c, rw_j, u);
-      }
-    } else if (!rw_pf) {
-      // wide control vectors: the general loops, operands loaded in place
-      if (LS) {
+        const float u = pfU + fmaf(s_alpha[rw_c], pfk, du);
+        if (rw_l8 == 0) {
+          if ((wbits >> rw_c) & 1u) a.Uc[(CI(rw_c) * T + t) * m + rw_j] = u;
+          put_u(rw_c, rw_j, u);
+        }
+      } else if (!rw_pf) {
+        // wide control vectors: the general loop, operands loaded in place
         const int l16 = tid & 15;
         for (int p = tid >> 4; p < GMPC_TB * m; p += blockDim.x >> 4) {
           const int c = p / m, j = p - c * m;
@@ -314,30 +392,27 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
             put_u(c, j, u);
           }
         }
-      } else {
-        for (int p = tid; p < GMPC_TB * m; p += blockDim.x) {
-          const int c = p / m, j = p - c * m;
-          put_u(c, j, a.U[((size_t)BI(c) * T + t) * m + j]);
-        }
       }
+      if (t + 1 < T) rw_prefetch(t + 1);
+      __syncthreads();
+      TS_(0)
     }
-    if (t + 1 < T) rw_prefetch(t + 1);
-    __syncthreads();
-    TS_(0)
     // ---- the dynamics network on the matrix pipe (see rw_layer)
-    uint32_t* mb = (LS ? a.maskc : a.masks) + (size_t)b0 * mstride + (size_t)t * Lh * GMPC_MW;
+    uint32_t* mb = a.maskc + (size_t)b0 * mstride + (size_t)t * Lh * GMPC_MW;   // (line search)
+    const int msoff = t * Lh * GMPC_MW * 4;                                      // (plain rollout: bytes into rsM)
     {
-      // layer 0: input rows (x ; u ; 0) of xcur, weights from registers
-      float ar[(K0Q + 3) / 4];
+      // layer 0: input rows (x ; u ; 0), weights from registers
+      float ar[NR0];
 #pragma unroll
-      for (int r = 0; r < (K0Q + 3) / 4; ++r) ar[r] = xf[64 * r + lane];
+      for (int r = 0; r < NR0; ++r) ar[r] = LS ? xf[64 * r + lane] : ar0[r];
       f32x4_t d0 = {rbias[0], rbias[0], rbias[0], rbias[0]}, d1 = {0.f, 0.f, 0.f, 0.f};
       rw_static_for<2 * K0Q>([&](auto kc) __attribute__((always_inline)) {
         constexpr int k = 2 * decltype(kc)::value;
         rw_mfma<k>(d0, ar[k >> 4], w0r[k]);
         rw_mfma<k + 1>(d1, ar[(k + 1) >> 4], w0r[k + 1]);
       });
-      rw_hidden_epilogue(d0 + d1, nnA, KH, actA, mb, mstride, wbits);
+      if constexpr (LS) rw_hidden_epilogue(d0 + d1, nnA, KH, actA, mb, mstride, wbits);
+      else rw_hidden_epilogue_counted(d0 + d1, nnA, KH, actA, rsM, moff, msoff);
     }
     __syncthreads();
     TS_(2)
@@ -346,7 +421,8 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
     rw_static_for<NHL>([&](auto hc) __attribute__((always_inline)) {
       constexpr int hl = decltype(hc)::value;
       const f32x4_t d = rw_layer<KH, (hl == NHL - 1 ? XK : 0)>(wr[hl], hin, wx_s, rbias[hl + 1]);
-      rw_hidden_epilogue(d, nnA, KH, hout, mb + (hl + 1) * GMPC_MW, mstride, wbits);
+      if constexpr (LS) rw_hidden_epilogue(d, nnA, KH, hout, mb + (hl + 1) * GMPC_MW, mstride, wbits);
+      else rw_hidden_epilogue_counted(d, nnA, KH, hout, rsM, moff, msoff + (hl + 1) * GMPC_MW * 4);
       __syncthreads();
       TS_(3 + hl)
       float4* tmp = hin; hin = hout; hout = tmp;
@@ -361,22 +437,50 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
       if (lane < 32) part[wave * 32 + lane] = make_float4(d[0], d[1], d[2], d[3]);
     }
     __syncthreads();
-    if (tid < 4 * n) {
-      const int no = tid >> 2, c = tid & 3;
-      float sum = pf[no * 4 + c];
+    if constexpr (LS) {
+      if (tid < 4 * n) {
+        const int no = tid >> 2, c = tid & 3;
+        float sum = pf[no * 4 + c];
 #pragma unroll
-      for (int w = 1; w < GMPC_RW_THREADS / 64; ++w) sum += pf[(w * 32 + no) * 4 + c];
-      const float v = (sum + rbl) + xf[no * 4 + c];
-      xf[no * 4 + c] = v;
-      if ((wbits >> c) & 1u) {
-        float* Xo = LS ? a.Xc : a.X;
-        Xo[((LS ? CI(c) : (size_t)BI(c)) * (T + 1) + t + 1) * n + no] = v;
+        for (int w = 1; w < GMPC_RW_THREADS / 64; ++w) sum += pf[(w * 32 + no) * 4 + c];
+        const float v = (sum + rbl) + xf[no * 4 + c];
+        xf[no * 4 + c] = v;
+        if ((wbits >> c) & 1u) a.Xc[(CI(c) * (T + 1) + t + 1) * n + no] = v;
       }
+      // the controls of step t + 1 read x_{t+1}
+      __syncthreads();
+    } else {
+      // the next step's layer-0 operand, in every wave (see above).  `part` is rewritten three barriers from here.
+      // The control loaded one step ahead is taken before the X store goes out and reloaded right here, so the wait
+      // in front of its use counts the stores behind it instead of draining them; past the horizon's end the reload
+      // reads the last step again.
+      const int tn = min(t + 2, T - 1);
+      float v[NR0];
+#pragma unroll
+      for (int r = 0; r < NR0; ++r) {
+        const int e = 64 * r + lane;                     // (row 16 r + lane / 4) * 4 + slot
+        float sum = pf[e];
+#pragma unroll
+        for (int w = 1; w < GMPC_RW_THREADS / 64; ++w) sum += pf[w * 128 + e];
+        v[r] = (sum + blr[r]) + ar0[r];
+        ar0[r] = isx[r] ? v[r] : pfu[r];
+      }
+#pragma unroll
+      for (int r = 0; r < NR0; ++r)
+        pfu[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsU, uoff[r], tn * m * 4, 0));
+#pragma unroll
+      for (int r = 0; r < NR0; ++r)
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), rsX, xoff[r], (t + 1) * n * 4, 0);
     }
-    // the line search's controls of step t + 1 read x_{t+1}; the plain rollout's do not, and its
-    // next barrier (after the controls) orders the writes above before layer 0 reads them
-    if (LS) __syncthreads();
     TS_(6)
+  }
+  if constexpr (!LS) {
+    // the final state for the terminal-cost network (the barrier of the stage-cost pass below orders it)
+    if (wave == 0) {
+#pragma unroll
+      for (int r = 0; r < NR0; ++r)
+        if (isx[r]) xf[64 * r + lane] = ar0[r];
+    }
   }
 #ifdef GMPC_TRAJ_STAMPS
   if (blockIdx.x == 0 && tid == 0)
@@ -461,6 +565,8 @@ __global__ __launch_bounds__(GMPC_RW_THREADS, 1) void k_traj_rw(TrajArgs a) {
 static int rw_width(const TrajArgs& a) {
   const int Lh = a.dyn.L - 1;
   if (Lh != 3 || a.n > 32 || a.m > 32 || a.n + a.m > 32) return 0;
+  // (the plain rollout addresses its workgroup's 4 trajectories of U, X and the mask words by 32-bit byte offsets)
+  if (a.T > (1 << 20)) return 0;
   const int H = a.dyn.dims[1];
   if (H != 200 && H != 128 && H != 64) return 0;
   for (int l = 1; l <= Lh; ++l)
