@@ -1,6 +1,7 @@
-// C-ABI entry points of the sampling solvers (DESIGN §20 - §24, §26): the cross-entropy method, MPPI and the
+// C-ABI entry points of the sampling solvers (DESIGN §20 - §24, §26, §28): the cross-entropy method, MPPI and the
 // sample-efficient cross-entropy method on one sampled rollout (gmpc_launch_sampled_rollout), its precision, its
-// dynamics ensemble and the ensemble's mode.  What the three solves share is written once, ahead of them.
+// dynamics ensemble, the ensemble's mode and its disagreement penalty.  What the three solves share is written once,
+// ahead of them.
 #include "gmpc_ctx.h"
 
 // The shapes the sampled rollout covers, for the sampling solvers (`who`: the message's prefix)
@@ -63,6 +64,29 @@ extern "C" int gmpc_set_sampled_ensemble_mode(gmpc_ctx* c, const gmpc_ensemble_m
   return 0;
 }
 
+// The one-step disagreement penalty of a set ensemble's planes: checked whole, then stored; nothing is
+// launched
+extern "C" int gmpc_set_sampled_disagreement(gmpc_ctx* c, int kind, float penalty) {
+  if (!c) return fail(GMPC_EINVAL, "disagreement: ctx is null");
+  if (kind != GMPC_DIS_OFF && kind != GMPC_DIS_ONESTEP)
+    return fail(GMPC_EINVAL, "disagreement: kind = %d outside [0, 1]", kind);
+  if (!std::isfinite(penalty)) return fail(GMPC_EINVAL, "disagreement: penalty = %g is not finite", (double)penalty);
+  if (kind == GMPC_DIS_OFF && penalty != 0.f)
+    return fail(GMPC_EINVAL, "disagreement: penalty = %g goes with GMPC_DIS_ONESTEP only", (double)penalty);
+  TRY(gmpc_sampled_coverage(c, "disagreement"));
+  c->dis_kind = kind;
+  c->dis_penalty = penalty;
+  return 0;
+}
+
+// What a solve refuses of the context's ensemble settings before its first launch: the disagreement measures a member
+// against the nominal model along one rollout, which the per-step member draws of TS1 do not have
+static int check_disagreement(const gmpc_ctx* c) {
+  if (c->dis_kind != GMPC_DIS_OFF && c->ens_P > 0 && c->ens_mode.propagation == GMPC_ENS_TS1)
+    return fail(GMPC_EINVAL, "disagreement: not with TS1 propagation");
+  return 0;
+}
+
 // bf16 mode: the packed bf16 images of both MLPs, allocated by the first call and packed again behind
 // every gmpc_set_params (one launch on `s`, ahead of the solve's own); called behind gmpc_sampled_coverage
 int gmpc_sampled_prepare(gmpc_ctx* c, hipStream_t s) {
@@ -118,6 +142,16 @@ static int ensemble_args(gmpc_ctx* c, int B, int ldc, CemEnsemble& e) {
   e.aggregate = c->ens_mode.aggregate;
   e.risk = c->ens_mode.risk;
   e.invQ = 1.0f / (float)e.Q;
+  e.disagree = c->dis_kind == GMPC_DIS_ONESTEP;
+  e.penalty = c->dis_penalty;
+  memset(&e.nom, 0, sizeof(e.nom));
+  if (e.disagree) {
+    const MlpDesc& nd = bf16 ? c->dyn16 : c->dyn;
+    for (int l = 0; l < nd.L; ++l) {
+      e.nom.W[l] = nd.W[l];
+      e.nom.b[l] = nd.b[l];
+    }
+  }
   TRY(c->cw.part.grow(c, (size_t)e.Q * B * ldc));
   e.part = c->cw.part.p;
   return 0;
@@ -226,6 +260,7 @@ extern "C" int gmpc_cem_solve(gmpc_ctx* c, int B, const float* x0, const float* 
                               float* obj, float* costs, int* elites, float* samples, void* stream) {
   TRY(check_call(c, B));
   TRY(gmpc_sampled_coverage(c, "cem"));
+  TRY(check_disagreement(c));
   if (!o) return fail(GMPC_EINVAL, "cem: opts is null");
   if (!x0 || !goal || !mean_io || !std_io) return fail(GMPC_EINVAL, "cem: x0, goal, mean_io and std_io must not be null");
   TRY(check_counts("cem", o->num_samples, &o->num_elites));
@@ -274,6 +309,7 @@ extern "C" int gmpc_mppi_solve(gmpc_ctx* c, int B, const float* x0, const float*
                                float* costs_trace, void* stream) {
   TRY(check_call(c, B));
   TRY(gmpc_sampled_coverage(c, "mppi"));
+  TRY(check_disagreement(c));
   TRY(gmpc_mppi_check_opts(o));
   if (!x0 || !goal || !mean_io || !std) return fail(GMPC_EINVAL, "mppi: x0, goal, mean_io and std must not be null");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -364,6 +400,7 @@ extern "C" int gmpc_icem_solve(gmpc_ctx* c, int B, const float* x0, const float*
   TRY(check_call(c, B));
   const gmpc_shape& sh = c->sh;
   TRY(gmpc_sampled_coverage(c, "icem"));
+  TRY(check_disagreement(c));
   TRY(icem_check_opts(o));
   if (!x0 || !goal || !mean_io || !std_io)
     return fail(GMPC_EINVAL, "icem: x0, goal, mean_io and std_io must not be null");

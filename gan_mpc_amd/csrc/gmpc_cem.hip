@@ -7,10 +7,12 @@
 //   k_sampled_rollout<CemDrawn, BF16, Ens>  (gmpc_cem_rollout.h) one 256-thread workgroup per 32
 //                   samples of one problem, the whole horizon: the states stay in registers (the accumulator layout of
 //                   dg_gemm), the layer inputs in LDS, every dynamics / cost layer on the matrix cores (dg_gemm,
-//                   gmpc_dg_gemm.h), weights streamed from L2.  This file instantiates its six forms over CEM's rows:
-//                   fp32 or bf16 operands (gmpc_set_sampled_precision, section 23); one model, every member of a
-//                   dynamics ensemble (gmpc_set_sampled_ensemble, section 24) or particles that draw their member
-//                   per step (gmpc_set_sampled_ensemble_mode, section 26).  MPPI launches the same six.
+//                   gmpc_dg_gemm.h), weights streamed from L2.  This file instantiates its eight forms over CEM's
+//                   rows: fp32 or bf16 operands (gmpc_set_sampled_precision, section 23); one model, every member of
+//                   a dynamics ensemble (gmpc_set_sampled_ensemble, section 24), particles that draw their member
+//                   per step (gmpc_set_sampled_ensemble_mode, section 26) or the nominal model with a member's
+//                   one-step disagreement beside it (gmpc_set_sampled_disagreement, section 28).  MPPI launches the
+//                   same eight.
 //   k_ens_reduce    one thread per (problem, row): the planes' costs summed in plane order, times 1 / Q, into the
 //                   cost buffer the update kernels read (shared with gmpc_icem.hip)
 //   k_ens_reduce_risk  the same thread for the other two aggregates of section 26: mean plus a multiple of the
@@ -54,6 +56,8 @@ template __global__ void k_sampled_rollout<CemDrawn, false, CemMember>(CemRollAr
 template __global__ void k_sampled_rollout<CemDrawn, true, CemMember>(CemRollArgs, CemMember);
 template __global__ void k_sampled_rollout<CemDrawn, false, CemParticle>(CemRollArgs, CemParticle);
 template __global__ void k_sampled_rollout<CemDrawn, true, CemParticle>(CemRollArgs, CemParticle);
+template __global__ void k_sampled_rollout<CemDrawn, false, CemDisagree>(CemRollArgs, CemDisagree);
+template __global__ void k_sampled_rollout<CemDrawn, true, CemDisagree>(CemRollArgs, CemDisagree);
 
 // The ensemble's cost of a row under GMPC_ENS_MEAN: the planes' costs part [P][B][ldc] (P: the planes, members or
 // particles) summed in ascending plane order, times invP, into costs [B][ldc]; one thread per (problem, row), rows

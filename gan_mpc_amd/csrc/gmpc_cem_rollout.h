@@ -87,12 +87,14 @@ __device__ __forceinline__ void cem_store_tiles16(float* Ab, __bf16* Hb, const D
 //   costs(c)                  the [B][ldc] plane the rows' costs are written to
 //   records()                 whether this workgroup writes the debug copy of the controls
 // CemOneModel: the arguments' own network and cost buffer (every kernel without an ensemble).  It and CemMember ignore
-// the step; CemParticle draws its member in step().
+// the step; CemParticle draws its member in step().  CemDisagree is
+// CemMember with a second, nominal network: its steps are cem_disagree_step's.
 // BF16: the layer inputs are rounded to bf16 into Hb, the [32][GMPC_DG_LDH] block behind Ab,
 // the layers run on dg_gemm_bf16, and dyn.W[l] / cost.W[l] point at the layers' packed bf16 images (dg_kp, dg_np);
 // Ab keeps the fp32 [x_t; u_t] and the last cost layer's output, which the cost terms read as before.  Without BF16
 // Hb is not used.
 struct CemOneModel {
+  static constexpr bool disagree = false;
   __device__ __forceinline__ uint32_t step(int) const { return 0; }
   __device__ __forceinline__ const float* W(const float* w, uint32_t) const { return w; }
   __device__ __forceinline__ const float* b(const float* v, uint32_t) const { return v; }
@@ -104,6 +106,7 @@ struct CemOneModel {
 // floats behind it (fp32 mode: both the members' parameter count; bf16 mode: W[l] are bf16 images, wstride half their
 // elements, the biases stay in the fp32 members), and its costs go to plane p of part [P][B][ldc].
 struct CemMember {
+  static constexpr bool disagree = false;
   size_t wstride, bstride, plane;
   float* part;
   __device__ __forceinline__ uint32_t step(int) const { return 0; }
@@ -121,6 +124,7 @@ struct CemMember {
 // evaluated by step(), once per step (W and b of the step's layers take its result), and read back as a scalar, so the
 // layers' pointers stay in scalar registers as CemMember's do.  Its costs go to plane `particle` of part [Q][B][ldc].
 struct CemParticle {
+  static constexpr bool disagree = false;
   size_t wstride, bstride, plane;
   float* part;
   uint32_t P, key0, key1, it;
@@ -134,6 +138,110 @@ struct CemParticle {
   __device__ __forceinline__ float* costs(float*) const { return part + blockIdx.y * plane; }
   __device__ __forceinline__ bool records() const { return blockIdx.y == 0; }
 };
+
+// The one-step disagreement of member blockIdx.y with the nominal model: CemMember's strides and
+// planes for the member, `nom` for the nominal layers -- the context's bound dynamics (bf16 mode: W[l] at their packed
+// images), which the rows are rolled out under.  The plane's cost is the nominal cost plus penalty times the summed
+// squared deviation of the member's one-step output along the nominal rollout.
+struct CemDisagree {
+  static constexpr bool disagree = true;
+  size_t wstride, bstride, plane;
+  float* part;
+  CemNominal nom;
+  float penalty;
+  __device__ __forceinline__ uint32_t step(int) const { return 0; }
+  __device__ __forceinline__ const float* W(const float* w, uint32_t) const { return w + blockIdx.y * wstride; }
+  __device__ __forceinline__ const float* b(const float* v, uint32_t) const { return v + blockIdx.y * bstride; }
+  __device__ __forceinline__ const CemNominal& nominal() const { return nom; }
+  __device__ __forceinline__ float* costs(float*) const { return part + blockIdx.y * plane; }
+  __device__ __forceinline__ bool records() const { return blockIdx.y == 0; }
+};
+
+// J + penalty D as two IEEE fp32 operations (the product rounded before it is added), so NumPy restates a plane's cost
+// from J and D bit for bit
+__device__ __forceinline__ float cem_penalised(float J, float penalty, float D) {
+#pragma clang fp contract(off)
+  const float pd = penalty * D;
+  return J + pd;
+}
+
+// One step of a disagreement rollout, the one copy of its arithmetic (k_sampled_rollout under CemDisagree and
+// k_ens_disagreement call it).  On entry the operand block holds the layer-0 input [x_t; u_t] of the 32 rows (bf16
+// mode: Hb), synchronised; xs is x_t.  Both networks' layer-0 products are taken from that input before anything
+// overwrites it, so it is neither saved nor formed twice; then the member's remaining layers run (pass 0), its output
+// o^p = acc + bias staying in registers, then the nominal's (pass 1: the same loop body, one copy of the products in
+// the code), o^0 formed by the same operations on the same kind of operands -- a member equal to the nominal layers
+// gives o^p - o^0 == 0 exactly.  The difference goes through Ab (columns 0 .. n-1)
+// to the row sums of the stage cost's pattern: d = sum_j (o^p_j - o^0_j)^2, fmaf over the columns j = rc, rc + 8, ..,
+// then the butterfly over the row's 8 lanes.  xs advances by the nominal output alone, with the operations of the
+// plain rollout.  Returns d of row rrow (the same in its 8 lanes); the operand block is free on return.
+template <bool BF16, typename Ens>
+__device__ __forceinline__ float cem_disagree_step(const MlpDesc& dyn, const Ens& ens, uint32_t mem, int n, float* Ab,
+                                                   __bf16* Hb, DgTiles& xs, int wave, int lane, int rrow, int rc) {
+  const int l16 = lane & 15, L = dyn.L;
+  const CemNominal& nom = ens.nominal();
+  auto prod = [&](int l, const float* W, DgTiles& out) {
+    const int K = dyn.dims[l], Nl = dyn.dims[l + 1];
+    if constexpr (BF16)
+      dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(W), wave, lane, out);
+    else
+      dg_gemm(Ab, K, Nl, W, wave, lane, out);
+  };
+  auto hidden = [&](int l, const DgTiles& v, const float* bias) {
+    const int Nl = dyn.dims[l + 1];
+    auto act = [bias](float x, int j) { return fmaxf(x + bias[j], 0.f); };
+    if constexpr (BF16)
+      cem_store_tiles16<false, true>(Ab, Hb, v, Nl, dg_kp(Nl), wave, lane, act);
+    else
+      cem_store_tiles(Ab, v, Nl, wave, lane, act);
+  };
+  // acc: the running layer's product.  om: first the nominal network's layer-0 product, taken beside the member's
+  // while the input stands; at the end of the member's pass the two change places -- acc the nominal product, om = o^p
+  DgTiles acc, om;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass)
+    for (int l = 0; l < L; ++l) {
+      const float* bias = pass ? nom.b[l] : ens.b(dyn.b[l], mem);
+      if (pass == 0 || l > 0) {
+        prod(l, pass ? nom.W[l] : ens.W(dyn.W[l], mem), acc);
+        if (pass == 0 && l == 0) prod(0, nom.W[0], om);
+        __syncthreads();   // every wave has read its operand rows (at layer 0: and the stage cost its row)
+      }
+      if (l < L - 1) {
+        hidden(l, acc, bias);
+        __syncthreads();
+        continue;
+      }
+#pragma unroll
+      for (int ci = 0; ci < 4; ++ci) {
+        const int j = (wave + 4 * ci) * 16 + l16;
+        const float bj = j < n ? bias[j] : 0.f;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const float op = acc.p[ci][rr] + bj, oq = acc.q[ci][rr] + bj;     // this pass's output
+          if (pass == 0) {
+            acc.p[ci][rr] = om.p[ci][rr];
+            acc.q[ci][rr] = om.q[ci][rr];
+            om.p[ci][rr] = op;
+            om.q[ci][rr] = oq;
+          } else if (j < n) {
+            om.p[ci][rr] = om.p[ci][rr] - op;
+            om.q[ci][rr] = om.q[ci][rr] - oq;
+            xs.p[ci][rr] = op + xs.p[ci][rr];
+            xs.q[ci][rr] = oq + xs.q[ci][rr];
+          }
+        }
+      }
+    }
+  cem_store_tiles(Ab, om, n, wave, lane, [](float v, int) { return v; });
+  __syncthreads();
+  const float* row = Ab + rrow * GMPC_DG_LDA;
+  float sd = 0.f;
+  for (int j = rc; j < n; j += 8) sd = fmaf(row[j], row[j], sd);
+  sd = cem_row8_sum(sd);
+  __syncthreads();   // the rows are read: the next step's input may be stored
+  return sd;
+}
 
 template <bool BF16, typename Src, typename Ens = CemOneModel>
 __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows, int ldc, float* Ab, __bf16* Hb,
@@ -158,6 +266,7 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
   if (a.X)
     for (int j = tid; j < n; j += GMPC_DG_THREADS) a.X[(size_t)b * (T + 1) * n + j] = a.x0[(size_t)b * n + j];
   float csum = 0.f;   // the cost of row rrow so far (the same in its 8 lanes)
+  [[maybe_unused]] float dsum = 0.f;   // CemDisagree: the disagreement D of row rrow so far
   DgTiles acc;
   for (int t = 0; t < T; ++t) {
     const uint32_t mem = ens.step(t);     // the member this step runs under (CemParticle; 0 and unused otherwise)
@@ -199,8 +308,10 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
       sx = cem_row8_sum(sx);
       csum += w0 * (sqrtf(su + al * al) - al) + w1 * (sqrtf(sx + al * al) - al);
     }
-    // ---- x_{t+1} = x_t + MLP([x_t; u_t])
-    for (int l = 0; l < a.dyn.L; ++l) {
+    // ---- x_{t+1} = x_t + MLP([x_t; u_t]); CemDisagree: the member's pass beside the nominal one, D += d_t
+    if constexpr (Ens::disagree)
+      dsum += cem_disagree_step<BF16>(a.dyn, ens, mem, n, Ab, Hb, xs, wave, lane, rrow, rc);
+    else for (int l = 0; l < a.dyn.L; ++l) {
       const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
       if constexpr (BF16)
         dg_gemm_bf16(Hb, dg_kp(K), dg_np(Nl), reinterpret_cast<const __bf16*>(ens.W(a.dyn.W[l], mem)), wave, lane,
@@ -268,13 +379,14 @@ __device__ __forceinline__ void cem_rollout_body(const CemRollArgs& a, int rows,
     for (int j = rc; j < fout; j += 8) sy = fmaf(row[j], row[j], sy);
     sy = cem_row8_sum(sy);
     csum += w2 * sy;
+    if constexpr (Ens::disagree) csum = cem_penalised(csum, ens.penalty, dsum);
     if (rc == 0 && s0 + rrow < rows) ens.costs(a.costs)[(size_t)b * ldc + s0 + rrow] = csum;
   }
 }
 
 // The one kernel of the sampled rollout: the operand block or blocks at the start of the dynamic LDS, the source's own
-// LDS behind them, then the body.  Twelve instantiations, {CemDrawn, IcemDrawn} x {fp32, bf16} x {CemOneModel,
-// CemMember, CemParticle}, explicit in gmpc_cem.hip and gmpc_icem.hip.
+// LDS behind them, then the body.  Sixteen instantiations, {CemDrawn, IcemDrawn} x {fp32, bf16} x {CemOneModel,
+// CemMember, CemParticle, CemDisagree}, explicit in gmpc_cem.hip and gmpc_icem.hip.
 template <typename Src, bool BF16, typename Ens>
 __global__ __launch_bounds__(GMPC_DG_THREADS) void k_sampled_rollout(typename Src::Args a, Ens e) {
   extern __shared__ __attribute__((aligned(16))) char smem_roll[];
@@ -297,7 +409,10 @@ static void sampled_launch_form(const typename Src::Args& a, size_t lds, const C
                        CemOneModel());
     return;
   }
-  if (ens->ts1) {
+  if (ens->disagree) {
+    const CemDisagree dg{ens->wstride, ens->bstride, (size_t)c.B * ldc, ens->part, ens->nom, ens->penalty};
+    hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemDisagree>), grid, dim3(GMPC_DG_THREADS), lds, s, a, dg);
+  } else if (ens->ts1) {
     const CemParticle pt{ens->wstride, ens->bstride, (size_t)c.B * ldc, ens->part, (uint32_t)ens->P, c.rng.key0,
                          c.rng.key1, c.rng.it};
     hipLaunchKernelGGL((k_sampled_rollout<Src, BF16, CemParticle>), grid, dim3(GMPC_DG_THREADS), lds, s, a, pt);
@@ -325,6 +440,7 @@ static int sampled_launch_rollout(const typename Src::Args& a0, bool bf16, const
   if (c.mean_row && (bf16 || ens)) return 1;     // (the returned sequence's rollout is the fp32 kernel's)
   if (ens && (c.X || ens->P < 1 || ens->P > GMPC_MAX_ENSEMBLE || !ens->part)) return 1;
   if (ens && (ens->Q < 1 || ens->Q > GMPC_MAX_ENSEMBLE || (!ens->ts1 && ens->Q != ens->P))) return 1;
+  if (ens && ens->disagree && ens->ts1) return 1;
   const size_t blocks = bf16 ? GMPC_CEM_LDS16 : GMPC_CEM_LDS32;
   size_t extra = 0;
   if (Src::plan(a, blocks, &extra)) return 1;

@@ -132,6 +132,10 @@ struct gmpc_ctx {
   // gmpc_set_sampled_ensemble_mode: how the planes of a set ensemble are propagated and aggregated; read
   // by every launch over sampled rows, inert while ens_P == 0
   gmpc_ensemble_mode ens_mode{GMPC_ENS_MEAN, 0.f, GMPC_ENS_FIXED, 0};
+  // gmpc_set_sampled_disagreement: the one-step disagreement penalty of the planes' costs; read by every
+  // launch over sampled rows, inert while ens_P == 0, kept by gmpc_set_params and gmpc_set_sampled_ensemble
+  int dis_kind = GMPC_DIS_OFF;
+  float dis_penalty = 0.f;
   // shared scratch
   float *wpart, *scratch;
   long wpart_floats;

@@ -10,6 +10,8 @@
 //                   per step, and the horizon may be cut short (S <= T steps, then without costs).
 //   k_ens_moments   one thread per (problem, step, state): mean and population variance over the members' planes,
 //                   both sums sequential in ascending member order.
+//   k_ens_disagreement  (gmpc_ensemble_disagreement) k_ens_rollout's grid, the rows rolled out
+//                   under the bound dynamics and member p's one-step output measured against theirs at every step.
 #include "gmpc_cem_rollout.h"
 
 __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) {
@@ -137,6 +139,72 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
   }
 }
 
+// A plan's one-step disagreement under every member (gmpc_ensemble_disagreement): k_ens_rollout's
+// tiles of 32 problems by members, the steps cem_disagree_step's -- the arithmetic of the sampled rollout under
+// CemDisagree, so d and D are bitwise what a disagreement solve adds to a row with these controls.  The rows run
+// under the nominal layers; member blockIdx.y only measures.  X (the nominal rollout) is written by grid row 0.
+struct EnsDisMember {
+  size_t mstride;
+  const CemNominal& nom;     // (the kernel's argument, read where it lies)
+  __device__ __forceinline__ const float* W(const float* w, uint32_t) const { return w + blockIdx.y * mstride; }
+  __device__ __forceinline__ const float* b(const float* v, uint32_t) const { return v + blockIdx.y * mstride; }
+  __device__ __forceinline__ const CemNominal& nominal() const { return nom; }
+};
+
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_disagreement(EnsDisArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ab[GMPC_CEM_ROWS * GMPC_DG_LDA];   // the layer inputs of the 32 rows
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
+  const int n = a.n, m = a.m, S = a.S, B = a.B;
+  const int b0 = blockIdx.x * GMPC_CEM_ROWS;     // row i of the tile is problem b0 + i
+  const size_t p = blockIdx.y;                   // the member
+  const int rrow = tid >> 3, rc = tid & 7;
+  // Rows past B (the last tile): every read goes to problem B - 1, a valid one, and nothing is written for them.
+  const int last = B - 1;
+  const bool rlive = b0 + rrow < B;
+  const EnsDisMember ens{a.mstride, a.nom};
+  DgTiles xs;
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci) {
+    const int j = (wave + 4 * ci) * 16 + l16;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int bp = min(b0 + 4 * kq + rr, last), bq = min(b0 + 16 + 4 * kq + rr, last);
+      xs.p[ci][rr] = j < n ? a.x0[(size_t)bp * n + j] : 0.f;
+      xs.q[ci][rr] = j < n ? a.x0[(size_t)bq * n + j] : 0.f;
+    }
+  }
+  float* Xp = a.X && p == 0 ? a.X : nullptr;
+  float* dp = a.d ? a.d + p * B * (size_t)S : nullptr;
+  float dsum = 0.f;   // D of row rrow so far (the same in its 8 lanes)
+  for (int t = 0; t < S; ++t) {
+    // ---- layer 0 input [x_t; u_t]
+    cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+    for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
+      const int i = e / m, j = e - i * m;
+      Ab[i * GMPC_DG_LDA + n + j] = a.U[((size_t)min(b0 + i, last) * S + t) * m + j];
+    }
+    __syncthreads();
+    // ---- x_t of every live row, from the operand block (read before the step's first barrier releases the block)
+    if (Xp)
+      for (int e = tid; e < GMPC_CEM_ROWS * n; e += GMPC_DG_THREADS) {
+        const int i = e / n, j = e - i * n;
+        if (b0 + i < B) Xp[((size_t)(b0 + i) * (S + 1) + t) * n + j] = Ab[i * GMPC_DG_LDA + j];
+      }
+    const float dt = cem_disagree_step<false>(a.dyn, ens, 0u, n, Ab, nullptr, xs, wave, lane, rrow, rc);
+    dsum += dt;
+    if (dp && rc == 0 && rlive) dp[(size_t)(b0 + rrow) * S + t] = dt;
+  }
+  if (a.D && rc == 0 && rlive) a.D[p * B + b0 + rrow] = dsum;
+  if (Xp) {
+    cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
+    __syncthreads();
+    for (int e = tid; e < GMPC_CEM_ROWS * n; e += GMPC_DG_THREADS) {
+      const int i = e / n, j = e - i * n;
+      if (b0 + i < B) Xp[((size_t)(b0 + i) * (S + 1) + S) * n + j] = Ab[i * GMPC_DG_LDA + j];
+    }
+  }
+}
+
 // Mean and population variance over the planes X [P][count] of one element each: sum_p x_p, then / P; sum_p (x_p -
 // mean)^2, then / P -- every operation one IEEE fp32 operation in ascending p (no contraction), so the result is a
 // function of the planes alone and NumPy restates it bit for bit.  mean / var: either may be null.
@@ -171,6 +239,16 @@ int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s) {
   if (a.goal && a.S != a.T) return 1;
   const dim3 grid((a.B + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS, P);
   hipLaunchKernelGGL(k_ens_rollout, grid, dim3(GMPC_DG_THREADS), 0, s, a);
+  return 0;
+}
+
+int gmpc_launch_ens_disagreement(const EnsDisArgs& a, int P, hipStream_t s) {
+  for (int l = 0; l <= a.dyn.L; ++l)
+    if (a.dyn.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
+  if (a.n + a.m > GMPC_SAMPLED_MAX_WIDTH || a.B < 1 || a.S < 1 || P < 1 || P > GMPC_MAX_ENSEMBLE) return 1;
+  if (!a.X && !a.d && !a.D) return 1;
+  const dim3 grid((a.B + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS, P);
+  hipLaunchKernelGGL(k_ens_disagreement, grid, dim3(GMPC_DG_THREADS), 0, s, a);
   return 0;
 }
 

@@ -7,9 +7,10 @@
 // fresh control is a pure function of (seed, iteration, problem, sample, step, control) -- icem_control, the one
 // place a pool row's control is formed -- and the update regenerates the elites' controls.
 //
-//   k_sampled_rollout<IcemDrawn, BF16, Ens>  (gmpc_cem_rollout.h) the rollout kernel over the pool's rows, six forms
-//                   as in gmpc_cem.hip: fp32 or bf16 operands; one model, every member of a dynamics ensemble or
-//                   particles that draw their member per step.  The
+//   k_sampled_rollout<IcemDrawn, BF16, Ens>  (gmpc_cem_rollout.h) the rollout kernel over the pool's rows, eight forms
+//                   as in gmpc_cem.hip: fp32 or bf16 operands; one model, every member of a dynamics ensemble,
+//                   particles that draw their member per step, or the nominal model with a member's one-step
+//                   disagreement beside it.  The
 //                   coloured sum of a control needs the T normals of its (row, control): formed once per tile in LDS
 //                   behind the operand blocks where 32 m T floats fit there (zlds), regenerated per element otherwise
 //                   -- the same sum in the same order either way.
@@ -127,6 +128,8 @@ template __global__ void k_sampled_rollout<IcemDrawn, false, CemMember>(IcemRoll
 template __global__ void k_sampled_rollout<IcemDrawn, true, CemMember>(IcemRollArgs, CemMember);
 template __global__ void k_sampled_rollout<IcemDrawn, false, CemParticle>(IcemRollArgs, CemParticle);
 template __global__ void k_sampled_rollout<IcemDrawn, true, CemParticle>(IcemRollArgs, CemParticle);
+template __global__ void k_sampled_rollout<IcemDrawn, false, CemDisagree>(IcemRollArgs, CemDisagree);
+template __global__ void k_sampled_rollout<IcemDrawn, true, CemDisagree>(IcemRollArgs, CemDisagree);
 
 // ---- the update -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GMPC_DG_THREADS) void k_icem_update(IcemUpdArgs a, int P) {

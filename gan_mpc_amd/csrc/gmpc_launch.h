@@ -288,13 +288,20 @@ int gmpc_launch_dyn_rows(int B, int T, int n, int m, const MlpDesc& dyn, const f
 // plane q member q as above; with ts1 the grid row q is a particle that draws its member anew at every step
 // (CemParticle of gmpc_cem_rollout.h) and Q is the number of particles -- and `aggregate` (GMPC_ENS_MEAN / MEAN_STD /
 // MAX) is the rule that takes part [Q][B][ldc] to costs; invQ = 1.0f / (float)Q, risk the multiple of the spread.
+// The one-step disagreement (gmpc_set_sampled_disagreement): with `disagree` (never with ts1) the rows are
+// rolled out under the nominal layers `nom` (bf16: W[l] at their packed images) and plane q's cost is the nominal cost
+// plus penalty times member q's summed squared one-step deviation from them (CemDisagree of gmpc_cem_rollout.h).
 #define GMPC_MAX_ENSEMBLE 16
+struct CemNominal { const float *W[GMPC_MAX_LAYERS], *b[GMPC_MAX_LAYERS]; };
 struct CemEnsemble {
   int P;
   size_t wstride, bstride;
   float* part;
   int Q, ts1, aggregate;
   float invQ, risk;
+  int disagree;
+  float penalty;
+  CemNominal nom;
 };
 
 // gmpc_cem.hip: the cross-entropy method's two kernels --------------------------------------------------
@@ -342,6 +349,20 @@ struct EnsRollArgs {
 // Non-zero (nothing launched) outside the sampled rollout's coverage, 1 <= S <= T, 1 <= P <= GMPC_MAX_ENSEMBLE and the
 // rules above
 int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s);
+// A plan's one-step disagreement: the rows of gmpc_launch_ens_rollout rolled S steps under the nominal
+// layers `nom` (fp32), member p (dyn: member 0, p mstride floats behind it) measured against them at every visited
+// (x_t, u_t).  X [B][S+1][n] the nominal states, d [P][B][S] the squared deviations of the one-step outputs, D [P][B]
+// their sums in step order; each may be null, not all of them.
+struct EnsDisArgs {
+  int B, S, n, m;
+  MlpDesc dyn;
+  size_t mstride;
+  CemNominal nom;
+  const float *x0, *U;
+  float *X, *d, *D;
+};
+// Non-zero (nothing launched) outside the sampled rollout's coverage, S >= 1 and 1 <= P <= GMPC_MAX_ENSEMBLE
+int gmpc_launch_ens_disagreement(const EnsDisArgs& a, int P, hipStream_t s);
 // mean / var [count] (either may be null) over the planes X [P][count]: the sum in member order / P, the squared
 // deviations' sum in member order / P
 void gmpc_launch_ens_moments(const float* X, int P, size_t count, float* mean, float* var, hipStream_t s);

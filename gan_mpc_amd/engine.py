@@ -219,6 +219,7 @@ class Engine:
         self._bound = None
         self._ensemble = None          # set_sampled_ensemble's members, kept alive
         self._ensemble_mode = None     # set_sampled_ensemble_mode's keywords; None: never set (the default mode)
+        self._disagreement = None      # set_sampled_disagreement's penalty; None: off
         self.solve_count = 0      # solves issued on this ctx (policy.differentiable: a backward checks it is current)
 
     def close(self):
@@ -446,6 +447,31 @@ class Engine:
                                  count)
         _lib.check(self.lib.gmpc_set_sampled_ensemble_mode(self.ctx, C.byref(mode)))
         self._ensemble_mode = dict(aggregate=aggregate, risk=risk32, propagation=propagation, particles=particles)
+
+    DISAGREEMENT_KINDS = {"off": 0, "onestep": 1}     # GMPC_DIS_OFF / GMPC_DIS_ONESTEP
+
+    def set_sampled_disagreement(self, penalty):
+        """A penalty on the members' one-step disagreement with the bound (nominal) dynamics along every sampled row
+        of cem_solve / mppi_solve / icem_solve (gmpc_set_sampled_disagreement).  penalty: None
+        -- off (the default) --, or a finite number: the rows are rolled out under the nominal model, and plane p's
+        cost is the nominal cost + penalty * sum_t |MLP_p([x_t; u_t]) - MLP_0([x_t; u_t])|^2; the planes then go
+        through set_sampled_ensemble_mode's aggregate.  penalty > 0 is pessimism, < 0 exploration, 0 allowed.
+        Independent of the members and the mode: set_sampled_ensemble and set_params keep it, and it does nothing while
+        no ensemble is set.  Propagation "ts1" is refused by the solves while it is on.  Every refusal is a
+        GmpcError("disagreement: ...") raised here, before the library is called.  No device work."""
+        who = "disagreement"
+        if penalty is None:
+            _lib.check(self.lib.gmpc_set_sampled_disagreement(self.ctx, self.DISAGREEMENT_KINDS["off"], 0.0))
+            self._disagreement = None
+            return
+        if isinstance(penalty, bool) or not isinstance(penalty, (int, float, np.integer, np.floating)):
+            raise _lib.GmpcError(f"{who}: penalty must be None or a number, got {penalty!r}")
+        with np.errstate(over="ignore"):
+            pen32 = float(np.float32(penalty))
+        if not np.isfinite(pen32):
+            raise _lib.GmpcError(f"{who}: penalty = {penalty!r} is not finite in float32")
+        _lib.check(self.lib.gmpc_set_sampled_disagreement(self.ctx, self.DISAGREEMENT_KINDS["onestep"], pen32))
+        self._disagreement = pen32
 
     CEM_WANT = ("costs", "elites", "samples")
 
@@ -857,6 +883,45 @@ class Engine:
         _lib.check(self.lib.gmpc_ensemble_rollout(
             self.ctx, B, S, P, _ptr(dev), _ptr(x0), _ptr(U), _ptr(goal), _ptr(out.get("X")), _ptr(out.get("costs")),
             _ptr(out.get("obj")), _ptr(out.get("mean")), _ptr(out.get("var")), self._stream()))
+        return out
+
+    ENSEMBLE_DISAGREEMENT_WANT = ("X", "d", "D")
+
+    def ensemble_disagreement(self, members, x0, U, want=("d", "D")):
+        """The one-step disagreement of every member with the bound (nominal) dynamics along a plan, in one launch
+        (gmpc_ensemble_disagreement).  members, x0 (B, n), U (B, S, m) with 1 <= S <= T as for
+        ensemble_rollout.  -> a dict of the `want`ed tensors: "X" (B, S + 1, n) the nominal rollout, "d" (P, B, S) the
+        squared deviation of member p's one-step output from the nominal one at every visited (x_t, u_t), "D" (P, B)
+        its sum over the steps.  fp32; the arithmetic is that of the solves under set_sampled_disagreement.
+        Stateless: the bound dynamics are read; the set ensemble, its mode, the disagreement setting, the sampled
+        precision and a held solution stay as they are.  Every refusal is a GmpcError("ensemble disagreement: ...");
+        nothing is synchronised."""
+        who = "ensemble disagreement"
+        P = self._check_ensemble_members(who, members)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - set(self.ENSEMBLE_DISAGREEMENT_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"{who}: want has unknown entries {sorted(unknown, key=str)}; known: "
+                                 f"{self.ENSEMBLE_DISAGREEMENT_WANT}")
+        if not want:
+            raise _lib.GmpcError(f"{who}: want is empty; known: {self.ENSEMBLE_DISAGREEMENT_WANT}")
+        n, m = self.n, self.m
+        for name, t in (("x0", x0), ("U", U)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32:
+                raise _lib.GmpcError(f"{who}: {name} must be a float32 tensor, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)}")
+        if x0.dim() != 2 or x0.shape[1] != n:
+            raise _lib.GmpcError(f"{who}: x0 must be (B, {n}), got {tuple(x0.shape)}")
+        B = int(x0.shape[0])
+        if U.dim() != 3 or U.shape[0] != B or U.shape[2] != m:
+            raise _lib.GmpcError(f"{who}: U must be ({B}, S, {m}), got {tuple(U.shape)}")
+        S = int(U.shape[1])
+        shapes = dict(X=(B, S + 1, n), d=(P, B, S), D=(P, B))
+        out = {k: self.new(*shapes[k]) for k in self.ENSEMBLE_DISAGREEMENT_WANT if k in want}
+        dev = self.to_dev(members)
+        _lib.check(self.lib.gmpc_ensemble_disagreement(
+            self.ctx, B, S, P, _ptr(dev), _ptr(x0), _ptr(U), _ptr(out.get("X")), _ptr(out.get("d")),
+            _ptr(out.get("D")), self._stream()))
         return out
 
     def _check_ensemble_members(self, who, members):

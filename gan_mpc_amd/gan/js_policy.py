@@ -15,13 +15,15 @@ class JS_MPC(base.BaseMPC):
     def __init__(self, config, cost_model, dynamics_model, expert_model, critic_model,
                  loss_vmap=(0,), trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None,
                  bilevel_sign=1.0, solver="rounds", control_bounds=None, cem_kwargs=None, mppi_kwargs=None,
-                 icem_kwargs=None, sampled_precision=None, dynamics_ensemble=None, ensemble_mode=None):
+                 icem_kwargs=None, sampled_precision=None, dynamics_ensemble=None, ensemble_mode=None,
+                 ensemble_disagreement=None):
         self.critic_model = critic_model
         super().__init__(config, cost_model, dynamics_model, expert_model, loss_vmap,
                          trajax_ilqr_kwargs, device=device, bilevel_sign=bilevel_sign, solver=solver,
                          control_bounds=control_bounds, cem_kwargs=cem_kwargs, mppi_kwargs=mppi_kwargs,
                          icem_kwargs=icem_kwargs, sampled_precision=sampled_precision,
-                         dynamics_ensemble=dynamics_ensemble, ensemble_mode=ensemble_mode)
+                         dynamics_ensemble=dynamics_ensemble, ensemble_mode=ensemble_mode,
+                         ensemble_disagreement=ensemble_disagreement)
         self.critic_model = critic_model
 
     def init(self, mpc_weights, cost_args, dynamics_args, expert_args, critic_args):

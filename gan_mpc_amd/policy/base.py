@@ -18,12 +18,13 @@ class BaseMPC(eval_policy.EvalMPC):
     def __init__(self, config, cost_model, dynamics_model, expert_model, loss_vmap=(0,),
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, bilevel_sign=1.0, solver="rounds",
                  control_bounds=None, cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None,
-                 sampled_precision=None, dynamics_ensemble=None, ensemble_mode=None):
+                 sampled_precision=None, dynamics_ensemble=None, ensemble_mode=None, ensemble_disagreement=None):
         super().__init__(config=config, cost_model=cost_model, dynamics_model=dynamics_model,
                          expert_model=expert_model, trajax_ilqr_kwargs=trajax_ilqr_kwargs,
                          device=device, solver=solver, control_bounds=control_bounds, cem_kwargs=cem_kwargs,
                          mppi_kwargs=mppi_kwargs, icem_kwargs=icem_kwargs, sampled_precision=sampled_precision,
-                         dynamics_ensemble=dynamics_ensemble, ensemble_mode=ensemble_mode)
+                         dynamics_ensemble=dynamics_ensemble, ensemble_mode=ensemble_mode,
+                         ensemble_disagreement=ensemble_disagreement)
         self.loss_vmap = loss_vmap
         # +1 reproduces the reference as written; -1 is the implicit-function gradient
         self.bilevel_sign = float(bilevel_sign)
@@ -53,6 +54,22 @@ class BaseMPC(eval_policy.EvalMPC):
         eng = self.bind(self.to_device_params(params), xs[0])
         out = eng.ensemble_rollout(self._ensemble_dev, eng.to_dev(x), eng.to_dev(U), want=("X", "var"))
         return out["X"], out["var"].sum(-1)
+
+    def plan_disagreement(self, params, x, U):
+        """The one-step disagreement of the policy's dynamics ensemble with params["dynamics_params"] along a plan
+        (Engine.ensemble_disagreement): x (B, n) initial states, U (B, T, m) controls.  -> (d
+        (P, B, T), member p's squared one-step deviation from the nominal model at every step of the nominal rollout;
+        D (P, B), its sum over the steps -- what ensemble_disagreement=penalty adds to a row's cost, per unit of
+        penalty).  Forward only."""
+        if self.dynamics_ensemble is None:
+            raise ValueError("plan_disagreement needs a dynamics_ensemble (the constructor's, or "
+                             "set_dynamics_ensemble): none is set")
+        xs, Us = tuple(getattr(x, "shape", np.shape(x))), tuple(getattr(U, "shape", np.shape(U)))
+        if len(xs) != 2 or len(Us) != 3 or Us[0] != xs[0]:
+            raise ValueError(f"plan_disagreement: x must be (B, n) and U (B, T, m), got {xs} and {Us}")
+        eng = self.bind(self.to_device_params(params), xs[0])
+        out = eng.ensemble_disagreement(self._ensemble_dev, eng.to_dev(x), eng.to_dev(U), want=("d", "D"))
+        return out["d"], out["D"]
 
     def loss(self, xcseq, useq, params, *args):
         """The upper-level loss of ONE trajectory (reference policy/base.py:84-85): xcseq (T+1, n) -- xc, carry

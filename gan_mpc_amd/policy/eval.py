@@ -50,7 +50,7 @@ class EvalMPC:
     def __init__(self, config, cost_model, dynamics_model, expert_model,
                  trajax_ilqr_kwargs=TRAJAX_iLQR_KWARGS, device=None, solver="rounds", control_bounds=None,
                  cem_kwargs=None, mppi_kwargs=None, icem_kwargs=None, sampled_precision=None,
-                 dynamics_ensemble=None, ensemble_mode=None):
+                 dynamics_ensemble=None, ensemble_mode=None, ensemble_disagreement=None):
         """solver: "rounds" -- gmpc_ilqr_solve, the host enqueues the iterations (every shape); "fused" --
         gmpc_ilqr_solve_fused, the whole solve in one kernel launch (MLP dynamics, n <= 64, m <= 32, T <= 32: the
         short-horizon / batch-1 MPC action); "box" -- gmpc_ilqr_solve_box, the one-launch solve with the controls
@@ -77,7 +77,11 @@ class EvalMPC:
         particles) -- with a "cem" / "mppi" / "icem" solver, what the solver does with the ensemble: mean plus
         a multiple of the members' spread or the worst member instead of the mean, and particles that draw their member
         per step.  Set next to the ensemble wherever the policy binds its engine; without dynamics_ensemble it is
-        accepted and inert."""
+        accepted and inert.
+        ensemble_disagreement: None, or a finite number -- with a "cem" / "mppi" / "icem" solver and a
+        dynamics_ensemble, the penalty on the members' one-step disagreement with params["dynamics_params"] along every
+        sampled row (Engine.set_sampled_disagreement, DESIGN §28: positive is pessimism, negative exploration), set
+        next to ensemble_mode wherever the policy binds its engine.  Not with propagation "ts1"."""
         if solver not in self.SOLVERS:
             raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
         if (solver in ("box", "cem", "mppi", "icem")) != (control_bounds is not None):
@@ -109,6 +113,20 @@ class EvalMPC:
             raise ValueError(f"control_bounds must be a pair (lo, hi), got {control_bounds!r}")
         self.solver = solver
         self.ensemble_mode = self._checked_ensemble_mode(ensemble_mode)
+        if ensemble_disagreement is not None:
+            if solver not in ("cem", "mppi", "icem"):
+                raise ValueError('ensemble_disagreement and solver="cem" / "mppi" / "icem" go together: got '
+                                 f"solver={solver!r}")
+            if dynamics_ensemble is None:
+                raise ValueError("ensemble_disagreement needs a dynamics_ensemble: the penalty measures its members")
+            if (self.ensemble_mode or {}).get("propagation", "fixed") == "ts1":
+                raise ValueError('ensemble_disagreement does not go with ensemble_mode propagation "ts1"')
+            if isinstance(ensemble_disagreement, bool) or not isinstance(
+                    ensemble_disagreement, (int, float, np.integer, np.floating)) or not np.isfinite(
+                    ensemble_disagreement):
+                raise ValueError(f"ensemble_disagreement must be None or a finite number, got "
+                                 f"{ensemble_disagreement!r}")
+        self.ensemble_disagreement = None if ensemble_disagreement is None else float(ensemble_disagreement)
         self.control_bounds = None if control_bounds is None else tuple(control_bounds)
         self.config = config
         self.cost_model = cost_model
@@ -196,6 +214,8 @@ class EvalMPC:
             eng.set_sampled_ensemble(self._ensemble_dev)
         if self.ensemble_mode is not None:
             eng.set_sampled_ensemble_mode(**self.ensemble_mode)
+        if self.ensemble_disagreement is not None:
+            eng.set_sampled_disagreement(self.ensemble_disagreement)
         return eng
 
     ENSEMBLE_MODE_KEYS = ("aggregate", "risk", "propagation", "particles")
@@ -218,6 +238,8 @@ class EvalMPC:
         Engine.set_sampled_ensemble_mode's keywords; none: the default mode.  Set on the bound engine now and by every
         later bind."""
         mode = self._checked_ensemble_mode(kw)
+        if getattr(self, "ensemble_disagreement", None) is not None and (mode or {}).get("propagation") == "ts1":
+            raise ValueError('ensemble_mode propagation "ts1" does not go with ensemble_disagreement')
         if self._engine is not None:
             self._engine.set_sampled_ensemble_mode(**mode)      # the engine checks the values: a refused mode is not kept
         self.ensemble_mode = mode

@@ -470,6 +470,41 @@ int gmpc_ensemble_rollout(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_m
                           const float* U, const float* goal, float* X, float* costs, float* obj, float* x_mean,
                           float* x_var, void* stream);
 
+/* A penalty on the members' one-step disagreement with the nominal model along a sampled row: a
+ * property of the context, like the precision, the ensemble and its mode; off until set.  No stream, no device work.
+ * Independent of the ensemble and of gmpc_set_params: neither resets it, it may be set before an ensemble is, and it
+ * has no effect while none is set.  With GMPC_DIS_ONESTEP and an ensemble set, every launch over sampled rows rolls
+ * the rows out under the context's bound (nominal) dynamics, once per member p, and plane p's cost is
+ *   J_p = J + penalty * D_p,   D_p = sum_{t<T} sum_{j<n} (o^p_{t,j} - o^0_{t,j})^2,
+ * J the row's cost of a solve without an ensemble, o^0_t = MLP_0([x_t; u_t]) the nominal network's output (bias
+ * included, before the residual add) at the nominal rollout's x_t, o^p_t member p's output on the same input; D_p in
+ * fp32, t ascending; the product rounded to fp32 before it is added.  The planes go through the aggregate of
+ * gmpc_set_sampled_ensemble_mode with Q = P.  A member equal to the nominal layers has D_p == 0 exactly.  penalty may
+ * have either sign (negative: exploration) and may be 0.  A non-finite member makes its own plane's cost NaN.
+ * `samples`, X and obj are as under gmpc_set_sampled_ensemble.  In bf16 mode both passes run on the bf16 operands;
+ * the difference, the sums and J stay fp32.
+ * GMPC_EINVAL ("disagreement: ...", the setting left as it was) for a null ctx, a kind outside 0..1, a non-finite
+ * penalty, penalty != 0 with GMPC_DIS_OFF, and a context the sampling solvers refuse.  While it is on and an ensemble is
+ * set, a solve under a mode with GMPC_ENS_TS1 is refused before any launch ("disagreement: not with TS1 propagation").
+ * gmpc_mppi_vjp stays refused while an ensemble is set. */
+enum { GMPC_DIS_OFF = 0, GMPC_DIS_ONESTEP = 1 };
+int gmpc_set_sampled_disagreement(gmpc_ctx* ctx, int kind, float penalty);
+
+/* The one-step disagreement of every member with the bound dynamics along a plan: the forward-
+ * only, stateless sibling of gmpc_ensemble_rollout for the quantity above.  dyn_members, x0, U, B, S, P as there.
+ *   -> X [B][S+1][n]  the rollout under the bound (nominal) dynamics, X[b][0] = x0[b]
+ *      d [P][B][S]    d_{p,t} = sum_j (o^p_{t,j} - o^0_{t,j})^2
+ *      D [P][B]       the fp32 sum of d[p][b][:], t ascending
+ *   each output may be NULL, not all of them.
+ * fp32 whatever the sampled precision; the arithmetic of a row is that of the sampling solvers under
+ * gmpc_set_sampled_disagreement, and a row's values depend on neither B, its place in the batch, nor P.  A non-finite
+ * member makes its own planes non-finite and leaves the others' as they are.  Asynchronous on `stream` (one launch),
+ * deterministic.  Every refusal is GMPC_EINVAL with a message starting "ensemble disagreement: ", before any launch: a
+ * null ctx, dyn_members, x0 or U; B, S or P out of range; parameters not set; every output NULL; LSTM dynamics, a width
+ * or n + m above 256. */
+int gmpc_ensemble_disagreement(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_members, const float* x0,
+                               const float* U, float* X, float* d, float* D, void* stream);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
