@@ -1,6 +1,6 @@
 // C-ABI entry point of the ensemble rollout: a plan's trajectories and costs under every member of a
-// dynamics ensemble, and the members' spread per step; and of the plan's one-step disagreement.  Forward
-// only, stateless; no kernel in this file.
+// dynamics ensemble, and the members' spread per step; of the plan's one-step disagreement; and of the
+// rollout's VJP under every member.  Stateless; no kernel in this file.
 #include "gmpc_ctx.h"
 
 // Two launches at most on the caller's stream (k_ens_rollout, k_ens_moments), nothing waited for.  It reads mpc_w and
@@ -78,6 +78,100 @@ extern "C" int gmpc_ensemble_disagreement(gmpc_ctx* c, int B, int S, int P, cons
   a.X = X; a.d = d; a.D = D;
   if (gmpc_launch_ens_disagreement(a, P, static_cast<hipStream_t>(stream)))
     return fail(GMPC_EINVAL, "%s: shape not covered", who);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The VJP of the ensemble rollout and its costs.  Launches on the caller's stream: the members'
+// transposes, the row pass, the sweep, the ascending-p reduce, then the weight-gradient GEMMs (mpc_w column sum and the
+// cost MLP over P B rows; the dynamics member by member).  Everything it writes is the caller's or the call
+// workspace's: save = the transposes [P][count], then the per-member x0 / U / goal gradients; aux = the relu masks;
+// aux2 = the mpc_w terms [P B][3]; acts / dels = per member B T + GMPC_WGRAD_PAD rows (the row pass zeroes the pad
+// rows); acts2 / dels2 = the cost MLP's P B rows.
+extern "C" int gmpc_ensemble_rollout_vjp(gmpc_ctx* c, int B, int P, const float* dyn_members, const float* X,
+                                         const float* U, const float* goal, const float* gX, const float* gcost,
+                                         float* grad_x0, float* grad_U, float* grad_goal, float* grad_theta_sum,
+                                         float* grad_members, void* stream) {
+  const char* who = "ensemble rollout vjp";
+  if (!c) return fail(GMPC_EINVAL, "%s: ctx is null", who);
+  if (!dyn_members || !X || !U || !goal)
+    return fail(GMPC_EINVAL, "%s: dyn_members, X, U and goal must not be null", who);
+  const gmpc_shape& sh = c->sh;
+  if (B < 1 || B > c->maxB) return fail(GMPC_EINVAL, "%s: B = %d outside [1, max_batch = %d]", who, B, c->maxB);
+  if (P < 1 || P > GMPC_MAX_ENSEMBLE) return fail(GMPC_EINVAL, "%s: P = %d outside [1, %d]", who, P, GMPC_MAX_ENSEMBLE);
+  if (!c->params_set) return fail(GMPC_EINVAL, "%s: gmpc_set_params has not been called", who);
+  if (!gX && !gcost) return fail(GMPC_EINVAL, "%s: gX and gcost are both null: no cotangent", who);
+  if (!grad_x0 && !grad_U && !grad_goal && !grad_theta_sum && !grad_members)
+    return fail(GMPC_EINVAL, "%s: every output is null", who);
+  TRY(gmpc_sampled_coverage(c, who));
+  if (hipSetDevice(c->device) != hipSuccess) return fail(GMPC_EHIP, "hipSetDevice failed");
+  (void)hipGetLastError();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = sh.n, m = sh.m, T = sh.T, Lh = sh.dyn_layers - 1;
+  const size_t count = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims), steps = (size_t)B * T, rows = (size_t)P * B;
+  const size_t ntheta = 3 + (size_t)mlp_count(sh.cost_layers, sh.cost_dims);
+  const bool want_theta = grad_theta_sum && gcost, want_goal = grad_goal && gcost;
+  EnsVjpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.T = T; a.n = n; a.m = m;
+  a.dr = c->drows; a.cr = c->crows;
+  a.mstride = count;
+  a.rstride = (steps + GMPC_WGRAD_PAD) * a.dr.stride;
+  // the call workspace
+  CallWork& k = c->cw;
+  const size_t plane[3] = {grad_x0 ? (size_t)B * n : 0, grad_U ? steps * m : 0,
+                           want_goal ? (size_t)B * (T + 1) * n : 0};
+  size_t off[4] = {(P * count + 3) & ~(size_t)3, 0, 0, 0};
+  for (int i = 0; i < 3; ++i) off[i + 1] = off[i] + ((P * plane[i] + 3) & ~(size_t)3);
+  TRY(k.save.grow(c, off[3]));
+  if (Lh > 0) TRY(k.aux.grow(c, (size_t)P * steps * Lh * GMPC_MW));
+  if (want_theta) TRY(k.aux2.grow(c, rows * 3 + 8));
+  if (gcost) {
+    TRY(k.acts2.reserve(c, rows, a.cr.stride, s));
+    TRY(k.dels2.reserve(c, rows, a.cr.stride, s));
+  }
+  if (grad_members) {
+    TRY(k.acts.grow(c, (size_t)P * a.rstride));
+    TRY(k.dels.grow(c, (size_t)P * a.rstride));
+  }
+  bind_mlp(a.dyn, sh.dyn_layers, sh.dyn_dims, dyn_members, k.save.p);
+  a.cost = c->cost; a.mpc_w = c->mpc_w;
+  a.X = X; a.U = U; a.goal = goal; a.gX = gX; a.gc = gcost;
+  a.masks = reinterpret_cast<uint32_t*>(k.aux.p);
+  a.gx0 = grad_x0 ? k.save.p + off[0] : nullptr;
+  a.gU = grad_U ? k.save.p + off[1] : nullptr;
+  a.ggoal = want_goal ? k.save.p + off[2] : nullptr;
+  a.gm = want_theta ? k.aux2.p : nullptr;
+  a.acts = grad_members ? k.acts.p : nullptr;
+  a.dels = grad_members ? k.dels.p : nullptr;
+  a.cacts = gcost ? k.acts2.p : nullptr;
+  a.cdels = gcost ? k.dels2.p : nullptr;
+  gmpc_launch_dynfit_transpose(a.dyn, count, P, k.save.p, s);
+  if (gmpc_launch_ens_rollout_vjp(a, P, s)) return fail(GMPC_EINVAL, "%s: shape not covered", who);
+  EnsVjpReduce r;
+  memset(&r, 0, sizeof(r));
+  r.P = P;
+  float* outs[3] = {grad_x0, grad_U, want_goal ? grad_goal : nullptr};
+  for (int i = 0; i < 3; ++i) {
+    r.count[i] = plane[i];
+    r.planes[i] = k.save.p + off[i];
+    r.out[i] = outs[i];
+  }
+  gmpc_launch_ens_vjp_reduce(r, s);
+  // no cost cotangent: nothing reaches the goals or the costs' parameters
+  if (grad_goal && !gcost) HIP_TRY(hipMemsetAsync(grad_goal, 0, (size_t)B * (T + 1) * n * sizeof(float), s));
+  if (grad_theta_sum && !gcost) HIP_TRY(hipMemsetAsync(grad_theta_sum, 0, ntheta * sizeof(float), s));
+  if (want_theta) {
+    float* gm = k.aux2.p;
+    gmpc_launch_wgrad((int)rows, 1, 3, gm, 0, gm, 3, gm + rows * 3, grad_theta_sum, (int)rows, c->wpart, s,
+                      c->wpart_floats, false);
+    gmpc_launch_wgrad_mlp((int)rows, (int)rows, sh.cost_layers, sh.cost_dims, k.acts2.p, k.dels2.p, a.cr,
+                          grad_theta_sum + 3, c->wpart, c->wpart_floats, s);
+  }
+  if (grad_members)
+    for (int p = 0; p < P; ++p)
+      gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, a.acts + p * a.rstride,
+                            a.dels + p * a.rstride, a.dr, grad_members + p * count, c->wpart, c->wpart_floats, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }

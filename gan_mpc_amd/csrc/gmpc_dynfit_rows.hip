@@ -353,6 +353,12 @@ __global__ __launch_bounds__(256) void k_dynfit_loss_sum(int B, const float* los
 // Host side -----------------------------------------------------------------------------------------------------------
 size_t gmpc_dynfit_rows_lds(int S) { return (32 * (size_t)GMPC_DG_LDA + (size_t)S) * sizeof(float); }
 
+void gmpc_launch_dynfit_transpose(const MlpDesc& d, size_t mstride, int P, float* WT0, hipStream_t s) {
+  int kn = 1;
+  for (int l = 0; l < d.L; ++l) kn = d.dims[l] * d.dims[l + 1] > kn ? d.dims[l] * d.dims[l + 1] : kn;
+  hipLaunchKernelGGL(k_dynfit_transpose, dim3((kn + 255) / 256, d.L, P), dim3(256), 0, s, d, mstride, WT0);
+}
+
 int gmpc_launch_dynfit_rows(const DynFitRowsArgs& a, int P, float* WT0, float* loss_sum, hipStream_t s) {
   const MlpDesc& d = a.dyn;
   int kn = 1;

@@ -367,6 +367,36 @@ int gmpc_launch_ens_disagreement(const EnsDisArgs& a, int P, hipStream_t s);
 // deviations' sum in member order / P
 void gmpc_launch_ens_moments(const float* X, int P, size_t count, float* mean, float* var, hipStream_t s);
 
+// gmpc_ens_rollout_vjp.hip: the VJP of that rollout and its costs under every member --------------------
+// dyn describes member 0 -- W / b in the caller's [P][count] vectors, WT in the call's transposes, laid out alike --,
+// member p lies p mstride floats behind it; cost: the bound cost MLP with its transposes.  X, gX [P][B][T+1][n], gc
+// [P][B][T+1] (gX or gc may be null), U [B][T][m], goal [B][T+1][n].  masks: [P][B T][L-1][GMPC_MW] words of the call
+// (unused for L == 1).  Per-member outputs, each may be null: gx0 [P][B][n], gU [P][B][T][m], ggoal [P][B][T+1][n]
+// (written only with gc), gm [P B][3].  acts / dels: per member B T + GMPC_WGRAD_PAD rows in the layout dr, rstride
+// floats apart, or both null; cacts / cdels: P B rows in the layout cr, needed with gc.
+struct EnsVjpArgs {
+  int B, T, n, m;
+  MlpDesc dyn, cost;
+  size_t mstride, rstride;
+  MlpRows dr, cr;
+  const float *mpc_w, *X, *U, *goal, *gX, *gc;
+  uint32_t* masks;
+  float *gx0, *gU, *ggoal, *gm;
+  float *acts, *dels, *cacts, *cdels;
+};
+// The row pass (masks, acts) and the sweep: two launches.  Non-zero (nothing launched) outside the sampled rollout's
+// coverage, 1 <= P <= GMPC_MAX_ENSEMBLE and the rules above.
+int gmpc_launch_ens_rollout_vjp(const EnsVjpArgs& a, int P, hipStream_t s);
+// out[s][i] = ((planes[s][0][i] + planes[s][1][i]) + ...) + planes[s][P-1][i], i < count[s], for up to three arrays in
+// one launch (count 0: none)
+struct EnsVjpReduce {
+  int P;
+  size_t count[3];
+  const float* planes[3];
+  float* out[3];
+};
+void gmpc_launch_ens_vjp_reduce(const EnsVjpReduce& r, hipStream_t s);
+
 // gmpc_icem.hip: the sample-efficient cross-entropy method's two kernels --------------------------------
 // The rows of one iteration's pool, per problem: rows 0 .. Nit-1 fresh samples (sample index = row), rows Nit ..
 // Nit+carry-1 the first `carry` rows of keep [B][nkeep][T][m], then -- with addmean -- the mean itself; every row
@@ -485,6 +515,8 @@ struct DynFitRowsArgs {
 // nothing launched, outside widths and n + m <= GMPC_SAMPLED_MAX_WIDTH, 1 <= P <= GMPC_MAX_ENSEMBLE, or where the S
 // discounts do not fit the workgroup's LDS.
 int gmpc_launch_dynfit_rows(const DynFitRowsArgs& a, int P, float* WT0, float* loss_sum, hipStream_t s);
+// its first launch alone: W_l -> W_l^T of every layer of the P members of `dyn` (as above) into WT0 (= dyn.WT[0])
+void gmpc_launch_dynfit_transpose(const MlpDesc& dyn, size_t mstride, int P, float* WT0, hipStream_t s);
 
 // gmpc_dynl.hip: LSTM dynamics variant --------------------------------------------------------------------------------
 void gmpc_launch_dynl_rollout(DynlTrajArgs a, hipStream_t s);

@@ -924,6 +924,51 @@ class Engine:
             _ptr(out.get("D")), self._stream()))
         return out
 
+    ENSEMBLE_ROLLOUT_VJP_WANT = ("x0", "U", "goal", "theta", "members")
+
+    def ensemble_rollout_vjp(self, members, X, U, goal, gX=None, gcost=None,
+                             want=("x0", "U", "goal", "theta", "members")):
+        """The VJP of ensemble_rollout's X and costs under every member, in one call (gmpc_ensemble_rollout_vjp;
+        DESIGN.md section 29).  members: float32 (P, dyn_count) tensor or array, 1 <= P <= 16, passed per call; X
+        (P, B, T + 1, n) the members' states for U (B, T, m), as ensemble_rollout returns them; goal (B, T + 1, n);
+        gX (P, B, T + 1, n) = dL/dX and / or gcost (P, B, T + 1) = dL/dcosts: float32 device tensors.  -> a dict of
+        the `want`ed tensors: "x0" (B, n), "U" (B, T, m), "goal" (B, T + 1, n) the members' gradients summed in
+        ascending member order, "theta" [3 + cost_count] summed over the batch and the members, "members"
+        (P, dyn_count) summed over the batch, one row per member.  Stateless as ensemble_rollout is.  Every refusal is
+        a GmpcError("ensemble rollout vjp: ..."); nothing is synchronised."""
+        who = "ensemble rollout vjp"
+        P = self._check_ensemble_members(who, members)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - set(self.ENSEMBLE_ROLLOUT_VJP_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"{who}: want has unknown entries {sorted(unknown, key=str)}; known: "
+                                 f"{self.ENSEMBLE_ROLLOUT_VJP_WANT}")
+        if not want:
+            raise _lib.GmpcError(f"{who}: want is empty; known: {self.ENSEMBLE_ROLLOUT_VJP_WANT}")
+        if gX is None and gcost is None:
+            raise _lib.GmpcError(f"{who}: gX and gcost are both None: no cotangent")
+        n, m, T = self.n, self.m, self.T
+        for name, t in (("X", X), ("U", U), ("goal", goal), ("gX", gX), ("gcost", gcost)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+                raise _lib.GmpcError(f"{who}: {name} must be a float32 tensor, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)}")
+        if X.dim() != 4 or X.shape[0] != P or tuple(X.shape[2:]) != (T + 1, n):
+            raise _lib.GmpcError(f"{who}: X must be ({P}, B, {T + 1}, {n}), got {tuple(X.shape)}")
+        B = int(X.shape[1])
+        for name, t, shape in (("U", U, (B, T, m)), ("goal", goal, (B, T + 1, n)), ("gX", gX, (P, B, T + 1, n)),
+                               ("gcost", gcost, (P, B, T + 1))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"{who}: {name} must be {shape}, got {tuple(t.shape)}")
+        shapes = dict(x0=(B, n), U=(B, T, m), goal=(B, T + 1, n), theta=(3 + self.cost_count,),
+                      members=(P, self.dyn_count))
+        out = {k: self.new(*shapes[k]) for k in self.ENSEMBLE_ROLLOUT_VJP_WANT if k in want}
+        dev = self.to_dev(members)
+        _lib.check(self.lib.gmpc_ensemble_rollout_vjp(
+            self.ctx, B, P, _ptr(dev), _ptr(X), _ptr(U), _ptr(goal), _ptr(gX), _ptr(gcost), _ptr(out.get("x0")),
+            _ptr(out.get("U")), _ptr(out.get("goal")), _ptr(out.get("theta")), _ptr(out.get("members")),
+            self._stream()))
+        return out
+
     def _check_ensemble_members(self, who, members):
         """The rank, width, count and dtype of a (P, dyn_count) float32 tensor or array -> P."""
         shape = tuple(getattr(members, "shape", ()))

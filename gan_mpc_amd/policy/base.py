@@ -71,6 +71,84 @@ class BaseMPC(eval_policy.EvalMPC):
         out = eng.ensemble_disagreement(self._ensemble_dev, eng.to_dev(x), eng.to_dev(U), want=("d", "D"))
         return out["d"], out["D"]
 
+    RISK_AGGREGATES = ("mean", "mean_std", "max")
+
+    @staticmethod
+    def _risk(J, aggregate, risk):
+        """DESIGN.md section 26's aggregate of the members' objectives J (P, B) -> (R (B,), dR/dJ (P, B)): mean; mean +
+        risk * the population standard deviation; max (the first member that attains it)."""
+        P = J.shape[0]
+        mean = J.sum(0) / P
+        if aggregate == "mean":
+            return mean, torch.full_like(J, 1.0 / P)
+        if aggregate == "mean_std":
+            d = J - mean
+            sd = torch.sqrt((d * d).sum(0) / P)
+            w = 1.0 / P + risk * d / (P * torch.where(sd > 0, sd, torch.ones_like(sd)))
+            return mean + risk * sd, w
+        R, arg = J.max(0)
+        return R, torch.zeros_like(J).scatter_(0, arg[None], 1.0)
+
+    def _plan_risk(self, eng, x, U, goal, aggregate, risk, grad):
+        out = eng.ensemble_rollout(self._ensemble_dev, x, U, goal, want=("X", "costs") if grad else ("costs",))
+        R, w = self._risk(out["costs"].sum(-1), aggregate, float(risk))
+        if not grad:
+            return R, None
+        gcost = w[:, :, None].expand(-1, -1, out["costs"].shape[2]).contiguous()
+        return R, eng.ensemble_rollout_vjp(self._ensemble_dev, out["X"], U, goal, gcost=gcost, want=("U",))["U"]
+
+    def _risk_engine(self, who, params, x, U, goal, aggregate):
+        if self.dynamics_ensemble is None:
+            raise ValueError(f"{who} needs a dynamics_ensemble (the constructor's, or set_dynamics_ensemble): "
+                             "none is set")
+        if aggregate not in self.RISK_AGGREGATES:
+            raise ValueError(f"{who}: aggregate must be one of {self.RISK_AGGREGATES}, got {aggregate!r}")
+        xs, Us, gs = (tuple(getattr(a, "shape", np.shape(a))) for a in (x, U, goal))
+        if len(xs) != 2 or len(Us) != 3 or Us[0] != xs[0] or len(gs) != 3 or gs[0] != xs[0]:
+            raise ValueError(f"{who}: x must be (B, n), U (B, T, m) and goal (B, T+1, n), got {xs}, {Us} and {gs}")
+        eng = self.bind(self.to_device_params(params), xs[0])
+        return eng, eng.to_dev(x), eng.to_dev(U), eng.to_dev(goal)
+
+    def plan_risk(self, params, x, U, goal, aggregate="mean", risk=0.0, grad=False):
+        """The risk of a plan under the policy's dynamics ensemble: R (B,) = the aggregate --
+        "mean", "mean_std" (mean + risk * standard deviation) or "max", section 26's formulas -- of the members'
+        objectives, each the sum of the member's per-step costs against goal (B, T+1, n) for x (B, n), U (B, T, m).
+        grad=True: -> (R, dR/dU (B, T, m)), one Engine.ensemble_rollout_vjp call behind the rollout."""
+        eng, x, U, goal = self._risk_engine("plan_risk", params, x, U, goal, aggregate)
+        R, g = self._plan_risk(eng, x, U, goal, aggregate, risk, grad)
+        return (R, g) if grad else R
+
+    def refine_plan(self, params, x, U, goal, steps=5, step_size=0.1, aggregate="mean", risk=0.0):
+        """Polish a plan by projected gradient steps on its ensemble risk (plan_risk): per step U <- clamp(U - a g),
+        g = dR/dU, clamped to the policy's control bounds when set.  Backtracking per problem: a starts at step_size and
+        is halved at most 10 times until the problem's R strictly decreases; a problem that finds no such a keeps its U.
+        Every round is one batched forward call.  -> (U' (B, T, m), R_before (B,), R_after (B,))."""
+        eng, x, U, goal = self._risk_engine("refine_plan", params, x, U, goal, aggregate)
+        lo = hi = None
+        if self.control_bounds is not None:
+            lo, hi = (torch.as_tensor(np.asarray(b, np.float32), device=U.device) for b in self.control_bounds)
+        U = U.clone()
+        R = R_before = self._plan_risk(eng, x, U, goal, aggregate, risk, False)[0]
+        for _ in range(int(steps)):
+            _, g = self._plan_risk(eng, x, U, goal, aggregate, risk, True)
+            alpha = torch.full_like(R, float(step_size))
+            done = torch.zeros_like(R, dtype=torch.bool)
+            U_next, R_next = U, R
+            for _ in range(11):
+                cand = U - alpha[:, None, None] * g
+                if lo is not None:
+                    cand = torch.minimum(torch.maximum(cand, lo), hi)
+                Rc = self._plan_risk(eng, x, cand.contiguous(), goal, aggregate, risk, False)[0]
+                take = (Rc < R) & ~done
+                U_next = torch.where(take[:, None, None], cand, U_next)
+                R_next = torch.where(take, Rc, R_next)
+                done = done | take
+                if bool(done.all()):
+                    break
+                alpha = torch.where(done, alpha, alpha * 0.5)
+            U, R = U_next.contiguous(), R_next
+        return U, R_before, R
+
     def loss(self, xcseq, useq, params, *args):
         """The upper-level loss of ONE trajectory (reference policy/base.py:84-85): xcseq (T+1, n) -- xc, carry
         columns included --, useq (T, m), params the device parameters; a scalar torch tensor.  A subclass with

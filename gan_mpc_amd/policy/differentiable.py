@@ -51,7 +51,13 @@ X, U, obj = mppi_layer(policy, params, x0, goal, init_U, control_bounds, ...) is
 (gmpc_mppi_solve) as a differentiable torch op: backward is one call of gmpc_mppi_vjp, the true
 derivative through the sampler w.r.t. x0, goal, init_U and the mpc_weights / cost_params (and, asked for,
 dynamics_params) ranges of params.flat.  It is the way to train through a control-limited controller at any horizon;
-it runs on the second engine, as rollout_layer does."""
+it runs on the second engine, as rollout_layer does.
+
+(X, costs) = ensemble_rollout_layer(policy, params, x0, U, goal, members=None) is rollout_layer under every member of a
+dynamics ensemble at once (Engine.ensemble_rollout; X (P, B, T+1, n), costs (P, B, T+1)): backward is one call of
+gmpc_ensemble_rollout_vjp, the true derivative w.r.t. x0, U, goal, the mpc_weights / cost_params
+ranges of params.flat and, for a members tensor that requires grad, the members' weights.  Any torch function of the
+members' states and costs -- a risk aggregate, their spread -- so reaches the plan and the cost network."""
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -196,6 +202,65 @@ def rollout_layer(policy, params, x0, U, goal, dynamics_grad=True):
     dparams = policy.to_device_params(params)
     eng = _rollout_engine(policy, dparams, x0.shape[0])
     return RolloutFunction.apply(eng, dparams, dparams.flat, x0, U, goal, bool(dynamics_grad))
+
+
+class EnsembleRolloutFunction(torch.autograd.Function):
+    """forward(eng, dparams, flat, members, x0, U, goal) -> (X (P, B, T+1, n), costs (P, B, T+1)); eng is bound to
+    dparams.  backward is one gmpc_ensemble_rollout_vjp call."""
+
+    @staticmethod
+    def forward(ctx, eng, dparams, flat, members, x0, U, goal):
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+        mem32, U32, goal32 = eng.to_dev(members.detach()), f32(U), f32(goal)
+        out = eng.ensemble_rollout(mem32, f32(x0), U32, goal32, want=("X", "costs"))
+        ctx.eng = eng
+        ctx.views = eng._bound
+        ctx.theta = dparams.range_of(_THETA_KEYS)
+        ctx.flat_shape = flat.shape
+        ctx.save_for_backward(mem32, out["X"], U32, goal32)
+        ctx.set_materialize_grads(False)
+        return out["X"], out["costs"]
+
+    @staticmethod
+    def backward(ctx, gX, gc):
+        want_theta, want_mem, want_x0, want_U, want_goal = ctx.needs_input_grad[2:7]
+        if (gX is None and gc is None) or not (want_theta or want_mem or want_x0 or want_U or want_goal):
+            return (None,) * 7
+        eng = ctx.eng
+        members, X, U, goal = ctx.saved_tensors
+        if eng._bound is None or any(a.data_ptr() != b.data_ptr() for a, b in zip(eng._bound, ctx.views)):
+            eng.set_params(*ctx.views)      # another layer rebound the engine in between
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        keys = [k for k, w in zip(Engine.ENSEMBLE_ROLLOUT_VJP_WANT, (want_x0, want_U, want_goal, want_theta, want_mem))
+                if w]
+        out = eng.ensemble_rollout_vjp(members, X, U, goal, f32(gX), f32(gc), want=keys)
+        gflat = None
+        if want_theta:
+            lo, cnt = ctx.theta
+            gflat = torch.zeros(ctx.flat_shape, dtype=torch.float32, device=X.device)
+            gflat[lo:lo + cnt] = out["theta"]
+        return None, None, gflat, out.get("members"), out.get("x0"), out.get("U"), out.get("goal")
+
+
+def ensemble_rollout_layer(policy, params, x0, U, goal, members=None):
+    """(X (P, B, T+1, n), costs (P, B, T+1)) = the rollout of (x0, U) under every member of a dynamics ensemble and
+    its per-step costs against goal (Engine.ensemble_rollout on the policy's second engine), differentiable w.r.t. x0,
+    U, goal and the mpc_weights / cost_params ranges of params.flat: backward is one call of gmpc_ensemble_rollout_vjp
+    (DESIGN.md section 29).  members: a float32 (P, dyn_count) tensor -- differentiated too when it requires grad --;
+    None: the policy's dynamics ensemble, which is not differentiated (ValueError when the policy has none).  The
+    dynamics_params range of params.flat gets no gradient: the members, not the nominal network, roll the plan out."""
+    dparams = policy.to_device_params(params)
+    eng = _rollout_engine(policy, dparams, x0.shape[0])
+    if members is None:
+        if policy.dynamics_ensemble is None:
+            raise ValueError("ensemble_rollout_layer needs members or a dynamics_ensemble (the constructor's, or "
+                             "set_dynamics_ensemble): none is set")
+        if policy._ensemble_dev is None or policy._ensemble_dev.device != eng.device:
+            policy._ensemble_dev = eng.to_dev(policy.dynamics_ensemble)
+        members = policy._ensemble_dev
+    elif not torch.is_tensor(members):
+        members = eng.to_dev(members)
+    return EnsembleRolloutFunction.apply(eng, dparams, dparams.flat, members, x0, U, goal)
 
 
 MPPI_CHUNK = 16     # problems whose sample rows mppi_layer's engine holds at once

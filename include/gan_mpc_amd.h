@@ -505,6 +505,41 @@ int gmpc_set_sampled_disagreement(gmpc_ctx* ctx, int kind, float penalty);
 int gmpc_ensemble_disagreement(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_members, const float* x0,
                                const float* U, float* X, float* d, float* D, void* stream);
 
+/* The vector-Jacobian product of gmpc_ensemble_rollout's X and costs under every member: per
+ * member p the derivation of gmpc_rollout_vjp with f_p(x, u) = x + MLP_p([x; u]), taken at (X[p], U, goal) as passed,
+ * under that member's cotangents; the whole horizon only (S = T).
+ *   dyn_members [P][dyn_param_count] as for gmpc_ensemble_rollout, passed per call (nothing is kept); 1 <= P <= 16
+ *   X [P][B][T+1][n]: member p's states for U [B][T][m], as gmpc_ensemble_rollout returns them; goal [B][T+1][n];
+ *   1 <= B <= max_batch
+ *   gX [P][B][T+1][n] = dL/dX, gcost [P][B][T+1] = dL/dcosts: either may be NULL, not both
+ *   -> grad_x0 [B][n], grad_U [B][T][m], grad_goal [B][T+1][n] (row T is 0): ((g^0 + g^1) + ...) + g^{P-1} of the
+ *      members' gradients, one fp32 addition per member in ascending p starting from member 0's value, so with P = 1
+ *      the member's value comes through bit for bit
+ *      grad_theta_sum [3 + cost_count] in gmpc_rollout_vjp's layout, SUMMED over the batch and the members in a fixed
+ *      order; all zeros (as is grad_goal) when gcost is NULL
+ *      grad_members [P][dyn_param_count], each row in gmpc_set_params' dyn layout, SUMMED over the batch, one row per
+ *      member
+ *   each output may be NULL (its work is skipped), not all of them.
+ * The relu masks are recomputed from (X[p], U) under member p's layers (a unit is active iff its output is > 0, as in
+ * gmpc_rollout_vjp).  fp32 whatever the sampled precision; deterministic (no atomics, fixed orders): a problem's
+ * gradients depend on neither B nor its place in the batch, grad_members[p] not on P.  A non-finite member makes its
+ * own row of grad_members and the shared sums non-finite and leaves the other rows as they are.
+ * Stateless like gmpc_ensemble_rollout: mpc_w and the cost MLP of the bound parameters are read; a set sampled
+ * ensemble, its mode, the disagreement setting, the sampled precision and a held solution are neither read nor
+ * changed.  Asynchronous on `stream`, except that the first call needing more call workspace than the ctx holds
+ * allocates it (a synchronising hipMalloc) and keeps it, in floats: P dyn_param_count (the members' transposes)
+ * + P B n (with grad_x0) + P B T m (with grad_U) + P B (T+1) n (with grad_goal and gcost) + P B T (dyn hidden layers) 8
+ * mask words; with gcost 2 (P B + 8) (summed cost widths), and with grad_theta_sum 3 P B + 8; with grad_members
+ * 2 P (B T + 8) (summed dyn widths).
+ * Every refusal is GMPC_EINVAL with a message starting "ensemble rollout vjp: ", before any launch: a null ctx,
+ * dyn_members, X, U or goal; B or P out of range; parameters not set; both cotangents NULL; every output NULL; LSTM
+ * dynamics, a width or n + m above 256. */
+int gmpc_ensemble_rollout_vjp(gmpc_ctx* ctx, int B, int P, const float* dyn_members,
+                              const float* X, const float* U, const float* goal,
+                              const float* gX, const float* gcost,
+                              float* grad_x0, float* grad_U, float* grad_goal,
+                              float* grad_theta_sum, float* grad_members, void* stream);
+
 /* a8-a11 (+a13/a16): upper-level loss and its bilevel gradient at the iLQR solution held by the ctx
  * after gmpc_ilqr_solve (policy/optimizers.py:61-73,78-105), per trajectory; the batch mean of
  * policy/base.py:126-127 is left to the caller (it is where the multi-GPU all-reduce goes).
