@@ -161,6 +161,7 @@ SIGNATURES = {
     "gmpc_set_sampled_disagreement": (C.c_int, [_P, C.c_int, C.c_float]),
     "gmpc_ensemble_disagreement": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_ensemble_rollout_vjp": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gmpc_ensemble_disagreement_vjp": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_box_qp_host":(C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_bilevel_grad": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, _P]),
     "gmpc_bilevel_grad_cotangent": (C.c_int, [_P, C.c_int, _P, _P, C.c_float, _P, _P]),

@@ -1,6 +1,7 @@
 // C-ABI entry point of the ensemble rollout: a plan's trajectories and costs under every member of a
-// dynamics ensemble, and the members' spread per step; of the plan's one-step disagreement; and of the
-// rollout's VJP under every member.  Stateless; no kernel in this file.
+// dynamics ensemble, and the members' spread per step; of the plan's one-step disagreement; of the
+// rollout's VJP under every member; and of the disagreement's VJP.  Stateless; no kernel in
+// this file.
 #include "gmpc_ctx.h"
 
 // Two launches at most on the caller's stream (k_ens_rollout, k_ens_moments), nothing waited for.  It reads mpc_w and
@@ -167,6 +168,98 @@ extern "C" int gmpc_ensemble_rollout_vjp(gmpc_ctx* c, int B, int P, const float*
                       c->wpart_floats, false);
     gmpc_launch_wgrad_mlp((int)rows, (int)rows, sh.cost_layers, sh.cost_dims, k.acts2.p, k.dels2.p, a.cr,
                           grad_theta_sum + 3, c->wpart, c->wpart_floats, s);
+  }
+  if (grad_members)
+    for (int p = 0; p < P; ++p)
+      gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, a.acts + p * a.rstride,
+                            a.dels + p * a.rstride, a.dr, grad_members + p * count, c->wpart, c->wpart_floats, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The VJP of the one-step disagreement.  Launches on the caller's stream: the members' transposes; the
+// local part (k_disvjp_rows, k_disvjp_back, k_disvjp_reduce); then, with grad_x0, grad_U or grad_nominal wanted, the
+// chain through the nominal rollout -- §29's row pass and sweep with P = 1 on the bound dynamics under gX = rx, no cost
+// cotangent -- and grad_U = ru + chain; then the weight-gradient GEMMs, the nominal's over dels = local + chain.
+// Everything it writes is the caller's or the call workspace's: save = the members' transposes [P][count], the outputs
+// [P+1][B T][n], the local input gradients [P+1][B T][n+m], rx, ru and the chain's dL/dU; aux = the relu masks
+// [P+1][B T][L-1][GMPC_MW], plane P the nominal's (the chain's row pass writes the same bits there again); acts = the
+// members' rows, then the nominal's (written by the chain's row pass); dels = the members' rows, the chain's, then the
+// nominal's local ones.
+extern "C" int gmpc_ensemble_disagreement_vjp(gmpc_ctx* c, int B, int P, const float* dyn_members, const float* X,
+                                              const float* U, const float* gd, const float* gD, float* grad_x0,
+                                              float* grad_U, float* grad_nominal, float* grad_members, void* stream) {
+  const char* who = "ensemble disagreement vjp";
+  if (!c) return fail(GMPC_EINVAL, "%s: ctx is null", who);
+  if (!dyn_members || !X || !U) return fail(GMPC_EINVAL, "%s: dyn_members, X and U must not be null", who);
+  const gmpc_shape& sh = c->sh;
+  if (B < 1 || B > c->maxB) return fail(GMPC_EINVAL, "%s: B = %d outside [1, max_batch = %d]", who, B, c->maxB);
+  if (P < 1 || P > GMPC_MAX_ENSEMBLE) return fail(GMPC_EINVAL, "%s: P = %d outside [1, %d]", who, P, GMPC_MAX_ENSEMBLE);
+  if (!c->params_set) return fail(GMPC_EINVAL, "%s: gmpc_set_params has not been called", who);
+  if (!gd && !gD) return fail(GMPC_EINVAL, "%s: gd and gD are both null: no cotangent", who);
+  if (!grad_x0 && !grad_U && !grad_nominal && !grad_members) return fail(GMPC_EINVAL, "%s: every output is null", who);
+  TRY(gmpc_sampled_coverage(c, who));
+  if (hipSetDevice(c->device) != hipSuccess) return fail(GMPC_EHIP, "hipSetDevice failed");
+  (void)hipGetLastError();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = sh.n, m = sh.m, T = sh.T, Lh = sh.dyn_layers - 1;
+  const size_t count = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims), steps = (size_t)B * T;
+  const bool chain = grad_x0 || grad_U || grad_nominal;
+  DisVjpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.T = T; a.n = n; a.m = m; a.P = P;
+  a.dr = c->drows;
+  a.mstride = count;
+  a.rstride = (steps + GMPC_WGRAD_PAD) * a.dr.stride;
+  // the call workspace
+  CallWork& k = c->cw;
+  const size_t part[6] = {P * count, (P + 1) * steps * n, (P + 1) * steps * (n + m), (size_t)B * (T + 1) * n,
+                          steps * m, steps * m};
+  size_t off[7] = {0};
+  for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + ((part[i] + 3) & ~(size_t)3);
+  TRY(k.save.grow(c, off[6]));
+  if (Lh > 0) TRY(k.aux.grow(c, (size_t)(P + 1) * steps * Lh * GMPC_MW));
+  if (grad_members || grad_nominal) {
+    TRY(k.acts.grow(c, (size_t)(P + 1) * a.rstride));
+    TRY(k.dels.grow(c, (size_t)(P + 2) * a.rstride));
+  }
+  bind_mlp(a.dyn, sh.dyn_layers, sh.dyn_dims, dyn_members, k.save.p);
+  a.nom = c->dyn;
+  a.X = X; a.U = U; a.gd = gd; a.gD = gD;
+  a.masks = reinterpret_cast<uint32_t*>(k.aux.p);
+  a.out = k.save.p + off[1];
+  a.q = k.save.p + off[2];
+  a.rx = k.save.p + off[3];
+  a.ru = k.save.p + off[4];
+  float* chain_gU = k.save.p + off[5];
+  a.acts = grad_members ? k.acts.p : nullptr;
+  a.dels = grad_members ? k.dels.p : nullptr;
+  float* nom_acts = grad_nominal ? k.acts.p + (size_t)P * a.rstride : nullptr;
+  float* chain_dels = grad_nominal ? k.dels.p + (size_t)P * a.rstride : nullptr;
+  a.ndels = grad_nominal ? k.dels.p + (size_t)(P + 1) * a.rstride : nullptr;
+  gmpc_launch_dynfit_transpose(a.dyn, count, P, k.save.p, s);
+  if (gmpc_launch_dis_vjp_local(a, s)) return fail(GMPC_EINVAL, "%s: shape not covered", who);
+  if (chain) {
+    EnsVjpArgs v;
+    memset(&v, 0, sizeof(v));
+    v.B = B; v.T = T; v.n = n; v.m = m;
+    v.dr = c->drows; v.cr = c->crows;
+    v.mstride = count; v.rstride = a.rstride;
+    v.dyn = c->dyn; v.cost = c->cost; v.mpc_w = c->mpc_w;
+    v.X = X; v.U = U; v.gX = a.rx;
+    v.masks = a.masks ? a.masks + (size_t)P * steps * Lh * GMPC_MW : nullptr;
+    v.gx0 = grad_x0;
+    v.gU = grad_U ? chain_gU : nullptr;
+    v.acts = nom_acts; v.dels = chain_dels;
+    if (gmpc_launch_ens_rollout_vjp(v, 1, s)) return fail(GMPC_EINVAL, "%s: shape not covered", who);
+    if (grad_U) gmpc_launch_dis_vjp_add(steps, m, (size_t)m, a.ru, chain_gU, grad_U, s);
+    if (grad_nominal) {
+      // dels = local + chain over every layer's columns of the B T rows, then one pass of the GEMMs
+      const int width = a.dr.doff[sh.dyn_layers - 1] + n;
+      gmpc_launch_dis_vjp_add(steps, width, (size_t)a.dr.stride, a.ndels, chain_dels, chain_dels, s);
+      gmpc_launch_wgrad_mlp((int)steps, (int)steps, sh.dyn_layers, sh.dyn_dims, nom_acts, chain_dels, a.dr,
+                            grad_nominal, c->wpart, c->wpart_floats, s);
+    }
   }
   if (grad_members)
     for (int p = 0; p < P; ++p)

@@ -397,6 +397,31 @@ struct EnsVjpReduce {
 };
 void gmpc_launch_ens_vjp_reduce(const EnsVjpReduce& r, hipStream_t s);
 
+// gmpc_ens_disagree_vjp.hip: the VJP of a plan's one-step disagreement, its local part -------------------
+// dyn describes member 0 as in EnsVjpArgs (W / b in the caller's [P][count] vectors, WT in the call's transposes, member
+// p mstride floats behind it); nom: the bound dynamics with their transposes.  X [B][T+1][n] the nominal rollout, U
+// [B][T][m]; gd [P][B][T] and gD [P][B], one may be null.  Planes of the call, plane P the nominal's: masks
+// [P+1][B T][L-1][GMPC_MW] (unused for L == 1), out [P+1][B T][n] the networks' outputs, q [P+1][B T][n+m] the local
+// input gradients.  rx [B][T+1][n] (row T zero) and ru [B][T][m]: their sum in ascending p, the nominal last.  acts /
+// dels: per member B T + GMPC_WGRAD_PAD rows in the layout dr, rstride floats apart, or both null; ndels: the B T rows of
+// the nominal's local deltas (c^N and what it becomes below the output layer), or null.
+struct DisVjpArgs {
+  int B, T, n, m, P;
+  MlpDesc dyn, nom;
+  size_t mstride, rstride;
+  MlpRows dr;
+  const float *X, *U, *gd, *gD;
+  uint32_t* masks;
+  float *out, *q, *rx, *ru;
+  float *acts, *dels, *ndels;
+};
+// Three launches (k_disvjp_rows, k_disvjp_back, k_disvjp_reduce).  Non-zero (nothing launched) outside the sampled
+// rollout's coverage, 1 <= P <= GMPC_MAX_ENSEMBLE and the rules above.
+int gmpc_launch_dis_vjp_local(const DisVjpArgs& a, hipStream_t s);
+// out[r][j] = x[r][j] + y[r][j] for j < width of `rows` rows ld floats apart; out may be x or y
+void gmpc_launch_dis_vjp_add(size_t rows, int width, size_t ld, const float* x, const float* y, float* out,
+                             hipStream_t s);
+
 // gmpc_icem.hip: the sample-efficient cross-entropy method's two kernels --------------------------------
 // The rows of one iteration's pool, per problem: rows 0 .. Nit-1 fresh samples (sample index = row), rows Nit ..
 // Nit+carry-1 the first `carry` rows of keep [B][nkeep][T][m], then -- with addmean -- the mean itself; every row

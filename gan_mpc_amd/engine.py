@@ -969,6 +969,50 @@ class Engine:
             self._stream()))
         return out
 
+    ENSEMBLE_DISAGREEMENT_VJP_WANT = ("x0", "U", "nominal", "members")
+
+    def ensemble_disagreement_vjp(self, members, X, U, gd=None, gD=None, want=("x0", "U", "nominal", "members")):
+        """The VJP of ensemble_disagreement's d and D, in one call (gmpc_ensemble_disagreement_vjp; DESIGN.md section
+        30).  members: float32 (P, dyn_count) tensor or array, 1 <= P <= 16, passed per call; X (B, T + 1, n) the
+        nominal rollout for U (B, T, m), as ensemble_disagreement returns it (the whole horizon); gd (P, B, T) = dL/dd
+        and / or gD (P, B) = dL/dD: float32 device tensors.  -> a dict of the `want`ed tensors: "x0" (B, n) and "U"
+        (B, T, m), through the members' and the nominal one-step outputs and through the nominal rollout; "nominal"
+        [dyn_count] w.r.t. the bound dynamics and "members" (P, dyn_count), one row per member, both summed over the
+        batch.  Stateless as ensemble_disagreement is.  Every refusal is a GmpcError("ensemble disagreement vjp:
+        ..."); nothing is synchronised."""
+        who = "ensemble disagreement vjp"
+        P = self._check_ensemble_members(who, members)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - set(self.ENSEMBLE_DISAGREEMENT_VJP_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"{who}: want has unknown entries {sorted(unknown, key=str)}; known: "
+                                 f"{self.ENSEMBLE_DISAGREEMENT_VJP_WANT}")
+        if not want:
+            raise _lib.GmpcError(f"{who}: want is empty; known: {self.ENSEMBLE_DISAGREEMENT_VJP_WANT}")
+        if gd is None and gD is None:
+            raise _lib.GmpcError(f"{who}: gd and gD are both None: no cotangent")
+        n, m, T = self.n, self.m, self.T
+        for name, t in (("X", X), ("U", U), ("gd", gd), ("gD", gD)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+                raise _lib.GmpcError(f"{who}: {name} must be a float32 tensor, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)}")
+        if X.dim() != 3 or tuple(X.shape[1:]) != (T + 1, n):
+            raise _lib.GmpcError(f"{who}: X must be (B, {T + 1}, {n}), got {tuple(X.shape)}")
+        B = int(X.shape[0])
+        for name, t, shape in (("U", U, (B, T, m)), ("gd", gd, (P, B, T)), ("gD", gD, (P, B))):
+            if t is not None and tuple(t.shape) != shape:
+                raise _lib.GmpcError(f"{who}: {name} must be {shape}, got {tuple(t.shape)}")
+        X, U = X.contiguous(), U.contiguous()
+        gd = None if gd is None else gd.contiguous()
+        gD = None if gD is None else gD.contiguous()
+        shapes = dict(x0=(B, n), U=(B, T, m), nominal=(self.dyn_count,), members=(P, self.dyn_count))
+        out = {k: self.new(*shapes[k]) for k in self.ENSEMBLE_DISAGREEMENT_VJP_WANT if k in want}
+        dev = self.to_dev(members)
+        _lib.check(self.lib.gmpc_ensemble_disagreement_vjp(
+            self.ctx, B, P, _ptr(dev), _ptr(X), _ptr(U), _ptr(gd), _ptr(gD), _ptr(out.get("x0")), _ptr(out.get("U")),
+            _ptr(out.get("nominal")), _ptr(out.get("members")), self._stream()))
+        return out
+
     def _check_ensemble_members(self, who, members):
         """The rank, width, count and dtype of a (P, dyn_count) float32 tensor or array -> P."""
         shape = tuple(getattr(members, "shape", ()))

@@ -109,28 +109,65 @@ class BaseMPC(eval_policy.EvalMPC):
         eng = self.bind(self.to_device_params(params), xs[0])
         return eng, eng.to_dev(x), eng.to_dev(U), eng.to_dev(goal)
 
-    def plan_risk(self, params, x, U, goal, aggregate="mean", risk=0.0, grad=False):
+    def _plan_risk_penalised(self, eng, x, U, goal, aggregate, risk, grad, penalty):
+        """plan_risk under the one-step disagreement penalty: the planes J_0 + penalty * D_p of
+        section 28 -- J_0 the nominal rollout's objective, the product rounded before it is added -- under section
+        26's aggregate; dR/dU = (sum_p w_p) dJ_0/dU + penalty * sum_p w_p dD_p/dU with w = dR/dJ_p: one
+        Engine.rollout_vjp under gcost and one Engine.ensemble_disagreement_vjp under gD = penalty * w."""
+        X, costs = eng.rollout_cost(x, U, goal)
+        D = eng.ensemble_disagreement(self._ensemble_dev, x, U, want=("D",))["D"]
+        R, w = self._risk(costs.sum(-1)[None] + penalty * D, aggregate, float(risk))
+        if not grad:
+            return R, None
+        gcost = w.sum(0)[:, None].expand(-1, costs.shape[1]).contiguous()
+        g = eng.rollout_vjp(X, U, goal, None, gcost, want_x0=False, want_goal=False, want_theta=False,
+                            want_dyn=False)["U"]
+        gD = (penalty * w).contiguous()
+        return R, g + eng.ensemble_disagreement_vjp(self._ensemble_dev, X, U, gD=gD, want=("U",))["U"]
+
+    def _plan_objective(self, eng, x, U, goal, aggregate, risk, grad, disagreement):
+        if disagreement is None:
+            return self._plan_risk(eng, x, U, goal, aggregate, risk, grad)
+        return self._plan_risk_penalised(eng, x, U, goal, aggregate, risk, grad, disagreement)
+
+    @staticmethod
+    def _check_disagreement(who, disagreement):
+        if disagreement is None:
+            return None
+        penalty = float(disagreement)
+        if not np.isfinite(penalty):
+            raise ValueError(f"{who}: disagreement must be None or a finite number, got {disagreement!r}")
+        return penalty
+
+    def plan_risk(self, params, x, U, goal, aggregate="mean", risk=0.0, grad=False, disagreement=None):
         """The risk of a plan under the policy's dynamics ensemble: R (B,) = the aggregate --
         "mean", "mean_std" (mean + risk * standard deviation) or "max", section 26's formulas -- of the members'
         objectives, each the sum of the member's per-step costs against goal (B, T+1, n) for x (B, n), U (B, T, m).
-        grad=True: -> (R, dR/dU (B, T, m)), one Engine.ensemble_rollout_vjp call behind the rollout."""
+        grad=True: -> (R, dR/dU (B, T, m)), one Engine.ensemble_rollout_vjp call behind the rollout.
+        disagreement=penalty (a finite number): the objective a policy built with
+        ensemble_disagreement=penalty chooses its plan on instead -- the aggregate of J_0 + penalty * D_p, J_0 the
+        objective of the rollout under params["dynamics_params"], D_p member p's summed one-step disagreement with it."""
+        disagreement = self._check_disagreement("plan_risk", disagreement)
         eng, x, U, goal = self._risk_engine("plan_risk", params, x, U, goal, aggregate)
-        R, g = self._plan_risk(eng, x, U, goal, aggregate, risk, grad)
+        R, g = self._plan_objective(eng, x, U, goal, aggregate, risk, grad, disagreement)
         return (R, g) if grad else R
 
-    def refine_plan(self, params, x, U, goal, steps=5, step_size=0.1, aggregate="mean", risk=0.0):
+    def refine_plan(self, params, x, U, goal, steps=5, step_size=0.1, aggregate="mean", risk=0.0, disagreement=None):
         """Polish a plan by projected gradient steps on its ensemble risk (plan_risk): per step U <- clamp(U - a g),
         g = dR/dU, clamped to the policy's control bounds when set.  Backtracking per problem: a starts at step_size and
         is halved at most 10 times until the problem's R strictly decreases; a problem that finds no such a keeps its U.
-        Every round is one batched forward call.  -> (U' (B, T, m), R_before (B,), R_after (B,))."""
+        Every round is one batched forward call.  -> (U' (B, T, m), R_before (B,), R_after (B,)).  disagreement: as
+        for plan_risk -- pass the policy's ensemble_disagreement penalty to polish the objective its solver chose the
+        plan on."""
+        disagreement = self._check_disagreement("refine_plan", disagreement)
         eng, x, U, goal = self._risk_engine("refine_plan", params, x, U, goal, aggregate)
         lo = hi = None
         if self.control_bounds is not None:
             lo, hi = (torch.as_tensor(np.asarray(b, np.float32), device=U.device) for b in self.control_bounds)
         U = U.clone()
-        R = R_before = self._plan_risk(eng, x, U, goal, aggregate, risk, False)[0]
+        R = R_before = self._plan_objective(eng, x, U, goal, aggregate, risk, False, disagreement)[0]
         for _ in range(int(steps)):
-            _, g = self._plan_risk(eng, x, U, goal, aggregate, risk, True)
+            _, g = self._plan_objective(eng, x, U, goal, aggregate, risk, True, disagreement)
             alpha = torch.full_like(R, float(step_size))
             done = torch.zeros_like(R, dtype=torch.bool)
             U_next, R_next = U, R
@@ -138,7 +175,7 @@ class BaseMPC(eval_policy.EvalMPC):
                 cand = U - alpha[:, None, None] * g
                 if lo is not None:
                     cand = torch.minimum(torch.maximum(cand, lo), hi)
-                Rc = self._plan_risk(eng, x, cand.contiguous(), goal, aggregate, risk, False)[0]
+                Rc = self._plan_objective(eng, x, cand.contiguous(), goal, aggregate, risk, False, disagreement)[0]
                 take = (Rc < R) & ~done
                 U_next = torch.where(take[:, None, None], cand, U_next)
                 R_next = torch.where(take, Rc, R_next)

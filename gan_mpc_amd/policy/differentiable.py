@@ -263,6 +263,67 @@ def ensemble_rollout_layer(policy, params, x0, U, goal, members=None):
     return EnsembleRolloutFunction.apply(eng, dparams, dparams.flat, members, x0, U, goal)
 
 
+class EnsembleDisagreementFunction(torch.autograd.Function):
+    """forward(eng, dparams, flat, members, x0, U) -> (d (P, B, T), D (P, B)); eng is bound to dparams.  backward is
+    one gmpc_ensemble_disagreement_vjp call at the nominal rollout the forward kept."""
+
+    @staticmethod
+    def forward(ctx, eng, dparams, flat, members, x0, U):
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+        mem32, U32 = eng.to_dev(members.detach()), f32(U)
+        out = eng.ensemble_disagreement(mem32, f32(x0), U32, want=("X", "d", "D"))
+        ctx.eng = eng
+        ctx.views = eng._bound
+        ctx.dyn = dparams.range_of(("dynamics_params",))
+        ctx.flat_shape = flat.shape
+        ctx.save_for_backward(mem32, out["X"], U32)
+        ctx.set_materialize_grads(False)
+        return out["d"], out["D"]
+
+    @staticmethod
+    def backward(ctx, gd, gD):
+        want_nom, want_mem, want_x0, want_U = ctx.needs_input_grad[2:6]
+        if (gd is None and gD is None) or not (want_nom or want_mem or want_x0 or want_U):
+            return (None,) * 6
+        eng = ctx.eng
+        members, X, U = ctx.saved_tensors
+        if eng._bound is None or any(a.data_ptr() != b.data_ptr() for a, b in zip(eng._bound, ctx.views)):
+            eng.set_params(*ctx.views)      # another layer rebound the engine in between
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        keys = [k for k, w in zip(Engine.ENSEMBLE_DISAGREEMENT_VJP_WANT, (want_x0, want_U, want_nom, want_mem)) if w]
+        out = eng.ensemble_disagreement_vjp(members, X, U, f32(gd), f32(gD), want=keys)
+        gflat = None
+        if want_nom:
+            lo, cnt = ctx.dyn
+            gflat = torch.zeros(ctx.flat_shape, dtype=torch.float32, device=X.device)
+            gflat[lo:lo + cnt] = out["nominal"]
+        return None, None, gflat, out.get("members"), out.get("x0"), out.get("U")
+
+
+def ensemble_disagreement_layer(policy, params, x0, U, members=None):
+    """(d (P, B, T), D (P, B)) = the one-step disagreement of every member of a dynamics ensemble with the policy's
+    (nominal) dynamics along the nominal rollout of (x0, U) (Engine.ensemble_disagreement on the policy's second
+    engine, the same bits), differentiable w.r.t. x0, U and the dynamics_params range of params.flat -- the nominal
+    network, a real gradient here: it both measures and rolls the plan out --: backward is one call of
+    gmpc_ensemble_disagreement_vjp.  members: a float32 (P, dyn_count) tensor -- differentiated
+    too when it requires grad --; None: the policy's dynamics ensemble, which is not differentiated (ValueError when
+    the policy has none).  The whole horizon only: U is (B, T, m)."""
+    dparams = policy.to_device_params(params)
+    eng = _rollout_engine(policy, dparams, x0.shape[0])
+    if members is None:
+        if policy.dynamics_ensemble is None:
+            raise ValueError("ensemble_disagreement_layer needs members or a dynamics_ensemble (the constructor's, or "
+                             "set_dynamics_ensemble): none is set")
+        if policy._ensemble_dev is None or policy._ensemble_dev.device != eng.device:
+            policy._ensemble_dev = eng.to_dev(policy.dynamics_ensemble)
+        members = policy._ensemble_dev
+    elif not torch.is_tensor(members):
+        members = eng.to_dev(members)
+    if U.dim() != 3 or U.shape[1] != eng.T:
+        raise ValueError(f"ensemble_disagreement_layer: U must be (B, T = {eng.T}, m), got {tuple(U.shape)}")
+    return EnsembleDisagreementFunction.apply(eng, dparams, dparams.flat, members, x0, U)
+
+
 MPPI_CHUNK = 16     # problems whose sample rows mppi_layer's engine holds at once
 
 

@@ -505,6 +505,41 @@ int gmpc_set_sampled_disagreement(gmpc_ctx* ctx, int kind, float penalty);
 int gmpc_ensemble_disagreement(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_members, const float* x0,
                                const float* U, float* X, float* d, float* D, void* stream);
 
+/* The vector-Jacobian product of gmpc_ensemble_disagreement's d and D; the whole horizon only
+ * (S = T).
+ *   dyn_members [P][dyn_param_count], 1 <= P <= 16, 1 <= B <= max_batch as there, passed per call (nothing is kept)
+ *   X [B][T+1][n]: the nominal rollout for U [B][T][m], as gmpc_ensemble_disagreement returns it
+ *   gd [P][B][T] = dL/dd, gD [P][B] = dL/dD: either may be NULL, not both.  The weight of a step is
+ *   w[p][b][t] = gd + gD (one fp32 addition; with one given, that value).
+ * With z_t = [x_t; u_t], e^p_t = o^p_t - o^0_t and c^p_t = 2 w[p][b][t] e^p_t:
+ *   q^p_t = (dMLP_p/dz)^T c^p_t;   c^N_t = -(((c^0_t + c^1_t) + ...) + c^{P-1}_t);   q^N_t = (dMLP_0/dz)^T c^N_t
+ *   r_t = ((((q^0_t + q^1_t) + ...) + q^{P-1}_t) + q^N_t) = [rx_t; ru_t]
+ *   lambda_T = 0, lambda_t = rx_t + lambda_{t+1} + (dMLP_0/dx)^T lambda_{t+1}   (through x_{t+1} = x_t + MLP_0(z_t))
+ *   -> grad_x0 [B][n] = lambda_0;  grad_U [B][T][m], grad_U_t = ru_t + (dMLP_0/du)^T lambda_{t+1}
+ *      grad_nominal [dyn_param_count] = sum_{b,t} (dMLP_0/dtheta)^T (c^N_t + lambda_{t+1}), w.r.t. the bound dynamics,
+ *      in gmpc_set_params' dyn layout (the two deltas are added per row and layer, then summed over the rows)
+ *      grad_members [P][dyn_param_count], row p = sum_{b,t} (dMLP_p/dtheta)^T c^p_t
+ *   each output may be NULL (its work is skipped), not all of them.
+ * The relu masks are recomputed from (X, U) under each network's layers (a unit is active iff its output is > 0).  Goals,
+ * costs, mpc_w and the cost MLP do not enter.  fp32 whatever the sampled precision; deterministic (no atomics, fixed
+ * orders): a problem's gradients depend on neither B nor its place in the batch, grad_members[p] neither on P nor on
+ * the other members' cotangents.  A member whose layers equal the bound layers has e = 0 exactly: its row of
+ * grad_members and its q^p are exact zeros.  A non-finite member makes its own row of grad_members and the shared
+ * outputs non-finite and leaves the other rows as they are.
+ * Stateless like gmpc_ensemble_rollout_vjp: the bound dynamics are read; a set sampled ensemble, its mode, the
+ * disagreement setting, the sampled precision and a held solution are neither read nor changed.  Asynchronous on
+ * `stream`, except that the first call needing more call workspace than the ctx holds allocates it (a synchronising
+ * hipMalloc) and keeps it, in floats: P dyn_param_count + (P+1) B T (2 n + m) + B (T+1) n + 2 B T m, (P+1) B T (dyn
+ * hidden layers) 8 mask words, and with grad_members or grad_nominal (2 P + 3) (B T + 8) (summed dyn widths).
+ * Every refusal is GMPC_EINVAL with a message starting "ensemble disagreement vjp: ", before any launch: a null ctx,
+ * dyn_members, X or U; B or P out of range; parameters not set; both cotangents NULL; every output NULL; LSTM
+ * dynamics, a width or n + m above 256. */
+int gmpc_ensemble_disagreement_vjp(gmpc_ctx* ctx, int B, int P, const float* dyn_members,
+                                   const float* X, const float* U,
+                                   const float* gd, const float* gD,
+                                   float* grad_x0, float* grad_U,
+                                   float* grad_nominal, float* grad_members, void* stream);
+
 /* The vector-Jacobian product of gmpc_ensemble_rollout's X and costs under every member: per
  * member p the derivation of gmpc_rollout_vjp with f_p(x, u) = x + MLP_p([x; u]), taken at (X[p], U, goal) as passed,
  * under that member's cotangents; the whole horizon only (S = T).
