@@ -158,6 +158,8 @@ SIGNATURES = {
     "gmpc_set_sampled_ensemble": (C.c_int, [_P, C.c_int, _P]),
     "gmpc_set_sampled_ensemble_mode": (C.c_int, [_P, C.POINTER(EnsembleMode)]),
     "gmpc_ensemble_rollout": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gmpc_ensemble_rollout_feedback": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_float, _P,
+                                                 _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_set_sampled_disagreement": (C.c_int, [_P, C.c_int, C.c_float]),
     "gmpc_ensemble_disagreement": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gmpc_ensemble_rollout_vjp": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

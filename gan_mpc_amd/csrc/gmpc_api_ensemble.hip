@@ -1,5 +1,6 @@
 // C-ABI entry point of the ensemble rollout: a plan's trajectories and costs under every member of a
-// dynamics ensemble, and the members' spread per step; of the plan's one-step disagreement; of the
+// dynamics ensemble, and the members' spread per step; of the same in closed loop around a reference trajectory
+// (DESIGN §31); of the plan's one-step disagreement; of the
 // rollout's VJP under every member; and of the disagreement's VJP.  Stateless; no kernel in
 // this file.
 #include "gmpc_ctx.h"
@@ -43,6 +44,62 @@ extern "C" int gmpc_ensemble_rollout(gmpc_ctx* c, int B, int S, int P, const flo
   a.goal = costs || obj ? goal : nullptr;     // a goal nobody costs against is not read
   a.X = planes; a.costs = costs; a.obj = obj;
   if (gmpc_launch_ens_rollout(a, P, s)) return fail(GMPC_EINVAL, "%s: shape not covered", who);
+  if (moments) gmpc_launch_ens_moments(planes, P, plane, x_mean, x_var, s);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The ensemble rollout in closed loop: gmpc_ensemble_rollout's checks, workspace rule and two launches,
+// the rollout kernel in its feedback form (k_ens_rollout_feedback).  alpha is used only with k.
+extern "C" int gmpc_ensemble_rollout_feedback(gmpc_ctx* c, int B, int S, int P, const float* dyn_members,
+                                              const float* x0, const float* X_ref, const float* U_ref, const float* K,
+                                              const float* k, float alpha, const float* u_lo, const float* u_hi,
+                                              const float* goal, float* X, float* U, float* costs, float* obj,
+                                              float* x_mean, float* x_var, void* stream) {
+  const char* who = "ensemble feedback";
+  if (!c) return fail(GMPC_EINVAL, "%s: ctx is null", who);
+  if (!dyn_members || !X_ref || !U_ref || !K)
+    return fail(GMPC_EINVAL, "%s: dyn_members, X_ref, U_ref and K must not be null", who);
+  if (!u_lo != !u_hi)
+    return fail(GMPC_EINVAL, "%s: u_lo and u_hi must both be given or both be null (u_lo %s, u_hi %s)", who,
+                u_lo ? "given" : "null", u_hi ? "given" : "null");
+  if (!std::isfinite(alpha)) return fail(GMPC_EINVAL, "%s: alpha = %g is not finite", who, (double)alpha);
+  const gmpc_shape& sh = c->sh;
+  if (B < 1 || B > c->maxB) return fail(GMPC_EINVAL, "%s: B = %d outside [1, max_batch = %d]", who, B, c->maxB);
+  if (S < 1 || S > sh.T) return fail(GMPC_EINVAL, "%s: S = %d outside [1, T = %d]", who, S, sh.T);
+  if (P < 1 || P > GMPC_MAX_ENSEMBLE) return fail(GMPC_EINVAL, "%s: P = %d outside [1, %d]", who, P, GMPC_MAX_ENSEMBLE);
+  if (!c->params_set) return fail(GMPC_EINVAL, "%s: gmpc_set_params has not been called", who);
+  if (!X && !U && !costs && !obj && !x_mean && !x_var) return fail(GMPC_EINVAL, "%s: every output is null", who);
+  if ((costs || obj) && !goal) return fail(GMPC_EINVAL, "%s: costs and obj need goal", who);
+  if ((costs || obj) && S != sh.T)
+    return fail(GMPC_EINVAL, "%s: costs and obj need the whole horizon, S = %d is not T = %d", who, S, sh.T);
+  TRY(gmpc_sampled_coverage(c, who));
+  if (hipSetDevice(c->device) != hipSuccess) return fail(GMPC_EHIP, "hipSetDevice failed");
+  (void)hipGetLastError();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t plane = (size_t)B * (S + 1) * sh.n;
+  const bool moments = x_mean || x_var;
+  float* planes = X;
+  if (moments && !planes) {
+    TRY(c->cw.save.grow(c, (size_t)P * plane));
+    planes = c->cw.save.p;
+  }
+  EnsRollArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.S = S; a.T = sh.T; a.n = sh.n; a.m = sh.m;
+  bind_mlp(a.dyn, sh.dyn_layers, sh.dyn_dims, dyn_members, nullptr);
+  a.mstride = (size_t)mlp_count(sh.dyn_layers, sh.dyn_dims);
+  a.cost = c->cost; a.mpc_w = c->mpc_w;
+  a.x0 = x0 ? x0 : X_ref;
+  a.goal = costs || obj ? goal : nullptr;     // a goal nobody costs against is not read
+  a.X = planes; a.costs = costs; a.obj = obj;
+  EnsFeedbackArgs f;
+  memset(&f, 0, sizeof(f));
+  f.X_ref = X_ref; f.U_ref = U_ref; f.K = K; f.k = k; f.alpha = alpha;
+  f.u_lo = u_lo; f.u_hi = u_hi;
+  f.x0_stride = x0 ? (size_t)sh.n : (size_t)(S + 1) * sh.n;
+  f.U = U;
+  if (gmpc_launch_ens_rollout_feedback(a, f, P, s)) return fail(GMPC_EINVAL, "%s: shape not covered", who);
   if (moments) gmpc_launch_ens_moments(planes, P, plane, x_mean, x_var, s);
   HIP_TRY(hipGetLastError());
   return 0;

@@ -8,14 +8,23 @@
 //                   the sampled rollout's mean_row form under the same network.  What differs: x0, goal and U are per
 //                   row, every row's states are written (from the LDS block, rows of n floats), the costs are kept
 //                   per step, and the horizon may be cut short (S <= T steps, then without costs).
+//   k_ens_rollout_feedback  (gmpc_ensemble_rollout_feedback) the same body in closed loop: a
+//                   row's controls are formed at every step from its own state by a time-varying feedback law around
+//                   a reference trajectory, clamped, and written out per member.
 //   k_ens_moments   one thread per (problem, step, state): mean and population variance over the members' planes,
 //                   both sums sequential in ascending member order.
 //   k_ens_disagreement  (gmpc_ensemble_disagreement) k_ens_rollout's grid, the rows rolled out
 //                   under the bound dynamics and member p's one-step output measured against theirs at every step.
 #include "gmpc_cem_rollout.h"
 
-__global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) {
-  __shared__ __attribute__((aligned(16))) float Ab[GMPC_CEM_ROWS * GMPC_DG_LDA];   // the layer inputs of the 32 rows
+// The body of k_ens_rollout and of k_ens_rollout_feedback, over where a step's controls come
+// from.  Fb false: U[b][t] as given (f is not read).  Fb true: the row's 8 lanes form u_t = clamp(U_ref + K (x_t -
+// X_ref) + alpha k) from the row's x_t in the operand block -- lane rc the controls rc, rc + 8, ..., each a sequential
+// fmaf chain over the states in ascending order, so a row's controls depend on neither its place in the tile nor on B
+// or P -- behind the step's first barrier, and a second barrier hands the block to layer 0.  The stage cost reads the
+// controls its own lane wrote.  Everything else is one text for both.
+template <bool Fb>
+__device__ __forceinline__ void ens_rollout_body(const EnsRollArgs& a, const EnsFeedbackArgs& f, float* Ab) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kq = lane >> 4;
   const int n = a.n, m = a.m, T = a.T, S = a.S, B = a.B;
   const int b0 = blockIdx.x * GMPC_CEM_ROWS;     // row i of the tile is problem b0 + i
@@ -31,6 +40,8 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
     w0 = sigmoidf_(a.mpc_w[0]); w1 = sigmoidf_(a.mpc_w[1]); w2 = sigmoidf_(a.mpc_w[2]);
   }
   const float al = GMPC_ALPHA;
+  // a.x0's rows: n floats apart, or -- the feedback call without an x0 of its own -- X_ref's, S + 1 states apart
+  const size_t xstride = Fb ? f.x0_stride : (size_t)n;
   // x_t of the 32 rows, in dg_gemm's accumulator layout: the output layer's tile of a thread is its tile of x
   DgTiles xs;
 #pragma unroll
@@ -39,8 +50,8 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int bp = min(b0 + 4 * kq + rr, last), bq = min(b0 + 16 + 4 * kq + rr, last);
-      xs.p[ci][rr] = j < n ? a.x0[(size_t)bp * n + j] : 0.f;
-      xs.q[ci][rr] = j < n ? a.x0[(size_t)bq * n + j] : 0.f;
+      xs.p[ci][rr] = j < n ? a.x0[(size_t)bp * xstride + j] : 0.f;
+      xs.q[ci][rr] = j < n ? a.x0[(size_t)bq * xstride + j] : 0.f;
     }
   }
   float* Xp = a.X ? a.X + p * B * (size_t)(S + 1) * n : nullptr;          // the member's planes
@@ -50,10 +61,11 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
   for (int t = 0; t < S; ++t) {
     // ---- layer 0 input [x_t; u_t]
     cem_store_tiles(Ab, xs, n, wave, lane, [](float v, int) { return v; });
-    for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
-      const int i = e / m, j = e - i * m;
-      Ab[i * GMPC_DG_LDA + n + j] = a.U[((size_t)min(b0 + i, last) * S + t) * m + j];
-    }
+    if constexpr (!Fb)
+      for (int e = tid; e < GMPC_CEM_ROWS * m; e += GMPC_DG_THREADS) {
+        const int i = e / m, j = e - i * m;
+        Ab[i * GMPC_DG_LDA + n + j] = a.U[((size_t)min(b0 + i, last) * S + t) * m + j];
+      }
     __syncthreads();
     // ---- x_t of every live row, from the operand block
     if (Xp)
@@ -61,6 +73,26 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
         const int i = e / n, j = e - i * n;
         if (b0 + i < B) Xp[((size_t)(b0 + i) * (S + 1) + t) * n + j] = Ab[i * GMPC_DG_LDA + j];
       }
+    // ---- the feedback law: u_t of row rrow from its x_t, into the block and to U[p][b][t]
+    if constexpr (Fb) {
+      float* row = Ab + rrow * GMPC_DG_LDA;
+      const size_t bt = (size_t)rb * S + t;
+      const float* xr = f.X_ref + ((size_t)rb * (S + 1) + t) * n;
+      for (int j = rc; j < m; j += 8) {
+        const float* Kj = f.K + (bt * m + j) * n;
+        float du = 0.f;
+        for (int c = 0; c < n; ++c) du = fmaf(Kj[c], row[c] - xr[c], du);
+        if (f.k) du = du + __fmul_rn(f.alpha, f.k[bt * m + j]);
+        float u = f.U_ref[bt * m + j] + du;
+        if (f.u_lo) {     // (comparisons, not fminf / fmaxf: a NaN control stays one)
+          const float lo = f.u_lo[j], hi = f.u_hi[j];
+          u = u < lo ? lo : u;
+          u = u > hi ? hi : u;
+        }
+        row[n + j] = u;
+        if (f.U && rlive) f.U[((p * B + b0 + rrow) * S + t) * m + j] = u;
+      }
+    }
     // ---- stage cost of (x_t, u_t) against goal_t
     if (costed) {
       const float* row = Ab + rrow * GMPC_DG_LDA;
@@ -79,6 +111,7 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
       csum += c;
       if (Cp && rc == 0 && rlive) Cp[(size_t)(b0 + rrow) * (T + 1) + t] = c;
     }
+    if constexpr (Fb) __syncthreads();   // every row's u_t is in the block
     // ---- x_{t+1} = x_t + MLP([x_t; u_t]) under member p
     for (int l = 0; l < a.dyn.L; ++l) {
       const int K = a.dyn.dims[l], Nl = a.dyn.dims[l + 1];
@@ -137,6 +170,16 @@ __global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) 
       if (a.obj) a.obj[p * B + b0 + rrow] = csum;
     }
   }
+}
+
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout(EnsRollArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ab[GMPC_CEM_ROWS * GMPC_DG_LDA];   // the layer inputs of the 32 rows
+  ens_rollout_body<false>(a, EnsFeedbackArgs{}, Ab);
+}
+
+__global__ __launch_bounds__(GMPC_DG_THREADS) void k_ens_rollout_feedback(EnsRollArgs a, EnsFeedbackArgs f) {
+  __shared__ __attribute__((aligned(16))) float Ab[GMPC_CEM_ROWS * GMPC_DG_LDA];
+  ens_rollout_body<true>(a, f, Ab);
 }
 
 // A plan's one-step disagreement under every member (gmpc_ensemble_disagreement): k_ens_rollout's
@@ -229,16 +272,31 @@ __global__ __launch_bounds__(GMPC_THREADS) void k_ens_moments(const float* __res
 }
 
 // Host-side launchers ---------------------------------------------------------------------------
-int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s) {
+// What both forms of the rollout cover
+static bool ens_rollout_covered(const EnsRollArgs& a, int P) {
   for (int l = 0; l <= a.dyn.L; ++l)
-    if (a.dyn.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
+    if (a.dyn.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return false;
   for (int l = 0; l <= a.cost.L; ++l)
-    if (a.cost.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return 1;
-  if (a.n + a.m > GMPC_SAMPLED_MAX_WIDTH || a.B < 1 || a.S < 1 || a.S > a.T || P < 1 || P > GMPC_MAX_ENSEMBLE) return 1;
-  if ((a.costs || a.obj) && !a.goal) return 1;
-  if (a.goal && a.S != a.T) return 1;
+    if (a.cost.dims[l] > GMPC_SAMPLED_MAX_WIDTH) return false;
+  if (a.n + a.m > GMPC_SAMPLED_MAX_WIDTH || a.B < 1 || a.S < 1 || a.S > a.T || P < 1 || P > GMPC_MAX_ENSEMBLE)
+    return false;
+  if ((a.costs || a.obj) && !a.goal) return false;
+  return !a.goal || a.S == a.T;
+}
+
+int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s) {
+  if (!ens_rollout_covered(a, P)) return 1;
   const dim3 grid((a.B + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS, P);
   hipLaunchKernelGGL(k_ens_rollout, grid, dim3(GMPC_DG_THREADS), 0, s, a);
+  return 0;
+}
+
+int gmpc_launch_ens_rollout_feedback(const EnsRollArgs& a, const EnsFeedbackArgs& f, int P, hipStream_t s) {
+  if (!ens_rollout_covered(a, P)) return 1;
+  if (!a.x0 || !f.X_ref || !f.U_ref || !f.K || !f.u_lo != !f.u_hi) return 1;
+  if (f.x0_stride != (size_t)a.n && f.x0_stride != (size_t)(a.S + 1) * a.n) return 1;
+  const dim3 grid((a.B + GMPC_CEM_ROWS - 1) / GMPC_CEM_ROWS, P);
+  hipLaunchKernelGGL(k_ens_rollout_feedback, grid, dim3(GMPC_DG_THREADS), 0, s, a, f);
   return 0;
 }
 

@@ -349,6 +349,18 @@ struct EnsRollArgs {
 // Non-zero (nothing launched) outside the sampled rollout's coverage, 1 <= S <= T, 1 <= P <= GMPC_MAX_ENSEMBLE and the
 // rules above
 int gmpc_launch_ens_rollout(const EnsRollArgs& a, int P, hipStream_t s);
+// The same rollout in closed loop: a.U is not read; per member and row u_t = clamp(U_ref[b][t] + K[b][t]
+// (x_t - X_ref[b][t]) + alpha k[b][t], u_lo, u_hi).  X_ref [B][S+1][n], U_ref [B][S][m], K [B][S][m][n]; k [B][S][m]
+// or null (no feed-forward term); u_lo / u_hi [m], both or neither (no clamp); U [P][B][S][m] the applied controls or
+// null.  a.x0's rows lie x0_stride floats apart: n, or (S + 1) n when a.x0 is X_ref itself.
+struct EnsFeedbackArgs {
+  const float *X_ref, *U_ref, *K, *k, *u_lo, *u_hi;
+  float alpha;
+  size_t x0_stride;
+  float* U;
+};
+// Non-zero (nothing launched) outside gmpc_launch_ens_rollout's rules and those above
+int gmpc_launch_ens_rollout_feedback(const EnsRollArgs& a, const EnsFeedbackArgs& f, int P, hipStream_t s);
 // A plan's one-step disagreement: the rows of gmpc_launch_ens_rollout rolled S steps under the nominal
 // layers `nom` (fp32), member p (dyn: member 0, p mstride floats behind it) measured against them at every visited
 // (x_t, u_t).  X [B][S+1][n] the nominal states, d [P][B][S] the squared deviations of the one-step outputs, D [P][B]

@@ -885,6 +885,79 @@ class Engine:
             _ptr(out.get("obj")), _ptr(out.get("mean")), _ptr(out.get("var")), self._stream()))
         return out
 
+    ENSEMBLE_FEEDBACK_WANT = ("X", "U", "costs", "obj", "mean", "var")
+
+    def ensemble_rollout_feedback(self, members, X_ref, U_ref, K, goal=None, x0=None, k=None, alpha=1.0, u_lo=None,
+                                  u_hi=None, want=("X", "U", "obj")):
+        """A reference trajectory tracked in closed loop under every member of a dynamics ensemble, in one launch
+        (gmpc_ensemble_rollout_feedback): per member u_t = clamp(U_ref_t + K_t (x_t - X_ref_t)
+        + alpha k_t, u_lo, u_hi), x_{t+1} = x_t + MLP_p([x_t; u_t]).  members as for ensemble_rollout; X_ref
+        (B, S + 1, n), U_ref (B, S, m) with 1 <= S <= T, K (B, S, m, n) (lqr_backward's layout), goal (B, T + 1, n) or
+        None, x0 (B, n) or None (then X_ref[:, 0]), k (B, S, m) or None (no feed-forward term): float32 device tensors;
+        alpha a finite number; u_lo, u_hi as for ilqr_solve_box (None, a scalar or m values), both or neither.  -> a
+        dict of the `want`ed tensors: "X" (P, B, S + 1, n) the members' states, "U" (P, B, S, m) the controls each
+        member applied, "costs" (P, B, T + 1) and "obj" (P, B) on those controls, "mean" / "var" (B, S + 1, n) the
+        members' moments per step and state.  "costs" and "obj" need goal and S == T.  With K = 0, no k and no bounds
+        it is ensemble_rollout(members, x0, U_ref) bit for bit.  Stateless as ensemble_rollout is.  Every refusal is a
+        GmpcError("ensemble feedback: ..."); nothing is synchronised."""
+        who = "ensemble feedback"
+        P = self._check_ensemble_members(who, members)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - set(self.ENSEMBLE_FEEDBACK_WANT)
+        if unknown:
+            raise _lib.GmpcError(f"{who}: want has unknown entries {sorted(unknown, key=str)}; known: "
+                                 f"{self.ENSEMBLE_FEEDBACK_WANT}")
+        if not want:
+            raise _lib.GmpcError(f"{who}: want is empty; known: {self.ENSEMBLE_FEEDBACK_WANT}")
+        if goal is None and ("costs" in want or "obj" in want):
+            raise _lib.GmpcError(f'{who}: "costs" and "obj" need goal (want = {want})')
+        n, m, T = self.n, self.m, self.T
+        for name, t in (("X_ref", X_ref), ("U_ref", U_ref), ("K", K), ("goal", goal), ("x0", x0), ("k", k)):
+            if name in ("X_ref", "U_ref", "K") and t is None:
+                raise _lib.GmpcError(f"{who}: {name} must not be None")
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+                raise _lib.GmpcError(f"{who}: {name} must be a float32 tensor, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)}")
+        if U_ref.dim() != 3 or U_ref.shape[2] != m:
+            raise _lib.GmpcError(f"{who}: U_ref must be (B, S, {m}), got {tuple(U_ref.shape)}")
+        B, S = int(U_ref.shape[0]), int(U_ref.shape[1])
+        if not 1 <= B <= self.max_batch:
+            raise _lib.GmpcError(f"{who}: B = {B} outside [1, max_batch = {self.max_batch}]")
+        if not 1 <= S <= T:
+            raise _lib.GmpcError(f"{who}: S = {S} outside [1, T = {T}]")
+        shapes = dict(X_ref=(B, S + 1, n), K=(B, S, m, n), goal=(B, T + 1, n), x0=(B, n), k=(B, S, m))
+        for name, t in (("X_ref", X_ref), ("K", K), ("goal", goal), ("x0", x0), ("k", k)):
+            if t is not None and tuple(t.shape) != shapes[name]:
+                raise _lib.GmpcError(f"{who}: {name} must be {shapes[name]}, got {tuple(t.shape)}")
+        for name, t in (("X_ref", X_ref), ("U_ref", U_ref), ("K", K), ("goal", goal), ("x0", x0), ("k", k)):
+            if t is not None and not t.is_contiguous():
+                raise _lib.GmpcError(f"{who}: {name} must be contiguous")
+        try:
+            alpha = float(alpha)
+        except (TypeError, ValueError):
+            raise _lib.GmpcError(f"{who}: alpha must be a finite number, got {alpha!r}") from None
+        if not np.isfinite(alpha):
+            raise _lib.GmpcError(f"{who}: alpha must be a finite number, got {alpha!r}")
+        if (u_lo is None) != (u_hi is None):
+            raise _lib.GmpcError(f"{who}: u_lo and u_hi must both be given or both be None")
+        lo_d = hi_d = None
+        if u_lo is not None:
+            try:
+                _, _, lo_d, hi_d = self._device_bounds(u_lo, u_hi)
+            except _lib.GmpcError as e:
+                raise _lib.GmpcError(f"{who}: {e}") from None
+        if S != T and ("costs" in want or "obj" in want):
+            raise _lib.GmpcError(f'{who}: "costs" and "obj" need the whole horizon, S = {S} is not T = {T}')
+        shapes = dict(X=(P, B, S + 1, n), U=(P, B, S, m), costs=(P, B, T + 1), obj=(P, B), mean=(B, S + 1, n),
+                      var=(B, S + 1, n))
+        out = {key: self.new(*shapes[key]) for key in self.ENSEMBLE_FEEDBACK_WANT if key in want}
+        dev = self.to_dev(members)
+        _lib.check(self.lib.gmpc_ensemble_rollout_feedback(
+            self.ctx, B, S, P, _ptr(dev), _ptr(x0), _ptr(X_ref), _ptr(U_ref), _ptr(K), _ptr(k), alpha, _ptr(lo_d),
+            _ptr(hi_d), _ptr(goal), _ptr(out.get("X")), _ptr(out.get("U")), _ptr(out.get("costs")),
+            _ptr(out.get("obj")), _ptr(out.get("mean")), _ptr(out.get("var")), self._stream()))
+        return out
+
     ENSEMBLE_DISAGREEMENT_WANT = ("X", "d", "D")
 
     def ensemble_disagreement(self, members, x0, U, want=("d", "D")):

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from gan_mpc_amd import parallel
+from gan_mpc_amd import params as params_lib
 from gan_mpc_amd.engine import TRAJAX_iLQR_KWARGS
 from gan_mpc_amd.policy import eval as eval_policy
 from gan_mpc_amd.policy import optimizers as opt
@@ -54,6 +55,48 @@ class BaseMPC(eval_policy.EvalMPC):
         eng = self.bind(self.to_device_params(params), xs[0])
         out = eng.ensemble_rollout(self._ensemble_dev, eng.to_dev(x), eng.to_dev(U), want=("X", "var"))
         return out["X"], out["var"].sum(-1)
+
+    def closed_loop_spread(self, params, x, U, goal, x0=None, members=None, feedforward=False):
+        """Where the members of a dynamics ensemble end up when each of them TRACKS a plan with the plan's own iLQR
+        gains (Engine.ensemble_rollout_feedback): x (B, n) the states the plan starts from, U
+        (B, T, m) its controls, goal (B, T+1, n).  The plan is rolled out from x under params["dynamics_params"]
+        (Engine.rollout_cost), the time-varying gains K (and k) are those of Engine.lqr_backward at that trajectory,
+        and every member then applies u_t = U_t + K_t (x_t - X_t) (+ k_t with feedforward=True) from x0 (B, n), default
+        x, clamped to the policy's control_bounds when it has them.  members: None -- the policy's dynamics_ensemble
+        (a "cem" / "mppi" / "icem" policy) --, or an explicit (P, dyn_count) float32 array or tensor, or a sequence of
+        dynamics parameter trees: the way in for the iLQR policies, which hold no ensemble.  -> (X_members
+        (P, B, T+1, n), U_members (P, B, T, m) the controls each member applied, spread (B, T+1) the members'
+        population variance per step summed over the state entries).  Forward only.  On a "box" policy the gains are
+        the unconstrained ones (lqr_backward knows no bounds) and the clamp does the rest: a saturated control does not
+        feed back."""
+        if members is None:
+            if self.dynamics_ensemble is None:
+                raise ValueError("closed_loop_spread needs members= or a dynamics_ensemble (the constructor's, or "
+                                 "set_dynamics_ensemble): neither is there")
+        elif not (torch.is_tensor(members) or isinstance(members, np.ndarray)):
+            if len(members) == 0:
+                raise ValueError("closed_loop_spread: members must hold at least one dynamics parameter tree")
+            members = np.stack([params_lib.pack_mlp(tree) for tree in members]).astype(np.float32)
+        xs, Us, gs = (tuple(getattr(a, "shape", np.shape(a))) for a in (x, U, goal))
+        if len(xs) != 2 or len(Us) != 3 or Us[0] != xs[0] or len(gs) != 3 or gs[0] != xs[0]:
+            raise ValueError(f"closed_loop_spread: x must be (B, n), U (B, T, m) and goal (B, T+1, n), got {xs}, {Us} "
+                             f"and {gs}")
+        if x0 is not None and tuple(getattr(x0, "shape", np.shape(x0))) != xs:
+            raise ValueError(f"closed_loop_spread: x0 must be {xs} as x is, got "
+                             f"{tuple(getattr(x0, 'shape', np.shape(x0)))}")
+        eng = self.bind(self.to_device_params(params), xs[0])
+        d = eng.to_dev
+        x, U, goal = d(x), d(U), d(goal)
+        X, _ = eng.rollout_cost(x, U, goal)
+        gains = eng.lqr_backward(X, U, goal, after_rollout=True)
+        lo = hi = None
+        if self.control_bounds is not None:
+            lo, hi = self.control_bounds
+            lo, hi = (-np.inf if lo is None else lo), (np.inf if hi is None else hi)
+        out = eng.ensemble_rollout_feedback(
+            self._ensemble_dev if members is None else members, X, U, gains["K"], x0=x if x0 is None else d(x0),
+            k=gains["k"] if feedforward else None, u_lo=lo, u_hi=hi, want=("X", "U", "var"))
+        return out["X"], out["U"], out["var"].sum(-1)
 
     def plan_disagreement(self, params, x, U):
         """The one-step disagreement of the policy's dynamics ensemble with params["dynamics_params"] along a plan

@@ -470,6 +470,33 @@ int gmpc_ensemble_rollout(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_m
                           const float* U, const float* goal, float* X, float* costs, float* obj, float* x_mean,
                           float* x_var, void* stream);
 
+/* The same rollout in closed loop: a reference trajectory tracked with its own time-varying
+ * feedback gains under every member, in one member-parallel launch; forward only.  Per member p and problem b, with
+ * x_0 = x0[b]:
+ *   du_j    = sum_c K[b][t][j][c] (x_t[c] - X_ref[b][t][c])     one fmaf per c, c ascending, from 0
+ *   du_j   += alpha * k[b][t][j]                                only with k; the product rounded first
+ *   u_t     = clamp(U_ref[b][t] + du, u_lo, u_hi)               the clamp only with bounds; a NaN control stays NaN
+ *   x_{t+1} = x_t + MLP_p([x_t; u_t])
+ *   dyn_members, B, S, P, goal as for gmpc_ensemble_rollout
+ *   x0 [B][n] or NULL: then X_ref[b][0]
+ *   X_ref [B][S+1][n], U_ref [B][S][m]: the reference trajectory; K [B][S][m][n]: the gains, gmpc_lqr_backward's layout
+ *   k [B][S][m] or NULL: no feed-forward term (alpha is then only checked)
+ *   u_lo, u_hi [m] device vectors, both or neither (NULL: no clamp); u_lo <= u_hi is the caller's to keep
+ *   -> X [P][B][S+1][n], costs [P][B][T+1], obj [P][B], x_mean, x_var [B][S+1][n] as gmpc_ensemble_rollout's, the costs
+ *      on the applied controls
+ *      U [P][B][S][m]  the applied controls, which differ per member
+ *   each output may be NULL, not all of them; costs and obj need goal and S == T.
+ * The dynamics' and the costs' arithmetic is gmpc_ensemble_rollout's own: with K = 0, no k and no bounds X, costs, obj
+ * and the moments are bitwise that call's for U = U_ref, and a member that reproduces X_ref bit for bit is returned
+ * U_ref and X_ref bit for bit.  A row's outputs depend on neither B, its place in the batch, nor P; no atomics.
+ * Stateless and asynchronous as gmpc_ensemble_rollout is (two launches at most, the same workspace rule).  Every
+ * refusal is GMPC_EINVAL with a message starting "ensemble feedback: ", before any launch: gmpc_ensemble_rollout's
+ * list (x0 excepted), a null X_ref, U_ref or K, exactly one of u_lo / u_hi, a non-finite alpha. */
+int gmpc_ensemble_rollout_feedback(gmpc_ctx* ctx, int B, int S, int P, const float* dyn_members, const float* x0,
+                                   const float* X_ref, const float* U_ref, const float* K, const float* k, float alpha,
+                                   const float* u_lo, const float* u_hi, const float* goal, float* X, float* U,
+                                   float* costs, float* obj, float* x_mean, float* x_var, void* stream);
+
 /* A penalty on the members' one-step disagreement with the nominal model along a sampled row: a
  * property of the context, like the precision, the ensemble and its mode; off until set.  No stream, no device work.
  * Independent of the ensemble and of gmpc_set_params: neither resets it, it may be set before an ensemble is, and it
